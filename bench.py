@@ -5,6 +5,10 @@
 Contract (driver):  python bench.py --gpus N --steps K --warmup W
   N > 1 is launched by torch.distributed.run, one rank per GPU (RCCL); weak scaling: every
   rank owns 64 graphs (ids 64r .. 64r+63).  Rank 0 prints ONE JSON line.
+  The timed region is exactly K steps after W warm-up steps (rounded up to an even count); `ms_per_step` in the line
+  is its wall clock over K.  `--dump-outputs DIR` writes what the last timed step computed to DIR/<name>.npy (rank 0):
+  pred (the mini-batch's predictions), loss, grad.<param> and param.<param> (after the step's Adam update), float32.
+  The inputs (synthetic graphs, initial weights, dropout streams) are seeded: the same arguments give the same inputs.
 
 What a "step" is: everything the reference does per mini-batch inside NeuralNet._epoch
 (NeuralNet.py:489-506) for data already on the device: zero_grad, model(batch) -- including
@@ -47,9 +51,6 @@ ALG_BYTES = {"GINet": (67668, 90208), "sGAT": (62440, 49904), "FoutNet": (52840,
 BYTES_TOPO = {"GINet": 4804 + 1800 + 5808 + 16 * 1000, "FoutNet": 4804 + 1800 + 5808 + 16 * 1000,
               "sGAT": 4804 + 1800 + 5808 + 16 * 1000 + 4000 + 4 * 200}
 HBM_PEAK_GBS = 8000.0                               # MI355X_MICROARCH.md: 8 TB/s spec
-# the K-step block is repeated until the timed region is this long: several SMI polling periods, so that an outside
-# observer (the driver's gpu_busy sampler) sees the GPU busy DURING the measurement
-MIN_TIMED_SECONDS = 7.0          # (sized from one untimed block, which runs a little slower than the timed ones: >= 6 s result)
 
 
 def source_hash():
@@ -144,9 +145,13 @@ def parse():
     ap.add_argument("--epoch-graphs", type=int, default=4096,
                     help="size of the resident graph set of the secondary whole-epoch measurement (0: skip it)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--min-seconds", type=float, default=MIN_TIMED_SECONDS,
-                    help="the K-step block is repeated until the timed region is at least this long (0: one block; "
-                         "used by the rocprofv3 counter passes, which only need a few launches)")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="0 (default): the timed region is exactly --steps steps.  > 0: the K-step block is repeated until the "
+                         "timed region is at least this long (sized from one untimed block; e.g. several SMI polling periods, "
+                         "so that an outside observer sees the GPU busy during the measurement)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (predictions, loss, gradients, "
+                         "updated parameters) to DIR/<name>.npy, float32, rank 0")
     return ap.parse_args()
 
 
@@ -232,6 +237,7 @@ def main():
     pipeline = native and not args.no_pipeline and not cached
     dp_path = world > 1 or args.force_dp_path
     state = {"k": 0}       # which of the two topology workspaces the next step trains from
+    step_out = {"pred": None, "replayed": None}     # the predictions of the last step (--dump-outputs)
     if native:
         from deeprank_gnn_amd.trainer import FusedTrainer
         trainer = FusedTrainer(net, lr=1e-3, task="reg", seed=1234 + rank)
@@ -303,6 +309,7 @@ def main():
             loss = F.mse_loss(pred.reshape(-1), batch.y)
             loss.backward()
             loss_out.copy_(loss.detach())
+            step_out["pred"] = pred.detach()
 
         def all_reduce():
             bucket.all_reduce()
@@ -318,6 +325,9 @@ def main():
         all_reduce()
         update_part()
 
+    def last_pred():
+        return getattr(trainer, "last_pred", None) if native else step_out["pred"]
+
     pre_steps = 0          # training steps already run while validating recorded graphs; counted as warm-up
     dp_mode = "eager all-reduce between %s" % ("graph replays" if capture else "eager launches")
     if capture:
@@ -329,11 +339,26 @@ def main():
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
 
+        class Recorded:
+            """A recorded hipGraph and the prediction tensor of the last step it records (None: it records no forward).
+            The tensor lives in the graph's memory pool and is rewritten by every replay; a replay makes it the one
+            --dump-outputs reads."""
+
+            def __init__(self, g, pred):
+                self.g, self.pred = g, pred
+
+            def replay(self):
+                self.g.replay()
+                if self.pred is not None:
+                    step_out["replayed"] = self.pred
+
         def graph_of(fn, **kw):
+            before = last_pred()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, **kw):
                 fn()
-            return g
+            after = last_pred()
+            return Recorded(g, after if after is not before else None)
 
         state["k"] = 0
         if split:
@@ -500,20 +525,22 @@ def main():
     warm += warm & 1
     run_steps(warm)
     torch.cuda.synchronize()
-    # One untimed block to size the timed region: the K-step block is repeated until the region is at least
-    # MIN_TIMED_SECONDS long (a single 20-step block is ~0.5 ms: shorter than a host timer tick is accurate for
-    # and invisible to an SMI poll).  Every rank uses the same repeat count.
-    t0 = time.perf_counter()
-    run_steps(args.steps)
-    torch.cuda.synchronize()
-    t_block = max(time.perf_counter() - t0, 1e-6)
-    if args.steps & 1:
-        run_steps(1)                          # parity back to 0
-    repeats = int(min(max(1, -(-args.min_seconds // t_block)), 200000))
-    if world > 1:
-        t = torch.tensor([repeats], device=dev, dtype=torch.int64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        repeats = int(t.item())
+    repeats = 1
+    if args.min_seconds > 0:
+        # One untimed block to size the timed region: the K-step block is repeated until the region is at least
+        # --min-seconds long (a single 20-step block is ~0.5 ms: shorter than a host timer tick is accurate for
+        # and invisible to an SMI poll).  Every rank uses the same repeat count.
+        t0 = time.perf_counter()
+        run_steps(args.steps)
+        torch.cuda.synchronize()
+        t_block = max(time.perf_counter() - t0, 1e-6)
+        if args.steps & 1:
+            run_steps(1)                          # parity back to 0
+        repeats = int(min(max(1, -(-args.min_seconds // t_block)), 200000))
+        if world > 1:
+            t = torch.tensor([repeats], device=dev, dtype=torch.int64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            repeats = int(t.item())
     # HIP events only every `stride` blocks (>= 200 steps apart): an event between every two 20-step replays costs the device a
     # marker per replay (measured: 20.2 vs 19.8 us per step under --steps 20), and the median block time does not need them
     stride = max(1, 200 // max(args.steps, 1))
@@ -543,6 +570,8 @@ def main():
         elapsed, block_med_ms = float(t[0].item()), float(t[1].item())
     timed_steps = args.steps * repeats
     final_loss = float(loss_out.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_out["replayed"] if capture else last_pred(), loss_out, net)
     in_sync = None
     if world > 1:
         # data parallel invariant: every rank applied the same averaged gradients, so the parameters agree bit
@@ -645,6 +674,22 @@ def main():
         except Exception:
             pass
         print(json.dumps(result), flush=True)
+
+
+def dump_outputs(out_dir, pred, loss, net):
+    """What the last timed step computed, as its caller receives it: the predictions of the mini-batch, the loss, every
+    parameter's gradient and every parameter after the step's update -- DIR/<name>.npy, float32 (about 45 K values for
+    GINet, far below 64 MB: nothing is sampled)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"pred": pred, "loss": loss}
+    for name, p in net.named_parameters():
+        arrays["grad." + name] = p.grad
+        arrays["param." + name] = p
+    for name, t in arrays.items():
+        if t is None:
+            raise SystemExit("--dump-outputs: the timed path left no %s" % name)
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().to("cpu", torch.float32).numpy())
 
 
 def measure_dp_distinct(trainer, dev, rank, world, need_w, all_reduce, update_part, dp_path, rccl, n_batches=32):
