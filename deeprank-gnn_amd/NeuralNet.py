@@ -3,12 +3,13 @@ without torch_geometric / h5py: same constructor vocabulary, ``train`` / ``eval`
 ``save_model`` / ``pretrained_model=`` flow and the same checkpoint dictionary
 (NeuralNet.py:775-790), with the per-batch body executed by ``FusedTrainer`` (native step).
 
-``PreCluster`` (MCL) runs on the device when the graphs do not carry
+``PreCluster`` (MCL, or the deterministic Louvain with ``cluster_nodes='louvain'``) runs on the device when the graphs do not carry
 ``clustering/<method>/depth_{0,1}`` yet.  ``database`` / ``database_eval`` / ``database_test`` take one path or a
 list of paths (.drgs native container, .npz, or .hdf5 where h5py exists).  The per-epoch export keeps the reference's
 group / dataset names (``epoch_%04d/{train,eval,test}/{mol,outputs,targets,raw_outputs}`` + the attributes task /
 target / batch_size, NeuralNet.py:827-872) in the native container; ``tools/native_to_hdf5.py`` turns it into the HDF5
-file the reference writes.  What is NOT reproduced: Louvain clustering, ``Metrics`` beyond the accuracy, plots.
+file the reference writes.  What is NOT reproduced: python-louvain's random visiting order, ``Metrics`` beyond the accuracy,
+plots.
 """
 import os
 import time
@@ -186,7 +187,7 @@ class NeuralNet(object):
         first = self.dataset[0]
         if getattr(first, "cluster0", None) is None:
             # the reference runs PreCluster at every construction (NeuralNet.py:139-143); here only
-            # when the graphs do not carry the labels yet (same result: MCL is deterministic)
+            # when the graphs do not carry the labels yet (same result: both methods are deterministic here)
             from .clustering import PreCluster
             print("Loading clusters")
             PreCluster(self.dataset, method=self.cluster_nodes or 'mcl', api=_api, device=self.device)

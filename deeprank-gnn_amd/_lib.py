@@ -224,6 +224,7 @@ class Api(object):
         lib.drgnn_cluster_offset.argtypes = [_vp, _vp, _c_i64, _vp, _vp]
         lib.drgnn_graclus.argtypes = [_vp, _c_i64, _c_i64, _c_i64, _c_i32, _c_i32, _vp, _vp, _vp, _vp]
         lib.drgnn_mcl.argtypes = [_vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp]
+        lib.drgnn_louvain.argtypes = [_vp, _c_i64, _vp, _vp, _c_i64, _c_i32, _c_i32, _vp, _vp, _vp, _vp]
         lib.drgnn_p2p_bytes.argtypes = [_c_i64]
         lib.drgnn_p2p_bytes.restype = _c_i64
         lib.drgnn_p2p_alloc.argtypes = [_c_i64, ctypes.POINTER(_vp), _vp]
@@ -459,6 +460,11 @@ class Api(object):
             info, stream):
         _check(self.lib.drgnn_mcl(_ptr(edge_index), n_edges, _ptr(node_ptr), _ptr(edge_ptr), _ptr(mat_ptr), n_graphs,
                                   _ptr(mat_scratch), _ptr(int_scratch), _ptr(labels), _ptr(info), stream), "drgnn_mcl")
+
+    def louvain(self, edge_index, n_edges, node_ptr, edge_ptr, n_graphs, max_nodes, max_edges, labels, info,
+                modularity, stream):
+        _check(self.lib.drgnn_louvain(_ptr(edge_index), n_edges, _ptr(node_ptr), _ptr(edge_ptr), n_graphs, max_nodes,
+                                      max_edges, _ptr(labels), _ptr(info), _ptr(modularity), stream), "drgnn_louvain")
 
     def collate(self, gset, ids, n_graphs, n_nodes, n_edges, x, edge_index, edge_attr, batch, cluster0, cluster1,
                 y, node_ptr, edge_ptr, c1_ptr, stream):

@@ -9,8 +9,9 @@ the torch_geometric / torch_scatter helpers its models import), on the device pa
 
 These return dynamically-shaped tensors, so -- like the reference -- they synchronise with the
 host; the shipped nets avoid them and run fused (see functional.net_body).  The OFFLINE half of
-the reference module (community_detection with method 'mcl', run once per dataset and cached with
-the graphs) is provided on the device through deeprank_gnn_amd.clustering; Louvain is not.
+the reference module (community_detection with method 'mcl' or 'louvain', run once per dataset and cached
+with the graphs) is provided on the device through deeprank_gnn_amd.clustering; its Louvain is deterministic
+(id-order visits, smallest-id ties, labels by first appearance) where python-louvain draws random orders.
 """
 import types
 
@@ -371,28 +372,34 @@ def scatter_sum(src, index, dim=0, out=None, dim_size=None):
 
 
 def community_detection(edge_index, num_nodes, edge_attr=None, method='mcl'):
-    """Cluster labels of ONE graph (reference community_pooling.py:95-158).  'mcl' runs on the device
-    (unweighted, like the reference's PreCluster call); 'louvain' (python-louvain, randomised, so
-    without a reproducible answer to match) is not provided."""
-    if method != 'mcl':
+    """Cluster labels of ONE graph (reference community_pooling.py:95-158), on the device and unweighted,
+    like the reference's PreCluster call.  'mcl' is Markov clustering; 'louvain' is a deterministic Louvain
+    (nodes visited in id order, ties to the smallest community id, labels numbered by first appearance), where
+    python-louvain draws random visiting orders and numbers labels through a set."""
+    if method not in ('mcl', 'louvain'):
         raise ValueError('Clustering method %s not supported' % method)
     if edge_attr is not None:
-        raise NotImplementedError("weighted MCL is never used by the reference's PreCluster")
-    from .clustering import community_detection_mcl
-    return community_detection_mcl(edge_index, num_nodes, api=_api())
+        raise NotImplementedError("weighted %s is never used by the reference's PreCluster" %
+                                  ('MCL' if method == 'mcl' else 'Louvain'))
+    from .clustering import community_detection_mcl, community_detection_louvain
+    detect = community_detection_mcl if method == 'mcl' else community_detection_louvain
+    return detect(edge_index, num_nodes, api=_api())
 
 
 def community_detection_per_batch(edge_index, batch, num_nodes, edge_attr=None, method='mcl'):
-    """Per-graph MCL with the reference's running label offset (community_pooling.py:33-92:
-    ``ncluster = max(cluster)`` after every graph, i.e. consecutive graphs SHARE one id)."""
-    if method != 'mcl':
+    """Per-graph MCL or (deterministic) Louvain with the reference's running label offset
+    (community_pooling.py:33-92: ``ncluster = max(cluster)`` after every graph, i.e. consecutive graphs SHARE one id)."""
+    if method not in ('mcl', 'louvain'):
         raise ValueError('Clustering method %s not supported' % method)
-    from .clustering import mcl_labels, _ptr_from_counts
+    if edge_attr is not None and method == 'louvain':
+        raise NotImplementedError("weighted Louvain is never used by the reference's PreCluster")
+    from .clustering import mcl_labels, louvain_labels, _ptr_from_counts
     batch = torch.as_tensor(batch, device=edge_index.device)
     B = int(batch.max()) + 1
     node_ptr = _ptr_from_counts(torch.bincount(batch, minlength=B), edge_index.device)
     edge_ptr = _ptr_from_counts(torch.bincount(batch[edge_index[0]], minlength=B), edge_index.device)
-    labels, _ = mcl_labels(edge_index, node_ptr, edge_ptr, api=_api())
+    labeller = mcl_labels if method == 'mcl' else louvain_labels
+    labels = labeller(edge_index, node_ptr, edge_ptr, api=_api())[0]
     tops = torch.stack([labels[batch == g].max() for g in range(B)])
     offset = torch.cat([tops.new_zeros(1), tops.cumsum(0)[:-1]])
     return labels + offset[batch]

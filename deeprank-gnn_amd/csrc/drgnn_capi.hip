@@ -1691,6 +1691,34 @@ int drgnn_mcl(const int64_t* edge_index, int64_t n_edges, const int32_t* node_pt
     return 0;
 }
 
+int drgnn_louvain(const int64_t* edge_index, int64_t n_edges, const int32_t* node_ptr, const int32_t* edge_ptr,
+                  int64_t n_graphs, int32_t max_nodes, int32_t max_edges, int64_t* labels, int32_t* info,
+                  double* modularity, void* stream) {
+    if (!node_ptr || !edge_ptr || !info || !modularity || n_graphs < 0 || n_edges < 0 || max_nodes < 0 ||
+        max_edges < 0)
+        return DRGNN_E_ARG;
+    if (n_edges > 0 && !edge_index) return DRGNN_E_ARG;
+    if (max_nodes > 0 && !labels) return DRGNN_E_ARG;
+    if (n_graphs == 0) return 0;
+    const int64_t words = louvain_lds_words(max_nodes, max_edges);
+    if (words * 4 > DRGNN_LDS_LIMIT) return DRGNN_E_CAPACITY;
+    LouvainArgs a;
+    a.edge_index = edge_index; a.n_edges = n_edges; a.node_ptr = node_ptr; a.edge_ptr = edge_ptr;
+    a.n_graphs = (int)n_graphs; a.capN = max_nodes; a.capE = max_edges;
+    a.labels = labels; a.info = info; a.modularity = modularity;
+#ifdef DRGNN_EMU
+    std::vector<int> buf((size_t)words + 16);
+    for (int g = 0; g < n_graphs; ++g) louvain_graph(a, g, buf.data());
+    (void)stream;
+#else
+    if (words * 4 > 64 * 1024)
+        HIP_TRY(hipFuncSetAttribute((const void*)k_louvain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(words * 4)));
+    hipLaunchKernelGGL(k_louvain, dim3((unsigned)n_graphs), dim3(LV_W), (size_t)(words * 4), (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+#endif
+    return 0;
+}
+
 // ---- mini-batch assembly from the resident graph set -----------------------------------------------
 int drgnn_collate(const drgnn_graph_set* set, const int32_t* ids, int64_t n_graphs, int64_t n_nodes,
                   int64_t n_edges, float* x, int64_t* edge_index, float* edge_attr, int64_t* batch,

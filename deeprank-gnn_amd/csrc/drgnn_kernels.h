@@ -11,6 +11,7 @@
 #include "drgnn_step3.h"
 #include "drgnn_layers.h"
 #include "drgnn_mcl.h"
+#include "drgnn_louvain.h"
 #include "drgnn_collate.h"
 #include "drgnn_p2p.h"
 
@@ -952,6 +953,10 @@ __global__ void __launch_bounds__(DRGNN_NTHREADS) k_mcl(MclArgs a) {
     __shared__ double red[DRGNN_NTHREADS];
     __shared__ int flag[2];
     mcl_graph(a, blockIdx.x, flag, red);
+}
+__global__ void __launch_bounds__(LV_W) k_louvain(LouvainArgs a) {
+    extern __shared__ __attribute__((aligned(16))) int smem_lv[];
+    louvain_graph(a, blockIdx.x, smem_lv);
 }
 __global__ void __launch_bounds__(DRGNN_NTHREADS) k_graclus(GraclusArgs a) {
     extern __shared__ __attribute__((aligned(16))) int smem_g[];

@@ -595,6 +595,22 @@ int drgnn_mcl(const int64_t* edge_index, int64_t n_edges, const int32_t* node_pt
               const int64_t* mat_ptr, int64_t n_graphs, double* mat_scratch, int32_t* int_scratch,
               int64_t* labels, int32_t* info, void* stream);
 
+/* Deterministic Louvain community detection of every graph of a batch: community_detection(edge_index,
+ * num_nodes, method='louvain') (community_pooling.py:95-158; python-louvain best_partition, resolution 1) on
+ * the unweighted graph, as PreCluster runs it on the internal-contact graph (DataSet.py:77-86).  Nodes are
+ * visited in id order and ties go to the smallest community id (python-louvain draws random orders); labels
+ * int64 [N] are per-graph local labels 0..k-1 in order of first appearance.  Each distinct pair {u, v} of a
+ * graph's edge slice (either direction, any repetition) has weight 1; all arithmetic is exact int64.
+ * info int32 [B, 2] = (recorded levels, total passes), (0, 0) for a graph without pairs, (-1, -1) for a graph
+ * beyond max_nodes / max_edges (labels untouched); modularity [B] = Q of the result.  One 64-lane workgroup
+ * per graph; max_nodes / max_edges (largest graph; edges counted as listed, so list each pair once to get the
+ * most out of the carve, as the Python louvain_labels does) size its LDS carve, louvain_lds_words() in
+ * drgnn_louvain.h: 4 * (199 + 6 * max_nodes + 8 * max(max_edges, 1)) bytes, DRGNN_E_CAPACITY beyond 160 KiB
+ * (1 024 nodes with 4 096 pairs listed once fit).  No allocation, no synchronisation. */
+int drgnn_louvain(const int64_t* edge_index, int64_t n_edges, const int32_t* node_ptr, const int32_t* edge_ptr,
+                  int64_t n_graphs, int32_t max_nodes, int32_t max_edges, int64_t* labels, int32_t* info,
+                  double* modularity, void* stream);
+
 /* ---- device-resident graph set and mini-batch assembly --------------------
  * Replaces the host collate of every mini-batch: torch_geometric DataLoader -> Batch.from_data_list over
  * HDF5DataSet.load_one_graph's Data objects (NeuralNet.py:153-154, DataSet.py:231-366).  The set is the

@@ -1,0 +1,170 @@
+"""Plain-Python statement of the package's deterministic Louvain (deeprank-gnn_amd/csrc/drgnn_louvain.h), exact
+integer arithmetic.  python-louvain's generate_dendrogram / __one_level at resolution 1, except that nodes are
+visited in id order, ties go to the smallest community id, and labels are numbered by first appearance.
+
+    N(P) = sum_c (2m A_c - K_c^2),  Q = N / (2m)^2;  move score s(c) = 2m k_{i,c} - K_{c minus i} k_i
+"""
+
+
+def _below(gain, two_m):
+    return float(gain) < (1e-7 * float(two_m)) * float(two_m)
+
+
+def _quality(adj, comm, K, two_m):
+    inside = sum(w for u, row in enumerate(adj) for v, w in row.items() if comm[u] == comm[v])
+    return two_m * inside - sum(k * k for k in K)
+
+
+def _level(adj, two_m):
+    """One level on the weighted graph adj[u] = {v: A[u][v]} (A[u][u] = 2 x self-loop weight)."""
+    n = len(adj)
+    deg = [sum(row.values()) for row in adj]
+    comm = list(range(n))
+    K = list(deg)
+    cur = _quality(adj, comm, K, two_m)
+    passes = 0
+    while True:
+        moved = 0
+        for i in range(n):
+            ki, own = deg[i], comm[i]
+            kic = {}
+            for j, w in adj[i].items():
+                if j != i:
+                    kic[comm[j]] = kic.get(comm[j], 0) + w
+            K[own] -= ki
+            s_own = two_m * kic.get(own, 0) - K[own] * ki
+            best = None
+            for c, k in kic.items():
+                if c == own:
+                    continue
+                s = two_m * k - K[c] * ki
+                if best is None or s > best[0] or (s == best[0] and c < best[1]):
+                    best = (s, c)
+            to = best[1] if best is not None and best[0] > s_own else own
+            K[to] += ki
+            comm[i] = to
+            moved += to != own
+        passes += 1
+        new = _quality(adj, comm, K, two_m)
+        gain, cur = new - cur, new
+        if moved == 0 or _below(gain, two_m):
+            return comm, cur, passes
+
+
+def louvain(pairs, n):
+    """pairs: iterable of (u, v) (one direction or both, repeats allowed, u == v a self-loop), n nodes.
+    Returns (labels list, (recorded levels, total passes), modularity float)."""
+    adj = [dict() for _ in range(n)]
+    for u, v in {(min(int(u), int(v)), max(int(u), int(v))) for u, v in pairs}:
+        adj[u][v] = 2 if u == v else 1
+        adj[v][u] = adj[u][v]
+    two_m = sum(sum(row.values()) for row in adj)
+    labels = list(range(n))
+    if two_m == 0:
+        return labels, (0, 0), 0.0
+    levels = passes = 0
+    rec = None
+    while True:
+        comm, q, p = _level(adj, two_m)
+        passes += p
+        if levels > 0 and _below(q - rec, two_m):
+            break
+        levels, rec = levels + 1, q
+        new_id = {}
+        for c in comm:
+            new_id.setdefault(c, len(new_id))
+        labels = [new_id[comm[x]] for x in labels]
+        induced = [dict() for _ in range(len(new_id))]
+        for u, row in enumerate(adj):
+            a = new_id[comm[u]]
+            for v, w in row.items():
+                b = new_id[comm[v]]
+                induced[a][b] = induced[a].get(b, 0) + w
+        adj = induced
+    return labels, (levels, passes), float(rec) / (float(two_m) * float(two_m))
+
+
+def louvain_precluster_ref(pairs, n):
+    """(depth_0, depth_1) as PreCluster(method='louvain') computes them: Louvain of the graph, the pooled graph
+    (distinct {c0[u], c0[v]} with c0[u] != c0[v]), Louvain of that."""
+    d0 = louvain(pairs, n)[0]
+    pooled = {(d0[int(u)], d0[int(v)]) for u, v in pairs if d0[int(u)] != d0[int(v)]}
+    d1 = louvain(sorted(pooled), max(d0) + 1 if n else 0)[0]
+    return d0, d1
+
+
+# ---- inputs shared by tests/test_louvain.py and tests/test_gpu_louvain.py -----------------------------------
+def fixture_pairs():
+    """[(name, pairs [E,2] both directions, n)] of the 10 internal-contact graphs of the committed fixture."""
+    import os
+    import numpy as np
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fixture_1ATN.npz"))
+    out = []
+    for mol in (str(m) for m in z["__mols__"]):
+        p = z[mol + "/internal_edge_index"]
+        out.append((mol, np.vstack((p, p[:, ::-1])), z[mol + "/node_data/pos"].shape[0]))
+    return out
+
+
+def clique_ring(n_cliques=6, size=5):
+    pairs = [(c * size + i, c * size + j) for c in range(n_cliques) for i in range(size) for j in range(i + 1, size)]
+    pairs += [(c * size, ((c + 1) % n_cliques) * size + 1) for c in range(n_cliques)]
+    return pairs, n_cliques * size
+
+
+def special_cases():
+    """[(name, pairs, n)]: the reference's toy graph and the edge cases of the edge-list format."""
+    import numpy as np
+    toy = [(0, 1), (1, 0), (1, 2), (2, 1), (3, 4), (4, 3), (4, 5), (5, 4)]
+    fx = fixture_pairs()[0]
+    one_way = fx[1][: len(fx[1]) // 2]
+    return [
+        ("toy6", toy, 6),
+        ("edgeless", [], 5),
+        ("single_node", [], 1),
+        ("isolated_nodes", [(0, 1), (1, 2), (2, 0), (3, 4), (4, 2)], 9),
+        ("one_direction", one_way, fx[2]),
+        ("duplicated", np.vstack((one_way, one_way[::-1], one_way[:, ::-1])), fx[2]),
+        ("self_loop", [(0, 0), (0, 1), (1, 2), (2, 0), (3, 3), (3, 4), (4, 5), (5, 3), (2, 3), (0, 0)], 6),
+        ("K8", [(i, j) for i in range(8) for j in range(8) if i != j], 8),
+        ("clique_ring", ) + clique_ring(),
+        ("star200", [(0, i) for i in range(1, 201)], 201),
+    ]
+
+
+def limit_graph(n=1024, n_pairs=4096, seed=7):
+    """(pairs, n): n_pairs distinct random pairs on n nodes, mostly inside blocks of 64, listed in both directions
+    as internal_edge_index lists them (1 024 / 4 096: the size the kernel's 160 KiB carve must take)."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    pairs = set()
+    while len(pairs) < n_pairs:
+        u, v = (int(x) for x in rng.integers(0, n, size=2))
+        if u != v and (u // 64 == v // 64 or rng.random() < 0.1):
+            pairs.add((min(u, v), max(u, v)))
+    one = sorted(pairs)
+    return one + [(v, u) for u, v in one], n
+
+
+def synthetic_pairs(count, **kw):
+    """[(name, pairs, n)] of the internal graphs of synthetic.make_graph(0..count-1, **kw)."""
+    import deeprank_gnn_amd.synthetic as synth
+    out = []
+    for i in range(count):
+        g = synth.make_graph(i, **kw)
+        out.append(("syn%d" % i, g.internal_edge_index.t().numpy(), g.num_nodes))
+    return out
+
+
+def batch_of(cases):
+    """One block-diagonal edge list of [(name, pairs, n)]: (edge_index int64 [2,E], node_ptr, edge_ptr int32 [B+1])."""
+    import numpy as np
+    import torch
+    rows, nptr, eptr = [], [0], [0]
+    for _, pairs, n in cases:
+        p = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        rows.append(p + nptr[-1])
+        nptr.append(nptr[-1] + n)
+        eptr.append(eptr[-1] + len(p))
+    ei = torch.from_numpy(np.concatenate(rows).T.copy()) if rows else torch.zeros((2, 0), dtype=torch.int64)
+    return ei, torch.tensor(nptr, dtype=torch.int32), torch.tensor(eptr, dtype=torch.int32)
