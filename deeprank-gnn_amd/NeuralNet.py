@@ -8,8 +8,10 @@ without torch_geometric / h5py: same constructor vocabulary, ``train`` / ``eval`
 list of paths (.drgs native container, .npz, or .hdf5 where h5py exists).  The per-epoch export keeps the reference's
 group / dataset names (``epoch_%04d/{train,eval,test}/{mol,outputs,targets,raw_outputs}`` + the attributes task /
 target / batch_size, NeuralNet.py:827-872) in the native container; ``tools/native_to_hdf5.py`` turns it into the HDF5
-file the reference writes.  What is NOT reproduced: python-louvain's random visiting order, ``Metrics`` beyond the accuracy,
-plots.
+file the reference writes.  ``get_metrics`` returns the reference's ``Metrics`` (metrics.py, computed on the device) of the
+last train / eval / test pass; ``train_out`` / ``train_y`` / ``valid_out`` / ``valid_y`` / ``test_out`` / ``test_y`` read
+that pass's outputs and targets (numpy arrays: class indices for classification).  What is NOT reproduced:
+python-louvain's random visiting order, plots.
 """
 import os
 import time
@@ -363,6 +365,43 @@ class NeuralNet(object):
         if self.target in ('fnat', 'bin_class'):
             return float(np.mean((o > thr) == (t > thr)))
         return float(np.mean((o < thr) == (t < thr)))
+
+    _PASSES = {'train': 'No training set has been provided', 'eval': 'No evaluation set has been provided',
+               'test': 'No test set has been provided'}
+
+    def _pass_arrays(self, data):
+        """(outputs, targets) of the last pass of kind ``data`` ('train' / 'eval' / 'test'): numpy arrays in the space
+        _accuracy reads (class indices for classification), targets None without them; ([], None) without that pass."""
+        store = getattr(self, 'data', {}).get(data)
+        arrays = getattr(store, 'arrays', None)
+        if arrays is None:
+            return [], None
+        return arrays
+
+    train_out = property(lambda self: self._pass_arrays('train')[0], doc="outputs of the last training pass")
+    train_y = property(lambda self: self._pass_arrays('train')[1], doc="targets of the last training pass")
+    valid_out = property(lambda self: self._pass_arrays('eval')[0], doc="outputs of the last validation pass")
+    valid_y = property(lambda self: self._pass_arrays('eval')[1], doc="targets of the last validation pass")
+    test_out = property(lambda self: self._pass_arrays('test')[0], doc="outputs of the last test pass")
+    test_y = property(lambda self: self._pass_arrays('test')[1], doc="targets of the last test pass (None without)")
+
+    def get_metrics(self, data='eval', threshold=4.0, binary=True):
+        """NeuralNet.get_metrics (NeuralNet.py:539-579): the ``Metrics`` of the last ``data`` pass ('eval', 'train' or
+        'test') at ``threshold`` (a class label for classification: mapped to its class index), on the device.
+        Prints the reference's message and raises ``ValueError`` when that pass, or its targets, is missing."""
+        if data not in self._PASSES:
+            raise ValueError("data must be 'eval', 'train' or 'test', not %r" % (data,))
+        if self.task == 'class':
+            threshold = self.classes_to_idx[threshold]
+        out, y = self._pass_arrays(data)
+        if len(out) == 0:
+            print(self._PASSES[data])
+            raise ValueError("get_metrics(%r): there is no %s pass to score" % (data, data))
+        if y is None:
+            print('You must provide ground truth target values to compute the metrics')
+            raise ValueError("get_metrics(%r): the %s pass has no target values" % (data, data))
+        from .metrics import Metrics
+        return Metrics(out, y, self.target, threshold, binary, api=self._api)
 
     @staticmethod
     def _new_store():

@@ -67,6 +67,7 @@ class TopologyRequest(ctypes.Structure):
 TOPO_HIER = 1          # drgnn_topology_request.flags: also build the hierarchical node order (HORD / HMP0 / HSPLIT)
 TOPO_LEAN = 2          # ... and ONLY what the aggregation-first training kernels read (no CSC0, no depth-0 member lists)
 TOPO_TILES = 4         # ... and the level-0 neighbour aggregation of every node (drgnn_topology_request.x / tiles)
+METRICS_COUNTS, METRICS_REGRESSION, METRICS_RANKING = 1, 2, 4     # drgnn_metrics: what to compute
 
 
 class GraphSet(ctypes.Structure):
@@ -225,6 +226,10 @@ class Api(object):
         lib.drgnn_graclus.argtypes = [_vp, _c_i64, _c_i64, _c_i64, _c_i32, _c_i32, _vp, _vp, _vp, _vp]
         lib.drgnn_mcl.argtypes = [_vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp]
         lib.drgnn_louvain.argtypes = [_vp, _c_i64, _vp, _vp, _c_i64, _c_i32, _c_i32, _vp, _vp, _vp, _vp]
+        lib.drgnn_metrics_workspace_bytes.argtypes = [_c_i64]
+        lib.drgnn_metrics_workspace_bytes.restype = _c_i64
+        lib.drgnn_metrics.argtypes = [_vp, _vp, _c_i64, _c_i32, _c_i32, ctypes.c_double, _c_i32, _c_i32, _vp, _c_i64,
+                                      _vp, _vp, _vp, _vp, _vp]
         lib.drgnn_p2p_bytes.argtypes = [_c_i64]
         lib.drgnn_p2p_bytes.restype = _c_i64
         lib.drgnn_p2p_alloc.argtypes = [_c_i64, ctypes.POINTER(_vp), _vp]
@@ -465,6 +470,15 @@ class Api(object):
                 modularity, stream):
         _check(self.lib.drgnn_louvain(_ptr(edge_index), n_edges, _ptr(node_ptr), _ptr(edge_ptr), n_graphs, max_nodes,
                                       max_edges, _ptr(labels), _ptr(info), _ptr(modularity), stream), "drgnn_louvain")
+
+    def metrics_workspace_bytes(self, n):
+        return int(self.lib.drgnn_metrics_workspace_bytes(n))
+
+    def metrics(self, pred, y, n, what, direction, threshold, label_lo, n_labels, workspace, counts, scores, order, hits,
+                stream):
+        _check(self.lib.drgnn_metrics(_ptr(pred), _ptr(y), n, what, direction, float(threshold), label_lo, n_labels,
+                                      _ptr(workspace), workspace.numel() * workspace.element_size(), _ptr(counts),
+                                      _ptr(scores), _ptr(order), _ptr(hits), stream), "drgnn_metrics")
 
     def collate(self, gset, ids, n_graphs, n_nodes, n_edges, x, edge_index, edge_attr, batch, cluster0, cluster1,
                 y, node_ptr, edge_ptr, c1_ptr, stream):

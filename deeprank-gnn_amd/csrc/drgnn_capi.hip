@@ -8,6 +8,7 @@
 #include "drgnn_kernels.h"
 
 #include <vector>
+#include <memory>
 #include <string.h>
 #include <stdlib.h>
 #ifdef DRGNN_EMU
@@ -1715,6 +1716,120 @@ int drgnn_louvain(const int64_t* edge_index, int64_t n_edges, const int32_t* nod
         HIP_TRY(hipFuncSetAttribute((const void*)k_louvain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(words * 4)));
     hipLaunchKernelGGL(k_louvain, dim3((unsigned)n_graphs), dim3(LV_W), (size_t)(words * 4), (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
+#endif
+    return 0;
+}
+
+// ---- evaluation scores (drgnn_metrics.h) ---------------------------------------------------------
+int64_t drgnn_metrics_workspace_bytes(int64_t n) {
+    if (n < 0 || n > INT32_MAX) return -1;
+    int64_t off[9];
+    mt_layout(n, off);
+    return off[8];
+}
+
+#ifdef DRGNN_EMU
+// a launch of the emulation: workgroups one after another
+#define MT_GRID(nblocks, body) do { for (int blk = 0; blk < (int)(nblocks); ++blk) { body; } } while (0)
+#else
+#define MT_LAUNCH(kernel, nblocks, nthreads, ...)                                                              \
+    do {                                                                                                       \
+        hipLaunchKernelGGL(kernel, dim3((unsigned)(nblocks)), dim3(nthreads), 0, st, __VA_ARGS__);             \
+        HIP_TRY(hipGetLastError());                                                                            \
+    } while (0)
+#endif
+
+// stable ascending LSD sort of a.keys[0] (payload a.vals[0] when set): MT_PASSES digits, the result back in buffer 0
+static int mt_sort(MetricsArgs& a, void* stream) {
+#ifdef DRGNN_EMU
+    (void)stream;
+    std::unique_ptr<MtHistShared> hs(new MtHistShared);
+    std::unique_ptr<MtScanShared> ss(new MtScanShared);
+    std::unique_ptr<MtScatterShared> xs(new MtScatterShared);
+    for (int pass = 0; pass < MT_PASSES; ++pass) {
+        MT_GRID(a.n_tiles, mt_hist_block(a, blk, pass, *hs));
+        mt_exscan_block<int32_t>(a.hist, (int64_t)MT_RADIX * a.n_tiles, *ss);
+        MT_GRID(a.n_tiles, mt_scatter_block(a, blk, pass, *xs));
+    }
+#else
+    hipStream_t st = (hipStream_t)stream;
+    for (int pass = 0; pass < MT_PASSES; ++pass) {
+        MT_LAUNCH(k_mt_hist, a.n_tiles, MT_NT, a, pass);
+        MT_LAUNCH(k_mt_scan, 1, MT_SNT, a);
+        MT_LAUNCH(k_mt_scatter, a.n_tiles, MT_NT, a, pass);
+    }
+#endif
+    return 0;
+}
+
+int drgnn_metrics(const double* pred, const double* y, int64_t n, int32_t what, int32_t direction, double threshold,
+                  int32_t label_lo, int32_t n_labels, void* workspace, int64_t workspace_bytes, int64_t* counts,
+                  double* scores, int32_t* order, int64_t* hits, void* stream) {
+    if (n < 1 || n > INT32_MAX || !pred || !y || !workspace || !counts || !scores) return DRGNN_E_ARG;
+    if ((what & ~(DRGNN_METRICS_COUNTS | DRGNN_METRICS_REGRESSION | DRGNN_METRICS_RANKING)) != 0) return DRGNN_E_ARG;
+    if ((direction != 1 && direction != -1) || n_labels < 0 || n_labels > MT_KMAX) return DRGNN_E_ARG;
+    if ((what & DRGNN_METRICS_RANKING) && (!order || !hits)) return DRGNN_E_ARG;
+    if (workspace_bytes < drgnn_metrics_workspace_bytes(n)) return DRGNN_E_CAPACITY;
+    if (n_labels > 0 && (label_lo < -(1 << 20) || label_lo > (1 << 20))) return DRGNN_E_ARG;
+    int64_t off[9];
+    mt_layout(n, off);
+    char* ws = (char*)workspace;
+    MetricsArgs a;
+    a.pred = pred; a.y = y; a.n = n; a.thr = threshold; a.dir = direction; a.lo = label_lo; a.K = n_labels;
+    a.G = (int)((n + 8 * MT_NT - 1) / (8 * MT_NT));
+    if (a.G > MT_RED_WGS) a.G = MT_RED_WGS;
+    a.n_tiles = (int)mt_tiles(n);
+    a.keys[0] = (unsigned long long*)(ws + off[0]); a.keys[1] = (unsigned long long*)(ws + off[1]);
+    a.vals[0] = order; a.vals[1] = (int32_t*)(ws + off[2]);
+    a.hist = (int32_t*)(ws + off[3]);
+    a.fpart = (double*)(ws + off[4]); a.ipart = (long long*)(ws + off[5]);
+    a.tsum = (long long*)(ws + off[6]); a.ssum = (long long*)(ws + off[7]);
+    a.counts = (long long*)counts; a.scores = scores; a.hits = (long long*)hits;
+    MetricsArgs r = a;                  // the |r| sort: keys only
+    r.vals[0] = r.vals[1] = nullptr;
+#ifdef DRGNN_EMU
+    std::unique_ptr<MtRedShared> rs(new MtRedShared);
+    std::unique_ptr<MtScanShared> ss(new MtScanShared);
+    std::unique_ptr<MtHitShared> hs(new MtHitShared);
+    if (what & (DRGNN_METRICS_COUNTS | DRGNN_METRICS_REGRESSION)) {
+        MT_GRID(a.G, mt_reduce_block(a, blk, 0, *rs));
+        mt_combine_block(a, 0);
+    }
+    if (what & DRGNN_METRICS_REGRESSION) {
+        MT_GRID(a.G, mt_reduce_block(a, blk, 1, *rs));
+        mt_combine_block(a, 1);
+        MT_GRID(a.n_tiles, mt_keys_block(r, blk, 1));
+        mt_sort(r, stream);
+        mt_median(r);
+    }
+    if (what & DRGNN_METRICS_RANKING) {
+        MT_GRID(a.n_tiles, mt_keys_block(a, blk, 0));
+        mt_sort(a, stream);
+        MT_GRID(a.n_tiles, mt_hit_block(a, blk, 0, *hs));
+        mt_hit_scan_block(a, *ss);
+        MT_GRID(a.n_tiles, mt_hit_block(a, blk, 1, *hs));
+    }
+#else
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if (what & (DRGNN_METRICS_COUNTS | DRGNN_METRICS_REGRESSION)) {
+        MT_LAUNCH(k_mt_reduce, a.G, MT_NT, a, 0);
+        MT_LAUNCH(k_mt_combine, 1, MT_NT, a, 0);
+    }
+    if (what & DRGNN_METRICS_REGRESSION) {
+        MT_LAUNCH(k_mt_reduce, a.G, MT_NT, a, 1);
+        MT_LAUNCH(k_mt_combine, 1, MT_NT, a, 1);
+        MT_LAUNCH(k_mt_keys, a.n_tiles, MT_NT, r, 1);
+        if ((rc = mt_sort(r, stream))) return rc;
+        MT_LAUNCH(k_mt_median, 1, 64, r);
+    }
+    if (what & DRGNN_METRICS_RANKING) {
+        MT_LAUNCH(k_mt_keys, a.n_tiles, MT_NT, a, 0);
+        if ((rc = mt_sort(a, stream))) return rc;
+        MT_LAUNCH(k_mt_hit, a.n_tiles, MT_NT, a, 0);
+        MT_LAUNCH(k_mt_hit_scan, 1, MT_SNT, a);
+        MT_LAUNCH(k_mt_hit, a.n_tiles, MT_NT, a, 1);
+    }
 #endif
     return 0;
 }

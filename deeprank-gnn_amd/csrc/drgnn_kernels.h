@@ -12,6 +12,7 @@
 #include "drgnn_layers.h"
 #include "drgnn_mcl.h"
 #include "drgnn_louvain.h"
+#include "drgnn_metrics.h"
 #include "drgnn_collate.h"
 #include "drgnn_p2p.h"
 
@@ -957,6 +958,36 @@ __global__ void __launch_bounds__(DRGNN_NTHREADS) k_mcl(MclArgs a) {
 __global__ void __launch_bounds__(LV_W) k_louvain(LouvainArgs a) {
     extern __shared__ __attribute__((aligned(16))) int smem_lv[];
     louvain_graph(a, blockIdx.x, smem_lv);
+}
+// evaluation scores (drgnn_metrics.h)
+__global__ void __launch_bounds__(MT_NT) k_mt_reduce(MetricsArgs a, int centred) {
+    __shared__ MtRedShared s;
+    mt_reduce_block(a, blockIdx.x, centred, s);
+}
+__global__ void __launch_bounds__(MT_NT) k_mt_combine(MetricsArgs a, int centred) { mt_combine_block(a, centred); }
+__global__ void __launch_bounds__(MT_NT) k_mt_keys(MetricsArgs a, int absres) { mt_keys_block(a, blockIdx.x, absres); }
+__global__ void __launch_bounds__(MT_NT) k_mt_hist(MetricsArgs a, int pass) {
+    __shared__ MtHistShared s;
+    mt_hist_block(a, blockIdx.x, pass, s);
+}
+__global__ void __launch_bounds__(MT_SNT) k_mt_scan(MetricsArgs a) {
+    __shared__ MtScanShared s;
+    mt_exscan_block<int32_t>(a.hist, (int64_t)MT_RADIX * a.n_tiles, s);
+}
+__global__ void __launch_bounds__(MT_NT) k_mt_scatter(MetricsArgs a, int pass) {
+    __shared__ MtScatterShared s;
+    mt_scatter_block(a, blockIdx.x, pass, s);
+}
+__global__ void __launch_bounds__(64) k_mt_median(MetricsArgs a) {
+    if (threadIdx.x == 0) mt_median(a);
+}
+__global__ void __launch_bounds__(MT_NT) k_mt_hit(MetricsArgs a, int write) {
+    __shared__ MtHitShared s;
+    mt_hit_block(a, blockIdx.x, write, s);
+}
+__global__ void __launch_bounds__(MT_SNT) k_mt_hit_scan(MetricsArgs a) {
+    __shared__ MtScanShared s;
+    mt_hit_scan_block(a, s);
 }
 __global__ void __launch_bounds__(DRGNN_NTHREADS) k_graclus(GraclusArgs a) {
     extern __shared__ __attribute__((aligned(16))) int smem_g[];

@@ -611,6 +611,31 @@ int drgnn_louvain(const int64_t* edge_index, int64_t n_edges, const int32_t* nod
                   int64_t n_graphs, int32_t max_nodes, int32_t max_edges, int64_t* labels, int32_t* info,
                   double* modularity, void* stream);
 
+/* Evaluation scores of n predictions against their targets: the reference's Metrics (Metrics.py) and the ranking its
+ * hitrate() / auc() read.  pred, y: float64 [n] on the device, 1 <= n <= 2^31 - 1.  `what` is a mask:
+ *   DRGNN_METRICS_COUNTS      confusion counts (sklearn confusion_matrix(y, pred, labels)) and the first-read sums;
+ *   DRGNN_METRICS_REGRESSION  also the second read (centred sums) and the median of |y - pred| (a stable sort);
+ *   DRGNN_METRICS_RANKING     stable ascending argsort of pred into order int32 [n] (ties in index order, -0 == +0,
+ *                             NaN last, as np.argsort(kind='stable')), reversed when direction = +1, and hits int64 [n]
+ *                             = cumsum of gt[idx] along that ranking, gt = y binarised.
+ * direction +1: 1 means x > threshold (fnat, bin_class); -1: 1 means x < threshold.  n_labels = 0: both vectors are
+ * binarised that way (labels {0, 1}); n_labels = K in 1..8: labels label_lo .. label_lo + K - 1 as given, a value that is
+ * not one of them is left out of the counts.
+ * counts int64 [8 + 64]: [0] pairs with a non-finite value, [1] pairs with a finite non-integral value, [2] y values
+ * among the labels, [3] P = number of gt == 1, [4] S = sum over i with gt[i] == 1 of idx[i] (the reference's AUC ranks
+ * the argsort indices: AUC = (S + P - P(P + 1) / 2) / (P N)), [8 + K a + b] samples with y label a and pred label b.
+ * scores float64 [16]: min y, min pred, sum y, sum r, sum |r|, sum r^2, max |r|, sum (log1p y - log1p pred)^2 (r = y -
+ * pred), sum (y - ybar)^2, sum (r - rbar)^2, median |r|.  Sums combine per-workgroup partials in a fixed order; there are
+ * no floating-point atomics, so the results repeat bit for bit.  workspace: drgnn_metrics_workspace_bytes(n) bytes
+ * (about 20 n + 1 KiB per 4 096 samples).  No allocation, no synchronisation. */
+#define DRGNN_METRICS_COUNTS     1
+#define DRGNN_METRICS_REGRESSION 2
+#define DRGNN_METRICS_RANKING    4
+int64_t drgnn_metrics_workspace_bytes(int64_t n);
+int drgnn_metrics(const double* pred, const double* y, int64_t n, int32_t what, int32_t direction, double threshold,
+                  int32_t label_lo, int32_t n_labels, void* workspace, int64_t workspace_bytes, int64_t* counts,
+                  double* scores, int32_t* order, int64_t* hits, void* stream);
+
 /* ---- device-resident graph set and mini-batch assembly --------------------
  * Replaces the host collate of every mini-batch: torch_geometric DataLoader -> Batch.from_data_list over
  * HDF5DataSet.load_one_graph's Data objects (NeuralNet.py:153-154, DataSet.py:231-366).  The set is the
