@@ -80,8 +80,11 @@ class StepEngine(object):
         self.convs = convs
         named = list(net.named_parameters())
         self.names = [n for n, _ in named]
-        owner, _, self.first_name = self.names[0].rpartition(".")
-        self._first_owner = weakref.proxy(net.get_submodule(owner) if owner else net)
+        # what engine_for compares before every call: the identity of every child module and every parameter that each module
+        # of the net holds, as (slot dict, name, object), and the size of every slot dict (a module or parameter added)
+        dicts = [d for m in net.modules() for d in (m._modules, m._parameters)]
+        self._slots = tuple((d, name, obj) for d in dicts for name, obj in d.items())
+        self._slot_sizes = tuple((d, len(d)) for d in dicts)
         self.params = [p for _, p in named]
         dev = self.params[0].device
         self.device = dev
@@ -445,12 +448,21 @@ class StepEngine(object):
 
 
 def engine_for(net):
-    """The net's engine (created on first use; rebuilt when parameters were replaced or moved to another device).  The check
-    is two identity tests, not a walk over the module tree: this runs in front of every ``model(batch)``."""
+    """The net's engine (created on first use; rebuilt when a parameter or a submodule anywhere in the net was replaced, or the
+    net moved to another device).  The check compares the recorded (module, child) and (module, parameter) slots by identity,
+    flat tuples rather than a walk over the module tree (named_parameters): this runs in front of every ``model(batch)``.
+    About 4 us per call for GINet (19 modules, 16 parameters), 2 us for sGAT / FoutNet, on the host."""
     eng = net.__dict__.get("_drgnn_engine")
-    if eng is not None:
-        first, last = eng.params[0], eng.params[-1]
-        if net.fc2.bias is last and eng._first_owner._parameters.get(eng.first_name) is first and first.device == eng.device:
-            return eng
+    # (the first slot dict is the net's own _modules)
+    if eng is not None and eng.params[0].device == eng.device and net._modules is eng._slot_sizes[0][0]:
+        for d, name, obj in eng._slots:
+            if d.get(name) is not obj:
+                break
+        else:
+            for d, n in eng._slot_sizes:
+                if len(d) != n:
+                    break
+            else:
+                return eng
     eng = net.__dict__["_drgnn_engine"] = StepEngine(net)
     return eng

@@ -222,15 +222,28 @@ def _as_ns(data):
     return ns
 
 
-def _branch(data, conv1, conv2, trace, tag):
+def _nudged(z, nudge, site):
+    """``z`` with ``nudge[site] = (flat indices, additive deltas)`` added, or ``z`` itself (the same tensor object, so no
+    arithmetic changes) when the site is not nudged.  A nudge is a constant: d out / d z is unchanged, only the decisions of
+    the ReLU and of the max-pool that read ``z`` can move (tests/elementwise.py: check_step_kinks)."""
+    if not nudge or site not in nudge:
+        return z
+    idx, delta = nudge[site]
+    idx = torch.as_tensor(idx, dtype=torch.long).reshape(-1)
+    delta = torch.as_tensor(delta, dtype=z.dtype).reshape(-1)
+    return z.reshape(-1).index_add(0, idx, delta).view_as(z)
+
+
+def _branch(data, conv1, conv2, trace, tag, nudge=None):
     """conv -> relu -> community_pooling -> conv -> relu -> max_pool_x
-    (reference ginet.py:103-114, sGAT.py:119-130, foutnet.py:108-117)."""
-    z1 = conv1(data.x, data.edge_index, data.edge_attr)
+    (reference ginet.py:103-114, sGAT.py:119-130, foutnet.py:108-117).  ``nudge``: see ``_nudged``; sites
+    ``tag + "z1"`` and ``tag + "z2"``."""
+    z1 = _nudged(conv1(data.x, data.edge_index, data.edge_attr), nudge, tag + "z1")
     data.x = F.relu(z1)
     cl0 = get_preloaded_cluster(data.cluster0, data.batch)
     pooled = community_pooling(cl0, data)
     xp = pooled.x
-    z2 = conv2(xp, pooled.edge_index, pooled.edge_attr)
+    z2 = _nudged(conv2(xp, pooled.edge_index, pooled.edge_attr), nudge, tag + "z2")
     pooled.x = F.relu(z2)
     cl1 = get_preloaded_cluster(pooled.cluster1, pooled.batch)
     x2, batch2 = max_pool_x(cl1, pooled.x, pooled.batch)
@@ -249,7 +262,15 @@ def _branch(data, conv1, conv2, trace, tag):
     return x2, batch2
 
 
-def ginet_forward(params, data, dropout=0.0, training=False, trace=None, drop_mask=None):
+def _head_hidden(feat, params, trace, nudge):
+    """relu(fc1(feat)); the pre-activation is traced as ``hid`` and is nudge site ``"hid"``."""
+    pre = _nudged(F.linear(feat, params["fc1.weight"], params["fc1.bias"]), nudge, "hid")
+    if trace is not None:
+        trace["hid"] = pre
+    return F.relu(pre)
+
+
+def ginet_forward(params, data, dropout=0.0, training=False, trace=None, drop_mask=None, nudge=None):
     """reference ginet.py:99-141 (GINet.forward).  ``params`` maps state_dict names to
     tensors.  The second branch convolves over the SAME edge_index.
     ``drop_mask`` ([B, 128] of 0 / 1): F.dropout's arithmetic (ginet.py:138) with the Bernoulli
@@ -260,14 +281,14 @@ def ginet_forward(params, data, dropout=0.0, training=False, trace=None, drop_ma
                                             params[prefix + ".fc_edge_attr.weight"],
                                             params[prefix + ".fc_attention.weight"])
     d_a, d_b = _as_ns(data), _as_ns(data)
-    xa, ba = _branch(d_a, conv("conv1"), conv("conv2"), trace, "a.")
-    xb, bb = _branch(d_b, conv("conv1_ext"), conv("conv2_ext"), trace, "b.")
+    xa, ba = _branch(d_a, conv("conv1"), conv("conv2"), trace, "a.", nudge)
+    xb, bb = _branch(d_b, conv("conv1_ext"), conv("conv2_ext"), trace, "b.", nudge)
     ra = scatter_mean(xa, ba)
     rb = scatter_mean(xb, bb)
     feat = torch.cat([ra, rb], dim=1)
     if trace is not None:
         trace["readout"] = feat
-    hid = F.relu(F.linear(feat, params["fc1.weight"], params["fc1.bias"]))
+    hid = _head_hidden(feat, params, trace, nudge)
     if drop_mask is not None:
         hid = hid * drop_mask.to(hid.dtype) / (1.0 - dropout)
     else:
@@ -275,33 +296,33 @@ def ginet_forward(params, data, dropout=0.0, training=False, trace=None, drop_ma
     return F.linear(hid, params["fc2.weight"], params["fc2.bias"])
 
 
-def sgat_forward(params, data, trace=None):
+def sgat_forward(params, data, trace=None, nudge=None):
     """reference sGAT.py:114-138 (sGAT.forward); act = relu (the Tanhshrink on :116 is
     overwritten on :117)."""
     def conv(prefix):
         return lambda x, ei, ea: sgat_conv(x, ei, ea, params[prefix + ".weight"],
                                            params[prefix + ".bias"])
     d = _as_ns(data)
-    x2, b2 = _branch(d, conv("conv1"), conv("conv2"), trace, "a.")
+    x2, b2 = _branch(d, conv("conv1"), conv("conv2"), trace, "a.", nudge)
     feat = scatter_mean(x2, b2)
     if trace is not None:
         trace["readout"] = feat
-    hid = F.relu(F.linear(feat, params["fc1.weight"], params["fc1.bias"]))
+    hid = _head_hidden(feat, params, trace, nudge)
     return F.linear(hid, params["fc2.weight"], params["fc2.bias"])
 
 
-def fout_forward(params, data, looped=True, trace=None):
+def fout_forward(params, data, looped=True, trace=None, nudge=None):
     """reference foutnet.py:103-125 (FoutNet.forward)."""
     def conv(prefix):
         return lambda x, ei, ea: fout_conv(x, ei, params[prefix + ".Wc"],
                                            params[prefix + ".Wn"], params[prefix + ".bias"],
                                            looped=looped)
     d = _as_ns(data)
-    x2, b2 = _branch(d, conv("conv1"), conv("conv2"), trace, "a.")
+    x2, b2 = _branch(d, conv("conv1"), conv("conv2"), trace, "a.", nudge)
     feat = scatter_mean(x2, b2)
     if trace is not None:
         trace["readout"] = feat
-    hid = F.relu(F.linear(feat, params["fc1.weight"], params["fc1.bias"]))
+    hid = _head_hidden(feat, params, trace, nudge)
     return F.linear(hid, params["fc2.weight"], params["fc2.bias"])
 
 
@@ -358,7 +379,7 @@ def init_params(net, n_feat, n_out=1, n_edge_feat=1, seed=0):
 def loss_and_grads(net, params, data, target, task="reg", **fw):
     """One training-step worth of math on CPU: forward, loss (MSE for regression,
     cross-entropy for classification: reference NeuralNet.py:239-263), backward.
-    Returns (pred, loss, {name: grad})."""
+    Returns (pred, loss, {name: grad}).  ``fw`` goes to the forward (``trace``, ``nudge``, ``looped``, ...)."""
     leaves = {k: v.detach().clone().requires_grad_(True) for k, v in params.items()}
     pred = FORWARD[net](leaves, data, **fw)
     if task == "reg":

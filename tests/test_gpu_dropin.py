@@ -446,6 +446,76 @@ def test_eval_mode_with_gradients_and_parameter_surgery():
     assert _engine(net).last_path == "inference"
 
 
+SWAPS = [("GINet", "fc1"), ("GINet", "conv2.fc.weight"), ("GINet", "conv1_ext"), ("sGAT", "conv2.weight"), ("FoutNet", "conv2.Wn")]
+
+
+def _swap(net, what, dev):
+    """Replaces the module or parameter ``what`` of ``net`` by a new one (values drawn on the CPU from a fixed seed, then moved
+    to ``dev``); returns the new parameter objects."""
+    gen = torch.Generator().manual_seed(8)
+    owner, _, name = what.rpartition(".")
+    owner = net.get_submodule(owner) if owner else net
+    old = getattr(owner, name)
+    if isinstance(old, torch.nn.Parameter):
+        bound = 1.0 / np.sqrt(old.shape[-1])
+        new = torch.nn.Parameter(((torch.rand(old.shape, generator=gen) * 2.0 - 1.0) * bound).to(dev))
+        setattr(owner, name, new)
+        return [new]
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(8)
+        layer = copy.deepcopy(old).to("cpu")
+        for p in layer.parameters():
+            with torch.no_grad():
+                p.uniform_(-0.5, 0.5)
+    layer = layer.to(dev)
+    setattr(owner, name, layer)
+    return list(layer.parameters())
+
+
+def _name_of(net, param):
+    return next(n for n, p in net.named_parameters() if p is param)
+
+
+@pytest.mark.parametrize("net_name,what", SWAPS)
+def test_replaced_parameter_or_layer_is_trained(net_name, what):
+    """A parameter or a layer replaced anywhere in the net -- the fine-tuning head swap net.fc1 = nn.Linear(...), a
+    re-initialised weight, a new conv layer -- is what the next step reads AND differentiates: a new engine, a .grad on every
+    parameter (the new ones included) that matches the oracle at the new parameters, and an optimiser step that moves the new
+    parameters.  (Before, the engine was kept when only an interior parameter changed, and the new ones never got a .grad.)"""
+    import deeprank_gnn_amd.synthetic as synth
+    from oracle import cpu_ref
+    dev = _dev()
+    batch_cpu = synth.make_batch(0, 16)
+    batch = batch_cpu.clone().to(dev)
+    net = _build(net_name, cpu_ref.init_params(net_name, 32, 1, 1, seed=1), 1)     # (seed 1: no decision within 5.9e-6 of its switch)
+    net.train()
+    F.mse_loss(net(batch).reshape(-1), batch.y).backward()
+    eng = _engine(net)
+    assert eng.last_path == "jacobian"
+    new = _swap(net, what, dev)
+    net.zero_grad(set_to_none=True)
+    out = net(batch)
+    assert _engine(net) is not eng and _engine(net).last_path == "jacobian", _engine(net).last_reason
+    loss = F.mse_loss(out.reshape(-1), batch.y)
+    loss.backward()
+    torch.cuda.synchronize()
+    grads = {}
+    for name, p in net.named_parameters():
+        assert p.grad is not None, name
+        grads[name] = p.grad.cpu().numpy()
+    params = {k: v.detach().cpu() for k, v in net.state_dict().items()}
+    ref_pred, ref_loss, ref_grads = cpu_ref.loss_and_grads(net_name, params, batch_cpu, batch_cpu.y, **_fw(net_name))
+    check_step("%s, %s replaced" % (net_name, what), Lazy64(net_name, params, batch_cpu, **_fw(net_name)), loss.item(),
+               out.detach().cpu().numpy(), grads, ref_loss, ref_pred.numpy(), {k: v.numpy() for k, v in ref_grads.items()})
+    # (a new GINet layer's attention weights are dead: their gradient is identically zero, as check_step just asserted)
+    live = [p for p in new if float(ref_grads[_name_of(net, p)].abs().max()) > 0.0]
+    assert live
+    before = [p.detach().clone() for p in live]
+    torch.optim.SGD(net.parameters(), lr=0.1).step()
+    for p, b in zip(live, before):
+        assert not torch.equal(p.detach(), b), _name_of(net, p)
+
+
 def test_classification_loop_recorded_in_a_graph():
     """GINet, two classes, dropout 0.4, CrossEntropyLoss + Adam: the two-launch form of the boundary (forward-only launch with the
     step's mask, training launch fed d loss / d pred) recorded in a hipGraph -- replays equal the eager steps (same mask stream:
