@@ -550,6 +550,56 @@ static int net_backward_impl(const drgnn_net_desc* net, const float* x, const fl
 }
 
 }  // extern "C"
+
+#ifdef DRGNN_EMU
+// The host emulation's fused step.  The aggregation-first kernels are SIMT code (MFMA fragments, DPP, lane reads) the
+// emulation cannot execute; it steps the launch with the launch pair's per-graph routines instead -- net_forward_graph for
+// both branches, then net_backward_graph with head_graph inside (inference: head_graph alone) -- and writes what the fused
+// step writes: pred, readout [B, R], one compact head slab per graph (head_graph's slab without its H x R dW_fc1 block), one
+// conv slab per (graph, branch) and Adam's step index step2[1].  Slot g reads graph gather_ids[g] of the workspace in cached
+// mode; xp / argmax, the full head slabs and the targets by slot live in host buffers.
+template <int KIND>
+static void emu_step(const StepArgs& a, bool train, int capN, int capE, int capC) {
+    const HeadFused& hf = a.hf;
+    const int B = a.n_graphs, nb = a.net.n_branch, R = hf.R, H = hf.H, O = hf.O, F = a.net.n_feat;
+    const int64_t P = head_partial_floats(R, H, O), PC = head_compact_floats(R, H, O);
+    std::vector<float> xp((size_t)nb * a.n_nodes * DRGNN_H1), full((size_t)B * P), y_reg(B, 0.0f);
+    std::vector<int32_t> arg0(xp.size()), arg1((size_t)nb * a.n_nodes * DRGNN_H2);
+    std::vector<int64_t> y_cls(B, 0);
+    const int64_t w0 = net_scratch_words(KIND, F, capN, capE, capC, 0), w1 = net_scratch_words(KIND, F, capN, capE, capC, 1);
+    std::vector<float> scratch((size_t)(w0 > w1 ? w0 : w1) + 16), gp(1024 + H + R + 2 * DRGNN_MAX_OUT), dr(DRGNN_H2);
+    auto graph_of = [&](int g) { return a.gather_ids ? a.gather_ids[g] : g; };
+    for (int g = 0; g < B && train; ++g) {      // (head_graph reads the target of slot g; inference: zero targets, loss unused)
+        if (hf.y_reg) y_reg[g] = hf.y_reg[graph_of(g)];
+        if (hf.y_cls) y_cls[g] = hf.y_cls[graph_of(g)];
+    }
+    NetArgs n;
+    n.net = a.net; n.x = a.x; n.tv = a.tv; n.n_nodes = a.n_nodes; n.n_graphs = a.ws_graphs;
+    n.xp = xp.data(); n.arg0 = arg0.data(); n.arg1 = arg1.data(); n.readout = const_cast<float*>(hf.readout);
+    n.grad_readout = nullptr; n.partials = a.partials; n.grad_x = nullptr; n.n_partial = a.n_partial; n.step_inc = nullptr;
+    n.hf = hf;
+    n.hf.y_reg = y_reg.data(); n.hf.y_cls = y_cls.data(); n.hf.partials = full.data(); n.hf.stage = 0;
+    for (int g = 0; g < B; ++g) {
+        const int gi = graph_of(g);
+        const GraphDims d = net_dims(a.tv, gi);
+        if (d.N > capN || d.E > capE || d.C > capC) {      // the caller's bounds were wrong: poisoned outputs, as on the device
+            for (int c = 0; c < R; ++c) n.readout[(long)g * R + c] = DRGNN_NAN;
+            for (int64_t i = 0; i < PC && train; ++i) hf.partials[g * PC + i] = DRGNN_NAN;
+            for (int o = 0; o < O; ++o) hf.pred[(long)g * O + o] = DRGNN_NAN;
+            continue;
+        }
+        for (int br = 0; br < nb; ++br) net_forward_graph<KIND>(n, g, gi, br, scratch.data(), capN, capE, capC);
+        if (!train) {
+            head_graph(n.hf, g, 0, gp.data(), dr.data(), hf.w1, R, hf.b1, hf.w2, hf.b2, hf.readout + (long)g * R);
+            continue;
+        }
+        for (int br = 0; br < nb; ++br) net_backward_graph<KIND>(n, g, gi, br, scratch.data(), capN, capE, capC);
+        memcpy(hf.partials + g * PC, full.data() + g * P + (int64_t)H * R, (size_t)PC * 4);
+    }
+    if (train) a.step2[1] = a.step2[0] + 1;
+}
+#endif
+
 extern "C" {
 
 int drgnn_net_backward(const drgnn_net_desc* net, const float* x, const float* grad_readout,
@@ -631,14 +681,14 @@ static int device_cu_count() {
 static int step_current_device() { int dev = 0; return hipGetDevice(&dev) == hipSuccess ? dev : 0; }
 #endif
 
-// the overrides of a plan (all 0 = automatic).  DRGNN_STEP_PLAN=<one|two|noclass|product|nosplit|seq>[,...] (read once) gives
-// the defaults of a process for launches whose plan overrides nothing: same-box A/B runs of whole programs
-struct StepOverrides { int force_wgs, no_class, no_aggregate, no_split, no_paired; };
+// the overrides of a plan (all 0 = automatic; no_paired is ignored).  DRGNN_STEP_PLAN=<one|two|noclass|product|nosplit>[,...]
+// (read once) gives the defaults of a process for launches whose plan overrides nothing: same-box A/B runs of whole programs
+struct StepOverrides { int force_wgs, no_class, no_aggregate, no_split; };
 static StepOverrides step_env_overrides() {
     static int parsed = 0;
-    static StepOverrides env = {0, 0, 0, 0, 0};
+    static StepOverrides env = {0, 0, 0, 0};
     if (!parsed) {
-        StepOverrides o = {0, 0, 0, 0, 0};
+        StepOverrides o = {0, 0, 0, 0};
         const char* v = getenv("DRGNN_STEP_PLAN");
         if (v) {
             if (strstr(v, "one")) o.force_wgs = 1;
@@ -646,7 +696,6 @@ static StepOverrides step_env_overrides() {
             if (strstr(v, "noclass")) o.no_class = 1;
             if (strstr(v, "product")) o.no_aggregate = 1;
             if (strstr(v, "nosplit")) o.no_split = 1;
-            if (strstr(v, "seq")) o.no_paired = 1;
         }
         env = o;
         parsed = 1;
@@ -660,14 +709,11 @@ static bool step_no_prefetch() {
     return v != 0;
 }
 static StepOverrides step_overrides_of(const drgnn_step_plan* p) {
-    if (p && (p->force_wgs || p->no_class || p->no_aggregate || p->no_split || p->no_paired))
-        return StepOverrides{p->force_wgs, p->no_class, p->no_aggregate, p->no_split, p->no_paired};
+    if (p && (p->force_wgs || p->no_class || p->no_aggregate || p->no_split))
+        return StepOverrides{p->force_wgs, p->no_class, p->no_aggregate, p->no_split};
     return step_env_overrides();
 }
 
-static int64_t step1_lds_bytes_form(int F, int capN, int capE, int capC, int H, int O, int paired) {
-    return 4 * step1_scratch_words(F, capN, capE, capC, H, O, paired);
-}
 // padded feature width of the width-specialised kernels a launch of these bounds may take (16 / 32 / 48 / 64), 0 = generic.
 // x == nullptr: alignment not judged here
 static int step_variant(int kind, const float* x, int F, int capN, int capE, int capC, int H, int O) {
@@ -700,10 +746,11 @@ struct StepAsk {
     int commit_wgs;         // single-branch nets: workgroups per graph the caller sized its buffers for (0: free choice)
     StepOverrides ov;
 };
-enum { SK_STEP = 0, SK_STEP1 = 1, SK_AF2 = 2, SK_AF3 = 3, SK_AF3B = 4 };
+// SK_EMU: the host emulation's stand-in for the fused kernels (train_step_impl); the others: drgnn_step_af.h
+enum { SK_EMU, SK_AF2, SK_AF3, SK_AF3B };
 struct StepPick {
     int rc;                 // 0, or the error a launch of this shape returns (family NONE)
-    int family, kernel, wgs, slabs, width, cls, paired, lean_ok, builder_roles;
+    int family, kernel, wgs, slabs, width, cls, lean_ok, builder_roles;
     int xg;                 // sGAT / FoutNet: 1 = the x-from-memory form (the S and the x tile together do not fit the LDS), 2 = S too
     int sg;                 // GINet, one workgroup per graph: the S-from-memory form (the S tile does not fit the LDS)
     int64_t lds, xchg_words;
@@ -724,10 +771,8 @@ static StepPick step_pick(const StepAsk& q) {
         if (q.ov.force_wgs == 2) return true;
         return 2 * q.B + extra <= cus;
     };
+    const int emu_width = q.x_ok ? step_variant(q.kind, nullptr, q.F, q.capN, q.capE, q.capC, q.H, q.O) : 0;
     // the aggregation-first family: a workspace with the hierarchical order and usable tiles, a width class, the reference head
-    k.width = step_variant(q.kind, nullptr, q.F, q.capN, q.capE, q.capC, q.H, q.O);
-    if (!q.x_ok) k.width = 0;
-    const int old_width = k.width;
 #ifdef DRGNN_EMU
     const bool af_shape = false;
     const int af_w = 0;
@@ -741,19 +786,18 @@ static StepPick step_pick(const StepAsk& q) {
     // graphs the staged forms have no LDS -- or no register burst -- for)
     const int sg_w = af_ws ? step_af_width(q.kind, q.F, q.capN, q.capE, q.capC, q.H, q.O, true) : 0;
 #endif
-    // The PRODUCT-FIRST family (drgnn_step.h / drgnn_step1.h, rounds 2 - 3) is the host emulation's only: the device library
-    // instantiates the aggregation-first kernels alone (round 6), and a launch they do not cover -- a head that is not the
-    // reference's, more than 64 features, a workspace without the hierarchical order or usable tiles, the no_aggregate override --
-    // is family NONE: the launch pair (drgnn_net_forward + drgnn_net_backward_fused_head) steps it.
+    // A launch the aggregation-first kernels do not cover -- a head that is not the reference's, more than 64 features, a
+    // workspace without the hierarchical order or usable tiles, the no_aggregate override -- is family NONE on the device: the
+    // launch pair (drgnn_net_forward + drgnn_net_backward_fused_head) steps it.  The host emulation has none of those kernels:
+    // it reports family PRODUCT for its stand-in (SK_EMU), bounded by the LDS of the retired product-first kernel.
 #ifdef DRGNN_EMU
-    const bool old_ok = true;
+    const int64_t lemu = step_lds_bytes(q.kind, q.F, q.capN, q.capE, q.capC, q.R, q.H, q.O);
 #else
-    const bool old_ok = false;
+    const int64_t lemu = STEP_LDS_NEVER;
 #endif
     if (q.kind == DRGNN_GINET) {
         const bool narrow = q.H < DRGNN_H2;      // (the exchange words of a graph are 2 x 32 of its 2 x H: a narrower head runs one workgroup per graph)
         const int64_t l2af = af_shape ? 4 * step3_scratch_words(q.F, q.capN, q.capE, q.capC, q.H, q.O) : STEP_LDS_NEVER;
-        const int64_t l2old = old_ok ? step_lds_bytes(q.kind, q.F, q.capN, q.capE, q.capC, q.R, q.H, q.O) : STEP_LDS_NEVER;
         int64_t l1af = af_shape ? 4 * step3b_scratch_words(q.F, q.capN, q.capE, q.capC, q.H, q.O) : STEP_LDS_NEVER;
 #ifndef DRGNN_EMU
         if (l1af > DRGNN_LDS_LIMIT && sg_w != 0) {
@@ -761,12 +805,9 @@ static StepPick step_pick(const StepAsk& q) {
             if (l1sg <= DRGNN_LDS_LIMIT) { l1af = l1sg; k.sg = 1; af_w = sg_w; }
         }
 #endif
-        const int64_t l1p = old_ok ? step1_lds_bytes_form(q.F, q.capN, q.capE, q.capC, q.H, q.O, 1) : STEP_LDS_NEVER;
-        const bool paired = !q.ov.no_paired && l1p <= DRGNN_LDS_LIMIT;
-        const int64_t l1old = paired ? l1p : old_ok ? step1_lds_bytes_form(q.F, q.capN, q.capE, q.capC, q.H, q.O, 0) : STEP_LDS_NEVER;
-        const bool af_two = l2af <= DRGNN_LDS_LIMIT, af_one = l1af <= DRGNN_LDS_LIMIT;
-        const bool can_two = !narrow && (af_two || l2old <= DRGNN_LDS_LIMIT);
-        const bool can_one = af_one || l1old <= DRGNN_LDS_LIMIT;
+        const bool af_two = l2af <= DRGNN_LDS_LIMIT, af_one = l1af <= DRGNN_LDS_LIMIT, emu_ok = lemu <= DRGNN_LDS_LIMIT;
+        const bool can_two = !narrow && (af_two || emu_ok);
+        const bool can_one = af_one || emu_ok;
         // two workgroups per graph only while every workgroup of the launch is resident -- with the builder at two
         // workgroups per graph if that fits, else at one; else one workgroup per graph; else two with the builder on its own
         int wgs = 0;
@@ -776,8 +817,8 @@ static StepPick step_pick(const StepAsk& q) {
         else if (can_two && two_ok(0)) { wgs = 2; k.builder_roles = 0; }
         else { k.rc = DRGNN_E_CAPACITY; return k; }
         k.wgs = wgs;
-        if (wgs == 2) { k.kernel = af_two ? SK_AF3 : SK_STEP; k.lds = af_two ? l2af : l2old; }
-        else { k.kernel = af_one ? SK_AF3B : SK_STEP1; k.lds = af_one ? l1af : l1old; k.paired = (!af_one && paired) ? 1 : 0; }
+        if (wgs == 2) { k.kernel = af_two ? SK_AF3 : SK_EMU; k.lds = af_two ? l2af : lemu; }
+        else { k.kernel = af_one ? SK_AF3B : SK_EMU; k.lds = af_one ? l1af : lemu; }
         if (wgs == 2) k.sg = 0;      // (the S-from-memory form is the one-workgroup kernel's)
         k.xchg_words = 2 * (int64_t)(q.H > DRGNN_H2 ? q.H : DRGNN_H2);
     } else {
@@ -795,7 +836,6 @@ static StepPick step_pick(const StepAsk& q) {
             if (lxg <= DRGNN_LDS_LIMIT) { laf = lxg; k.xg = 2; af_w = sg_w; }
         }
 #endif
-        const int64_t lold = old_ok ? step_lds_bytes(q.kind, q.F, q.capN, q.capE, q.capC, q.R, q.H, q.O) : STEP_LDS_NEVER;
         const bool af_ok = laf <= DRGNN_LDS_LIMIT;
         // the node-split layout: training launches of the aggregation-first kernels under GINet's residency rule
         int wgs = 1;
@@ -820,7 +860,7 @@ static StepPick step_pick(const StepAsk& q) {
         }
         k.wgs = wgs;
         if (af_ok) { k.kernel = SK_AF2; k.lds = laf; }
-        else if (lold <= DRGNN_LDS_LIMIT) { k.kernel = SK_STEP; k.lds = lold; }
+        else if (lemu <= DRGNN_LDS_LIMIT) { k.kernel = SK_EMU; k.lds = lemu; }
         else { k.rc = DRGNN_E_CAPACITY; return k; }
         k.slabs = wgs;
         k.xchg_words = (wgs == 2) ? step2_xchg_words(q.capC > 0 ? q.capC : 1) : 0;
@@ -829,25 +869,20 @@ static StepPick step_pick(const StepAsk& q) {
     // (measured, tools/r03_split_sweep.sh: sGAT at batch 128, 128 step + 256 builder workgroups = two rounds, 37.2 us per
     // step; 128 + 128 = one round, 29.0 us)
     if (k.builder_roles == 2 && k.wgs == 1 && q.B + 2 * co > cus && q.B + co <= cus) k.builder_roles = 1;
-    k.lean_ok = (k.kernel == SK_AF2 || k.kernel == SK_AF3 || k.kernel == SK_AF3B) ? 1 : 0;
-    k.width = k.lean_ok ? af_w : old_width;
+    k.lean_ok = (k.kernel != SK_EMU) ? 1 : 0;
+    k.width = k.lean_ok ? af_w : emu_width;
     k.family = k.lean_ok ? DRGNN_STEP_FAMILY_AGGREGATE : DRGNN_STEP_FAMILY_PRODUCT;
-    // Capacity class (drgnn_step.h: STEP_CLS_*): a batch whose maxima lie inside the class is stepped by the 32-wide kernels
-    // whose LDS layout is a compile-time constant (of the one-workgroup product-first GINet layouts the paired form; of the
-    // aggregation-first kernels the training and the inference instances)
+    // Capacity class (drgnn_step.h: STEP_CLS_*): a batch whose maxima lie inside the class is stepped by the 32- or 48-wide
+    // kernels whose LDS layout is a compile-time constant (the training and the inference instances; 48 features: the feature
+    // count of the reference's shipped regression models)
 #ifndef DRGNN_EMU
-    // (48-wide: the aggregation-first kernels only -- the feature count of the reference's shipped regression models)
-    if (!q.ov.no_class && !k.sg && !k.xg && (k.width == 32 || (k.width == 48 && k.lean_ok)) && q.capN <= STEP_CLS_N && q.capE <= STEP_CLS_E &&
-        q.capC <= STEP_CLS_C && !(k.kernel == SK_STEP1 && !k.paired) &&
-        (k.lean_ok ? step_af_width(q.kind, q.F, STEP_CLS_N, STEP_CLS_E, STEP_CLS_C, q.H, q.O)
-                   : step_variant(q.kind, nullptr, q.F, STEP_CLS_N, STEP_CLS_E, STEP_CLS_C, q.H, q.O)) == k.width) {
+    if (!q.ov.no_class && !k.sg && !k.xg && (k.width == 32 || k.width == 48) && q.capN <= STEP_CLS_N && q.capE <= STEP_CLS_E &&
+        q.capC <= STEP_CLS_C && step_af_width(q.kind, q.F, STEP_CLS_N, STEP_CLS_E, STEP_CLS_C, q.H, q.O) == k.width) {
         // (the 32-wide class instance of the one-workgroup kernel keeps Z1 / XP / dS per branch: STEP3B_DUAL)
         const int64_t lc = k.kernel == SK_AF3B ? 4 * (step3b_scratch_words(q.F, STEP_CLS_N, STEP_CLS_E, STEP_CLS_C, q.H, q.O) +
                                                       (STEP3B_DUAL(k.width, 1, q.train) ? step3b_dual_extra_words(STEP_CLS_N, STEP_CLS_C) : 0))
                          : k.kernel == SK_AF3 ? 4 * step3_scratch_words(q.F, STEP_CLS_N, STEP_CLS_E, STEP_CLS_C, q.H, q.O)
-                         : k.kernel == SK_AF2 ? 4 * step2_scratch_words(q.kind, q.F, STEP_CLS_N, STEP_CLS_E, STEP_CLS_C, q.H, q.O)
-                         : k.kernel == SK_STEP1 ? step1_lds_bytes_form(q.F, STEP_CLS_N, STEP_CLS_E, STEP_CLS_C, q.H, q.O, 1)
-                                                : step_lds_bytes(q.kind, q.F, STEP_CLS_N, STEP_CLS_E, STEP_CLS_C, q.R, q.H, q.O);
+                                              : 4 * step2_scratch_words(q.kind, q.F, STEP_CLS_N, STEP_CLS_E, STEP_CLS_C, q.H, q.O);
         if (lc <= DRGNN_LDS_LIMIT) {
             k.cls = 1;
             k.capN = STEP_CLS_N; k.capE = STEP_CLS_E; k.capC = STEP_CLS_C;
@@ -986,7 +1021,7 @@ static int train_step_impl(const drgnn_net_desc* net, const drgnn_head_desc* hd,
     // a workspace built with DRGNN_TOPO_LEAN holds only what the aggregation-first kernels read
     if (hints && (hints->topo_flags & DRGNN_TOPO_LEAN) && !k.lean_ok) return DRGNN_E_ARG;
     // the autograd boundary (an upstream gradient instead of a target, a forward with the dropout mask of the step) is the
-    // aggregation-first kernels': the product-first family predates it
+    // aggregation-first kernels' alone
     if ((hd->task == DRGNN_TASK_GRAD || hd->train == 2) && !k.lean_ok) return DRGNN_E_ARG;
     // a plan handed along with its `out` members filled (drgnn_net_step_plan) is a commitment: the launch takes the kernel
     // family, width class and slab layout the caller planned (and sized its buffers / made its assertions from) or fails --
@@ -996,7 +1031,6 @@ static int train_step_impl(const drgnn_net_desc* net, const drgnn_head_desc* hd,
         return DRGNN_E_CAPACITY;
     if (co_ok && k.builder_roles == 0) co_ok = false;      // the builder gets a launch of its own
     if (co_ok) T.roles = k.builder_roles;
-    const bool one_wg = (kind == DRGNN_GINET) && k.wgs == 1;
 
     StepLaunch L;
     L.capN = k.capN; L.capE = k.capE; L.capC = k.capC;
@@ -1052,37 +1086,13 @@ static int train_step_impl(const drgnn_net_desc* net, const drgnn_head_desc* hd,
     hf.y_cls = (hd->task == DRGNN_TASK_CLASS) ? (const int64_t*)target : nullptr;
     hf.readout = readout; hf.step = step2; hf.pred = pred; hf.partials = head_partials; hf.stage = 0;
 
-    // grid of the step part: graphs in groups of 8 x 2 when a graph has two workgroups (see step_block)
+    // grid of the step part: graphs in groups of 8 x 2 when a graph has two workgroups (step2_block, step3_block)
     const int blocks = (k.wgs == 2) ? (int)((n_graphs + 7) / 8) * 16 : (int)n_graphs;
     if (blocks > 0) {
 #ifdef DRGNN_EMU
-        // workgroups run one after the other here: two passes (up to the readout exchange, then the
-        // rest), each workgroup keeping its "LDS" in a slab of its own between the passes
-        std::vector<float> slabs((size_t)blocks * (size_t)(L.words + 16));
-        if (one_wg) {
-            for (int b = 0; b < blocks; ++b) {
-                if (k.paired) {
-                    if (gather_ids) step_block_both<0, true, true>(L, b, slabs.data());
-                    else step_block_both<0, false, true>(L, b, slabs.data());
-                } else {
-                    if (gather_ids) step_block_both<0, true, false>(L, b, slabs.data());
-                    else step_block_both<0, false, false>(L, b, slabs.data());
-                }
-            }
-        } else
-        for (int pass = 1; pass <= 2; ++pass)
-            for (int b = 0; b < blocks; ++b) {
-                float* lds_b = slabs.data() + (size_t)b * (size_t)(L.words + 16);
-                if (gather_ids) {
-                    if (kind == DRGNN_GINET) step_block<DRGNN_GINET, 0, true>(L, b, lds_b, pass);
-                    else if (kind == DRGNN_SGAT) step_block<DRGNN_SGAT, 0, true>(L, b, lds_b, pass);
-                    else step_block<DRGNN_FOUT, 0, true>(L, b, lds_b, pass);
-                } else {
-                    if (kind == DRGNN_GINET) step_block<DRGNN_GINET, 0>(L, b, lds_b, pass);
-                    else if (kind == DRGNN_SGAT) step_block<DRGNN_SGAT, 0>(L, b, lds_b, pass);
-                    else step_block<DRGNN_FOUT, 0>(L, b, lds_b, pass);
-                }
-            }
+        if (kind == DRGNN_GINET) emu_step<DRGNN_GINET>(a, full_step, k.capN, k.capE, k.capC);
+        else if (kind == DRGNN_SGAT) emu_step<DRGNN_SGAT>(a, full_step, k.capN, k.capE, k.capC);
+        else emu_step<DRGNN_FOUT>(a, full_step, k.capN, k.capE, k.capC);
         if (co_ok) {
             std::vector<int> tbuf((size_t)(tlds / 4) + 16);
             for (int g = 0; g < T.args.n_graphs * T.roles; ++g) topo_block<true>(T, g, tbuf.data());
@@ -1117,7 +1127,7 @@ static int train_step_impl(const drgnn_net_desc* net, const drgnn_head_desc* hd,
             case SK_AF3B: kern = af_step_kernel(k.sg ? DRGNN_AF_GINET_SG : DRGNN_AF_GINET_ONE, k.width, gather, k.cls, 1, q.train); break;
             case SK_AF2: kern = af_step_kernel(k.xg ? (kind == DRGNN_SGAT ? DRGNN_AF_SGAT_XG : DRGNN_AF_FOUT_XG)
                                                     : (kind == DRGNN_SGAT ? DRGNN_AF_SGAT : DRGNN_AF_FOUT), k.width, gather, k.cls, k.wgs, q.train, k.xg); break;
-            default: return DRGNN_E_CAPACITY;      // (the product-first family is not part of the device library: step_pick never picks it)
+            default: return DRGNN_E_CAPACITY;      // (SK_EMU: the host emulation's; step_pick never picks it here)
         }
         if ((rc = step_launch(kern, both, (unsigned)(blocks + extra), (hipStream_t)stream_, C))) return rc;
 #endif
@@ -1931,7 +1941,6 @@ drgnn_step_plan epoch_plan_of(const drgnn_epoch_plan* p, const EpochBatch& b, in
     if (p->step_overrides) {
         const drgnn_step_plan* o = p->step_overrides;
         pl.force_wgs = o->force_wgs; pl.no_class = o->no_class; pl.no_aggregate = o->no_aggregate; pl.no_split = o->no_split;
-        pl.no_paired = o->no_paired;
     }
     drgnn_net_step_plan(&pl);
     return pl;

@@ -6,7 +6,6 @@
 #pragma once
 #include "drgnn_head.h"
 #include "drgnn_step.h"
-#include "drgnn_step1.h"
 #include "drgnn_step2.h"
 #include "drgnn_step3.h"
 #include "drgnn_layers.h"
@@ -79,7 +78,7 @@ struct TopoLaunch {
 };
 
 // ---- L2 prefetch of one graph of a cached set (the launch's workgroup n_net + g: XCD g % 8, where slot g of the next launch
-// runs, step_block).  A step on graphs that are not cache-resident waits 1.6 - 1.7 us longer in its prologue than a replayed one
+// runs, step3_block).  A step on graphs that are not cache-resident waits 1.6 - 1.7 us longer in its prologue than a replayed one
 // (profiles/r05_cold_path.txt: the aggregation tiles 1.05 us, the index arrays 0.45 us): first-byte latency, not bandwidth.  In
 // cached mode half the CUs are idle: one workgroup per graph of the NEXT mini-batch requests everything that graph's step
 // workgroups will stage -- tile rows, (x rows, D, C), the hierarchical order, the pooled level's arrays, counts, target -- and
@@ -134,7 +133,7 @@ template <bool LDS, int WEIGHTS = -1>
 DEV void topo_block(const TopoLaunch& L, int blk, int* lds) {
     TopoScratch s;
     // Two workgroups per graph: within full groups of 8 graphs both land on XCD (graph % 8) -- workgroups are dealt
-    // round-robin to the 8 XCDs and the step kernels put graph g there too (step_block), so what the builder writes
+    // round-robin to the 8 XCDs and the step kernels put graph g there too (step3_block), so what the builder writes
     // is read back through the same L2 by the launch that trains on it.
     if (L.pf_ids != nullptr) { prefetch_block(L, blk); return; }      // (cached-topology launch: nothing to build)
 #ifdef DRGNN_TOPO_EXIT0
@@ -400,11 +399,11 @@ DEV void net_block(const NetLaunch& L, int blk, float* lds) {
         const int64_t per_branch = net_gscratch_base(KIND, F, L.a.n_nodes, L.n_edges, L.a.n_graphs, BWD);
         scratch = L.gscratch + (int64_t)br * per_branch + net_gscratch_base(KIND, F, n0, e0, g, BWD);
     }
-    if (BWD) net_backward_graph<KIND>(L.a, g, br, scratch, capN, capE, capC);
-    else net_forward_graph<KIND>(L.a, g, br, scratch, capN, capE, capC);
+    if (BWD) net_backward_graph<KIND>(L.a, g, g, br, scratch, capN, capE, capC);
+    else net_forward_graph<KIND>(L.a, g, g, br, scratch, capN, capE, capC);
 }
 
-// ---- fused training step (drgnn_step.h): one launch for body fwd + head/loss + body bwd, sharing the
+// ---- fused training step (drgnn_step2.h / drgnn_step3.h): one launch for body fwd + head/loss + body bwd, sharing the
 // grid with the topology builder of the next mini-batch exactly like CoLaunch above ---------------
 // Offsets and sizes of the launch's graphs when the HOST knows them (mini-batches assembled from host-side size tables:
 // Batch.from_data_list, the resident set's epoch loops): carried in the kernel arguments, so a workgroup does not have
@@ -418,7 +417,7 @@ struct StepDims {
 struct StepLaunch {
     StepArgs a;
     int capN, capE, capC;
-    int64_t words;          // scratch words per workgroup (emulation: one persistent slab each)
+    int64_t words;          // scratch words per workgroup
     StepDims dims;
 };
 struct StepCoLaunch {
@@ -426,87 +425,6 @@ struct StepCoLaunch {
     TopoLaunch topo;
     int n_net;
 };
-
-// GATHER: cached-topology mode (slot g of the launch = graph gather_ids[g] of a whole-set workspace).  A template
-// parameter, not a run-time branch: the per-mini-batch kernels keep exactly the code (and register allocation) they had
-template <int KIND, int XF, bool GATHER = false, int CLS = 0>
-DEV void step_block(const StepLaunch& L, int blk, float* lds, int part) {
-    constexpr int nb = (KIND == DRGNN_GINET) ? 2 : 1;
-    // Workgroups go to the 8 XCDs round robin (block id mod 8) and each XCD has its own L2.  The two
-    // branch workgroups of a graph read the same x tile and the same topology: they are placed 8
-    // block ids apart so that they share an L2 (the second one's misses merge with the first one's).
-    int g, br;
-    if (nb == 2) { g = ((blk >> 4) << 3) + (blk & 7); br = (blk >> 3) & 1; }
-    else { g = blk; br = 0; }
-    if (g >= L.a.n_graphs) return;                // padding of the last group of 8 graphs
-    if (L.dims.count > 0) {
-        // host-supplied offsets / sizes: everything the prologue needs to address its loads is in the kernel arguments;
-        // the device-computed counts are requested here and resolved inside (late)
-        const int gi = GATHER ? L.dims.gi[g] : g;
-        GraphDims d;
-        d.n0 = L.dims.n0[g]; d.N = L.dims.n[g]; d.e0 = L.dims.e0[g]; d.E = L.dims.e[g];
-        d.rowbase = d.n0 + gi;
-        d.C = 0; d.E1 = 0; d.C1 = 0;
-        const int cnt_c = L.a.tv.p[DRGNN_TI_NC0][gi], cnt_e1 = L.a.tv.p[DRGNN_TI_NE1][gi], cnt_c1 = L.a.tv.p[DRGNN_TI_NC1][gi];
-        // (N <= capN, E <= capE hold by construction: the host derived the capacities from the same table; a cluster
-        // count beyond capC can only come from malformed input, which the builder has flagged: such graphs poison
-        // their outputs through the status words like any other bad graph, and the loads below stay inside LDS because
-        // their bounds are clamped to the capacities)
-        net_step_graph<KIND, XF, GATHER, CLS>(L.a, d, g, gi, br, lds, L.capN, L.capE, L.capC, part, true, cnt_c, cnt_e1, cnt_c1);
-        return;
-    }
-    const int gi = GATHER ? WG_UNIFORM(L.a.gather_ids[g]) : g;      // cached mode: graph number in the set
-    const GraphDims d = net_dims(L.a.tv, gi);     // ONE round trip for all per-graph sizes
-    if (d.N > L.capN || d.E > L.capE || d.C > L.capC) {
-        // the caller's bounds were wrong: poison the outputs instead of overrunning LDS
-        if (part != 2) {
-            const uint32_t tag = (uint32_t)L.a.step2[0] + 1u;
-            FOR_TID(c, DRGNN_H2) { const_cast<float*>(L.a.hf.readout)[(long)g * L.a.hf.R + br * DRGNN_H2 + c] = DRGNN_NAN; }
-            if (nb > 1) {
-                FOR_TID(h, L.a.hf.H) { xchg_publish(L.a.xchg + ((long)g * nb + br) * L.a.hf.H + h, tag, DRGNN_NAN); }
-            }
-        }
-        if (part != 1 && br == 0) {
-            if (L.a.hf.train) {
-                float* hp = L.a.hf.partials + (long)g * head_compact_floats(L.a.hf.R, L.a.hf.H, L.a.hf.O);
-                FOR_TID(i, (int)head_compact_floats(L.a.hf.R, L.a.hf.H, L.a.hf.O)) { hp[i] = DRGNN_NAN; }
-            }
-            FOR_TID(o, L.a.hf.O) { L.a.hf.pred[(long)g * L.a.hf.O + o] = DRGNN_NAN; }
-        }
-        return;
-    }
-    net_step_graph<KIND, XF, GATHER, CLS>(L.a, d, g, gi, br, lds, L.capN, L.capE, L.capC, part);
-}
-
-// GINet, one workgroup per graph, both branches one after the other (drgnn_step1.h): the launch layout whenever the
-// two-workgroup exchange could meet a non-resident partner (2 B + builder workgroups > CUs).  No cross-workgroup wait.
-template <int XF, bool GATHER = false, bool PAIRED = false, int CLS = 0>
-DEV void step_block_both(const StepLaunch& L, int g, float* lds) {
-    if (g >= L.a.n_graphs) return;
-    if (L.dims.count > 0) {
-        const int gi = GATHER ? L.dims.gi[g] : g;
-        GraphDims d;
-        d.n0 = L.dims.n0[g]; d.N = L.dims.n[g]; d.e0 = L.dims.e0[g]; d.E = L.dims.e[g];
-        d.rowbase = d.n0 + gi;
-        d.C = 0; d.E1 = 0; d.C1 = 0;
-        const int cnt_c = L.a.tv.p[DRGNN_TI_NC0][gi], cnt_e1 = L.a.tv.p[DRGNN_TI_NE1][gi], cnt_c1 = L.a.tv.p[DRGNN_TI_NC1][gi];
-        net_step_graph_both<XF, GATHER, PAIRED, CLS>(L.a, d, g, gi, lds, L.capN, L.capE, L.capC, true, cnt_c, cnt_e1, cnt_c1);
-        return;
-    }
-    const int gi = GATHER ? WG_UNIFORM(L.a.gather_ids[g]) : g;      // cached mode: graph number in the set
-    const GraphDims d = net_dims(L.a.tv, gi);
-    if (d.N > L.capN || d.E > L.capE || d.C > L.capC) {
-        // the caller's bounds were wrong: poison the outputs instead of overrunning LDS
-        FOR_TID(c, L.a.hf.R) { const_cast<float*>(L.a.hf.readout)[(long)g * L.a.hf.R + c] = DRGNN_NAN; }
-        if (L.a.hf.train) {
-            float* hp = L.a.hf.partials + (long)g * head_compact_floats(L.a.hf.R, L.a.hf.H, L.a.hf.O);
-            FOR_TID(i, (int)head_compact_floats(L.a.hf.R, L.a.hf.H, L.a.hf.O)) { hp[i] = DRGNN_NAN; }
-        }
-        FOR_TID(o, L.a.hf.O) { L.a.hf.pred[(long)g * L.a.hf.O + o] = DRGNN_NAN; }
-        return;
-    }
-    net_step_graph_both<XF, GATHER, PAIRED, CLS>(L.a, d, g, gi, lds, L.capN, L.capE, L.capC);
-}
 
 #ifndef DRGNN_EMU
 // sGAT / FoutNet, aggregation first, SPLIT workgroups per graph (drgnn_step2.h).  SPLIT = 2: the two halves of a graph are 8
@@ -552,7 +470,9 @@ DEV void step2_block(const StepLaunch& L, int blk, float* lds) {
 #endif
 
 #ifndef DRGNN_EMU
-// GINet, aggregation first (drgnn_step3.h): two branch workgroups per graph, placed like step_block's
+// GINet, aggregation first (drgnn_step3.h): two branch workgroups per graph.  Workgroups go to the 8 XCDs round robin (block
+// id mod 8) and each XCD has its own L2; the two branch workgroups of a graph read the same x tile and the same topology: they
+// are placed 8 block ids apart so that they share an L2 (the second one's misses merge with the first one's).
 template <int XF, bool GATHER, int CLS, bool TRAIN>
 DEV void step3_block(const StepLaunch& L, int blk, float* lds) {
     const int g = ((blk >> 4) << 3) + (blk & 7), br = (blk >> 3) & 1;
@@ -570,7 +490,7 @@ DEV void step3_block(const StepLaunch& L, int blk, float* lds) {
     const int gi = GATHER ? WG_UNIFORM(L.a.gather_ids[g]) : g;
     const GraphDims d = net_dims(L.a.tv, gi);
     if (d.N > L.capN || d.E > L.capE || d.C > L.capC) {
-        // the caller's bounds were wrong: poison the outputs instead of overrunning LDS (as step_block does)
+        // the caller's bounds were wrong: poison the outputs instead of overrunning LDS
         const uint32_t tag = (uint32_t)L.a.step2[0] + 1u;
         FOR_TID(c, DRGNN_H2) { const_cast<float*>(L.a.hf.readout)[(long)g * L.a.hf.R + br * DRGNN_H2 + c] = DRGNN_NAN; }
         FOR_TID(h, L.a.hf.H) { xchg_publish(L.a.xchg + ((long)g * 2 + br) * L.a.hf.H + h, tag, DRGNN_NAN); }
@@ -868,28 +788,6 @@ DEV void co_kernarg_touch() {
     const bool co_is_step_ = (int)blockIdx.x < (C).n_net;                      \
     const int co_step_blk_ = (int)blockIdx.x, co_topo_blk_ = (int)blockIdx.x - (C).n_net
 #endif
-template <int KIND, int XF, bool GATHER, int CLS = 0>
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_step_co_topo(StepCoLaunch C_by_value) {
-    extern __shared__ __attribute__((aligned(16))) float smem_s[];
-    PHASE_BEGIN();
-    const StepCoLaunch& C = step_kernarg();
-    co_kernarg_touch();
-    STEP_CO_ROLES(C);
-    if (co_is_step_) step_block<KIND, XF, GATHER, CLS>(C.step, co_step_blk_, smem_s, 0);
-    else topo_block<true, (KIND == DRGNN_SGAT) ? -1 : 0>(C.topo, co_topo_blk_, (int*)smem_s);      // (train_step_impl keeps weighted requests of the other kinds out of the launch)
-}
-// GINet, one workgroup per graph (both branches), + the builder's workgroups of the next mini-batch
-// PAIRED: both branches share every phase (drgnn_step1.h); instantiated for the generic and the 32-wide kernels
-template <int XF, bool GATHER, bool PAIRED, int CLS = 0>
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_step1_co_topo(StepCoLaunch C_by_value) {
-    extern __shared__ __attribute__((aligned(16))) float smem_s1[];
-    PHASE_BEGIN();
-    const StepCoLaunch& C = step_kernarg();
-    co_kernarg_touch();
-    STEP_CO_ROLES(C);
-    if (co_is_step_) step_block_both<XF, GATHER, PAIRED, CLS>(C.step, co_step_blk_, smem_s1);
-    else topo_block<true, 0>(C.topo, co_topo_blk_, (int*)smem_s1);
-}
 // sGAT / FoutNet, aggregation first, SPLIT workgroups per graph (drgnn_step2.h) + the builder's workgroups
 template <int KIND, int XF, bool GATHER, int CLS, int SPLIT, bool TRAIN, int XG = 0>
 __global__ void __launch_bounds__(DRGNN_NTHREADS) k_step2_co_topo(StepCoLaunch C_by_value) {
@@ -1131,7 +1029,6 @@ __global__ void __launch_bounds__(256) k_topo_begin(const int32_t* node_ptr, con
 #endif  // DRGNN_KERNELS_MAIN
 // The instantiations of the aggregation-first step kernels live in drgnn_step_tu.hip (one translation unit per (family, width),
 // drgnn_step_af.h) when the library is built from several translation units (Makefile: DRGNN_SPLIT_TU); a single-unit build
-// (profiling variants) instantiates them at their lookup functions.  k_step_co_topo / k_step1_co_topo (the product-first family)
-// are not instantiated in the device library at all: the host emulation steps through their bodies.
+// (profiling variants) instantiates them at their lookup functions.
 #endif  // !DRGNN_EMU
 #include "drgnn_step_af.h"

@@ -616,14 +616,16 @@ DEV void net_cluster_max(int nc, const int* mp, const int* mem, const float* z, 
 
 // ---------------------------------------------------------------------------------
 // forward
+// g: the graph's slot in the outputs (readout, partials, head); gi: its number in the workspace `tv` (a.n_graphs graphs).
+// The launches pass gi = g; the host emulation's fused step (train_step_impl) gathers graphs of a cached set.
 // ---------------------------------------------------------------------------------
 template <int KIND>
-DEV void net_forward_graph(const NetArgs& a, int g, int br, float* scratch, int capN, int capE,
+DEV void net_forward_graph(const NetArgs& a, int g, int gi, int br, float* scratch, int capN, int capE,
                            int capC) {
     constexpr int HC1 = (KIND == DRGNN_GINET) ? DRGNN_H1 : 2 * DRGNN_H1;
     constexpr int HC2 = (KIND == DRGNN_GINET) ? DRGNN_H2 : 2 * DRGNN_H2;
     const TopoView& tv = a.tv;
-    const GraphDims d = net_dims(tv, g);
+    const GraphDims d = net_dims(tv, gi);
     const int F = a.net.n_feat;
     NetScratch s = net_carve(scratch, KIND, F, capN, capE, capC, 0);
     const long nodeoff = (long)br * a.n_nodes + d.n0;
@@ -716,7 +718,7 @@ DEV void net_forward_graph(const NetArgs& a, int g, int br, float* scratch, int 
     net_cluster_max<DRGNN_H2>(d.C1, s.mp1, s.mem1, s.z2, s.p2, nullptr, a.arg1 + nodeoff * DRGNN_H2);
     BARRIER();
     // graph readout: mean over the depth-1 clusters (scatter_mean with count clamp)
-    const int bad = tv.p[DRGNN_TI_ERR][0] | tv.p[DRGNN_TI_GSTAT][g] | tv.p[DRGNN_TI_GSTAT][a.n_graphs + g];
+    const int bad = tv.p[DRGNN_TI_ERR][0] | tv.p[DRGNN_TI_GSTAT][gi] | tv.p[DRGNN_TI_GSTAT][a.n_graphs + gi];
     const int width = DRGNN_H2 * a.net.n_branch;
     FOR_TID(c, DRGNN_H2) {
         float acc = 0.0f;
@@ -796,12 +798,12 @@ DEV void net_aggregate_bwd(int n, const int* deg_rp, const int* cp, const IdxT* 
 }
 
 template <int KIND>
-DEV void net_backward_graph(const NetArgs& a, int g, int br, float* scratch, int capN, int capE,
+DEV void net_backward_graph(const NetArgs& a, int g, int gi, int br, float* scratch, int capN, int capE,
                             int capC) {
     constexpr int HC1 = (KIND == DRGNN_GINET) ? DRGNN_H1 : 2 * DRGNN_H1;
     constexpr int HC2 = (KIND == DRGNN_GINET) ? DRGNN_H2 : 2 * DRGNN_H2;
     const TopoView& tv = a.tv;
-    const GraphDims d = net_dims(tv, g);
+    const GraphDims d = net_dims(tv, gi);
     const int F = a.net.n_feat;
     NetScratch s = net_carve(scratch, KIND, F, capN, capE, capC, 1);
     const long nodeoff = (long)br * a.n_nodes + d.n0;

@@ -357,7 +357,7 @@ DEV __amdgpu_buffer_rsrc_t buf_rsrc(const void* p, int bytes) {
 // words x 4) that stay in its registers until the LDS store one phase later.  Why: every instruction that all 16 waves of
 // a workgroup execute occupies every SIMD (4 waves each, no issue slack) whether its lanes hold data or not; a dozen arrays of a few
 // hundred words each, staged by all waves, cost ~150 instructions per wave and burst -- as one job per wave they cost ~25.
-// `src` / `n` / `dst` are wave-uniform.  dst is 16-byte aligned and padded to a multiple of 4 words (step_carve); the
+// `src` / `n` / `dst` are wave-uniform.  dst is 16-byte aligned and padded to a multiple of 4 words (the step kernels' carves); the
 // source needs 4-byte alignment only (the hardware range check is per word: tools/probes/buffer_x4_range_probe.hip).
 // ---------------------------------------------------------------------------------
 struct StageJob { const void* src; int n; void* dst; int narrow; };      // narrow: store the words as 16-bit values

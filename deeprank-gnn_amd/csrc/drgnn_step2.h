@@ -33,7 +33,7 @@
 // exchange): the layout beyond the resident batch size.
 //
 // Gradient slabs: one per (graph, half); the update kernel sums 2 B slabs (fixed order).  Half 0 writes the head slab,
-// the predictions and the readout.  GPU only: the host emulation keeps stepping these nets through drgnn_step.h.
+// the predictions and the readout.  GPU only: the host emulation steps a fused launch through the launch pair's routines (train_step_impl).
 // Instantiated per padded feature width 16 / 32 / 48 / 64 (any feature count up to 64: padded tile rows, and with F % 4 != 0 a
 // padded copy of x in the tiles), SPLIT 1 / 2 for training, SPLIT 1 for inference launches (TRAIN = false).
 #ifndef DRGNN_STEP2_H
@@ -175,7 +175,7 @@ DEV Step2Scratch step2_carve(float* base, int kind, int F, int capN, int capE, i
     const int xld = step_pad16(F) + 4;
     Step2Scratch s;
     int o = 0;
-    // run-time capacities: every offset pinned in a register once (drgnn_step.h, step_carve); capacity class: immediates
+    // run-time capacities: every offset pinned in a register once (STEP2_PIN); capacity class: immediates
 #define X(name, words, cond)                                                          \
     { int off = o; if (CLS == 0) { STEP2_PIN(off); } s.name = (decltype(s.name))(base + off);         \
       o = off + ((cond) ? (int)(((long)(words) + 3) & ~3L) : 0); }
@@ -290,7 +290,7 @@ DEV void step2_receive(int nc, const int* cid, int qbase, unsigned long long* sl
     }
 }
 
-// ---- phase E: [S | T] of the own pooled rows (row q <-> pooled node cid[q]); 16 lanes per row as step_pooled_gather -----
+// ---- phase E: [S | T] of the own pooled rows (row q <-> pooled node cid[q]); 16 lanes per row, 4 x 4 -----
 template <int KIND, class IdxT>
 DEV void step2_pooled_gather(int n, const int* cid, int qbase, const int* rp, const IdxT* col, const float* w, float* dv,
                              float* sc, const float* xp, float* ts) {
@@ -571,8 +571,8 @@ DEV void step2_dw1_sparse(int Ch, const short* a0, const float* dxp, const float
 
 // =========================================================================================================================
 // XF: padded feature width (16 / 32 / 48 / 64; the host has checked step_burst_guaranteed: register-burst prologue, reference
-// head width); CLS as in drgnn_step.h; SPLIT: workgroups per graph; half: which one.  `late` as in net_step_graph: sizes and
-// offsets came with the launch arguments, the device-computed counts (clusters, pooled edges, split point) are in flight.
+// head width); CLS as in drgnn_step.h; SPLIT: workgroups per graph; half: which one.  `late` as in net_step3_graph (drgnn_step3.h),
+// the split point among the device-computed counts in flight.
 // TRAIN = false: the inference launch (forward + head, predictions only; one workgroup per graph).
 // XG: x rows read from memory instead of staged in LDS -- what lets 200-node graphs with up to 64 features into the 160 KiB
 // (133 KB instead of 189 KB at SYN size) and, at the narrower widths, graphs of 260 - 350 nodes; the host takes it only when

@@ -13,14 +13,14 @@
 // the topology (DRGNN_TOPO_TILES: S rows in node order + the inverse hierarchical order; include/drgnn.h) -- in the workgroups
 // co-launched with the PREVIOUS step, or once per graph in cached-topology mode -- and this kernel's prologue loads the S rows
 // of the graph, filing row i at its hierarchical position.
-// Per branch workgroup: 12 barrier-separated phases (drgnn_step.h: 16), LDS at SYN size 77 KB (136 KB), staged index words
+// Per branch workgroup: 12 barrier-separated phases (the product-first kernel of rounds 2 - 3: 16), LDS at SYN size 77 KB (136 KB), staged index words
 // per graph 2 500 (6 300).  Same sums as the reference up to the association (G W instead of the per-edge products): parity
 // 1e-4 like every other kernel (tests/test_gpu_fused_fullsize.py, test_gpu_width_classes.py: the reference's goldens directly).
-// GPU only: the host emulation steps GINet through drgnn_step.h.  Instantiated per padded feature width 16 / 32 / 48 / 64
+// GPU only: the host emulation steps a fused launch through the launch pair's routines (train_step_impl).  Instantiated per padded feature width 16 / 32 / 48 / 64
 // (any feature count up to 64: the tiles' rows are padded), for training and for inference launches (TRAIN = false: forward +
 // head), with one workgroup per (graph, branch) or both branches in one workgroup (net_step3_graph_both); launched by
 // train_step_impl whenever the workspace holds the hierarchical order and the tiles and the head is the reference's
-// (step_pick); everything else keeps the drgnn_step.h / drgnn_step1.h kernels.
+// (step_pick); everything else is stepped by the launch pair (drgnn_net.h).
 #ifndef DRGNN_STEP3_H
 #define DRGNN_STEP3_H
 
@@ -264,8 +264,12 @@ DEV void step3_conv1_sg(int n, const float* sgl, int gtf, const int* hord, const
 
 // =========================================================================================================================
 // XF: padded feature width (the host has checked step_burst_guaranteed and the reference head width 128); CLS as in
-// drgnn_step.h; `late` as in net_step_graph.  TRAIN = false: the inference launch (forward + head, predictions only: the
+// drgnn_step.h.  TRAIN = false: the inference launch (forward + head, predictions only: the
 // arrays only the backward reads are not staged, the kernel returns behind the head).
+// `late`: the graph's offsets and sizes (d_in.n0 / N / e0 / E) came with the launch arguments (host-known, StepDims) and its
+// device-computed counts (clusters of both depths, pooled edges) are still IN FLIGHT in cnt_c / cnt_e1 / cnt_c1: the prologue
+// then issues its loads with host-known bounds and resolves the counts afterwards -- one dependent memory round trip less at
+// the start of every workgroup (sizes -> arrays becomes a single wave of loads).
 template <int XF, bool GATHER, int CLS, bool TRAIN = true>
 DEV void net_step3_graph(const StepArgs& a, const GraphDims& d_in, int g, int gi, int br, float* scratch, int capN, int capE,
                          int capC, bool late, int cnt_c, int cnt_e1, int cnt_c1) {
@@ -460,8 +464,7 @@ DEV void net_step3_graph(const StepArgs& a, const GraphDims& d_in, int g, int gi
 
 // =========================================================================================================================
 // The same step with BOTH branches of a graph in ONE workgroup, one after the other: the launch layout beyond the resident
-// batch size (2 B + builder workgroups > CUs), where a workgroup must never wait for a partner (drgnn_step1.h's role for the
-// product-first kernels).  The branches convolve over the same edge_index (ginet.py:101-128), so G = A X -- the S rows of the
+// batch size (2 B + builder workgroups > CUs), where a workgroup must never wait for a partner.  The branches convolve over the same edge_index (ginet.py:101-128), so G = A X -- the S rows of the
 // tiles -- is SHARED: loaded once, multiplied with either branch's W1, and the K operand of both dW1.  Per-branch state kept
 // from the forward to the backward: the argmax of both depths, S2 = A1 XP (dW2's operand) and dZ2; Z1 / XP / dS are
 // reused.  fc1's column block of branch 0 sits in LDS, branch 1's in registers until branch 0's d readout is done.

@@ -1,7 +1,6 @@
 // drgnn_step_tu.hip -- one translation unit of the fused step kernels' instantiations.
 //   -DDRGNN_AF_FAM=<1..8> -DDRGNN_AF_W=<16|32|48|64>: one (family, width) of the aggregation-first kernels (drgnn_step_af.h:
 //       the unit defines that family's kernel lookup, which instantiates the kernels);
-// (The product-first kernels of rounds 2 - 3, drgnn_step.h / drgnn_step1.h, are no longer instantiated for the device.)
 #include "drgnn_kernels.h"
 #if defined(DRGNN_AF_FAM)
 #if DRGNN_AF_FAM == DRGNN_AF_GINET_TWO

@@ -70,8 +70,8 @@ class FusedTrainer(object):
         self.step2 = torch.zeros(4, dtype=torch.int32, device=dev)
         self.step = self.step2[:1]
         self.fused_step = True       # one launch for fwd + head + bwd whenever a graph fits LDS
-        # overrides of the fused step's launch plan (drgnn_step_plan: force_wgs / no_class / no_aggregate / no_split /
-        # no_paired; tests and A/B runs) -- per trainer, handed to every plan query and every launch
+        # overrides of the fused step's launch plan (drgnn_step_plan: force_wgs / no_class / no_aggregate / no_split; tests
+        # and A/B runs) -- per trainer, handed to every plan query and every launch
         self.plan_overrides = {}
         self._xchg = {}              # exchange words of the fused step, one grow-only buffer per batch size
         # what a co-built topology must hold: the hierarchical node order, read by the aggregation-first step kernels

@@ -456,9 +456,8 @@ int drgnn_train_update(const drgnn_net_desc* net, const float* conv_partials, in
  *            (DRGNN_TOPO_HIER); padded feature widths 16 / 32 / 48 / 64, the reference heads (fc1 width 128 / 64), training and
  *            inference launches.  DRGNN_STEP_FAMILY_NONE: no fused kernel covers the launch -- a graph beyond the LDS budget,
  *            more than 64 features, a head that is not the reference's, a workspace without hierarchical order / tiles (use
- *            drgnn_net_forward + drgnn_net_backward_fused_head).  DRGNN_STEP_FAMILY_PRODUCT (csrc/drgnn_step.h / drgnn_step1.h,
- *            the product-first kernels of rounds 2 - 3): the host emulation build of the CPU test suite only; the device
- *            library does not instantiate them and never reports this family.
+ *            drgnn_net_forward + drgnn_net_backward_fused_head).  DRGNN_STEP_FAMILY_PRODUCT: the host emulation's stand-in (the
+ *            CPU test suite's build, which has no aggregation-first kernels); never returned by the device library.
  *   wgs_per_graph  GINet (ginet.py:99-141: two branches over the same edge_index): 2 = one workgroup per branch, readouts
  *            exchanged, taken ONLY while all 2 * n_graphs (+ the co-launched builder's) workgroups are resident at once (one
  *            workgroup per CU: HIP promises nothing about dispatch order); 1 = both branches in one workgroup, no cross-workgroup
@@ -480,9 +479,9 @@ int drgnn_train_update(const drgnn_net_desc* net, const float* conv_partials, in
  * Overrides (0 = automatic; tests and same-box A/B runs): force_wgs 1 / 2 = always that many workgroups per graph (2 beyond the
  * resident size is MEASUREMENT ONLY: the exchange then leans on in-order dispatch; bounded wait + fault bit); no_class;
  * no_aggregate (never the aggregation-first family: family NONE on the device, the launch pair steps the mini-batch);
- * no_split (sGAT / FoutNet never divided); no_paired (emulation build: the one-workgroup product-first GINet kernel runs
- * branch after branch).  The environment variable DRGNN_STEP_PLAN (comma list of one, two, noclass, product, nosplit, seq;
- * read once) sets the defaults of a process for plans that override nothing. */
+ * no_split (sGAT / FoutNet never divided); no_paired is ignored (kept for the ABI).  The environment variable
+ * DRGNN_STEP_PLAN (comma list of one, two, noclass, product, nosplit; read once) sets the defaults of a process for plans
+ * that override nothing. */
 #define DRGNN_STEP_FAMILY_NONE 0
 #define DRGNN_STEP_FAMILY_PRODUCT 1
 #define DRGNN_STEP_FAMILY_AGGREGATE 2
@@ -532,9 +531,10 @@ int64_t drgnn_net_step_xchg_elems(int32_t kind, int32_t max_nodes, int32_t max_c
 int64_t drgnn_net_step_lds_bytes(int32_t kind, int32_t n_feat, int32_t max_nodes, int32_t max_edges,
                                  int32_t max_c0, int32_t R, int32_t H, int32_t O);
 int64_t drgnn_head_compact_elems(int32_t R, int32_t H, int32_t O);
-/* Which instantiation of the PRODUCT-FIRST step kernel (emulation build; kept in the ABI for hosts that query it) a launch of
- * these bounds would take: the padded feature width (16/32/48/64) of the width-specialised kernel, or 0 for the generic
- * one.  The device library's launches are described by drgnn_net_step_plan (width / cls).  Host-side only. */
+/* drgnn_net_step_lds_bytes / drgnn_net_step_variant describe the retired product-first step kernel of rounds 2 - 3 (kept in
+ * the ABI for hosts that query them): its LDS bytes per workgroup, and the padded feature width (16/32/48/64) of the
+ * width-specialised instance a launch of these bounds would have taken, or 0 for the generic one.  The library's launches
+ * are described by drgnn_net_step_plan (lds_bytes / width / cls).  Host-side only. */
 int32_t drgnn_net_step_variant(int32_t kind, const float* x, int32_t n_feat, int32_t max_nodes, int32_t max_edges,
                                int32_t max_c0, int32_t H, int32_t O);
 int drgnn_net_train_step(const drgnn_net_desc* net, const drgnn_head_desc* head, const float* x,

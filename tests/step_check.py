@@ -8,7 +8,7 @@ from deeprank_gnn_amd.data import Batch
 from deeprank_gnn_amd.trainer import FusedTrainer
 
 
-def ragged_batch(seed, n_feat):
+def ragged_graphs(seed, n_feat):
     from test_emu_topology import random_graph
     rng = np.random.default_rng(seed)
     graphs = []
@@ -21,7 +21,11 @@ def ragged_batch(seed, n_feat):
         graphs.append(g)
     graphs.insert(2, random_graph(rng, 1, 0, 1, 1))              # single node, no edge
     graphs[2].x = torch.from_numpy(rng.standard_normal((1, n_feat)).astype(np.float32))
-    return Batch.from_data_list(graphs)
+    return graphs
+
+
+def ragged_batch(seed, n_feat):
+    return Batch.from_data_list(ragged_graphs(seed, n_feat))
 
 
 def check_fused_matches_pair(Net, n_feat, task, device, api=None, seed=0, steps=2):
@@ -103,7 +107,7 @@ def check_fused_predict(Net, n_feat, task, device, api=None, seed=0):
 
 class plan_overrides(object):
     """``with plan_overrides(trainer, force_wgs=1):`` every fused-step launch of THAT trainer inside the block is planned
-    with these overrides of drgnn_step_plan (force_wgs / no_class / no_aggregate / no_split / no_paired); other trainers of the
+    with these overrides of drgnn_step_plan (force_wgs / no_class / no_aggregate / no_split); other trainers of the
     process are not affected (the overrides travel with the plan, there is no process-wide switch)."""
 
     def __init__(self, trainer, **ov):
@@ -119,30 +123,37 @@ class plan_overrides(object):
         return False
 
 
-def one_workgroup_layout(trainer, paired=True):
+def one_workgroup_layout(trainer):
     """every GINet fused-step launch of ``trainer`` runs both branches of a graph in ONE workgroup, the layout the library
-    takes by itself beyond the resident batch size.  paired: both branches share every phase (the default form of the
-    product-first kernel); False: branch after branch (the form graphs too large for the paired LDS plan take)"""
-    return plan_overrides(trainer, force_wgs=1, no_paired=0 if paired else 1)
+    takes by itself beyond the resident batch size"""
+    return plan_overrides(trainer, force_wgs=1)
 
 
-def check_one_workgroup_layout(n_feat, task, device, api=None, seed=0, paired=True):
+def check_one_workgroup_layout(n_feat, task, device, api=None, seed=0, cached=False):
     """GINet: the one-workgroup-per-graph step (both branches in sequence) against the two-workgroup step on the same
-    ragged batch -- loss, predictions, every gradient, two Adam steps, inference."""
+    ragged batch -- loss, predictions, every gradient, two Adam steps, inference.  cached: the one-workgroup trainer steps
+    the batch's graphs out of a resident set's topology cache, gathered in another order than the set's (slot g of the
+    launch = graph ids[g] of the set, ids[g] != g)."""
     from deeprank_gnn_amd import _lib
     from deeprank_gnn_amd.ginet import GINet
+    from deeprank_gnn_amd.resident import ResidentGraphSet
     from deeprank_gnn_amd.topology import Topology
     api = api or _lib.get()
     kw = {"api": api}
     torch.manual_seed(seed)
-    batch = ragged_batch(seed, n_feat)
+    graphs = ragged_graphs(seed, n_feat)
     n_out = 1 if task == "reg" else 3
     cw = None
     if task == "class":
-        batch.y = torch.tensor([k % 3 for k in range(batch.num_graphs)])
+        y = torch.tensor([k % 3 for k in range(len(graphs))])
         cw = torch.tensor([0.2, 0.5, 0.3]).to(device)
     else:
-        batch.y = torch.arange(batch.num_graphs, dtype=torch.float32) * 0.3 - 1.0
+        y = torch.arange(len(graphs), dtype=torch.float32) * 0.3 - 1.0
+    for g, yv in zip(graphs, y):
+        g.y = yv.reshape(1)
+    ids = list(range(len(graphs)))[::-1] if cached else list(range(len(graphs)))
+    batch = Batch.from_data_list([graphs[i] for i in ids])
+    batch.y = y[ids]
     a = GINet(n_feat, n_out, 1)
     a.dropout = 0.0
     b = copy.deepcopy(a)
@@ -152,13 +163,21 @@ def check_one_workgroup_layout(n_feat, task, device, api=None, seed=0, paired=Tr
     topo = Topology.from_batch(batch, need_weights=False, **kw)
     assert ta._can_fuse(topo, n_feat)
     assert ta._plan_for(topo, n_feat).wgs_per_graph == 2      # a handful of graphs: resident, two workgroups per graph
-    with one_workgroup_layout(ta, paired):
+    with one_workgroup_layout(ta):
         assert ta._plan_for(topo, n_feat).wgs_per_graph == 1
         assert tb._plan_for(topo, n_feat).wgs_per_graph == 2      # (the other trainer of the process keeps its own plan)
+    if cached:
+        rs = ResidentGraphSet(graphs, device, api=api)
+        rs.set_targets(y)
+        cache = rs.topology_cache(need_weights=True)
     for it in range(2):
-        with one_workgroup_layout(ta, paired):
-            pa = ta.predict(batch).cpu().numpy()
-            la = ta.train_step(batch)
+        with one_workgroup_layout(ta):
+            if cached:
+                pa = ta.predict_cached(cache, ids).cpu().numpy()
+                la = ta.train_step_cached(cache, ids)
+            else:
+                pa = ta.predict(batch).cpu().numpy()
+                la = ta.train_step(batch)
         pb = tb.predict(batch).cpu().numpy()
         lb = tb.train_step(batch)
         np.testing.assert_allclose(pa, pb, rtol=1e-5, atol=1e-6)

@@ -1,4 +1,5 @@
-"""Fused training-step kernel (host-emulation build) on ragged batches, odd feature widths and both
+"""Fused training step (host-emulation build: its stand-in runs the launch pair's per-graph routines, so these tests check
+the step's plumbing -- slot / workspace indexing, slabs, step counter, plan) on ragged batches, odd feature widths and both
 tasks, against the forward/backward pair of kernels.  CPU only."""
 import pytest
 
@@ -22,11 +23,12 @@ def test_fused_inference(Net, n_feat, task):
     check_fused_predict(Net, n_feat, task, "cpu", api=emu(), seed=7 + n_feat)
 
 
-@pytest.mark.parametrize("paired", [True, False])
+@pytest.mark.parametrize("cached", [True, False])
 @pytest.mark.parametrize("n_feat,task", [(32, "reg"), (5, "class"), (40, "reg"), (16, "reg")])
-def test_ginet_one_workgroup_layout_matches_two_workgroup_layout(n_feat, task, paired):
+def test_ginet_one_workgroup_layout_matches_two_workgroup_layout(n_feat, task, cached):
+    """cached: the one-workgroup launches read the batch's graphs out of a resident set's topology cache, in reversed order"""
     from step_check import check_one_workgroup_layout
-    check_one_workgroup_layout(n_feat, task, "cpu", api=emu(), seed=3 + n_feat, paired=paired)
+    check_one_workgroup_layout(n_feat, task, "cpu", api=emu(), seed=3 + n_feat, cached=cached)
 
 
 @pytest.mark.parametrize("Net", [GINet, sGAT, FoutNet])

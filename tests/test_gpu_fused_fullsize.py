@@ -1,6 +1,6 @@
 """The BENCHMARKED kernel instance against the oracle at the BENCHMARKED shape.
 
-bench.py times ``k_step_co_topo<kind, 32>`` (the width-specialised fused training step, launched
+bench.py times ``k_step3_co_topo`` / ``k_step2_co_topo`` at width 32 (the width-specialised fused training step, launched
 through ``FusedTrainer.compute_gradients`` / ``train_step`` with the next batch's topology co-built by
 the same launch) on ``synthetic.make_batch(0, 64)`` = BASELINE.json configs[1..3].  These tests run
 exactly that launch on exactly that batch and compare predictions, loss and EVERY gradient with
@@ -126,7 +126,7 @@ def test_fused_step_syn64_dropout_on_matches_oracle_elementwise(layout):
     """The launch bench.py times runs GINet with dropout = 0.4 (ginet.py:97,138); the product's Bernoulli draw is a counter
     hash, not torch's Philox, so the dropout-on code path is compared through an EXPLICIT mask: the kernels take a [B, 128]
     0 / 1 mask (drgnn_head_desc.drop_mask) instead of the hash decision, the oracle applies F.dropout's arithmetic
-    hid * mask / (1 - p) with the same mask.  Everything else is the benchmarked launch (k_step_co_topo<GINet, 32>, p_drop =
+    hid * mask / (1 - p) with the same mask.  Everything else is the benchmarked launch (k_step3_co_topo at width 32, p_drop =
     0.4, keep_scale = 1 / 0.6 in the forward and in d hid).  Both GINet layouts (two branch workgroups / one per graph)."""
     import deeprank_gnn_amd.synthetic as synth
     from deeprank_gnn_amd import _lib
@@ -162,7 +162,7 @@ def test_fused_step_syn64_dropout_on_matches_oracle_elementwise(layout):
 
 @pytest.mark.parametrize("net_name", NETS)
 def test_fused_step_syn64_three_adam_steps_match_oracle(net_name):
-    """Three optimiser steps through the benchmarked launches (k_step_co_topo + k_update, topologies
+    """Three optimiser steps through the benchmarked launches (k_step3_co_topo + k_update, topologies
     ping-ponging as in bench.py) vs the oracle trained with torch.optim.Adam."""
     import deeprank_gnn_amd.synthetic as synth
     from deeprank_gnn_amd.topology import Topology
@@ -263,11 +263,12 @@ def test_ginet_one_workgroup_step_at_syn_size_matches_oracle_and_two_workgroup_s
     np.testing.assert_allclose(pred_one, pred_two, rtol=1e-4, atol=1e-5)
 
 
-@pytest.mark.parametrize("paired", [True, False])
+@pytest.mark.parametrize("cached", [True, False])
 @pytest.mark.parametrize("n_feat,task", [(32, "reg"), (5, "class"), (40, "reg"), (16, "reg")])
-def test_ginet_one_workgroup_layout_matches_two_workgroup_layout(n_feat, task, paired):
+def test_ginet_one_workgroup_layout_matches_two_workgroup_layout(n_feat, task, cached):
+    """cached: the one-workgroup launches read the batch's graphs out of a resident set's topology cache, in reversed order"""
     from step_check import check_one_workgroup_layout
-    check_one_workgroup_layout(n_feat, task, "cuda:0", seed=3 + n_feat, paired=paired)
+    check_one_workgroup_layout(n_feat, task, "cuda:0", seed=3 + n_feat, cached=cached)
 
 
 @pytest.mark.parametrize("net_name,n_nodes,n_pairs", [("GINet", 272, 320), ("FoutNet", 264, 300)])
@@ -460,7 +461,7 @@ def test_capacity_class_kernels_equal_the_runtime_layout_bit_for_bit(net_name, c
     count of the reference's shipped regression models, for the aggregation-first kernels) is stepped by kernels
     whose LDS layout is a compile-time constant (drgnn_step.h: CLS); the layout moves arrays, not arithmetic: three training
     steps give the same bits with the class kernels (default) and without (plan override no_class), rebuilt and cached;
-    136 graphs: GINet's one-workgroup (paired) layout and the other kinds beyond one round of workgroups."""
+    136 graphs: GINet's one-workgroup layout and the other kinds beyond one round of workgroups."""
     import deeprank_gnn_amd.synthetic as synth
     from deeprank_gnn_amd import _lib
     from deeprank_gnn_amd.foutnet import FoutNet
