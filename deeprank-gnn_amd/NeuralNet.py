@@ -174,7 +174,11 @@ class NeuralNet(object):
                 self.threshold = self.classes[1] if self.task == 'class' else 0.3
             opt_state = model_state = None
         else:
-            state = torch.load(pretrained_model, map_location='cpu', weights_only=False)
+            # a list of checkpoints: an ensemble of them (inference only, ensemble.py); the settings are the first one's
+            members = list(pretrained_model) if isinstance(pretrained_model, (list, tuple)) else None
+            if members is not None and not members:
+                raise ValueError("pretrained_model: an empty list of checkpoints")
+            state = torch.load(members[0] if members else pretrained_model, map_location='cpu', weights_only=False)
             for dst, src in (('node_feature', 'node'), ('edge_feature', 'edge'), ('target', 'target'),
                              ('batch_size', 'batch_size'), ('percent', 'percent'), ('lr', 'lr'), ('index', 'index'),
                              ('class_weights', 'class_weight'), ('task', 'task'), ('classes', 'classes'),
@@ -183,6 +187,7 @@ class NeuralNet(object):
                 setattr(self, dst, state[src])
             opt_state, model_state = state['optimizer'], state['model']
         self.pretrained = pretrained_model is not None
+        ensemble_members = members if pretrained_model is not None else None
         self.dataset = GraphDataSet(database, node_feature=self.node_feature, edge_feature=self.edge_feature,
                                     target=self.target, clustering_method=self.cluster_nodes or 'mcl',
                                     index=None if self.pretrained else self.index)     # load_pretrained_model: no index
@@ -215,9 +220,6 @@ class NeuralNet(object):
         n_out = 1 if self.task == 'reg' else len(self.classes)
         self.classes_to_idx = {c: i for i, c in enumerate(self.classes)}
         self.idx_to_classes = {i: c for i, c in enumerate(self.classes)}
-        self.model = Net(first.num_features, n_out, len(self.edge_feature)).to(self.device)
-        if model_state is not None:
-            self.model.load_state_dict(model_state)
         weights = None
         if self.task == 'class' and self.class_weights is True:      # NeuralNet.py:247-258
             ys = [int(self.dataset[i].y) for i in self.train_index]
@@ -226,13 +228,25 @@ class NeuralNet(object):
             weights = w / w.sum()
         elif self.task == 'class' and isinstance(self.class_weights, (list, tuple)):
             weights = torch.tensor(self.class_weights, dtype=torch.float32)
-        self.trainer = FusedTrainer(self.model, lr=self.lr, task=self.task, class_weights=weights, api=_api,
-                                    transform_sigmoid=bool(self.transform_sigmoid))
-        if opt_state is not None:
-            self.trainer.load_optimizer_state_dict(opt_state)
-        # data parallel: the replicas start as ONE model -- rank 0's parameters, Adam moments and step counter -- whatever
-        # each rank's RNG produced at construction
-        self.trainer.broadcast_state(src=0)
+        self.ensemble = None
+        if ensemble_members is not None:
+            # an ensemble (inference only): its first member stands for `model` / `trainer` (no second copy of it)
+            from .ensemble import Ensemble
+            self.ensemble = Ensemble(Net, ensemble_members, device=self.device, api=_api, edge_dim=len(self.edge_feature))
+            self.model, self.trainer = self.ensemble.nets[0], self.ensemble.trainers[0]
+            if weights is not None:
+                self.trainer.class_w = weights.to(self.device).contiguous()
+        else:
+            self.model = Net(first.num_features, n_out, len(self.edge_feature)).to(self.device)
+            if model_state is not None:
+                self.model.load_state_dict(model_state)
+            self.trainer = FusedTrainer(self.model, lr=self.lr, task=self.task, class_weights=weights, api=_api,
+                                        transform_sigmoid=bool(self.transform_sigmoid))
+            if opt_state is not None:
+                self.trainer.load_optimizer_state_dict(opt_state)
+            # data parallel: the replicas start as ONE model -- rank 0's parameters, Adam moments and step counter -- whatever
+            # each rank's RNG produced at construction
+            self.trainer.broadcast_state(src=0)
         self.train_loss, self.valid_loss, self.train_acc, self.valid_acc = [], [], [], []
         self.data = {}
         self._resident_sets = {}
@@ -322,6 +336,8 @@ class NeuralNet(object):
         loss = None if loss is None else float(loss)
         if pred is None:
             return loss
+        if host.get('ens') is not None:
+            return self._finish_ensemble(store, pred, host['ens'], y, loss)
         # (the lists of the reference's record are formed when somebody reads them: _PassStore)
         if self.task == 'class':
             prob = torch.softmax(pred, dim=1)
@@ -333,6 +349,26 @@ class NeuralNet(object):
             store.arrays = (top.numpy(), None if y is None else y.numpy().astype(np.int64))
         else:
             flat = pred.reshape(-1)
+            store.defer('raw_outputs', lambda: flat.tolist())
+            store.defer('outputs', lambda: flat.tolist())
+            if y is not None:
+                store.defer('targets', lambda: y.tolist())
+            store.arrays = (flat.numpy(), None if y is None else y.numpy())
+        return loss
+
+    def _finish_ensemble(self, store, mean, per, y, loss):
+        """_finish of an ensemble pass: ``mean`` is the mean output (regression) or the mean probabilities (classification)"""
+        dict.__setitem__(store, 'ensemble_raw_outputs', [])
+        store.defer('ensemble_raw_outputs', lambda: per.tolist())
+        if self.task == 'class':
+            top = mean.argmax(dim=1)
+            store.defer('raw_outputs', lambda: mean.tolist())
+            store.defer('outputs', lambda: [self.idx_to_classes[i] for i in top.tolist()])
+            if y is not None:
+                store.defer('targets', lambda: [self.idx_to_classes[int(i)] for i in y.tolist()])
+            store.arrays = (top.numpy(), None if y is None else y.numpy().astype(np.int64))
+        else:
+            flat = mean.reshape(-1)
             store.defer('raw_outputs', lambda: flat.tolist())
             store.defer('outputs', lambda: flat.tolist())
             if y is not None:
@@ -571,6 +607,8 @@ class NeuralNet(object):
         indices = self.valid_index if indices is None else indices
         store = self._new_store()
         order = [int(i) for i in indices]
+        if self.ensemble is not None:
+            return self._eval_ensemble(dataset, order, store)
         if self.native_epoch and order:
             rs = self._resident(dataset)
             pred = self.trainer.predict_epoch(rs, order, self.batch_size, cached=self._use_cache(rs))
@@ -605,11 +643,35 @@ class NeuralNet(object):
             batch, topo = nxt, nxt_topo
         return self._stage(store, total)
 
+    def _eval_ensemble(self, dataset, order, store):
+        """The forward pass of an ensemble: every member over the same resident set (and cached topology); the pass's
+        outputs are the ensemble mean (Ensemble.combine), the members' own in ``ensemble_raw_outputs``."""
+        if not order:
+            return self._stage(store, torch.zeros((), dtype=torch.float32, device=self.device))
+        rs = self._resident(dataset)
+        ens = self.ensemble
+        preds = ens.predict(rs, order, batch_size=self.batch_size, cached=self._use_cache(rs))
+        mean, per = ens.combine(preds)
+        store.defer('mol', lambda: [rs.mols[i] for i in order])
+        total, y_host = None, None
+        if rs.y is not None:
+            y = rs.y[_index_on(rs.y.device, order)]
+            y_host = rs.y_host[torch.as_tensor(order, dtype=torch.int64)]
+            # (classification: the loss of the mean probabilities -- their logarithms are logits of the same softmax)
+            total = self._sum_of_batch_losses(mean if self.task == 'reg' else torch.log(mean), y)
+        store.pop('_pred'), store.pop('_y')
+        faults = torch.stack([f.reshape(()) for f in ens.faults()]).max().reshape(1)
+        store['_staged'] = _Staged(pred=mean, y=y_host, loss=total, faults=faults, ens=per)
+        return store
+
     def train(self, nepoch=1, validate=False, save_model='last', hdf5='train_data.drgs', save_epoch='intermediate',
               save_every=5):
         """NeuralNet.train (NeuralNet.py:265-355): same arguments; epoch data is exported for the last epoch and, with
         ``save_epoch='all'`` / ``'intermediate'``, for every / every ``save_every``-th epoch; the other epochs' outputs are
         dropped as soon as the epoch is over.  'best' checkpoints carry the reference's file name."""
+        if self.ensemble is not None:
+            raise _lib.DrgnnError("NeuralNet.train: a NeuralNet built from a list of checkpoints is an ensemble, which is "
+                                  "inference only (test() / eval())")
         self.nepoch = nepoch
         fname = self.update_name(self._rank_name(hdf5), self.outdir) if hdf5 else None
         self.data, pending = {}, {}

@@ -10,5 +10,6 @@ from .ginet import GINet  # noqa: F401
 from .sGAT import sGAT  # noqa: F401
 from .foutnet import FoutNet  # noqa: F401
 from .metrics import Metrics  # noqa: F401
+from .ensemble import Ensemble  # noqa: F401
 
 __version__ = "0.1.0"

@@ -52,6 +52,11 @@ class NetDesc(ctypes.Structure):
                 ("conv1", ConvParams * MAX_BRANCH), ("conv2", ConvParams * MAX_BRANCH)]
 
 
+class EnsMember(ctypes.Structure):
+    """drgnn_ens_member: one entry of an ensemble's member table (its array lives in device memory)"""
+    _fields_ = [("net", NetDesc), ("w1", _vp), ("b1", _vp), ("w2", _vp), ("b2", _vp)]
+
+
 class TopologyRequest(ctypes.Structure):
     _fields_ = [("edge_index", _vp), ("edge_attr", _vp), ("batch", _vp), ("cluster0", _vp), ("cluster1", _vp),
                 ("node_ptr", _vp), ("edge_ptr", _vp), ("c1_ptr", _vp),
@@ -202,6 +207,11 @@ class Api(object):
         lib.drgnn_net_train_step_cached.argtypes = ([ctypes.POINTER(NetDesc), ctypes.POINTER(HeadDesc),
                                                      ctypes.POINTER(TopologyCacheDesc), _vp, _c_i64] + [_c_i32] * 3 +
                                                     [_vp] * 6 + [ctypes.POINTER(StepHints), _vp])
+        lib.drgnn_ens_step_plan.argtypes = [ctypes.POINTER(StepPlan), _c_i32]
+        lib.drgnn_ens_step_plan.restype = _c_i32
+        lib.drgnn_ens_predict_cached.argtypes = ([ctypes.POINTER(NetDesc), ctypes.POINTER(HeadDesc), _vp, _c_i32,
+                                                  ctypes.POINTER(TopologyCacheDesc), _vp, _c_i64] + [_c_i32] * 3 +
+                                                 [_vp] * 3 + [ctypes.POINTER(StepHints), _vp])
         lib.drgnn_step_update.argtypes = ([ctypes.POINTER(NetDesc), _vp, _c_i64] +
                                           [ctypes.POINTER(ConvGrads)] * 2 + [_vp, _vp] + [_c_i32] * 3 +
                                           [_c_i64] + [_vp] * 4 + [_c_i64] + [_vp] * 2 +
@@ -393,6 +403,21 @@ class Api(object):
             None if hints is None else ctypes.byref(hints), stream),
             "drgnn_net_train_step_cached")
 
+
+    def ens_step_plan(self, K, kind, n_feat, max_nodes, max_edges, max_c0, R, H, O, n_graphs, topo_flags=0):
+        """The plan (StepPlan) of an ensemble launch of K models; ``family == 0``: no fused ensemble launch takes it."""
+        p = StepPlan()
+        p.kind, p.n_feat, p.max_nodes, p.max_edges, p.max_c0 = int(kind), int(n_feat), int(max_nodes), int(max_edges), int(max_c0)
+        p.R, p.H, p.O, p.n_graphs, p.topo_flags = int(R), int(H), int(O), int(n_graphs), int(topo_flags)
+        self.lib.drgnn_ens_step_plan(ctypes.byref(p), int(K))
+        return p
+
+    def ens_predict_cached(self, desc, head, members, K, cache, ids, n_graphs, max_nodes, max_edges, max_c0, step2, pred,
+                           readout, stream, hints):
+        _check(self.lib.drgnn_ens_predict_cached(
+            ctypes.byref(desc), ctypes.byref(head), _ptr(members), int(K), ctypes.byref(cache), _ptr(ids), n_graphs,
+            max_nodes, max_edges, max_c0, _ptr(step2), _ptr(pred), _ptr(readout), ctypes.byref(hints), stream),
+            "drgnn_ens_predict_cached")
 
     def step_update(self, desc, conv_partials, n_graphs, g1, g2, head_partials, readout, R, H, O, head_offset,
                     flat_p, flat_g, exp_avg, exp_avg_sq, step2, loss, lr, beta1, beta2, eps, stream,

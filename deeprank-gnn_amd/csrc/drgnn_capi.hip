@@ -935,7 +935,9 @@ int32_t drgnn_net_step_variant(int32_t kind, const float* x, int32_t n_feat, int
 #ifndef DRGNN_EMU
 // One launch of a step kernel instance (+ the co-launched builder's workgroups).  These kernels use up to the whole 160 KiB of
 // LDS: the attribute is raised once per kernel instance and device (the call costs host time on every launch otherwise).
-static int step_launch(drgnn_step_kernel_t kern, int64_t lds_bytes, unsigned grid, hipStream_t stream, const StepCoLaunch& C) {
+// (ens: an ensemble instance, drgnn_kernels.h k_step3b_ens / k_step2_ens -- its member table and K follow the launch arguments)
+static int step_launch(drgnn_step_kernel_t kern, int64_t lds_bytes, unsigned grid, hipStream_t stream, const StepCoLaunch& C,
+                       const drgnn_ens_member* ens = nullptr, int ens_K = 0) {
     if (!kern) return DRGNN_E_ARG;
     if (lds_bytes > 64 * 1024) {
         struct Seen { const void* fn; int dev; };
@@ -956,7 +958,7 @@ static int step_launch(drgnn_step_kernel_t kern, int64_t lds_bytes, unsigned gri
             }
         }
     }
-    void* args[] = {const_cast<StepCoLaunch*>(&C)};
+    void* args[] = {const_cast<StepCoLaunch*>(&C), &ens, &ens_K};
     HIP_TRY(hipLaunchKernel((const void*)kern, dim3(grid), dim3(DRGNN_NTHREADS), args, (size_t)lds_bytes, stream));
     return 0;
 }
@@ -970,9 +972,14 @@ static int train_step_impl(const drgnn_net_desc* net, const drgnn_head_desc* hd,
                            const int32_t* gather_ids, int32_t max_nodes,
                            int32_t max_edges, int32_t max_c0, float* pred, float* readout,
                            float* head_partials, float* partials, uint64_t* xchg,
-                           const drgnn_topology_request* next, const drgnn_step_hints* hints, void* stream_) {
+                           const drgnn_topology_request* next, const drgnn_step_hints* hints, void* stream_,
+                           const drgnn_ens_member* ens = nullptr, int ens_K = 0) {
     int rc = net_check(net);
     if (rc) return rc;
+#ifdef DRGNN_EMU
+    if (ens) return DRGNN_E_CAPACITY;      // (the host emulation has no ensemble launch: drgnn_ens_step_plan answers NONE)
+#endif
+    if (ens && (ens_K < 1 || !gather_ids || hd->train || !(hints && hints->plan))) return DRGNN_E_ARG;
     if (!hd || !hd->w1 || !hd->b1 || !hd->w2 || !hd->b2 || !x || !step2 || !ws_i32 || !pred || !readout)
         return DRGNN_E_ARG;
     // hd->train: 1 = the whole step; 0 = inference; 2 = the forward of a training step (predictions only, dropout on)
@@ -981,7 +988,7 @@ static int train_step_impl(const drgnn_net_desc* net, const drgnn_head_desc* hd,
     if (full_step && (!target || !head_partials || !partials)) return DRGNN_E_ARG;      // inference needs neither
     if (hd->task != DRGNN_TASK_REG && hd->task != DRGNN_TASK_CLASS && hd->task != DRGNN_TASK_GRAD) return DRGNN_E_ARG;
     if (hd->task == DRGNN_TASK_GRAD && gather_ids) return DRGNN_E_ARG;      // (the upstream gradient is indexed by slot)
-    if (net->n_branch > 1 && !xchg) return DRGNN_E_ARG;
+    if (net->n_branch > 1 && !xchg && !ens) return DRGNN_E_ARG;      // (the ensemble forms exchange nothing)
     if (net->kind == DRGNN_SGAT && !ws_f32) return DRGNN_E_ARG;
     if (hd->R != DRGNN_H2 * net->n_branch || hd->H < 1 || hd->H > 512 || hd->O < 1 || hd->O > DRGNN_MAX_OUT)
         return DRGNN_E_WIDTH;
@@ -1015,6 +1022,7 @@ static int train_step_impl(const drgnn_net_desc* net, const drgnn_head_desc* hd,
     const drgnn_step_plan* plan = hints ? hints->plan : nullptr;
     q.ov = step_overrides_of(plan);
     q.commit_wgs = (kind == DRGNN_GINET) ? 0 : (plan && plan->wgs_per_graph == 2) ? 2 : 1;
+    if (ens) { q.ov.force_wgs = 1; q.commit_wgs = (kind == DRGNN_GINET) ? 0 : 1; }      // (the ensemble forms: one workgroup per graph)
     if (q.commit_wgs == 2 && !xchg) return DRGNN_E_CAPACITY;
     const StepPick k = step_pick(q);
     if (k.rc) return k.rc;
@@ -1030,6 +1038,7 @@ static int train_step_impl(const drgnn_net_desc* net, const drgnn_head_desc* hd,
         (plan->family != k.family || plan->width != k.width || plan->cls != k.cls || plan->slabs_per_graph != k.slabs))
         return DRGNN_E_CAPACITY;
     if (co_ok && k.builder_roles == 0) co_ok = false;      // the builder gets a launch of its own
+    if (ens && (k.wgs != 1 || (k.kernel != SK_AF3B && k.kernel != SK_AF2))) return DRGNN_E_CAPACITY;
     if (co_ok) T.roles = k.builder_roles;
 
     StepLaunch L;
@@ -1087,7 +1096,8 @@ static int train_step_impl(const drgnn_net_desc* net, const drgnn_head_desc* hd,
     hf.readout = readout; hf.step = step2; hf.pred = pred; hf.partials = head_partials; hf.stage = 0;
 
     // grid of the step part: graphs in groups of 8 x 2 when a graph has two workgroups (step2_block, step3_block)
-    const int blocks = (k.wgs == 2) ? (int)((n_graphs + 7) / 8) * 16 : (int)n_graphs;
+    // (ensemble: graphs in groups of 8 x K, see ens_slot)
+    const int blocks = ens ? (int)((n_graphs + 7) / 8) * 8 * ens_K : (k.wgs == 2) ? (int)((n_graphs + 7) / 8) * 16 : (int)n_graphs;
     if (blocks > 0) {
 #ifdef DRGNN_EMU
         if (kind == DRGNN_GINET) emu_step<DRGNN_GINET>(a, full_step, k.capN, k.capE, k.capC);
@@ -1119,6 +1129,11 @@ static int train_step_impl(const drgnn_net_desc* net, const drgnn_head_desc* hd,
             Q.pf_coef = (kind != DRGNN_GINET) ? 1 : 0;
             Q.pf_y = full_step ? target : nullptr; Q.pf_y_bytes = (hd->task == DRGNN_TASK_REG) ? 4 : 8;
             if (Q.pf_tiles != nullptr) extra = Q.pf_n; else Q.pf_ids = nullptr;
+        }
+        if (ens) {
+            const drgnn_ens_kernel_t ek = af_ens_kernel(kind, k.width, k.cls, kind == DRGNN_GINET ? (k.sg ? 1 : 0) : k.xg);
+            if (!ek) return DRGNN_E_CAPACITY;
+            return step_launch(reinterpret_cast<drgnn_step_kernel_t>(ek), k.lds, (unsigned)blocks, (hipStream_t)stream_, C, ens, ens_K);
         }
         drgnn_step_kernel_t kern = nullptr;
         const bool gather = gather_ids != nullptr;
@@ -1159,6 +1174,36 @@ int drgnn_net_train_step_cached(const drgnn_net_desc* net, const drgnn_head_desc
     return train_step_impl(net, hd, cache->x, cache->y, step2, cache->ws_i32, cache->ws_f32, cache->n_nodes,
                            cache->n_edges, n_graphs, cache->n_graphs, ids, max_nodes, max_edges, max_c0, pred, readout,
                            head_partials, partials, xchg, nullptr, hints, stream_);
+}
+
+int32_t drgnn_ens_step_plan(drgnn_step_plan* p, int32_t K) {
+    if (!p) return 0;
+    p->train = 0;
+    p->force_wgs = 1;      // the one-workgroup-per-graph forms: no workgroup of the launch waits for another
+    p->co_built_graphs = 0;
+    const int32_t wgs = drgnn_net_step_plan(p);
+#ifdef DRGNN_EMU
+    p->family = DRGNN_STEP_FAMILY_NONE;
+    return 0;
+#else
+    if (K < 1 || wgs != 1 || p->family != DRGNN_STEP_FAMILY_AGGREGATE || p->lds_bytes <= 0 || p->lds_bytes > DRGNN_LDS_LIMIT ||
+        (int64_t)K * ((p->n_graphs + 7) / 8) * 8 > (int64_t)INT32_MAX) {
+        p->family = DRGNN_STEP_FAMILY_NONE;
+        return 0;
+    }
+    return 1;
+#endif
+}
+
+int drgnn_ens_predict_cached(const drgnn_net_desc* net, const drgnn_head_desc* hd, const drgnn_ens_member* members,
+                             int32_t K, const drgnn_topology_cache* cache, const int32_t* ids, int64_t n_graphs,
+                             int32_t max_nodes, int32_t max_edges, int32_t max_c0, int32_t* step2, float* pred,
+                             float* readout, const drgnn_step_hints* hints, void* stream_) {
+    if (!members || K < 1 || !hd || hd->train || !pred || !readout) return DRGNN_E_ARG;
+    if (!cache || !ids || !cache->ws_i32 || !cache->x || n_graphs < 0 || n_graphs > cache->n_graphs) return DRGNN_E_ARG;
+    return train_step_impl(net, hd, cache->x, cache->y, step2, cache->ws_i32, cache->ws_f32, cache->n_nodes,
+                           cache->n_edges, n_graphs, cache->n_graphs, ids, max_nodes, max_edges, max_c0, pred, readout,
+                           nullptr, nullptr, nullptr, nullptr, hints, stream_, members, K);
 }
 
 int drgnn_net_reduce_grads(const drgnn_net_desc* net, const float* partials, int64_t n_nodes,

@@ -431,41 +431,41 @@ struct StepCoLaunch {
 // block ids apart (same XCD: they read the same x tile and topology and hand each other pooled rows), graphs in groups
 // of 8 like GINet's branch workgroups.
 template <int KIND, int XF, bool GATHER, int CLS, int SPLIT, bool TRAIN, int XG = 0>
-DEV void step2_block(const StepLaunch& L, int blk, float* lds) {
+DEV void step2_block(const StepLaunch& L, const StepArgs& A, int blk, float* lds) {
     int g, half;
     if (SPLIT == 2) { g = ((blk >> 4) << 3) + (blk & 7); half = (blk >> 3) & 1; }
     else { g = blk; half = 0; }
-    if (g >= L.a.n_graphs) return;
+    if (g >= A.n_graphs) return;
     if (L.dims.count > 0) {
         const int gi = GATHER ? L.dims.gi[g] : g;
         GraphDims d;
         d.n0 = L.dims.n0[g]; d.N = L.dims.n[g]; d.e0 = L.dims.e0[g]; d.E = L.dims.e[g];
         d.rowbase = d.n0 + gi;
         d.C = 0; d.E1 = 0; d.C1 = 0;
-        const int cnt_c = L.a.tv.p[DRGNN_TI_NC0][gi], cnt_e1 = L.a.tv.p[DRGNN_TI_NE1][gi], cnt_c1 = L.a.tv.p[DRGNN_TI_NC1][gi];
-        const int32_t* hs = L.a.tv.p[DRGNN_TI_HSPLIT] + 4 * gi;
+        const int cnt_c = A.tv.p[DRGNN_TI_NC0][gi], cnt_e1 = A.tv.p[DRGNN_TI_NE1][gi], cnt_c1 = A.tv.p[DRGNN_TI_NC1][gi];
+        const int32_t* hs = A.tv.p[DRGNN_TI_HSPLIT] + 4 * gi;
         const int hk = (SPLIT == 2) ? hs[0] : 0, hq = (SPLIT == 2) ? hs[1] : 0, hn = (SPLIT == 2) ? hs[2] : 0;
-        net_step2_graph<KIND, XF, GATHER, CLS, SPLIT, TRAIN, XG>(L.a, d, g, gi, half, lds, L.capN, L.capE, L.capC, true, cnt_c, cnt_e1,
+        net_step2_graph<KIND, XF, GATHER, CLS, SPLIT, TRAIN, XG>(A, d, g, gi, half, lds, L.capN, L.capE, L.capC, true, cnt_c, cnt_e1,
                                                              cnt_c1, hk, hq, hn);
         return;
     }
-    const int gi = GATHER ? WG_UNIFORM(L.a.gather_ids[g]) : g;
-    const GraphDims d = net_dims(L.a.tv, gi);
-    const int32_t* hs = L.a.tv.p[DRGNN_TI_HSPLIT] + 4 * gi;
+    const int gi = GATHER ? WG_UNIFORM(A.gather_ids[g]) : g;
+    const GraphDims d = net_dims(A.tv, gi);
+    const int32_t* hs = A.tv.p[DRGNN_TI_HSPLIT] + 4 * gi;
     const int hk = (SPLIT == 2) ? WG_UNIFORM(hs[0]) : 0, hq = (SPLIT == 2) ? WG_UNIFORM(hs[1]) : 0, hn = (SPLIT == 2) ? WG_UNIFORM(hs[2]) : 0;
     if (d.N > L.capN || d.E > L.capE || d.C > L.capC) {
         // the caller's bounds were wrong: poison the outputs instead of overrunning LDS (the partner does the same: no wait)
         if (half == 0) {
-            FOR_TID(c, L.a.hf.R) { const_cast<float*>(L.a.hf.readout)[(long)g * L.a.hf.R + c] = DRGNN_NAN; }
+            FOR_TID(c, A.hf.R) { const_cast<float*>(A.hf.readout)[(long)g * A.hf.R + c] = DRGNN_NAN; }
             if (TRAIN) {
-                float* hp = L.a.hf.partials + (long)g * head_compact_floats(L.a.hf.R, L.a.hf.H, L.a.hf.O);
-                FOR_TID(i, (int)head_compact_floats(L.a.hf.R, L.a.hf.H, L.a.hf.O)) { hp[i] = DRGNN_NAN; }
+                float* hp = A.hf.partials + (long)g * head_compact_floats(A.hf.R, A.hf.H, A.hf.O);
+                FOR_TID(i, (int)head_compact_floats(A.hf.R, A.hf.H, A.hf.O)) { hp[i] = DRGNN_NAN; }
             }
-            FOR_TID(o, L.a.hf.O) { L.a.hf.pred[(long)g * L.a.hf.O + o] = DRGNN_NAN; }
+            FOR_TID(o, A.hf.O) { A.hf.pred[(long)g * A.hf.O + o] = DRGNN_NAN; }
         }
         return;
     }
-    net_step2_graph<KIND, XF, GATHER, CLS, SPLIT, TRAIN, XG>(L.a, d, g, gi, half, lds, L.capN, L.capE, L.capC, false, 0, 0, 0, hk, hq, hn);
+    net_step2_graph<KIND, XF, GATHER, CLS, SPLIT, TRAIN, XG>(A, d, g, gi, half, lds, L.capN, L.capE, L.capC, false, 0, 0, 0, hk, hq, hn);
 }
 #endif
 
@@ -510,34 +510,34 @@ DEV void step3_block(const StepLaunch& L, int blk, float* lds) {
 #ifndef DRGNN_EMU
 // GINet, aggregation first, both branches of a graph in one workgroup (drgnn_step3.h, net_step3_graph_both)
 template <int XF, bool GATHER, int CLS, bool TRAIN, bool SG = false>
-DEV void step3b_block(const StepLaunch& L, int g, float* lds) {
+DEV void step3b_block(const StepLaunch& L, const StepArgs& A, int g, float* lds) {
     // the capacity-class training instance of the 32-wide kernel works the two branches off side by side (drgnn_step3.h: DUAL;
     // step_pick sizes the launch's LDS for it)
     constexpr bool DUAL = !SG && STEP3B_DUAL(XF, CLS, TRAIN);
-    if (g >= L.a.n_graphs) return;
+    if (g >= A.n_graphs) return;
     if (L.dims.count > 0) {
         const int gi = GATHER ? L.dims.gi[g] : g;
         GraphDims d;
         d.n0 = L.dims.n0[g]; d.N = L.dims.n[g]; d.e0 = L.dims.e0[g]; d.E = L.dims.e[g];
         d.rowbase = d.n0 + gi;
         d.C = 0; d.E1 = 0; d.C1 = 0;
-        const int cnt_c = L.a.tv.p[DRGNN_TI_NC0][gi], cnt_e1 = L.a.tv.p[DRGNN_TI_NE1][gi], cnt_c1 = L.a.tv.p[DRGNN_TI_NC1][gi];
-        net_step3_graph_both<XF, GATHER, CLS, TRAIN, DUAL, SG>(L.a, d, g, gi, lds, L.capN, L.capE, L.capC, true, cnt_c, cnt_e1, cnt_c1);
+        const int cnt_c = A.tv.p[DRGNN_TI_NC0][gi], cnt_e1 = A.tv.p[DRGNN_TI_NE1][gi], cnt_c1 = A.tv.p[DRGNN_TI_NC1][gi];
+        net_step3_graph_both<XF, GATHER, CLS, TRAIN, DUAL, SG>(A, d, g, gi, lds, L.capN, L.capE, L.capC, true, cnt_c, cnt_e1, cnt_c1);
         return;
     }
-    const int gi = GATHER ? WG_UNIFORM(L.a.gather_ids[g]) : g;
-    const GraphDims d = net_dims(L.a.tv, gi);
+    const int gi = GATHER ? WG_UNIFORM(A.gather_ids[g]) : g;
+    const GraphDims d = net_dims(A.tv, gi);
     if (d.N > L.capN || d.E > L.capE || d.C > L.capC) {
         // the caller's bounds were wrong: poison the outputs instead of overrunning LDS
-        FOR_TID(c, L.a.hf.R) { const_cast<float*>(L.a.hf.readout)[(long)g * L.a.hf.R + c] = DRGNN_NAN; }
+        FOR_TID(c, A.hf.R) { const_cast<float*>(A.hf.readout)[(long)g * A.hf.R + c] = DRGNN_NAN; }
         if (TRAIN) {
-            float* hp = L.a.hf.partials + (long)g * head_compact_floats(L.a.hf.R, L.a.hf.H, L.a.hf.O);
-            FOR_TID(i, (int)head_compact_floats(L.a.hf.R, L.a.hf.H, L.a.hf.O)) { hp[i] = DRGNN_NAN; }
+            float* hp = A.hf.partials + (long)g * head_compact_floats(A.hf.R, A.hf.H, A.hf.O);
+            FOR_TID(i, (int)head_compact_floats(A.hf.R, A.hf.H, A.hf.O)) { hp[i] = DRGNN_NAN; }
         }
-        FOR_TID(o, L.a.hf.O) { L.a.hf.pred[(long)g * L.a.hf.O + o] = DRGNN_NAN; }
+        FOR_TID(o, A.hf.O) { A.hf.pred[(long)g * A.hf.O + o] = DRGNN_NAN; }
         return;
     }
-    net_step3_graph_both<XF, GATHER, CLS, TRAIN, DUAL, SG>(L.a, d, g, gi, lds, L.capN, L.capE, L.capC, false, 0, 0, 0);
+    net_step3_graph_both<XF, GATHER, CLS, TRAIN, DUAL, SG>(A, d, g, gi, lds, L.capN, L.capE, L.capC, false, 0, 0, 0);
 }
 #endif
 
@@ -796,7 +796,7 @@ __global__ void __launch_bounds__(DRGNN_NTHREADS) k_step2_co_topo(StepCoLaunch C
     const StepCoLaunch& C = step_kernarg();
     co_kernarg_touch();
     STEP_CO_ROLES(C);
-    if (co_is_step_) step2_block<KIND, XF, GATHER, CLS, SPLIT, TRAIN, XG>(C.step, co_step_blk_, smem_s2);
+    if (co_is_step_) step2_block<KIND, XF, GATHER, CLS, SPLIT, TRAIN, XG>(C.step, C.step.a, co_step_blk_, smem_s2);
     else topo_block<true, (KIND == DRGNN_SGAT) ? -1 : 0>(C.topo, co_topo_blk_, (int*)smem_s2);
 }
 // GINet, aggregation first (drgnn_step3.h) + the builder's workgroups
@@ -819,8 +819,54 @@ __global__ void __launch_bounds__(DRGNN_NTHREADS) k_step3b_co_topo(StepCoLaunch 
     const StepCoLaunch& C = step_kernarg();
     co_kernarg_touch();
     STEP_CO_ROLES(C);
-    if (co_is_step_) step3b_block<XF, GATHER, CLS, TRAIN, SG>(C.step, co_step_blk_, smem_s3b);
+    if (co_is_step_) step3b_block<XF, GATHER, CLS, TRAIN, SG>(C.step, C.step.a, co_step_blk_, smem_s3b);
     else topo_block<true, 0>(C.topo, co_topo_blk_, (int*)smem_s3b);
+}
+// ---- ensemble inference (include/drgnn.h: drgnn_ens_member): K checkpoints of one net in one launch, one workgroup per
+// (model, graph), forward + head only.  Graph g of model m takes block ((g >> 3) K + m) 8 + (g & 7): a graph keeps the XCD
+// (block id mod 8) the single-model numbering gives it and its K models sit 8 block ids apart, so its topology, tiles and x rows
+// are read into one L2 and served from there to the other K - 1 workgroups.  Only the one-workgroup-per-graph forms exist: no
+// workgroup waits for another, so any K x B is safe whatever stays resident.  Model m's conv parameters and head come from
+// entry m of the member table (plain loads, uniform per workgroup); its outputs go to pred + m B O and readout + m B R.
+DEV bool ens_slot(int blk, int K, int n_graphs, int& g, int& m) {
+    const int q = blk >> 3;
+    m = q % K;
+    g = (q / K) * 8 + (blk & 7);
+    return g < n_graphs;
+}
+DEV void ens_args(StepArgs& a, const drgnn_ens_member* models, int m) {
+    const drgnn_ens_member& mm = models[m];
+    a.net = mm.net;
+    a.hf.w1 = mm.w1; a.hf.b1 = mm.b1; a.hf.w2 = mm.w2; a.hf.b2 = mm.b2;
+    a.hf.pred = a.hf.pred + (long)m * a.hf.B * a.hf.O;
+    a.hf.readout = a.hf.readout + (long)m * a.hf.B * a.hf.R;
+}
+typedef void (*drgnn_ens_kernel_t)(StepCoLaunch, const drgnn_ens_member*, int);
+// GINet, both branches of a graph in one workgroup (SG: the S-from-memory form)
+template <int XF, int CLS, bool SG>
+__global__ void __launch_bounds__(DRGNN_NTHREADS) k_step3b_ens(StepCoLaunch C_by_value, const drgnn_ens_member* models, int K) {
+    extern __shared__ __attribute__((aligned(16))) float smem_e3[];
+    PHASE_BEGIN();
+    const StepCoLaunch& C = step_kernarg();
+    co_kernarg_touch();
+    int g, m;
+    if (!ens_slot((int)blockIdx.x, K, C.step.a.n_graphs, g, m)) return;
+    StepArgs a = C.step.a;
+    ens_args(a, models, m);
+    step3b_block<XF, true, CLS, false, SG>(C.step, a, g, smem_e3);
+}
+// sGAT / FoutNet, one workgroup per graph (XG: the from-memory levels)
+template <int KIND, int XF, int CLS, int XG>
+__global__ void __launch_bounds__(DRGNN_NTHREADS) k_step2_ens(StepCoLaunch C_by_value, const drgnn_ens_member* models, int K) {
+    extern __shared__ __attribute__((aligned(16))) float smem_e2[];
+    PHASE_BEGIN();
+    const StepCoLaunch& C = step_kernarg();
+    co_kernarg_touch();
+    int g, m;
+    if (!ens_slot((int)blockIdx.x, K, C.step.a.n_graphs, g, m)) return;
+    StepArgs a = C.step.a;
+    ens_args(a, models, m);
+    step2_block<KIND, XF, true, CLS, 1, false, XG>(C.step, a, g, smem_e2);
 }
 #ifdef DRGNN_KERNELS_MAIN
 __global__ void __launch_bounds__(DRGNN_NTHREADS) k_conv_gemm(ConvLayerArgs a) { conv_gemm_block(a, blockIdx.x); }

@@ -21,6 +21,9 @@ typedef void (*drgnn_step_kernel_t)(StepCoLaunch);
 #define DRGNN_AF_SGAT_XG 6        // k_step2_co_topo<DRGNN_SGAT, ., ., 0, ., ., true>: x rows read from memory (graphs beyond the staged form's LDS)
 #define DRGNN_AF_FOUT_XG 7        // ... of FoutNet
 #define DRGNN_AF_GINET_SG 8       // k_step3b_co_topo<., ., 0, ., true>: S rows read from memory (graphs beyond the staged form's LDS)
+#define DRGNN_AF_GINET_ENS 9      // k_step3b_ens: ensemble inference (K models per launch), GINet
+#define DRGNN_AF_SGAT_ENS 10      // k_step2_ens<DRGNN_SGAT>
+#define DRGNN_AF_FOUT_ENS 11      // k_step2_ens<DRGNN_FOUT>
 
 // (cls: 1 = capacity-class layout, honoured for the 32- and 48-wide kernels only, training and inference launches -- the host
 // asks for nothing else; 48: the feature count of the reference's shipped regression models)
@@ -84,6 +87,32 @@ template <int KIND, int XF> drgnn_step_kernel_t af_pick_single_xg(bool gather, i
     if constexpr (XF >= 32) { if (level == 2) return af_pick_single_xg_level<KIND, XF, 2>(gather, split, train); }
     return level == 1 ? af_pick_single_xg_level<KIND, XF, 1>(gather, split, train) : nullptr;
 }
+// the ensemble instances (drgnn_kernels.h: k_step3b_ens / k_step2_ens): the inference instances of the one-workgroup forms a
+// single-model launch takes, with a model axis.  level: GINet 1 = S from memory; sGAT / FoutNet 1 / 2 = the from-memory levels
+template <int XF> drgnn_ens_kernel_t af_pick_ginet_ens(int cls, int level) {
+    constexpr int C1 = (XF == 32 || XF == 48) ? 1 : 0;
+    if (level) return k_step3b_ens<XF, 0, true>;
+    if (cls && C1) return k_step3b_ens<XF, C1, false>;
+    return k_step3b_ens<XF, 0, false>;
+}
+template <int KIND, int XF> drgnn_ens_kernel_t af_pick_single_ens(int cls, int level) {
+    constexpr int C1 = (XF == 32 || XF == 48) ? 1 : 0;
+    if (level == 1) return k_step2_ens<KIND, XF, 0, 1>;
+    if constexpr (XF >= 32) { if (level == 2) return k_step2_ens<KIND, XF, 0, 2>; }
+    if (level) return nullptr;
+    if (cls && C1) return k_step2_ens<KIND, XF, C1, 0>;
+    return k_step2_ens<KIND, XF, 0, 0>;
+}
+#define DRGNN_AF_DEFINE_GINET_ENS(W) DRGNN_AF_DEFINE_GINET_ENS_X(W)
+#define DRGNN_AF_DEFINE_SGAT_ENS(W) DRGNN_AF_DEFINE_SGAT_ENS_X(W)
+#define DRGNN_AF_DEFINE_FOUT_ENS(W) DRGNN_AF_DEFINE_FOUT_ENS_X(W)
+#define DRGNN_AF_DEFINE_GINET_ENS_X(W) \
+    drgnn_ens_kernel_t af_ginet_ens_##W(int cls, int level) { return af_pick_ginet_ens<W>(cls, level); }
+#define DRGNN_AF_DEFINE_SGAT_ENS_X(W) \
+    drgnn_ens_kernel_t af_sgat_ens_##W(int cls, int level) { return af_pick_single_ens<DRGNN_SGAT, W>(cls, level); }
+#define DRGNN_AF_DEFINE_FOUT_ENS_X(W) \
+    drgnn_ens_kernel_t af_fout_ens_##W(int cls, int level) { return af_pick_single_ens<DRGNN_FOUT, W>(cls, level); }
+
 #define DRGNN_AF_DEFINE_SGAT_XG(W) DRGNN_AF_DEFINE_SGAT_XG_X(W)
 #define DRGNN_AF_DEFINE_FOUT_XG(W) DRGNN_AF_DEFINE_FOUT_XG_X(W)
 #define DRGNN_AF_DEFINE_SGAT_XG_X(W) \
@@ -100,6 +129,9 @@ template <int KIND, int XF> drgnn_step_kernel_t af_pick_single_xg(bool gather, i
     drgnn_step_kernel_t af_sgat_##W(bool gather, int cls, int split, bool train);              \
     drgnn_step_kernel_t af_fout_##W(bool gather, int cls, int split, bool train);              \
     drgnn_step_kernel_t af_sgat_whole_##W(int cls);                                            \
+    drgnn_ens_kernel_t af_ginet_ens_##W(int cls, int level);                                   \
+    drgnn_ens_kernel_t af_sgat_ens_##W(int cls, int level);                                    \
+    drgnn_ens_kernel_t af_fout_ens_##W(int cls, int level);                                    \
     template <> inline drgnn_step_kernel_t af_sgat_whole<W>(int cls) { return af_sgat_whole_##W(cls); }
 DRGNN_AF_DECLARE(16) DRGNN_AF_DECLARE(32) DRGNN_AF_DECLARE(48) DRGNN_AF_DECLARE(64)
 #undef DRGNN_AF_DECLARE
@@ -138,6 +170,9 @@ DRGNN_AF_FOR_WIDTHS(DRGNN_AF_DEFINE_SGAT)
 DRGNN_AF_FOR_WIDTHS(DRGNN_AF_DEFINE_FOUT)
 DRGNN_AF_FOR_WIDTHS(DRGNN_AF_DEFINE_SGAT_WHOLE)
 DRGNN_AF_FOR_WIDTHS(DRGNN_AF_DEFINE_SGAT_XG)
+DRGNN_AF_FOR_WIDTHS(DRGNN_AF_DEFINE_GINET_ENS)
+DRGNN_AF_FOR_WIDTHS(DRGNN_AF_DEFINE_SGAT_ENS)
+DRGNN_AF_FOR_WIDTHS(DRGNN_AF_DEFINE_FOUT_ENS)
 DRGNN_AF_FOR_WIDTHS(DRGNN_AF_DEFINE_FOUT_XG)
 #endif
 // family: DRGNN_AF_*; width: 16 / 32 / 48 / 64.  nullptr: no such instance
@@ -160,6 +195,22 @@ static drgnn_step_kernel_t af_step_kernel(int family, int width, bool gather, in
     default: return nullptr;
     }
 #undef DRGNN_AF_CASE
+}
+// the ensemble instance of (kind, width, cls, from-memory level)
+static drgnn_ens_kernel_t af_ens_kernel(int kind, int width, int cls, int level) {
+#define DRGNN_AF_ENS_CASE(W)                                                                   \
+    case W:                                                                                     \
+        switch (kind) {                                                                         \
+        case DRGNN_GINET: return af_ginet_ens_##W(cls, level);                                  \
+        case DRGNN_SGAT: return af_sgat_ens_##W(cls, level);                                    \
+        case DRGNN_FOUT: return af_fout_ens_##W(cls, level);                                    \
+        default: return nullptr;                                                                \
+        }
+    switch (width) {
+        DRGNN_AF_FOR_WIDTHS(DRGNN_AF_ENS_CASE)
+    default: return nullptr;
+    }
+#undef DRGNN_AF_ENS_CASE
 }
 #endif  // DRGNN_KERNELS_MAIN
 

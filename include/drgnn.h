@@ -692,6 +692,27 @@ int drgnn_net_train_step_cached(const drgnn_net_desc* net, const drgnn_head_desc
                                 float* readout, float* head_partials, float* partials, uint64_t* xchg,
                                 const drgnn_step_hints* hints /* optional */, void* stream);
 
+/* Ensemble inference: K checkpoints of one net (same kind, F, R, H, O) over the same cached graphs in ONE launch, one
+ * workgroup per (model, graph).  The member table lives in DEVICE memory, K entries, written once by the caller: member m's
+ * conv parameters (same strides as a single model's) and FC head. */
+typedef struct drgnn_ens_member {
+    drgnn_net_desc net;
+    const float* w1; const float* b1; const float* w2; const float* b2;
+} drgnn_ens_member;
+/* The plan of an ensemble launch of K models over plan->n_graphs graphs (inference; the `in` members as for
+ * drgnn_net_step_plan, whose `out` members it fills).  Returns 1 when the fused ensemble launch takes these bounds (its
+ * workgroups never wait for each other: every K x n_graphs), 0 otherwise (family NONE: the caller launches the K models
+ * one by one). */
+int32_t drgnn_ens_step_plan(drgnn_step_plan* plan, int32_t K);
+/* The ensemble launch over the graphs ids[0..n_graphs) of a cached set: pred [K][n_graphs][O], readout [K][n_graphs][R]
+ * (member m's slot g = what drgnn_net_train_step_cached of that member alone writes for graph ids[g] with the plan's
+ * layout).  `net` / `head`: member 0's descriptors (shapes, task, sigmoid; their pointers are not read).  hints->plan: the
+ * plan drgnn_ens_step_plan returned (required). */
+int drgnn_ens_predict_cached(const drgnn_net_desc* net, const drgnn_head_desc* head, const drgnn_ens_member* members,
+                             int32_t K, const drgnn_topology_cache* cache, const int32_t* ids, int64_t n_graphs,
+                             int32_t max_nodes, int32_t max_edges, int32_t max_c0, int32_t* step2, float* pred,
+                             float* readout, const drgnn_step_hints* hints, void* stream);
+
 /* Data-parallel hook of the native epoch loop: called on the host once per mini-batch, after the launches that leave
  * this rank's gradient of mini-batch `batch_index` in flat_grad have been ENQUEUED on `stream`; it must enqueue the
  * exchange (one all-reduce of flat_grad, weighted n_local / n_global) on the same stream and return 0.  The loop then
