@@ -17,10 +17,18 @@ consecutive_cluster, pool_edge; here: the topology kernel) -- MSE loss, backward
 step.  The step is captured once in a hipGraph and replayed (``--mode eager`` runs the same
 Python step without capture).
 
-Extra objects in the JSON line:
+A plain run does only what the headline needs: set up, warm up, time the K steps, write --dump-outputs, print the
+line.  `--full` adds the secondary figures below, each measured after the timed steps and the dump (so they change
+neither `value` nor the dumped arrays); --no-cpu-baseline, --no-dropin, --no-other-nets and --epoch-graphs 0 drop
+single ones of them again.  Opt-in checks (--dp-selftest, --dp-distinct) run whenever they are asked for.
+
+Extra objects in the JSON line under --full:
   roofline      HBM roofline of the dominant kernel: algorithmic bytes per launch
                 (SURVEY.md §8(d) per-graph figures x 64 graphs) / its average duration measured
                 here with HIP events over back-to-back launches on the launch stream.
+  distinct_batches, epoch_loop, dropin_loop, neuralnet_train, inference_loop, other_nets
+                the same step over different mini-batches, the native epoch / inference loops, the
+                drop-in trainer loop, NeuralNet.train end to end, sGAT and FoutNet (N=1 only).
   cpu_baseline  the CPU oracle (oracle/cpu_ref.py: the reference's algorithm, op for op, in
                 PyTorch) timed on this box's host cores on a bounded sample, rank 0, N=1 only.
 """
@@ -132,6 +140,10 @@ def parse():
     ap.add_argument("--dp-distinct", action="store_true",
                     help="also time the same (data-parallel) schedule over a cycle of 32 DIFFERENT synthetic mini-batches per rank "
                          "(`dp_distinct` in the line): the figure without the L2 residency of a replayed mini-batch")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the secondary figures of the line (roofline, distinct_batches, "
+                         "epoch_loop, dropin_loop, neuralnet_train, inference_loop, other_nets, cpu_baseline); a plain run "
+                         "reports the timed steps alone")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-dropin", action="store_true", help="skip the drop-in loop figures (dropin_loop)")
     ap.add_argument("--counter-pass", action="store_true",
@@ -613,7 +625,7 @@ def main():
                                     "rebuilt every step; the build of step t+1 shares step t's backward launch "
                                     "(double-buffered)" if pipeline else "rebuilt every step, own launch"),
                        "input": "ONE synthetic mini-batch replayed every step (its graphs stay in the XCDs' L2 between steps: "
-                                "`distinct_batches` and `epoch_loop` in this line are the figures without that)",
+                                "`distinct_batches` and `epoch_loop` of the --full line are the figures without that)",
                        "final_loss": final_loss, "host_pool_threads": torch.get_num_threads()},
         }
         if split:
@@ -629,10 +641,10 @@ def main():
             result["config"]["dp_selftest"] = selftest
         if dp_distinct is not None:
             result["dp_distinct"] = dp_distinct
-        if native:
+        if native and args.full:
             result["roofline"] = measure_roofline(net, args.net, batch, dev, value / world,
                                                   cache=(cache, ids_host, ids_dev) if cached else None)
-        if world == 1 and native and args.epoch_graphs > 0:
+        if args.full and world == 1 and native and args.epoch_graphs > 0:
             try:
                 result["distinct_batches"] = measure_distinct_batches(Net, args.net, dev)
             except Exception as exc:                      # secondary figure: never lose the bench line over it
@@ -652,7 +664,7 @@ def main():
                 result["inference_loop"] = measure_inference_loop(Net, args.net, args.epoch_graphs, dev)
             except Exception as exc:                      # secondary figure: never lose the bench line over it
                 result["inference_loop"] = {"error": repr(exc)[:200]}
-        if world == 1 and native and args.net == "GINet" and not args.no_other_nets and N_FEAT == 32:
+        if args.full and world == 1 and native and args.net == "GINet" and not args.no_other_nets and N_FEAT == 32:
             # BASELINE.json configs[2] / configs[3] in the same line (driver evidence for the single-branch nets)
             result["other_nets"] = {}
             for other in ("sGAT", "FoutNet"):
@@ -660,7 +672,7 @@ def main():
                     result["other_nets"][other] = measure_other_net(other, batch, dev)
                 except Exception as exc:                  # secondary figure: never lose the bench line over it
                     result["other_nets"][other] = {"error": repr(exc)[:200]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(args.net, batch_cpu, args.cpu_seconds)
     if world > 1:
         dist.barrier()

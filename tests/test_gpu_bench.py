@@ -12,13 +12,34 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
 
-def _bench(out_dir, steps, warmup):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
-           "--dump-outputs", out_dir, "--no-cpu-baseline", "--epoch-graphs", "0", "--no-other-nets"]
+FULL_ONLY = ("roofline", "distinct_batches", "epoch_loop", "dropin_loop", "neuralnet_train", "inference_loop", "other_nets",
+             "cpu_baseline")
+
+
+def _line(*args):
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + list(args)
     run = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert run.returncode == 0, run.stderr.decode()[-2000:]
     line = [ln for ln in run.stdout.decode().splitlines() if ln.startswith("{")][-1]
     return json.loads(line)
+
+
+def _bench(out_dir, steps, warmup):
+    return _line("--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", out_dir, "--no-cpu-baseline",
+                 "--epoch-graphs", "0", "--no-other-nets")
+
+
+def test_plain_run_reports_the_timed_steps_alone_and_full_adds_the_secondary_figures():
+    plain = _line("--steps", "3", "--warmup", "1")
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in plain, key
+    assert plain["value"] > 0 and plain["unit"] == "graphs/s" and plain["higher_is_better"] is True
+    assert not [k for k in FULL_ONLY if k in plain]
+    # --full, with the long legs dropped again by their own options: the roofline and the CPU oracle come back
+    full = _line("--steps", "3", "--warmup", "1", "--full", "--epoch-graphs", "0", "--no-other-nets", "--cpu-seconds", "1")
+    assert full["roofline"]["kernel_us"] > 0 and full["roofline"]["kernel"] in full["roofline"]["kernels"]
+    assert full["cpu_baseline"]["value"] > 0
+    assert not [k for k in FULL_ONLY if k in full and k not in ("roofline", "cpu_baseline")]
 
 
 def test_steps_are_the_timed_steps_and_dumped_outputs_repeat(tmp_path):

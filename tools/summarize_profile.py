@@ -93,7 +93,7 @@ for b in ("benchline.json", "benchline_driver_args.json"):
     if os.path.exists(os.path.join(src, b)) and os.path.getsize(os.path.join(src, b)) > 0:
         shutil.copy(os.path.join(src, b), os.path.join(out, name + "_" + b))
 with open(os.path.join(out, name + "_summary.md"), "w") as f:
-    f.write("# %s -- rocprofv3 --kernel-trace --stats -- python bench.py --net %s --no-cpu-baseline --epoch-graphs 0 --no-dropin\n\n" % (name, net))
+    f.write("# %s -- rocprofv3 --kernel-trace --stats -- python bench.py --full --net %s --no-cpu-baseline --epoch-graphs 0 --no-dropin\n\n" % (name, net))
     f.write("kernel sources hash `%s`\n\n" % meta["source_hash"])
     f.write("| kernel | calls | avg us | min us | max us | % of GPU time |\n|---|---|---|---|---|---|\n")
     for r in rows[:16]:
