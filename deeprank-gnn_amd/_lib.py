@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("DRGNN_LIB") or os.path.join(_HERE, "csrc", "libdrgnn.
 
 GINET, SGAT, FOUT = 0, 1, 2
 MAX_BRANCH = 2
+LDS_LIMIT = 160 * 1024     # LDS bytes one workgroup may allocate (gfx950)
 
 # enum drgnn_topo_i32 / drgnn_topo_f32 (include/drgnn.h)
 TI = {name: i for i, name in enumerate([

@@ -17,6 +17,7 @@ import torch
 
 from . import _lib
 from .functional import _describe
+from .launch import NetLayout, cached_flags, fused, head_desc, set_hints
 from .trainer import FusedTrainer
 
 # the properties the members of an ensemble must share (the ValueError names the first that differs)
@@ -96,17 +97,18 @@ class Ensemble(object):
             tr = FusedTrainer(net.to(self.device), task=self.task, api=api, transform_sigmoid=self.transform_sigmoid)
             tr.exp_avg = tr.exp_avg_sq = None          # inference only: no optimiser state
             self.trainers.append(tr)
+        tr0 = self.trainers[0]
+        lay = NetLayout(tr0.net)
         # the K parameter sets packed in ONE device buffer [K, P] (the members' parameters are views of their rows)
         self.params = torch.stack([tr.flat_p for tr in self.trainers])
         for m, tr in enumerate(self.trainers):
             tr.flat_p = self.params[m]
             with torch.no_grad():
-                for name, p in tr.net.named_parameters():
-                    off = tr.offset[name]
-                    p.data = self.params[m, off:off + p.numel()].view(p.shape)
-        tr0 = self.trainers[0]
-        self.kind, self.api, self.n_branch = tr0.kind, tr0.api, tr0.n_branch
-        self.R, self.H = tr0.R, tr0.H
+                lay.bind(tr.net, self.params[m])
+        self.kind, self.api, self.n_branch = lay.kind, tr0.api, lay.n_branch
+        self.R, self.H = lay.R, lay.H
+        self._head = head_desc(tr0.net, _lib.TASK_REG if self.task == "reg" else _lib.TASK_CLASS, False, 0.0, tr0.seed,
+                               self.transform_sigmoid)
         # the member table (drgnn_ens_member[K]) in device memory, written once; the host descriptors it was made from keep
         # the layout the launch checks against (member 0's)
         table = (_lib.EnsMember * self.K)()
@@ -182,11 +184,7 @@ class Ensemble(object):
         """drgnn_ens_step_plan of the ensemble launch over the graphs ``ids`` of ``cache`` (with the topology flags and tiles
         that launch reads), and those (flags, tiles)"""
         max_nodes, max_edges, max_c0 = cache.bounds(ids)
-        flags = int(getattr(cache.topo, "flags", 0))
-        tiles = cache.tiles_for(self.kind == _lib.SGAT) if (flags & _lib.TOPO_TILES) else None
-        if tiles is None or (self.n_feat % 4 == 0 and cache.set.x.data_ptr() % 16 != 0):
-            flags &= ~_lib.TOPO_TILES
-            tiles = None
+        flags, tiles = cached_flags(self.kind, cache)
         p = self.api.ens_step_plan(self.K, self.kind, self.n_feat, max_nodes, max_edges, max_c0, self.R, self.H, self.O,
                                    len(ids), flags)
         return p, (max_nodes, max_edges, max_c0), flags, tiles
@@ -195,16 +193,15 @@ class Ensemble(object):
         """[K, B, O] of ONE ensemble launch over the graphs ``ids``, or None when its plan is NONE"""
         ids = np.asarray(ids, dtype=np.int64).reshape(-1)
         p, (mn, me, mc), flags, tiles = self.plan(cache, ids)
-        if p.family == _lib.STEP_FAMILY_NONE or not (0 < p.lds_bytes <= 160 * 1024):
+        if not fused(p):
             return None
-        B, gset, tr0 = int(ids.size), cache.set, self.trainers[0]
+        B, gset = int(ids.size), cache.set
         pred = torch.empty((self.K, B, self.O), dtype=torch.float32, device=self.device)
         readout = torch.empty((self.K, B, self.R), dtype=torch.float32, device=self.device)
-        hints = _lib.step_hints(set_node_ptr=gset.node_ptr, set_edge_ptr=gset.edge_ptr, ids=ids, topo_flags=flags,
-                                tiles=tiles, plan=p)
-        self.api.ens_predict_cached(self._descs[0], tr0._head_desc(False), self.table, self.K,
-                                    cache.desc_for(self.kind == _lib.SGAT), ids_dev, B, mn, me, mc, tr0.step2, pred, readout,
-                                    _lib.current_stream(gset.x), hints[0])
+        hints = set_hints(gset, ids, flags, tiles, p)
+        self.api.ens_predict_cached(self._descs[0], self._head, self.table, self.K, cache.desc_for(self.kind == _lib.SGAT),
+                                    ids_dev, B, mn, me, mc, self.trainers[0].step2, pred, readout, _lib.current_stream(gset.x),
+                                    hints[0])
         return pred
 
     def _predict_batches(self, tr, rs, order, batch_size):

@@ -82,6 +82,17 @@ def _describe(kind, n_feat, params, n_branch):
     return desc
 
 
+def _conv_grads(kind, n_feat, grads, n_branch):
+    """(g_conv1, g_conv2): where the gradients of conv1 / conv2 of every branch go, inside the tensors ``grads`` (the live
+    parameters' order, include/drgnn.h: drgnn_conv_grads[DRGNN_MAX_BRANCH])"""
+    array = ConvGrads * _lib.MAX_BRANCH
+    g1, g2 = array(), array()
+    for b, (l1, l2) in enumerate(_split(kind, grads, n_branch)):
+        _fill_grads(g1[b], kind, l1, n_feat, H1)
+        _fill_grads(g2[b], kind, l2, H1, H2)
+    return g1, g2
+
+
 class _NetBody(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, topo, kind, n_branch, *params):
@@ -105,7 +116,7 @@ class _NetBody(torch.autograd.Function):
         readout = torch.empty((B, H2 * n_branch), dtype=torch.float32, device=dev)
         scratch = None
         lds = api.net_lds_bytes(kind, n_feat, topo.max_nodes, topo.max_edges, topo.max_c0, False)
-        if lds == 0 or lds > 160 * 1024:
+        if lds == 0 or lds > _lib.LDS_LIMIT:
             scratch = torch.empty(api.net_scratch_elems(kind, n_feat, n_nodes, topo.n_edges, B),
                                   dtype=torch.float32, device=dev)
         desc = _describe(kind, n_feat, params, n_branch)
@@ -134,15 +145,11 @@ class _NetBody(torch.autograd.Function):
             grad_x = torch.empty((n_branch, n_nodes, n_feat), dtype=torch.float32, device=dev)
         scratch = None
         lds = api.net_lds_bytes(kind, n_feat, topo.max_nodes, topo.max_edges, topo.max_c0, True)
-        if lds == 0 or lds > 160 * 1024:
+        if lds == 0 or lds > _lib.LDS_LIMIT:
             scratch = torch.empty(api.net_scratch_elems(kind, n_feat, n_nodes, topo.n_edges, B),
                                   dtype=torch.float32, device=dev)
         desc = _describe(kind, n_feat, params, n_branch)
-        g1 = (ConvGrads * _lib.MAX_BRANCH)()
-        g2 = (ConvGrads * _lib.MAX_BRANCH)()
-        for b, (l1, l2) in enumerate(_split(kind, grads, n_branch)):
-            _fill_grads(g1[b], kind, l1, n_feat, H1)
-            _fill_grads(g2[b], kind, l2, H1, H2)
+        g1, g2 = _conv_grads(kind, n_feat, grads, n_branch)
         stream = _lib.current_stream(x)
         api.net_backward(desc, x, grad_readout, topo.ws_i32, topo.ws_f32, n_nodes, topo.n_edges, B,
                          topo.max_nodes, topo.max_edges, topo.max_c0, xp, arg0, arg1, grad_x, partials,

@@ -30,22 +30,11 @@ import weakref
 import torch
 
 from . import _lib
-from .functional import H1, H2, _describe, _fill_grads, _split
+from .functional import H2, _conv_grads, _describe
+from .launch import ExchangeWords, NetLayout, batch_hints, fused, head_desc, tiles_match, usable_flags
 from .topology import Topology
 
-__all__ = ["StepEngine", "engine_for", "net_layout"]
-
-
-def net_layout(net):
-    """(kind, n_branch, [conv modules in kernel order]) of one of the three reference nets."""
-    name = type(net).__name__
-    if name == "GINet":
-        return _lib.GINET, 2, [net.conv1, net.conv2, net.conv1_ext, net.conv2_ext]
-    if name == "sGAT":
-        return _lib.SGAT, 1, [net.conv1, net.conv2]
-    if name == "FoutNet":
-        return _lib.FOUT, 1, [net.conv1, net.conv2]
-    raise TypeError("the fused step drives GINet / sGAT / FoutNet, not %s" % name)
+__all__ = ["StepEngine", "engine_for"]
 
 
 class _Call(object):
@@ -76,8 +65,11 @@ class StepEngine(object):
     def __init__(self, net, api=None):
         self.api = api or _lib.get()
         self.net = weakref.proxy(net)
-        self.kind, self.n_branch, convs = net_layout(net)
-        self.convs = convs
+        lay = NetLayout(net)
+        self.kind, self.n_branch, self.convs, self.offset, self.total = lay.kind, lay.n_branch, lay.convs, lay.offset, lay.total
+        self.head_offset, self.live, self.dead, self.R, self.H, self.O = lay.head_offset, lay.live, lay.dead, lay.R, lay.H, lay.O
+        if len(self.dead) > _lib.ZERO_RANGES:
+            raise _lib.DrgnnError("more untouched parameters than drgnn_step_gradients clears")
         named = list(net.named_parameters())
         self.names = [n for n, _ in named]
         # what engine_for compares before every call: the identity of every child module and every parameter that each module
@@ -88,27 +80,6 @@ class StepEngine(object):
         self.params = [p for _, p in named]
         dev = self.params[0].device
         self.device = dev
-        self.offset, off = {}, 0
-        for n, p in named:
-            self.offset[n] = off
-            off += p.numel()
-        self.total = off
-        head = ["fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias"]
-        expect = self.offset[head[0]]
-        self.head_offset = expect
-        lookup = dict(named)
-        for n in head:      # the slab sum writes the head's gradient as one contiguous block
-            if self.offset[n] != expect:
-                raise _lib.DrgnnError("unexpected parameter order for the FC head")
-            expect += lookup[n].numel()
-        self.live = tuple(p for c in convs for p in c.live_parameters())
-        live_ids = {id(p) for p in self.live}
-        head_ids = {id(lookup[n]) for n in head}
-        # parameters no kernel writes a gradient for (GINetConvLayer's attention: identically zero, ginet.py:63-66)
-        self.dead = [(self.offset[n], p.numel()) for n, p in named if id(p) not in live_ids and id(p) not in head_ids]
-        if len(self.dead) > _lib.ZERO_RANGES:
-            raise _lib.DrgnnError("more untouched parameters than drgnn_step_gradients clears")
-        self.R, self.H, self.O = net.fc1.in_features, net.fc1.out_features, net.fc2.out_features
         # Every backward writes ONE fresh flat buffer (a cached-allocator block, no launch) and hands autograd fresh views of it:
         # nobody else holds them, so AccumulateGrad adopts them as the parameters' .grad without a copy (16 copy launches per
         # step otherwise), and a gradient still referenced somewhere -- a .grad kept by the caller, a sum over several forwards
@@ -122,7 +93,7 @@ class StepEngine(object):
         self.seed = int(torch.initial_seed()) & 0xFFFFFFFF
         self._desc_key, self._desc, self._heads = None, None, {}
         self._bufs = {}            # (B, n_feat, slabs) -> [readout, partials, head slabs, owner weakref]
-        self._xchg = {}
+        self._xchg = ExchangeWords(self.n_branch, self.H)
         self._ones = {}
         self._fwd_readout = {}     # per batch size: the readout of forward-only launches (an output nobody reads)
         self._topos = weakref.WeakKeyDictionary()
@@ -168,12 +139,7 @@ class StepEngine(object):
             if self._live_slots is None:
                 index = {id(p): i for i, p in enumerate(self.params)}
                 self._live_slots = tuple(index[id(p)] for p in self.live)
-            live_grads = tuple(views[i] for i in self._live_slots)
-            g1 = (_lib.ConvGrads * _lib.MAX_BRANCH)()
-            g2 = (_lib.ConvGrads * _lib.MAX_BRANCH)()
-            for b, (l1, l2) in enumerate(_split(self.kind, live_grads, self.n_branch)):
-                _fill_grads(g1[b], self.kind, l1, n_feat, H1)
-                _fill_grads(g2[b], self.kind, l2, H1, H2)
+            g1, g2 = _conv_grads(self.kind, n_feat, tuple(views[i] for i in self._live_slots), self.n_branch)
             patch = [(g[b], f, getattr(g[b], f) - base) for g in (g1, g2) for b in range(self.n_branch)
                      for f in ("w_nbr", "w_self", "bias") if getattr(g[b], f)]
             zp = (ctypes.c_void_p * _lib.ZERO_RANGES)()
@@ -193,16 +159,8 @@ class StepEngine(object):
         key = (int(train), task, float(p_drop), None if mask is None else mask.data_ptr())
         hd = self._heads.get(key)
         if hd is None:
-            hd = self._heads[key] = _lib.HeadDesc()
-            n = self.net
-            hd.R, hd.H, hd.O, hd.task, hd.train = self.R, self.H, self.O, task, int(train)
-            hd.p_drop = float(p_drop)
-            hd.seed = self.seed
-            hd.transform_sigmoid = 0        # (NeuralNet.format_output transforms outside the model, NeuralNet.py:616-631)
-            hd.w1, hd.b1 = n.fc1.weight.data_ptr(), n.fc1.bias.data_ptr()
-            hd.w2, hd.b2 = n.fc2.weight.data_ptr(), n.fc2.bias.data_ptr()
-            hd.class_w = None
-            hd.drop_mask = None if mask is None else mask.data_ptr()
+            # (no sigmoid: NeuralNet.format_output transforms outside the model, NeuralNet.py:616-631)
+            hd = self._heads[key] = head_desc(self.net, task, train, p_drop, self.seed, drop_mask=mask)
         return hd
 
     # -- topology of a batch ---------------------------------------------------------------------------------------------
@@ -242,18 +200,6 @@ class StepEngine(object):
                 pass
         return topo
 
-    def _usable_flags(self, topo, x):
-        flags = int(getattr(topo, "flags", 0))
-        tiles = getattr(topo, "tiles", None)
-        ok = tiles is not None and (flags & _lib.TOPO_TILES) and ((topo.ws_f32 is not None) == (self.kind == _lib.SGAT))
-        if ok:
-            tx = getattr(topo, "x", None)
-            ok = (tx is not None and tx.data_ptr() == x.data_ptr() and tuple(tx.shape) == tuple(x.shape) and
-                  (x.shape[1] % 4 != 0 or x.data_ptr() % 16 == 0) and getattr(topo, "_tiles_x_version", None) == x._version)
-        if not ok:
-            flags &= ~_lib.TOPO_TILES
-        return flags
-
     def _plan(self, n_feat, topo, train, topo_flags):
         return self.api.step_plan(self.kind, n_feat, topo.max_nodes, topo.max_edges, topo.max_c0, self.R, self.H, self.O,
                                   topo.n_graphs, 0, train, topo_flags, self.plan_overrides)
@@ -277,16 +223,6 @@ class StepEngine(object):
             self._bufs[key] = fresh
         # (else: the cached set belongs to a forward whose backward is still to come -- this call keeps a private one)
         return fresh[:3], slabs
-
-    def _xchg_for(self, plan, B):
-        words = int(plan.xchg_words)
-        if words <= 0 and self.n_branch == 1:
-            return None
-        words = max(words, self.n_branch * max(self.H, 32))
-        buf = self._xchg.get(B)
-        if buf is None or buf.shape[1] < words:
-            buf = self._xchg[B] = torch.zeros((max(B, 1), words), dtype=torch.int64, device=self.device)
-        return buf
 
     # -- one call --------------------------------------------------------------------------------------------------------
     def _outside(self, why):
@@ -331,18 +267,13 @@ class StepEngine(object):
             if mode == "two-launch" and p_drop > 0.0 and any(not c.done for c in self._pending):
                 return self._outside("dropout with an earlier forward still awaiting its backward")
             return self._issue(mode, x, topo, plan, hints, bplan, bhints, B, n_feat, p_drop, want_grad)
-        flags = self._usable_flags(topo, x)
-        if not (flags & _lib.TOPO_TILES) and getattr(topo, "tiles", None) is not None and \
-                ((topo.ws_f32 is not None) == (self.kind == _lib.SGAT)) and tuple(topo.x.shape) == tuple(x.shape) and \
-                (n_feat % 4 != 0 or x.data_ptr() % 16 == 0) and getattr(topo, "_inputs", None) is not None:
-            # tiles formed from other node features than the ones stepped (x replaced / modified in place): form them again
-            topo.x = x
-            topo.rebuild(int(topo.flags) | _lib.TOPO_TILES)
-            flags = self._usable_flags(topo, x)
+        flags = usable_flags(self.kind, topo, x, reform="keep")
         plan = self._plan(n_feat, topo, mode == "jacobian", flags)
-        if plan.family != _lib.STEP_FAMILY_AGGREGATE or not (0 < plan.lds_bytes <= 160 * 1024):
+        # (AGGREGATE only: the emulation build's plan answers PRODUCT for its stand-in step, which this path leaves to the
+        # launch pair)
+        if not fused(plan, _lib.STEP_FAMILY_AGGREGATE):
             why = ""
-            if getattr(topo, "tiles", None) is not None and (topo.ws_f32 is not None) != (self.kind == _lib.SGAT):
+            if getattr(topo, "tiles", None) is not None and not tiles_match(self.kind, topo):
                 why = "; the workspace's tiles are %s sums, this net starts from %s ones (Topology.from_batch(need_weights=...))" % (
                     ("edge-weighted", "plain") if topo.ws_f32 is not None else ("plain", "edge-weighted"))
             return self._outside("no fused kernel for this launch (family %d, topology flags 0x%x, %d features, %d / %d / %d "
@@ -350,25 +281,15 @@ class StepEngine(object):
                                                                                    topo.max_edges, topo.max_c0, why))
         if mode == "two-launch":
             chk = self._plan(n_feat, topo, True, flags)
-            if chk.family != _lib.STEP_FAMILY_AGGREGATE or not (0 < chk.lds_bytes <= 160 * 1024):
+            if not fused(chk, _lib.STEP_FAMILY_AGGREGATE):
                 return self._outside("no fused training kernel for this launch (family %d)" % chk.family)
             if p_drop > 0.0 and any(not c.done for c in self._pending):
                 return self._outside("dropout with an earlier forward still awaiting its backward")      # (an earlier forward's backward would move the dropout stream between this forward and its own)
         bplan = bhints = None
-        bd = getattr(data, "__dict__", {})
-        hn, he = bd.get("_host_node_ptr"), bd.get("_host_edge_ptr")
-        if hn is None:           # (a foreign batch object: the tables Topology.from_batch derived)
-            hn, he = getattr(topo, "host_node_ptr", None), getattr(topo, "host_edge_ptr", None)
-        tiles = topo.tiles if (flags & _lib.TOPO_TILES) else None
-
-        def hints_for(pl):
-            if hn is not None and he is not None and len(hn) == B + 1 and B <= 64:
-                return _lib.step_hints(node_ptr=hn, edge_ptr=he, topo_flags=flags, tiles=tiles, plan=pl)
-            return _lib.step_hints(topo_flags=flags, tiles=tiles, plan=pl)
-        hints = hints_for(plan)
+        hints = batch_hints(data, topo, flags, plan, from_topo=True)
         if mode == "two-launch":
             bplan = self._plan(n_feat, topo, True, flags)
-            bhints = hints_for(bplan)
+            bhints = batch_hints(data, topo, flags, bplan, from_topo=True)
         if held is not None and held[1] is topo:
             held[2][ctx_key] = (flags, plan, hints, bplan, bhints)
         return self._issue(mode, x, topo, plan, hints, bplan, bhints, B, n_feat, p_drop, want_grad)
@@ -391,7 +312,7 @@ class StepEngine(object):
         api, topo, x, B = self.api, call.topo, call.x, call.B
         desc = self._descs(call.n_feat)
         pred = torch.empty((B, self.O), dtype=torch.float32, device=x.device)
-        xchg = self._xchg_for(call.plan, B)
+        xchg = self._xchg.get(call.plan, B, self.device)
         if call.mode == "jacobian":
             if self._uncommitted:
                 # a training launch whose backward has not run (yet): its step index was never committed, and a second launch
@@ -438,7 +359,7 @@ class StepEngine(object):
             head = self._head_desc(1, _lib.TASK_GRAD, call.p_drop)
             api.net_train_step(desc, head, x, gpred, self.step2, topo.ws_i32, topo.ws_f32, topo.n_nodes, topo.n_edges, B,
                                topo.max_nodes, topo.max_edges, topo.max_c0, pred, readout, hp, partials,
-                               self._xchg_for(bplan, B), stream, hints=bhints[0])
+                               self._xchg.get(bplan, B, self.device), stream, hints=bhints[0])
             weight = None
         api.step_gradients(desc, partials, B, g1, g2, hp, readout, self.R, self.H, self.O, head_grad, weight, zp, zl,
                            len(self.dead), self.step2, slabs, stream)

@@ -39,8 +39,8 @@ class Topology(object):
         # level-0 aggregation tiles (TOPO_TILES): the node features they are formed from and the output buffer
         # ([S n x F | D n | C n], include/drgnn.h); None: not available for this batch
         # CONTRACT: with TOPO_TILES a build reads the VALUES of x (S = sums of x rows over the neighbours); a launch may use
-        # the tiles only for that same tensor, unmodified since (FusedTrainer checks storage and version and forms the
-        # tiles again otherwise).  Everything else in the workspace depends on the index tensors only.
+        # the tiles only for that same tensor, unmodified since (launch.usable_flags checks storage and version and forms
+        # the tiles again otherwise).  Everything else in the workspace depends on the index tensors only.
         self.x = None
         self.tiles = None
         self._tiles_x_version = None
@@ -175,7 +175,7 @@ class Topology(object):
             if self.tiles is None:
                 raise ValueError("this topology has no aggregation tiles (no float32 x the builder's LDS holds a tile of)")
             r.x, r.tiles, r.n_feat = p(self.x), p(self.tiles), self.n_feat
-            # the tiles bake values of x in: what x was when the builder read it (trainer._usable_flags compares)
+            # the tiles bake values of x in: what x was when the builder read it (launch.usable_flags compares)
             self._tiles_x_version = self.x._version
         self.flags = int(r.flags)
         self._finalized = False

@@ -17,23 +17,17 @@ keep working), their ``.grad`` views into a second one, so the data-parallel exc
 all-reduce of one buffer (deeprank_gnn_amd.parallel) and Adam is one launch.
 Everything is enqueued on torch's current stream and is hipGraph-capturable.
 """
+import types
+
 import torch
 import torch.distributed as dist
 
 from . import _lib, hostcpu
-from .functional import H1, H2, _describe, _fill_grads, _split
+from .functional import H1, H2, _conv_grads, _describe
+from .launch import ExchangeWords, NetLayout, batch_hints, cached_flags, fused, head_desc, set_hints, tiles_match, usable_flags
 from .topology import Topology
 
 __all__ = ["FusedTrainer"]
-
-
-from .fused_autograd import net_layout as _net_layout      # noqa: E402  (kind, n_branch, convs) of a reference net
-
-
-class _BatchView(object):
-    """the two members of a batch _fused_prepare reads"""
-    def __init__(self, x, y):
-        self.x, self.y = x, y
 
 
 class FusedTrainer(object):
@@ -46,7 +40,9 @@ class FusedTrainer(object):
         self.net = net
         self.transform_sigmoid = bool(transform_sigmoid)      # regression: sigmoid on the output before the loss
         self.api = api or _lib.get()
-        self.kind, self.n_branch, self.convs = _net_layout(net)
+        lay = NetLayout(net)
+        self.kind, self.n_branch, self.convs, self.offset, self.live = lay.kind, lay.n_branch, lay.convs, lay.offset, lay.live
+        self.head_grad_offset, self.R, self.H, self.O = lay.head_offset, lay.R, lay.H, lay.O
         self.task = _lib.TASK_REG if task == "reg" else _lib.TASK_CLASS
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), betas, float(eps), float(weight_decay)
         if seed is None:
@@ -59,7 +55,7 @@ class FusedTrainer(object):
         dev = params[0].device
         if self.api is _lib._API:
             _lib.require_device(*params)
-        total = sum(p.numel() for p in params)
+        total = lay.total
         self.flat_p = torch.empty(total, dtype=torch.float32, device=dev)
         self.flat_g = torch.zeros(total, dtype=torch.float32, device=dev)
         self.exp_avg = torch.zeros(total, dtype=torch.float32, device=dev)
@@ -73,7 +69,7 @@ class FusedTrainer(object):
         # overrides of the fused step's launch plan (drgnn_step_plan: force_wgs / no_class / no_aggregate / no_split; tests
         # and A/B runs) -- per trainer, handed to every plan query and every launch
         self.plan_overrides = {}
-        self._xchg = {}              # exchange words of the fused step, one grow-only buffer per batch size
+        self._xchg = ExchangeWords(self.n_branch, self.H)
         # what a co-built topology must hold: the hierarchical node order, read by the aggregation-first step kernels
         # (sGAT / FoutNet: every training launch; GINet: the two-workgroup layout only, see _flags_for)
         self.topo_flags = _lib.TOPO_HIER
@@ -82,28 +78,14 @@ class FusedTrainer(object):
         self._ids_memo = {}           # (set, inference) -> (host order, its ids on the device) of the last such pass
         self._epoch_scratch = None
         self._loss_buf = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.offset = {}
-        off = 0
         with torch.no_grad():
             for name, p in net.named_parameters():
-                n = p.numel()
-                self.flat_p[off:off + n].copy_(p.detach().reshape(-1))
-                p.data = self.flat_p[off:off + n].view(p.shape)
-                p.grad = self.flat_g[off:off + n].view(p.shape)
-                self.offset[name] = off
-                off += n
-        head = ["fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias"]
-        o0 = self.offset[head[0]]
-        expect = o0
-        for name in head:      # the head reducer writes one contiguous block
-            assert self.offset[name] == expect, "unexpected parameter order for the FC head"
-            expect += dict(net.named_parameters())[name].numel()
-        self.head_grad_offset = o0
-        self.R, self.H, self.O = net.fc1.in_features, net.fc1.out_features, net.fc2.out_features
+                off = self.offset[name]
+                self.flat_p[off:off + p.numel()].copy_(p.detach().reshape(-1))
+            lay.bind(net, self.flat_p, self.flat_g)
         self.class_w = None
         if class_weights is not None:
             self.class_w = torch.as_tensor(class_weights, dtype=torch.float32, device=dev).contiguous()
-        self.live = tuple(p for c in self.convs for p in c.live_parameters())
         self.live_grads = tuple(p.grad for p in self.live)
 
     # ---------------------------------------------------------------------------
@@ -115,21 +97,9 @@ class FusedTrainer(object):
         return self._loss_buf
 
     def _head_desc(self, train):
-        hd = _lib.HeadDesc()
-        hd.R, hd.H, hd.O, hd.task, hd.train = self.R, self.H, self.O, self.task, int(train)
-        hd.p_drop = float(getattr(self.net, "dropout", 0.0)) if train else 0.0
-        hd.seed = self.seed
-        hd.transform_sigmoid = int(self.transform_sigmoid and self.task == _lib.TASK_REG)
-        n = self.net
-        hd.w1, hd.b1 = n.fc1.weight.data_ptr(), n.fc1.bias.data_ptr()
-        hd.w2, hd.b2 = n.fc2.weight.data_ptr(), n.fc2.bias.data_ptr()
-        hd.class_w = None if self.class_w is None else self.class_w.data_ptr()
-        # test hook (drgnn_head_desc.drop_mask): an explicit [B, H] 0 / 1 mask instead of the hash stream
-        mask = getattr(self, "drop_mask", None) if train else None
-        if mask is not None:
-            assert mask.dtype == torch.float32 and mask.is_contiguous() and mask.shape[-1] == self.H
-        hd.drop_mask = None if mask is None else mask.data_ptr()
-        return hd
+        return head_desc(self.net, self.task, train, getattr(self.net, "dropout", 0.0) if train else 0.0, self.seed,
+                         self.transform_sigmoid and self.task == _lib.TASK_REG, self.class_w,
+                         getattr(self, "drop_mask", None) if train else None)
 
     def _body_forward(self, batch, topo, stream, step_inc=None):
         api = self.api
@@ -145,7 +115,7 @@ class FusedTrainer(object):
         scratch = None
         need = max(api.net_lds_bytes(self.kind, n_feat, topo.max_nodes, topo.max_edges, topo.max_c0, b)
                    for b in (False, True))
-        if topo.max_nodes == 0 or need > 160 * 1024:
+        if topo.max_nodes == 0 or need > _lib.LDS_LIMIT:
             scratch = torch.empty(api.net_scratch_elems(self.kind, n_feat, n_nodes, topo.n_edges, B),
                                   dtype=torch.float32, device=dev)
         desc = _describe(self.kind, n_feat, self.live, nb)
@@ -154,26 +124,6 @@ class FusedTrainer(object):
         return x, desc, xp, arg0, arg1, readout, scratch
 
     # -- launch plan ------------------------------------------------------------------------------------------------
-    def _tiles_match(self, topo):
-        """The aggregation tiles of a workspace built WITH edge weights are weighted sums (what sGAT starts from); GINet /
-        FoutNet start from plain sums: a workspace of the other flavour is stepped without its tiles."""
-        return (getattr(topo, "ws_f32", None) is not None) == (self.kind == _lib.SGAT)
-
-    def _usable_flags(self, topo, x=None):
-        """The TOPO_* flags of ``topo`` as a launch of this net may rely on them: TILES only with tiles of this kind's
-        flavour that were formed from the ``x`` the launch steps (a Topology bakes the neighbour sums of its ``x`` in at
-        build time: another tensor, or the same one modified in place since, makes them stale) in 16-byte aligned memory."""
-        flags = int(getattr(topo, "flags", 0))
-        tiles = getattr(topo, "tiles", None)
-        ok = tiles is not None and (flags & _lib.TOPO_TILES) and self._tiles_match(topo)
-        if ok and x is not None:
-            tx = getattr(topo, "x", None)
-            ok = (tx is not None and tx.data_ptr() == x.data_ptr() and tuple(tx.shape) == tuple(x.shape) and
-                  (x.shape[1] % 4 != 0 or x.data_ptr() % 16 == 0) and getattr(topo, "_tiles_x_version", None) == x._version)
-        if not ok:
-            flags &= ~_lib.TOPO_TILES
-        return flags
-
     def _plan(self, n_feat, max_nodes, max_edges, max_c0, B, co=0, train=True, topo_flags=0):
         return self.api.step_plan(self.kind, n_feat, max_nodes, max_edges, max_c0, self.R, self.H, self.O, B, co, train,
                                   topo_flags, self.plan_overrides)
@@ -181,39 +131,26 @@ class FusedTrainer(object):
     def _plan_for(self, topo, n_feat, next_topo=None, train=True, x=None, flags=None):
         return self._plan(n_feat, topo.max_nodes, topo.max_edges, topo.max_c0, topo.n_graphs,
                           0 if next_topo is None else next_topo.n_graphs, train,
-                          self._usable_flags(topo, x) if flags is None else flags)
+                          usable_flags(self.kind, topo, x) if flags is None else flags)
 
     def _can_fuse(self, topo, n_feat, next_topo=None, train=True, x=None):
         """True when the launch on ``topo`` (what it holds NOW, for the ``x`` given) is one of the fused step kernels --
         judged by the plan of exactly that launch (kernel family, layout and LDS need: drgnn_net_step_plan)."""
         if not self.fused_step or topo.max_nodes <= 0:
             return False
-        p = self._plan_for(topo, n_feat, next_topo, train, x)
-        return p.family != _lib.STEP_FAMILY_NONE and 0 < p.lds_bytes <= 160 * 1024
+        return fused(self._plan_for(topo, n_feat, next_topo, train, x))
 
-    def _xchg_for(self, plan, B, dev):
-        """Exchange words of a launch with this plan: ONE buffer per batch size, grown to the largest need seen (the words
-        carry the step index as a tag, so stale ones are harmless; the launch is told the stride through its bounds)."""
-        words = int(plan.xchg_words)
-        if words <= 0 and self.n_branch == 1:
-            return None
-        words = max(words, self.n_branch * max(self.H, 32))
-        buf = self._xchg.get(B)
-        if buf is None or buf.shape[1] < words:
-            buf = self._xchg[B] = torch.zeros((max(B, 1), words), dtype=torch.int64, device=dev)
-        return buf
+    def _descs(self, n_feat):
+        """(g_conv1, g_conv2, net descriptor) of a fused step over ``n_feat`` features (built once per width)"""
+        ck = self._desc_cache.get(n_feat)
+        if ck is None:
+            g1, g2 = _conv_grads(self.kind, n_feat, self.live_grads, self.n_branch)
+            ck = self._desc_cache[n_feat] = (g1, g2, _describe(self.kind, n_feat, self.live, self.n_branch))
+        return ck
 
     def _step_buffers(self, plan, n_feat, B, dev):
         """descriptors (per feature width) and slabs (per batch size and layout) of a fused step"""
         nb = self.n_branch
-        ck = self._desc_cache.get(n_feat)
-        if ck is None:
-            g1 = (_lib.ConvGrads * _lib.MAX_BRANCH)()
-            g2 = (_lib.ConvGrads * _lib.MAX_BRANCH)()
-            for b, (l1, l2) in enumerate(_split(self.kind, self.live_grads, nb)):
-                _fill_grads(g1[b], self.kind, l1, n_feat, H1)
-                _fill_grads(g2[b], self.kind, l2, H1, H2)
-            ck = self._desc_cache[n_feat] = (g1, g2, _describe(self.kind, n_feat, self.live, nb))
         slabs = max(int(plan.slabs_per_graph), nb)
         bk = self._slab_cache.get((B, n_feat, slabs))
         if bk is None:
@@ -221,7 +158,7 @@ class FusedTrainer(object):
                 torch.empty((B, H2 * nb), dtype=torch.float32, device=dev),
                 torch.empty((max(B * slabs, 1), self.api.net_partial_elems(self.kind, n_feat)), dtype=torch.float32, device=dev),
                 torch.empty((max(B, 1), self.api.head_compact_elems(self.R, self.H, self.O)), dtype=torch.float32, device=dev))
-        return ck, bk, slabs
+        return self._descs(n_feat), bk, slabs
 
     def _fused_prepare(self, batch, topo, train=True, next_topo=None):
         """Buffers and descriptors of one fused step (allocation only, no launch)."""
@@ -232,30 +169,12 @@ class FusedTrainer(object):
         y = getattr(batch, "y", None)
         if y is not None:
             y = y.to(torch.float32).contiguous() if self.task == _lib.TASK_REG else y.to(torch.int64).contiguous()
-        topo_flags = self._usable_flags(topo, x)
-        if (int(getattr(topo, "flags", 0)) & _lib.TOPO_TILES) and not (topo_flags & _lib.TOPO_TILES) and \
-                self._tiles_match(topo) and getattr(topo, "tiles", None) is not None and \
-                getattr(topo, "_inputs", None) is not None and \
-                (x.shape[1] % 4 != 0 or x.data_ptr() % 16 == 0) and tuple(x.shape) == tuple(topo.x.shape):
-            # the tiles were formed from other node features than the ones being stepped (x replaced or modified in place
-            # since the build): form them again from this x (own launch, same stream)
-            topo.x = x
-            topo.rebuild()
-            topo_flags = self._usable_flags(topo, x)
-        plan = self._plan_for(topo, n_feat, next_topo, train, x, flags=topo_flags)
+        flags = usable_flags(self.kind, topo, x, reform="full")
+        plan = self._plan_for(topo, n_feat, next_topo, train, x, flags=flags)
         (g1, g2, desc), (readout, partials, hp), slabs = self._step_buffers(plan, n_feat, B, dev)
-        xchg = self._xchg_for(plan, B, dev)
-        # host copies of the mini-batch's offsets (Batch.from_data_list / the resident set record them): they travel in
-        # the launch arguments, so a workgroup need not fetch them from the workspace first
-        bd = getattr(batch, "__dict__", {})
-        hn, he = bd.get("_host_node_ptr"), bd.get("_host_edge_ptr")
-        tiles = getattr(topo, "tiles", None) if (topo_flags & _lib.TOPO_TILES) else None
-        if hn is not None and he is not None and len(hn) == B + 1 and B <= 64:
-            hints = _lib.step_hints(node_ptr=hn, edge_ptr=he, topo_flags=topo_flags, tiles=tiles, plan=plan)
-        else:
-            hints = _lib.step_hints(topo_flags=topo_flags, tiles=tiles, plan=plan)
+        xchg = self._xchg.get(plan, B, dev)
         return dict(
-            hints=hints, slabs=slabs, plan=plan,
+            hints=batch_hints(batch, topo, flags, plan), slabs=slabs, plan=plan,
             x=x, y=y, topo=topo, B=B, n_nodes=n_nodes, xchg=xchg, g1=g1, g2=g2, desc=desc,
             stream=_lib.current_stream(x), pred=torch.empty((B, self.O), dtype=torch.float32, device=dev),
             readout=readout, partials=partials, hp=hp)
@@ -265,7 +184,7 @@ class FusedTrainer(object):
         aggregation-first kernels (judged by its plan, for a following mini-batch of the same size): the hierarchical node
         order, the aggregation tiles, and nothing those kernels do not read (TOPO_LEAN: the builder's short chains);
         _fused_launch_step rebuilds in full should that turn out wrong.  Otherwise the plain build."""
-        if getattr(topo, "tiles", None) is not None and self._tiles_match(topo) and not getattr(topo, "_tiles_separately", False):
+        if getattr(topo, "tiles", None) is not None and tiles_match(self.kind, topo) and not getattr(topo, "_tiles_separately", False):
             af = _lib.TOPO_HIER | _lib.TOPO_LEAN | _lib.TOPO_TILES
             if self._plan(n_feat, topo.max_nodes, topo.max_edges, topo.max_c0, topo.n_graphs, topo.n_graphs, train, af).lean_ok:
                 return af
@@ -277,7 +196,7 @@ class FusedTrainer(object):
         if (int(getattr(t, "flags", 0)) & _lib.TOPO_LEAN) and not c["plan"].lean_ok:
             # a lean workspace under a launch that reads more: build the rest (own launch, same stream), plan again
             t.rebuild()
-            c.update(self._fused_prepare(_BatchView(c["x"], c["y"]), t, True, next_topo))
+            c.update(self._fused_prepare(types.SimpleNamespace(x=c["x"], y=c["y"]), t, True, next_topo))
         self.api.net_train_step(c["desc"], self._head_desc(True), c["x"], c["y"], self.step2, t.ws_i32, t.ws_f32,
                                 c["n_nodes"], t.n_edges, c["B"], t.max_nodes, t.max_edges, t.max_c0, c["pred"],
                                 c["readout"], c["hp"], c["partials"], c["xchg"], c["stream"],
@@ -306,30 +225,22 @@ class FusedTrainer(object):
         ``cache`` (resident.TopologyCache).  ``next_ids_dev``: the NEXT mini-batch's graph numbers (device int32): spare
         workgroups of this launch prefetch them (drgnn_step_hints.next_ids)."""
         import numpy as np
-        api = self.api
         ids = np.asarray(ids, dtype=np.int64).reshape(-1)
         B = int(ids.size)
         gset = cache.set
         if ids_dev is None:
             ids_dev = gset.upload_ids(ids)
-        n_feat, dev, nb = gset.n_feat, gset.device, self.n_branch
+        n_feat, dev = gset.n_feat, gset.device
         if self.kind == _lib.SGAT and not cache.with_weights:
             raise ValueError("sGAT needs a topology cache built with edge weights (topology_cache(need_weights=True))")
         max_nodes, max_edges, max_c0 = cache.bounds(ids)
-        topo_flags = int(getattr(cache.topo, "flags", 0))
-        tiles = cache.tiles_for(self.kind == _lib.SGAT) if (topo_flags & _lib.TOPO_TILES) else None
-        if tiles is None or (n_feat % 4 == 0 and gset.x.data_ptr() % 16 != 0):
-            topo_flags &= ~_lib.TOPO_TILES
-            tiles = None
-        plan = self._plan(n_feat, max_nodes, max_edges, max_c0, B, 0, train, topo_flags)
-        if not (plan.family != _lib.STEP_FAMILY_NONE and 0 < plan.lds_bytes <= 160 * 1024):
+        flags, tiles = cached_flags(self.kind, cache)
+        plan = self._plan(n_feat, max_nodes, max_edges, max_c0, B, 0, train, flags)
+        if not fused(plan):
             raise _lib.DrgnnError("a graph of this mini-batch does not fit the fused step kernel's LDS budget")
         (g1, g2, desc), (readout, partials, hp), slabs = self._step_buffers(plan, n_feat, B, dev)
-        xchg = self._xchg_for(plan, B, dev)
-        # (beyond 64 graphs the offsets no longer travel in the kernel arguments, but the library still range-checks the ids)
-        hints = _lib.step_hints(set_node_ptr=gset.node_ptr, set_edge_ptr=gset.edge_ptr, ids=ids,
-                                topo_flags=topo_flags, tiles=tiles, plan=plan, next_ids=next_ids_dev)
-        return dict(hints=hints, slabs=slabs, plan=plan,
+        xchg = self._xchg.get(plan, B, dev)
+        return dict(hints=set_hints(gset, ids, flags, tiles, plan, next_ids_dev), slabs=slabs, plan=plan,
                     cache=cache, ids_dev=ids_dev, B=B, bounds=(max_nodes, max_edges, max_c0), xchg=xchg, g1=g1, g2=g2,
                     desc=desc, stream=_lib.current_stream(gset.x), readout=readout, partials=partials, hp=hp,
                     pred=torch.empty((B, self.O), dtype=torch.float32, device=dev))
@@ -395,11 +306,7 @@ class FusedTrainer(object):
         y = y.to(torch.float32).contiguous() if self.task == _lib.TASK_REG else y.to(torch.int64).contiguous()
         partials = torch.empty((max(B * self.n_branch, 1), api.net_partial_elems(self.kind, n_feat)),
                                dtype=torch.float32, device=dev)
-        g1 = (_lib.ConvGrads * _lib.MAX_BRANCH)()
-        g2 = (_lib.ConvGrads * _lib.MAX_BRANCH)()
-        for b, (l1, l2) in enumerate(_split(self.kind, self.live_grads, self.n_branch)):
-            _fill_grads(g1[b], self.kind, l1, n_feat, H1)
-            _fill_grads(g2[b], self.kind, l2, H1, H2)
+        g1, g2 = _conv_grads(self.kind, n_feat, self.live_grads, self.n_branch)
         hp = torch.empty((max(B, 1), api.head_partial_elems(self.R, self.H, self.O)),
                          dtype=torch.float32, device=dev)
         api.net_backward_fused_head(desc, self._head_desc(True), x, readout, y, self.step, topo.ws_i32,
@@ -600,15 +507,7 @@ class FusedTrainer(object):
             ids_dev = gset.upload_ids(ids_host)
             self._ids_memo[(id(gset), bool(inference))] = (ids_host.copy(), ids_dev)
         n_feat = gset.n_feat
-        ck = self._desc_cache.get(n_feat)
-        if ck is None:
-            g1 = (_lib.ConvGrads * _lib.MAX_BRANCH)()
-            g2 = (_lib.ConvGrads * _lib.MAX_BRANCH)()
-            for b, (l1, l2) in enumerate(_split(self.kind, self.live_grads, self.n_branch)):
-                _fill_grads(g1[b], self.kind, l1, n_feat, H1)
-                _fill_grads(g2[b], self.kind, l2, H1, H2)
-            ck = self._desc_cache[n_feat] = (g1, g2, _describe(self.kind, n_feat, self.live, self.n_branch))
-        g1, g2, desc = ck
+        g1, g2, desc = self._descs(n_feat)
         head = self._head_desc(not inference)
         vp = ctypes.c_void_p
         plan = _lib.EpochPlan()
@@ -760,8 +659,7 @@ class FusedTrainer(object):
                 steps.add(int(float(st['step'])))
             if steps:
                 self.step.fill_(max(steps))
-            for buf in self._xchg.values():      # tags of an earlier run must not match again
-                buf.zero_()
+            self._xchg.zero()
 
     @torch.no_grad()
     def predict(self, batch, topo=None, next_topo=None):
