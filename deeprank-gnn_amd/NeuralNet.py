@@ -796,3 +796,70 @@ class NeuralNet(object):
                  'threshold': self.threshold, 'cluster_nodes': self.cluster_nodes,
                  'transform_sigmoid': self.transform_sigmoid}
         torch.save(state, filename)
+
+    def cross_validate(self, k=10, nepoch=1, validate=True, save_model=None, seed=0, threshold=4.0):
+        """k-fold cross-validation over ``self.dataset`` with this NeuralNet's settings (net class, lr, batch size, task,
+        loss), the k fold models trained TOGETHER as a ``Cohort``: one resident set, one topology cache, two launches per
+        optimisation step of all k models; after every epoch each model is evaluated on its held-out fold by one ensemble
+        launch per mini-batch of the whole set (member m's outputs on fold m).  The fold models are fresh nets configured as
+        ``self.model`` (its ``dropout``); ``self.model`` itself is not trained.
+
+        ``save_model``: a path prefix -- k checkpoints ``<prefix>_fold<m>.pth.tar`` in ``save_model``'s layout, which
+        ``NeuralNet(db, Net, pretrained_model=[...])`` loads as an ensemble.  Returns a dictionary: ``folds`` (the held-out
+        graph numbers per fold), ``train_loss`` / ``valid_loss`` (per fold, one value per epoch), ``metrics`` (the ``Metrics``
+        of each fold model on its held-out fold after the last epoch, when ``validate``), ``paths``, and for inspection
+        ``cohort``, ``set``, ``start`` (the start state dicts) and ``orders`` (per epoch, per fold: the visiting order)."""
+        from .cohort import Cohort, kfold_indices
+        from .metrics import Metrics
+        if self.ensemble is not None:
+            raise _lib.DrgnnError("NeuralNet.cross_validate: an ensemble of checkpoints is inference only")
+        rs = self._resident(self.dataset)
+        n = len(rs)
+        folds = kfold_indices(n, k, shuffle=True, seed=seed)
+        train_sets = [np.setdiff1d(np.arange(n, dtype=np.int64), f) for f in folds]
+        coh = Cohort(type(self.model), int(k), n_feat=rs.n_feat, n_out=self.trainer.O, lr=self.lr, task=self.task,
+                     class_weights=self.trainer.class_w, transform_sigmoid=bool(self.transform_sigmoid), device=self.device,
+                     api=self._api, edge_dim=len(self.edge_feature))
+        if hasattr(self.model, "dropout"):
+            for net in coh.nets:
+                net.dropout = self.model.dropout
+        out = {'folds': folds, 'cohort': coh, 'set': rs, 'start': coh.state_dicts(), 'orders': [],
+               'train_loss': [[] for _ in range(k)], 'valid_loss': [[] for _ in range(k)], 'metrics': [None] * k, 'paths': []}
+        ens = coh.ensemble() if validate else None
+        cached = self._use_cache(rs)
+        held = [_index_on(self.device, f) for f in folds]
+        pred = None
+        for _ in range(int(nepoch)):
+            orders = [t[torch.randperm(len(t)).numpy()].tolist() if self.shuffle else t.tolist() for t in train_sets]
+            out['orders'].append(orders)
+            losses = coh.train_epoch(rs, orders, self.batch_size, cached=cached)          # [steps, K], NaN = no mini-batch
+            vl = None
+            if validate:
+                pred = ens.predict(rs, batch_size=self.batch_size, cached=cached)            # [K, n, O]
+                vl = [self._fold_loss(pred[m].index_select(0, held[m]), rs.y.index_select(0, held[m])) for m in range(k)]
+            tl = torch.nanmean(losses, dim=0).cpu().tolist()                                # (the epoch's one synchronisation)
+            coh.raise_on_faults()
+            for m in range(k):
+                out['train_loss'][m].append(tl[m])
+                if vl is not None:
+                    out['valid_loss'][m].append(float(vl[m]))
+        if validate and pred is not None and rs.y is not None:
+            thr = self.classes_to_idx[threshold] if self.task == 'class' else threshold
+            for m in range(k):
+                p = pred[m].index_select(0, held[m])
+                p = p.argmax(dim=1) if self.task == 'class' else p.reshape(-1)
+                out['metrics'][m] = Metrics(p.cpu().numpy(), rs.y.index_select(0, held[m]).cpu().numpy(), self.target, thr,
+                                            True, api=self._api)
+        if save_model:
+            paths = ["%s_fold%d.pth.tar" % (save_model, m) for m in range(k)]
+            out['paths'] = coh.save(paths, node=self.node_feature, edge=self.edge_feature, target=self.target,
+                                    classes=self.classes, class_weight=self.class_weights, batch_size=self.batch_size,
+                                    percent=self.percent, index=self.index, shuffle=self.shuffle, threshold=self.threshold,
+                                    cluster_nodes=self.cluster_nodes, transform_sigmoid=self.transform_sigmoid)
+        return out
+
+    def _fold_loss(self, pred, y):
+        """the loss of NeuralNet's task on predictions as the trainers report them (after the sigmoid when set)"""
+        if self.task == 'class':
+            return torch.nn.functional.cross_entropy(pred, y, weight=self.trainer.class_w)
+        return torch.nn.functional.mse_loss(pred.reshape(-1), y)

@@ -11,5 +11,6 @@ from .sGAT import sGAT  # noqa: F401
 from .foutnet import FoutNet  # noqa: F401
 from .metrics import Metrics  # noqa: F401
 from .ensemble import Ensemble  # noqa: F401
+from .cohort import Cohort, kfold_indices  # noqa: F401
 
 __version__ = "0.1.0"

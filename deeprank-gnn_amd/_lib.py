@@ -58,6 +58,15 @@ class EnsMember(ctypes.Structure):
     _fields_ = [("net", NetDesc), ("w1", _vp), ("b1", _vp), ("w2", _vp), ("b2", _vp)]
 
 
+class CohortMember(ctypes.Structure):
+    """drgnn_cohort_member: one entry of a training cohort's member table (its array lives in device memory)"""
+    _fields_ = [("net", NetDesc), ("w1", _vp), ("b1", _vp), ("w2", _vp), ("b2", _vp),
+                ("flat_param", _vp), ("flat_grad", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp),
+                ("step2", _vp), ("pred", _vp), ("readout", _vp), ("head_partials", _vp), ("partials", _vp), ("loss", _vp),
+                ("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
+                ("seed", ctypes.c_uint32), ("reserved", _c_i32)]
+
+
 class TopologyRequest(ctypes.Structure):
     _fields_ = [("edge_index", _vp), ("edge_attr", _vp), ("batch", _vp), ("cluster0", _vp), ("cluster1", _vp),
                 ("node_ptr", _vp), ("edge_ptr", _vp), ("c1_ptr", _vp),
@@ -213,6 +222,13 @@ class Api(object):
         lib.drgnn_ens_predict_cached.argtypes = ([ctypes.POINTER(NetDesc), ctypes.POINTER(HeadDesc), _vp, _c_i32,
                                                   ctypes.POINTER(TopologyCacheDesc), _vp, _c_i64] + [_c_i32] * 3 +
                                                  [_vp] * 3 + [ctypes.POINTER(StepHints), _vp])
+        lib.drgnn_cohort_step_plan.argtypes = [ctypes.POINTER(StepPlan), _c_i32]
+        lib.drgnn_cohort_step_plan.restype = _c_i32
+        lib.drgnn_cohort_train_step_cached.argtypes = ([ctypes.POINTER(NetDesc), ctypes.POINTER(HeadDesc), _vp, _c_i32,
+                                                        ctypes.POINTER(TopologyCacheDesc), _vp, _vp, _c_i64, _c_i64] +
+                                                       [_c_i32] * 3 + [ctypes.POINTER(StepHints), _vp])
+        lib.drgnn_cohort_update.argtypes = ([ctypes.POINTER(NetDesc), _vp, _c_i32, _vp] + [ctypes.POINTER(ConvGrads)] * 2 +
+                                            [_c_i32] * 3 + [_c_i64, _c_i64, _vp, _c_i32, _vp])
         lib.drgnn_step_update.argtypes = ([ctypes.POINTER(NetDesc), _vp, _c_i64] +
                                           [ctypes.POINTER(ConvGrads)] * 2 + [_vp, _vp] + [_c_i32] * 3 +
                                           [_c_i64] + [_vp] * 4 + [_c_i64] + [_vp] * 2 +
@@ -419,6 +435,26 @@ class Api(object):
             ctypes.byref(desc), ctypes.byref(head), _ptr(members), int(K), ctypes.byref(cache), _ptr(ids), n_graphs,
             max_nodes, max_edges, max_c0, _ptr(step2), _ptr(pred), _ptr(readout), ctypes.byref(hints), stream),
             "drgnn_ens_predict_cached")
+
+    def cohort_step_plan(self, K, kind, n_feat, max_nodes, max_edges, max_c0, R, H, O, n_graphs, topo_flags=0):
+        """The plan (StepPlan) of a cohort's fused step launch of K members; ``family == 0``: the members are stepped one by one."""
+        p = StepPlan()
+        p.kind, p.n_feat, p.max_nodes, p.max_edges, p.max_c0 = int(kind), int(n_feat), int(max_nodes), int(max_edges), int(max_c0)
+        p.R, p.H, p.O, p.n_graphs, p.topo_flags = int(R), int(H), int(O), int(n_graphs), int(topo_flags)
+        self.lib.drgnn_cohort_step_plan(ctypes.byref(p), int(K))
+        return p
+
+    def cohort_train_step_cached(self, desc, head, members, K, cache, ids, counts, ids_stride, n_graphs, max_nodes, max_edges,
+                                 max_c0, stream, hints):
+        """``ids`` / ``counts``: raw device addresses (this step's rows of the epoch's tables)"""
+        _check(self.lib.drgnn_cohort_train_step_cached(
+            ctypes.byref(desc), ctypes.byref(head), _ptr(members), int(K), ctypes.byref(cache), ids, counts, int(ids_stride),
+            int(n_graphs), max_nodes, max_edges, max_c0, ctypes.byref(hints), stream), "drgnn_cohort_train_step_cached")
+
+    def cohort_update(self, desc, members, K, counts, g1, g2, R, H, O, head_offset, n_param, stream, losses=None, apply_adam=True):
+        """``counts`` / ``losses``: raw device addresses (this step's rows of the epoch's tables; ``losses`` may be None)"""
+        _check(self.lib.drgnn_cohort_update(ctypes.byref(desc), _ptr(members), int(K), counts, g1, g2, R, H, O, int(head_offset),
+                                            int(n_param), losses, 1 if apply_adam else 0, stream), "drgnn_cohort_update")
 
     def step_update(self, desc, conv_partials, n_graphs, g1, g2, head_partials, readout, R, H, O, head_offset,
                     flat_p, flat_g, exp_avg, exp_avg_sq, step2, loss, lr, beta1, beta2, eps, stream,

@@ -935,9 +935,10 @@ int32_t drgnn_net_step_variant(int32_t kind, const float* x, int32_t n_feat, int
 #ifndef DRGNN_EMU
 // One launch of a step kernel instance (+ the co-launched builder's workgroups).  These kernels use up to the whole 160 KiB of
 // LDS: the attribute is raised once per kernel instance and device (the call costs host time on every launch otherwise).
-// (ens: an ensemble instance, drgnn_kernels.h k_step3b_ens / k_step2_ens -- its member table and K follow the launch arguments)
+// (ens: an ensemble instance, drgnn_kernels.h k_step3b_ens / k_step2_ens -- its member table and K follow the launch arguments;
+// coh: a cohort instance, k_step3b_cohort / k_step2_cohort -- its CohortStep follows them instead)
 static int step_launch(drgnn_step_kernel_t kern, int64_t lds_bytes, unsigned grid, hipStream_t stream, const StepCoLaunch& C,
-                       const drgnn_ens_member* ens = nullptr, int ens_K = 0) {
+                       const drgnn_ens_member* ens = nullptr, int ens_K = 0, const CohortStep* coh = nullptr) {
     if (!kern) return DRGNN_E_ARG;
     if (lds_bytes > 64 * 1024) {
         struct Seen { const void* fn; int dev; };
@@ -959,6 +960,7 @@ static int step_launch(drgnn_step_kernel_t kern, int64_t lds_bytes, unsigned gri
         }
     }
     void* args[] = {const_cast<StepCoLaunch*>(&C), &ens, &ens_K};
+    if (coh) args[1] = const_cast<CohortStep*>(coh);
     HIP_TRY(hipLaunchKernel((const void*)kern, dim3(grid), dim3(DRGNN_NTHREADS), args, (size_t)lds_bytes, stream));
     return 0;
 }
@@ -973,22 +975,28 @@ static int train_step_impl(const drgnn_net_desc* net, const drgnn_head_desc* hd,
                            int32_t max_edges, int32_t max_c0, float* pred, float* readout,
                            float* head_partials, float* partials, uint64_t* xchg,
                            const drgnn_topology_request* next, const drgnn_step_hints* hints, void* stream_,
-                           const drgnn_ens_member* ens = nullptr, int ens_K = 0) {
+                           const drgnn_ens_member* ens = nullptr, int ens_K = 0, const CohortStep* coh = nullptr) {
     int rc = net_check(net);
     if (rc) return rc;
 #ifdef DRGNN_EMU
-    if (ens) return DRGNN_E_CAPACITY;      // (the host emulation has no ensemble launch: drgnn_ens_step_plan answers NONE)
+    if (ens || coh) return DRGNN_E_CAPACITY;      // (the host emulation has no ensemble / cohort launch: their plans answer NONE)
+#else
+    // a cohort launch (drgnn_cohort_train_step_cached): the members' parameters, outputs, slabs and step words come from the
+    // member table; what the checks below ask of a single model's are member 0's stand-ins
+    if (coh && (coh->K < 1 || !coh->members || !coh->ids || !coh->counts || !hd || hd->train != 1 || hd->task == DRGNN_TASK_GRAD ||
+                hd->drop_mask || !(hints && hints->plan) || !target || ens))
+        return DRGNN_E_ARG;
 #endif
     if (ens && (ens_K < 1 || !gather_ids || hd->train || !(hints && hints->plan))) return DRGNN_E_ARG;
-    if (!hd || !hd->w1 || !hd->b1 || !hd->w2 || !hd->b2 || !x || !step2 || !ws_i32 || !pred || !readout)
-        return DRGNN_E_ARG;
+    if (!hd || !x || !ws_i32) return DRGNN_E_ARG;
+    if (!coh && (!hd->w1 || !hd->b1 || !hd->w2 || !hd->b2 || !step2 || !pred || !readout)) return DRGNN_E_ARG;
     // hd->train: 1 = the whole step; 0 = inference; 2 = the forward of a training step (predictions only, dropout on)
     if (hd->train < 0 || hd->train > 2) return DRGNN_E_ARG;
     const bool full_step = hd->train == 1;
-    if (full_step && (!target || !head_partials || !partials)) return DRGNN_E_ARG;      // inference needs neither
+    if (full_step && !coh && (!target || !head_partials || !partials)) return DRGNN_E_ARG;      // inference needs neither
     if (hd->task != DRGNN_TASK_REG && hd->task != DRGNN_TASK_CLASS && hd->task != DRGNN_TASK_GRAD) return DRGNN_E_ARG;
     if (hd->task == DRGNN_TASK_GRAD && gather_ids) return DRGNN_E_ARG;      // (the upstream gradient is indexed by slot)
-    if (net->n_branch > 1 && !xchg && !ens) return DRGNN_E_ARG;      // (the ensemble forms exchange nothing)
+    if (net->n_branch > 1 && !xchg && !ens && !coh) return DRGNN_E_ARG;      // (the ensemble / cohort forms exchange nothing)
     if (net->kind == DRGNN_SGAT && !ws_f32) return DRGNN_E_ARG;
     if (hd->R != DRGNN_H2 * net->n_branch || hd->H < 1 || hd->H > 512 || hd->O < 1 || hd->O > DRGNN_MAX_OUT)
         return DRGNN_E_WIDTH;
@@ -1022,7 +1030,7 @@ static int train_step_impl(const drgnn_net_desc* net, const drgnn_head_desc* hd,
     const drgnn_step_plan* plan = hints ? hints->plan : nullptr;
     q.ov = step_overrides_of(plan);
     q.commit_wgs = (kind == DRGNN_GINET) ? 0 : (plan && plan->wgs_per_graph == 2) ? 2 : 1;
-    if (ens) { q.ov.force_wgs = 1; q.commit_wgs = (kind == DRGNN_GINET) ? 0 : 1; }      // (the ensemble forms: one workgroup per graph)
+    if (ens || coh) { q.ov.force_wgs = 1; q.commit_wgs = (kind == DRGNN_GINET) ? 0 : 1; }      // (the ensemble / cohort forms: one workgroup per graph)
     if (q.commit_wgs == 2 && !xchg) return DRGNN_E_CAPACITY;
     const StepPick k = step_pick(q);
     if (k.rc) return k.rc;
@@ -1038,7 +1046,7 @@ static int train_step_impl(const drgnn_net_desc* net, const drgnn_head_desc* hd,
         (plan->family != k.family || plan->width != k.width || plan->cls != k.cls || plan->slabs_per_graph != k.slabs))
         return DRGNN_E_CAPACITY;
     if (co_ok && k.builder_roles == 0) co_ok = false;      // the builder gets a launch of its own
-    if (ens && (k.wgs != 1 || (k.kernel != SK_AF3B && k.kernel != SK_AF2))) return DRGNN_E_CAPACITY;
+    if ((ens || coh) && (k.wgs != 1 || (k.kernel != SK_AF3B && k.kernel != SK_AF2))) return DRGNN_E_CAPACITY;
     if (co_ok) T.roles = k.builder_roles;
 
     StepLaunch L;
@@ -1096,8 +1104,9 @@ static int train_step_impl(const drgnn_net_desc* net, const drgnn_head_desc* hd,
     hf.readout = readout; hf.step = step2; hf.pred = pred; hf.partials = head_partials; hf.stage = 0;
 
     // grid of the step part: graphs in groups of 8 x 2 when a graph has two workgroups (step2_block, step3_block)
-    // (ensemble: graphs in groups of 8 x K, see ens_slot)
-    const int blocks = ens ? (int)((n_graphs + 7) / 8) * 8 * ens_K : (k.wgs == 2) ? (int)((n_graphs + 7) / 8) * 16 : (int)n_graphs;
+    // (ensemble / cohort: graphs in groups of 8 x K, see ens_slot)
+    const int multi_K = ens ? ens_K : coh ? coh->K : 0;
+    const int blocks = multi_K ? (int)((n_graphs + 7) / 8) * 8 * multi_K : (k.wgs == 2) ? (int)((n_graphs + 7) / 8) * 16 : (int)n_graphs;
     if (blocks > 0) {
 #ifdef DRGNN_EMU
         if (kind == DRGNN_GINET) emu_step<DRGNN_GINET>(a, full_step, k.capN, k.capE, k.capC);
@@ -1115,7 +1124,7 @@ static int train_step_impl(const drgnn_net_desc* net, const drgnn_head_desc* hd,
         int extra = 0;
         C.topo.pf_ids = nullptr; C.topo.pf_n = 0; C.topo.pf_graphs = 0;
         if (co_ok) { C.topo = T; both = k.lds > tlds ? k.lds : tlds; extra = T.args.n_graphs * T.roles; }
-        else if (gather_ids && hints && hints->next_ids && hints->n_next > 0 && (blocks % 8) == 0 &&
+        else if (!coh && gather_ids && hints && hints->next_ids && hints->n_next > 0 && (blocks % 8) == 0 &&
                  blocks + hints->n_next <= device_cu_count() && !step_no_prefetch()) {
             // cached topology, CUs to spare: one extra workgroup per graph of the NEXT mini-batch warms the L2 of the XCD that
             // will step it (prefetch_block; beyond the resident size the workgroups would only queue behind the step's)
@@ -1134,6 +1143,11 @@ static int train_step_impl(const drgnn_net_desc* net, const drgnn_head_desc* hd,
             const drgnn_ens_kernel_t ek = af_ens_kernel(kind, k.width, k.cls, kind == DRGNN_GINET ? (k.sg ? 1 : 0) : k.xg);
             if (!ek) return DRGNN_E_CAPACITY;
             return step_launch(reinterpret_cast<drgnn_step_kernel_t>(ek), k.lds, (unsigned)blocks, (hipStream_t)stream_, C, ens, ens_K);
+        }
+        if (coh) {
+            const drgnn_cohort_kernel_t ck = af_cohort_kernel(kind, k.width, k.cls, kind == DRGNN_GINET ? (k.sg ? 1 : 0) : k.xg);
+            if (!ck) return DRGNN_E_CAPACITY;
+            return step_launch(reinterpret_cast<drgnn_step_kernel_t>(ck), k.lds, (unsigned)blocks, (hipStream_t)stream_, C, nullptr, 0, coh);
         }
         drgnn_step_kernel_t kern = nullptr;
         const bool gather = gather_ids != nullptr;
@@ -1204,6 +1218,44 @@ int drgnn_ens_predict_cached(const drgnn_net_desc* net, const drgnn_head_desc* h
     return train_step_impl(net, hd, cache->x, cache->y, step2, cache->ws_i32, cache->ws_f32, cache->n_nodes,
                            cache->n_edges, n_graphs, cache->n_graphs, ids, max_nodes, max_edges, max_c0, pred, readout,
                            nullptr, nullptr, nullptr, nullptr, hints, stream_, members, K);
+}
+
+int32_t drgnn_cohort_step_plan(drgnn_step_plan* p, int32_t K) {
+    if (!p) return 0;
+    p->train = 1;
+    p->force_wgs = 1;      // the one-workgroup-per-graph forms: no workgroup of the launch waits for another
+    p->co_built_graphs = 0;
+    const int32_t wgs = drgnn_net_step_plan(p);
+#ifdef DRGNN_EMU
+    p->family = DRGNN_STEP_FAMILY_NONE;
+    return 0;
+#else
+    if (K < 1 || K > 65535 || wgs != 1 || p->family != DRGNN_STEP_FAMILY_AGGREGATE || p->lds_bytes <= 0 ||
+        p->lds_bytes > DRGNN_LDS_LIMIT || (int64_t)K * ((p->n_graphs + 7) / 8) * 8 > (int64_t)INT32_MAX) {
+        p->family = DRGNN_STEP_FAMILY_NONE;
+        return 0;
+    }
+    return 1;
+#endif
+}
+
+int drgnn_cohort_train_step_cached(const drgnn_net_desc* net, const drgnn_head_desc* hd, const drgnn_cohort_member* members,
+                                   int32_t K, const drgnn_topology_cache* cache, const int32_t* ids, const int32_t* counts,
+                                   int64_t ids_stride, int64_t n_graphs, int32_t max_nodes, int32_t max_edges, int32_t max_c0,
+                                   const drgnn_step_hints* hints, void* stream_) {
+    if (!members || K < 1 || K > 65535 || !hd || hd->train != 1 || !ids || !counts || ids_stride < n_graphs) return DRGNN_E_ARG;
+    if (!cache || !cache->ws_i32 || !cache->x || n_graphs < 0 || n_graphs > cache->n_graphs) return DRGNN_E_ARG;
+    if (!cache->y || cache->y_bytes != (hd->task == DRGNN_TASK_REG ? 4 : 8)) return DRGNN_E_ARG;
+#ifdef DRGNN_EMU
+    (void)net; (void)max_nodes; (void)max_edges; (void)max_c0; (void)hints; (void)stream_;
+    return DRGNN_E_CAPACITY;      // (the host emulation has no cohort launch: drgnn_cohort_step_plan answers NONE)
+#else
+    CohortStep coh;
+    coh.members = members; coh.ids = ids; coh.counts = counts; coh.K = K; coh.stride = ids_stride;
+    return train_step_impl(net, hd, cache->x, cache->y, nullptr, cache->ws_i32, cache->ws_f32, cache->n_nodes,
+                           cache->n_edges, n_graphs, cache->n_graphs, ids, max_nodes, max_edges, max_c0, nullptr, nullptr,
+                           nullptr, nullptr, nullptr, nullptr, hints, stream_, nullptr, 0, &coh);
+#endif
 }
 
 int drgnn_net_reduce_grads(const drgnn_net_desc* net, const float* partials, int64_t n_nodes,
@@ -1412,11 +1464,14 @@ static int update_impl(int32_t slabs_per_graph, const drgnn_net_desc* net, const
                        int64_t head_offset, float* flat_param,
                        float* flat_grad, float* exp_avg, float* exp_avg_sq, int64_t n_param,
                        int32_t* step, float* loss, float lr, float beta1, float beta2, float eps,
-                       int32_t apply_adam, void* stream_, float* loss2 = nullptr) {
+                       int32_t apply_adam, void* stream_, float* loss2 = nullptr,
+                       const drgnn_cohort_member* coh_members = nullptr, int coh_K = 0, const int32_t* coh_counts = nullptr) {
     int rc = net_check(net);
     if (rc) return rc;
-    if (!conv_partials || !g_conv1 || !g_conv2 || !head_partials || !flat_grad) return DRGNN_E_ARG;
-    if (apply_adam && (!flat_param || !exp_avg || !exp_avg_sq || !step)) return DRGNN_E_ARG;
+    // (a cohort launch, drgnn_cohort_update: sources, flat buffers, step words and Adam's scalars come from the member table)
+    if (!coh_members && (!conv_partials || !head_partials || !flat_grad)) return DRGNN_E_ARG;
+    if (!g_conv1 || !g_conv2) return DRGNN_E_ARG;
+    if (!coh_members && apply_adam && (!flat_param || !exp_avg || !exp_avg_sq || !step)) return DRGNN_E_ARG;
     UpdateArgs u;
     ReduceArgs& r = u.r;
     if (slabs_per_graph != 0 && slabs_per_graph != net->n_branch && !(net->n_branch == 1 && slabs_per_graph == 2)) return DRGNN_E_ARG;
@@ -1436,7 +1491,7 @@ static int update_impl(int32_t slabs_per_graph, const drgnn_net_desc* net, const
     u.h.grad = flat_grad + head_offset; u.h.loss = loss; u.h.step = nullptr;
     u.readout = readout; u.hR = R; u.hH = H;
     u.step2 = readout ? step : nullptr;
-    u.loss2 = loss ? loss2 : nullptr;
+    u.loss2 = (loss || coh_members) ? loss2 : nullptr;
     u.ad.param = flat_param; u.ad.grad = flat_grad; u.ad.exp_avg = exp_avg; u.ad.exp_avg_sq = exp_avg_sq;
     u.ad.step = (readout && step) ? step + 1 : step; u.ad.n = n_param;
     u.ad.lr = lr; u.ad.beta1 = beta1; u.ad.beta2 = beta2; u.ad.eps = eps; u.ad.weight_decay = 0.0f;
@@ -1448,6 +1503,7 @@ static int update_impl(int32_t slabs_per_graph, const drgnn_net_desc* net, const
     const int head_items = (readout ? H * R : 0) + u.h.P - 1;
     const int head_blocks = (head_items + 63) / 64;
 #ifdef DRGNN_EMU
+    if (coh_members) return DRGNN_E_CAPACITY;
     for (int64_t i = 0; i < pitems; ++i) {
         const int br = (int)(i / r.n_partial), p = (int)(i % r.n_partial);
         if (!reduce_live(r, p)) continue;
@@ -1458,7 +1514,11 @@ static int update_impl(int32_t slabs_per_graph, const drgnn_net_desc* net, const
     if (u.step2) u.step2[0] = u.step2[1];
     (void)stream_; (void)head_blocks;
 #else
-    hipLaunchKernelGGL(k_update, dim3((unsigned)(u.conv_blocks + head_blocks)), dim3(DRGNN_UPDATE_THREADS), 0, (hipStream_t)stream_, u);
+    if (coh_members)
+        hipLaunchKernelGGL(k_update_cohort, dim3((unsigned)(u.conv_blocks + head_blocks), (unsigned)coh_K), dim3(DRGNN_UPDATE_THREADS), 0,
+                           (hipStream_t)stream_, u, coh_members, coh_counts, head_offset);
+    else
+        hipLaunchKernelGGL(k_update, dim3((unsigned)(u.conv_blocks + head_blocks)), dim3(DRGNN_UPDATE_THREADS), 0, (hipStream_t)stream_, u);
     HIP_TRY(hipGetLastError());
 #endif
     return 0;
@@ -1489,6 +1549,19 @@ int drgnn_step_update(const drgnn_net_desc* net, const float* conv_partials, int
     return update_impl(slabs_per_graph, net, conv_partials, n_graphs, g_conv1, g_conv2, head_partials, n_graphs, readout, R, H, O,
                        head_offset, flat_param, flat_grad, exp_avg, exp_avg_sq, n_param, step2, loss, lr, beta1,
                        beta2, eps, apply_adam, stream_);
+}
+
+int drgnn_cohort_update(const drgnn_net_desc* net, const drgnn_cohort_member* members, int32_t K, const int32_t* counts,
+                        drgnn_conv_grads* g_conv1, drgnn_conv_grads* g_conv2, int32_t R, int32_t H, int32_t O,
+                        int64_t head_offset, int64_t n_param, float* losses, int32_t apply_adam, void* stream_) {
+    if (!members || K < 1 || K > 65535 || !counts || n_param < 1 || head_offset < 0 || head_offset >= n_param) return DRGNN_E_ARG;
+    if (!net || R != DRGNN_H2 * net->n_branch || H < 1 || H > 512 || O < 1 || O > DRGNN_MAX_OUT) return DRGNN_E_WIDTH;
+    // (readout / step: non-null stand-ins select the fused-step slab layout; the kernel takes every member's own from the table)
+    static float stand_in_f;
+    static int32_t stand_in_i[2];
+    return update_impl(0, net, nullptr, 0, g_conv1, g_conv2, nullptr, 0, &stand_in_f, R, H, O, head_offset, nullptr, nullptr,
+                       nullptr, nullptr, n_param, stand_in_i, nullptr, 0.0f, 0.0f, 0.0f, 0.0f, apply_adam, stream_, losses,
+                       members, K, counts);
 }
 
 int drgnn_step_gradients(const drgnn_net_desc* net, const float* conv_partials, int64_t n_graphs,

@@ -649,6 +649,14 @@ DEV void update_head_store(const UpdateArgs& u, int item, float acc) {
     else if (item == n_grad && u.h.loss) { u.h.loss[0] = acc; if (u.loss2) u.loss2[0] = acc; }
 }
 
+// what a cohort launch adds to a step launch's arguments (k_step3b_cohort / k_step2_cohort below)
+struct CohortStep {
+    const drgnn_cohort_member* members;
+    const int32_t* ids;         // member m's graph numbers: ids + m * stride
+    const int32_t* counts;      // [K] mini-batch sizes
+    int K;
+    int64_t stride;
+};
 #ifndef DRGNN_EMU
 #ifdef DRGNN_KERNELS_MAIN
 __global__ void __launch_bounds__(256) k_ptrs(PtrArgs a) {
@@ -868,6 +876,62 @@ __global__ void __launch_bounds__(DRGNN_NTHREADS) k_step2_ens(StepCoLaunch C_by_
     ens_args(a, models, m);
     step2_block<KIND, XF, true, CLS, 1, false, XG>(C.step, a, g, smem_e2);
 }
+// ---- cohort training (include/drgnn.h: drgnn_cohort_member): K members of one net stepped in one launch, one workgroup per
+// (member, graph) with ens_slot's block numbering, the TRAINING instances of the one-workgroup forms.  Everything a member owns
+// -- parameters, slabs, outputs, its step2 words (step index, fault bits), its dropout seed -- and its mini-batch of this step
+// (graph numbers ids + m stride, counts[m] of them; the loss scale hf.B with it) is set in its workgroups' private StepArgs.
+// No workgroup waits for another.  The launch's StepDims describe ONE list of graphs: the host passes dims.count = 0 unless
+// all members step the same graphs.
+// every 32-bit word of a workgroup-uniform value through readfirstlane: the compiler then keeps it in scalar registers (the
+// member table is plain memory, not kernel arguments: left alone, its ~40 live words would sit in vector registers for the whole
+// kernel, on top of a block routine that already fills them)
+template <class T> DEV T wg_uniform_words(const T& v) {
+    static_assert(sizeof(T) % 4 == 0, "whole words");
+    union { T t; int w[sizeof(T) / 4]; } in, out;
+    in.t = v;
+#pragma unroll
+    for (int i = 0; i < (int)(sizeof(T) / 4); ++i) out.w[i] = __builtin_amdgcn_readfirstlane(in.w[i]);
+    return out.t;
+}
+DEV bool cohort_args(StepArgs& a, const CohortStep& c, int m, int g) {
+    const int B = WG_UNIFORM(c.counts[m]);
+    if (g >= B) return false;
+    const drgnn_cohort_member mm = wg_uniform_words(c.members[m]);
+    a.net = mm.net;
+    a.n_graphs = B;
+    a.gather_ids = c.ids + (int64_t)m * c.stride;
+    a.partials = mm.partials;
+    a.step2 = mm.step2;
+    a.hf.B = B; a.hf.seed = mm.seed; a.hf.step = mm.step2;
+    a.hf.w1 = mm.w1; a.hf.b1 = mm.b1; a.hf.w2 = mm.w2; a.hf.b2 = mm.b2;
+    a.hf.pred = mm.pred; a.hf.readout = mm.readout; a.hf.partials = mm.head_partials;
+    return true;
+}
+typedef void (*drgnn_cohort_kernel_t)(StepCoLaunch, CohortStep);
+template <int XF, int CLS, bool SG>
+__global__ void __launch_bounds__(DRGNN_NTHREADS) k_step3b_cohort(StepCoLaunch C_by_value, CohortStep coh) {
+    extern __shared__ __attribute__((aligned(16))) float smem_c3[];
+    PHASE_BEGIN();
+    const StepCoLaunch& C = step_kernarg();
+    co_kernarg_touch();
+    int g, m;
+    if (!ens_slot((int)blockIdx.x, coh.K, C.step.a.n_graphs, g, m)) return;
+    StepArgs a = C.step.a;
+    if (!cohort_args(a, coh, m, g)) return;
+    step3b_block<XF, true, CLS, true, SG>(C.step, a, g, smem_c3);
+}
+template <int KIND, int XF, int CLS, int XG>
+__global__ void __launch_bounds__(DRGNN_NTHREADS) k_step2_cohort(StepCoLaunch C_by_value, CohortStep coh) {
+    extern __shared__ __attribute__((aligned(16))) float smem_c2[];
+    PHASE_BEGIN();
+    const StepCoLaunch& C = step_kernarg();
+    co_kernarg_touch();
+    int g, m;
+    if (!ens_slot((int)blockIdx.x, coh.K, C.step.a.n_graphs, g, m)) return;
+    StepArgs a = C.step.a;
+    if (!cohort_args(a, coh, m, g)) return;
+    step2_block<KIND, XF, true, CLS, 1, true, XG>(C.step, a, g, smem_c2);
+}
 #ifdef DRGNN_KERNELS_MAIN
 __global__ void __launch_bounds__(DRGNN_NTHREADS) k_conv_gemm(ConvLayerArgs a) { conv_gemm_block(a, blockIdx.x); }
 __global__ void __launch_bounds__(256) k_conv_aggregate(ConvLayerArgs a) {
@@ -958,12 +1022,13 @@ __global__ void __launch_bounds__(256) k_head_reduce(HeadReduceArgs a) {
 // A FIFTH wave (q == 4) forms Adam's bias corrections meanwhile -- a chain of ~35 dependent double-precision operations
 // behind the load of the step index, which used to sit in front of wave 0's slab loads -- and hands them over through LDS.
 #define DRGNN_UPDATE_THREADS 320
-__global__ void __launch_bounds__(DRGNN_UPDATE_THREADS) k_update(UpdateArgs u) {
-    kernarg_touch_lines<DRGNN_KA_LINES(0, (int)sizeof(UpdateArgs))>(0);
-    __shared__ float quarter[4][64];
-    __shared__ float bias_scalars[2];
+// The body of one update block, shared by k_update and k_update_cohort.  u: the sums' sources, the head's destinations, Adam's
+// buffers and scalars (k_update: the kernel arguments; the cohort: a per-member copy whose descriptor arrays are never indexed).
+// dst: the conv gradient descriptors (strides, destinations) -- always the kernel arguments, so that the run-time branch index
+// stays a scalar load; gshift: added to every conv destination (the cohort: member m's flat gradient relative to member 0's).
+DEV void update_block(const UpdateArgs& u, const ReduceArgs& dst, int blk_id, int64_t gshift, float (*quarter)[64], float* bias_scalars) {
     const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
-    const bool conv = (int)blockIdx.x < u.conv_blocks;
+    const bool conv = blk_id < u.conv_blocks;
     // ONE textual barrier for all five waves: before it the four quarter waves issue their loads and sums and the
     // fifth forms Adam's two scalars; behind it wave 0 owns the element's update.
     float* d = nullptr;
@@ -984,20 +1049,21 @@ __global__ void __launch_bounds__(DRGNN_UPDATE_THREADS) k_update(UpdateArgs u) {
         // pointers, strides) are then scalar loads from the argument block.  With a per-lane branch (item / n_partial) the
         // compiler fetched them with vector loads from argument memory, one dependent round trip after the other in
         // reduce_dst's chain of cases -- microseconds in front of wave 0's slab loads.
-        int br = 0, blk = (int)blockIdx.x;
+        int br = 0, blk = blk_id;
         while (blk >= u.blocks_per_branch && br + 1 < a.n_branch) { blk -= u.blocks_per_branch; ++br; }
         const int p_raw = blk * 64 + lane;
-        live = p_raw < a.n_partial && reduce_live(a, p_raw);
+        live = p_raw < a.n_partial && reduce_live(dst, p_raw);
         const int p = live ? p_raw : 0;
         // wave 0 owns the element's update: its parameter / moment loads are issued BEFORE the slab loads, so that Adam
         // starts from registers once the quarter sums are in
-        d = (q == 0 && live) ? reduce_dst(a, br, p) : nullptr;
+        d = (q == 0 && live) ? reduce_dst(dst, br, p) : nullptr;
+        if (d) d += gshift;
         upd = d != nullptr && u.apply_adam;
         idx = upd ? (int64_t)(d - u.ad.grad) : -1;
         pre = adam_prefetch_state(u.ad, idx);
         quarter[q][lane] = live ? reduce_sum(a, br, p, q, 4) : 0.0f;
     } else {
-        item = ((int)blockIdx.x - u.conv_blocks) * 64 + lane;
+        item = (blk_id - u.conv_blocks) * 64 + lane;
         live = item < update_head_items(u);
         n_grad = update_head_items(u) - 1;
         d = (q == 0 && live && item < n_grad) ? u.h.grad + item : nullptr;
@@ -1019,7 +1085,38 @@ __global__ void __launch_bounds__(DRGNN_UPDATE_THREADS) k_update(UpdateArgs u) {
         }
     }
     // nobody reads step2[0] in this launch (Adam reads step2[1]): safe to commit it here
-    if (u.step2 && blockIdx.x == 0 && threadIdx.x == 0) u.step2[0] = u.step2[1];
+    if (u.step2 && blk_id == 0 && threadIdx.x == 0) u.step2[0] = u.step2[1];
+}
+__global__ void __launch_bounds__(DRGNN_UPDATE_THREADS) k_update(UpdateArgs u) {
+    kernarg_touch_lines<DRGNN_KA_LINES(0, (int)sizeof(UpdateArgs))>(0);
+    __shared__ float quarter[4][64];
+    __shared__ float bias_scalars[2];
+    update_block(u, u.r, (int)blockIdx.x, 0, quarter, bias_scalars);
+}
+// The update of a cohort (include/drgnn.h: drgnn_cohort_update): k_update's block once per member, the member from the second
+// grid dimension.  u: member 0's launch (shapes, strides, conv destinations); what differs per member comes from entry m of the
+// member table (plain loads, uniform per workgroup; conv destinations: member 0's shifted by the distance of the members' flat
+// gradients).  A member without a mini-batch this step (counts[m] == 0) is left alone:
+// no sums, no Adam, no commit, loss word unchanged.
+__global__ void __launch_bounds__(DRGNN_UPDATE_THREADS) k_update_cohort(UpdateArgs u_by_value, const drgnn_cohort_member* members,
+                                                                         const int32_t* counts, int64_t head_offset) {
+    kernarg_touch_lines<DRGNN_KA_LINES(0, (int)sizeof(UpdateArgs))>(0);
+    __shared__ float quarter[4][64];
+    __shared__ float bias_scalars[2];
+    const UpdateArgs& u0 = *reinterpret_cast<const UpdateArgs*>((const char*)__builtin_amdgcn_kernarg_segment_ptr());
+    const int m = (int)blockIdx.y;
+    const int B = __builtin_amdgcn_readfirstlane(counts[m]);
+    if (B <= 0) return;
+    const drgnn_cohort_member mm = wg_uniform_words(members[m]);
+    UpdateArgs u = u0;
+    u.r.partials = mm.partials; u.r.n_graphs = B;
+    u.h.partials = mm.head_partials; u.h.n_wg = B;
+    u.h.grad = mm.flat_grad + head_offset; u.h.loss = mm.loss;
+    u.readout = mm.readout; u.step2 = mm.step2; u.loss2 = u0.loss2 ? u0.loss2 + m : nullptr;      // (losses [K] of this step)
+    u.ad.param = mm.flat_param; u.ad.grad = mm.flat_grad; u.ad.exp_avg = mm.exp_avg; u.ad.exp_avg_sq = mm.exp_avg_sq;
+    u.ad.step = mm.step2 + 1;
+    u.ad.lr = mm.lr; u.ad.beta1 = mm.beta1; u.ad.beta2 = mm.beta2; u.ad.eps = mm.eps;
+    update_block(u, u0.r, (int)blockIdx.x, (int64_t)(mm.flat_grad - wg_uniform_words(members[0].flat_grad)), quarter, bias_scalars);
 }
 // drgnn_step_gradients: k_update's fixed-order sums without the optimiser -- the gradient of the step's slabs, each slab
 // optionally weighted by its graph's d loss / d pred (the autograd boundary, include/drgnn.h), plus one block that clears the

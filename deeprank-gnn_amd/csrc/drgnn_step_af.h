@@ -24,6 +24,9 @@ typedef void (*drgnn_step_kernel_t)(StepCoLaunch);
 #define DRGNN_AF_GINET_ENS 9      // k_step3b_ens: ensemble inference (K models per launch), GINet
 #define DRGNN_AF_SGAT_ENS 10      // k_step2_ens<DRGNN_SGAT>
 #define DRGNN_AF_FOUT_ENS 11      // k_step2_ens<DRGNN_FOUT>
+#define DRGNN_AF_GINET_COHORT 12  // k_step3b_cohort: cohort training (K members per launch), GINet
+#define DRGNN_AF_SGAT_COHORT 13   // k_step2_cohort<DRGNN_SGAT>
+#define DRGNN_AF_FOUT_COHORT 14   // k_step2_cohort<DRGNN_FOUT>
 
 // (cls: 1 = capacity-class layout, honoured for the 32- and 48-wide kernels only, training and inference launches -- the host
 // asks for nothing else; 48: the feature count of the reference's shipped regression models)
@@ -103,6 +106,31 @@ template <int KIND, int XF> drgnn_ens_kernel_t af_pick_single_ens(int cls, int l
     if (cls && C1) return k_step2_ens<KIND, XF, C1, 0>;
     return k_step2_ens<KIND, XF, 0, 0>;
 }
+// the cohort instances (drgnn_kernels.h: k_step3b_cohort / k_step2_cohort): the TRAINING instances of the same forms, with a
+// member axis; same classes and from-memory levels as the ensemble's
+template <int XF> drgnn_cohort_kernel_t af_pick_ginet_cohort(int cls, int level) {
+    constexpr int C1 = (XF == 32 || XF == 48) ? 1 : 0;
+    if (level) return k_step3b_cohort<XF, 0, true>;
+    if (cls && C1) return k_step3b_cohort<XF, C1, false>;
+    return k_step3b_cohort<XF, 0, false>;
+}
+template <int KIND, int XF> drgnn_cohort_kernel_t af_pick_single_cohort(int cls, int level) {
+    constexpr int C1 = (XF == 32 || XF == 48) ? 1 : 0;
+    if (level == 1) return k_step2_cohort<KIND, XF, 0, 1>;
+    if constexpr (XF >= 32) { if (level == 2) return k_step2_cohort<KIND, XF, 0, 2>; }
+    if (level) return nullptr;
+    if (cls && C1) return k_step2_cohort<KIND, XF, C1, 0>;
+    return k_step2_cohort<KIND, XF, 0, 0>;
+}
+#define DRGNN_AF_DEFINE_GINET_COHORT(W) DRGNN_AF_DEFINE_GINET_COHORT_X(W)
+#define DRGNN_AF_DEFINE_SGAT_COHORT(W) DRGNN_AF_DEFINE_SGAT_COHORT_X(W)
+#define DRGNN_AF_DEFINE_FOUT_COHORT(W) DRGNN_AF_DEFINE_FOUT_COHORT_X(W)
+#define DRGNN_AF_DEFINE_GINET_COHORT_X(W) \
+    drgnn_cohort_kernel_t af_ginet_cohort_##W(int cls, int level) { return af_pick_ginet_cohort<W>(cls, level); }
+#define DRGNN_AF_DEFINE_SGAT_COHORT_X(W) \
+    drgnn_cohort_kernel_t af_sgat_cohort_##W(int cls, int level) { return af_pick_single_cohort<DRGNN_SGAT, W>(cls, level); }
+#define DRGNN_AF_DEFINE_FOUT_COHORT_X(W) \
+    drgnn_cohort_kernel_t af_fout_cohort_##W(int cls, int level) { return af_pick_single_cohort<DRGNN_FOUT, W>(cls, level); }
 #define DRGNN_AF_DEFINE_GINET_ENS(W) DRGNN_AF_DEFINE_GINET_ENS_X(W)
 #define DRGNN_AF_DEFINE_SGAT_ENS(W) DRGNN_AF_DEFINE_SGAT_ENS_X(W)
 #define DRGNN_AF_DEFINE_FOUT_ENS(W) DRGNN_AF_DEFINE_FOUT_ENS_X(W)
@@ -132,6 +160,9 @@ template <int KIND, int XF> drgnn_ens_kernel_t af_pick_single_ens(int cls, int l
     drgnn_ens_kernel_t af_ginet_ens_##W(int cls, int level);                                   \
     drgnn_ens_kernel_t af_sgat_ens_##W(int cls, int level);                                    \
     drgnn_ens_kernel_t af_fout_ens_##W(int cls, int level);                                    \
+    drgnn_cohort_kernel_t af_ginet_cohort_##W(int cls, int level);                             \
+    drgnn_cohort_kernel_t af_sgat_cohort_##W(int cls, int level);                              \
+    drgnn_cohort_kernel_t af_fout_cohort_##W(int cls, int level);                              \
     template <> inline drgnn_step_kernel_t af_sgat_whole<W>(int cls) { return af_sgat_whole_##W(cls); }
 DRGNN_AF_DECLARE(16) DRGNN_AF_DECLARE(32) DRGNN_AF_DECLARE(48) DRGNN_AF_DECLARE(64)
 #undef DRGNN_AF_DECLARE
@@ -174,6 +205,9 @@ DRGNN_AF_FOR_WIDTHS(DRGNN_AF_DEFINE_GINET_ENS)
 DRGNN_AF_FOR_WIDTHS(DRGNN_AF_DEFINE_SGAT_ENS)
 DRGNN_AF_FOR_WIDTHS(DRGNN_AF_DEFINE_FOUT_ENS)
 DRGNN_AF_FOR_WIDTHS(DRGNN_AF_DEFINE_FOUT_XG)
+DRGNN_AF_FOR_WIDTHS(DRGNN_AF_DEFINE_GINET_COHORT)
+DRGNN_AF_FOR_WIDTHS(DRGNN_AF_DEFINE_SGAT_COHORT)
+DRGNN_AF_FOR_WIDTHS(DRGNN_AF_DEFINE_FOUT_COHORT)
 #endif
 // family: DRGNN_AF_*; width: 16 / 32 / 48 / 64.  nullptr: no such instance
 // level: 1 / 2 of the from-memory families (DRGNN_AF_SGAT_XG / _FOUT_XG)
@@ -211,6 +245,22 @@ static drgnn_ens_kernel_t af_ens_kernel(int kind, int width, int cls, int level)
     default: return nullptr;
     }
 #undef DRGNN_AF_ENS_CASE
+}
+// the cohort instance of (kind, width, cls, from-memory level)
+static drgnn_cohort_kernel_t af_cohort_kernel(int kind, int width, int cls, int level) {
+#define DRGNN_AF_COHORT_CASE(W)                                                                \
+    case W:                                                                                     \
+        switch (kind) {                                                                         \
+        case DRGNN_GINET: return af_ginet_cohort_##W(cls, level);                               \
+        case DRGNN_SGAT: return af_sgat_cohort_##W(cls, level);                                 \
+        case DRGNN_FOUT: return af_fout_cohort_##W(cls, level);                                 \
+        default: return nullptr;                                                                \
+        }
+    switch (width) {
+        DRGNN_AF_FOR_WIDTHS(DRGNN_AF_COHORT_CASE)
+    default: return nullptr;
+    }
+#undef DRGNN_AF_COHORT_CASE
 }
 #endif  // DRGNN_KERNELS_MAIN
 

@@ -713,6 +713,49 @@ int drgnn_ens_predict_cached(const drgnn_net_desc* net, const drgnn_head_desc* h
                              int32_t max_nodes, int32_t max_edges, int32_t max_c0, int32_t* step2, float* pred,
                              float* readout, const drgnn_step_hints* hints, void* stream);
 
+/* Cohort training: K members of one net (same kind, F, R, H, O: cross-validation folds, seeds, a learning-rate sweep) stepped
+ * over the same cached set in TWO launches per optimisation step of all K -- the training counterpart of the ensemble launch.
+ * drgnn_cohort_train_step_cached: one workgroup per (member, graph) with the ensemble's block numbering (a graph's K members
+ * sit on one XCD); only the one-workgroup-per-graph forms, so no workgroup waits for another and any K x B is safe.
+ * drgnn_cohort_update: drgnn_step_update's fixed-order sums and Adam once per member (second grid dimension).
+ * Member m's result is what drgnn_net_train_step_cached (plan force_wgs = 1) + drgnn_step_update give for that member alone,
+ * bit for bit.  The member table lives in DEVICE memory, K entries, written once by the caller.  The members' parameters have
+ * the same layout: every gradient tensor sits at the same offset of its member's flat gradient buffer. */
+typedef struct drgnn_cohort_member {
+    drgnn_net_desc net;                                          /* conv parameters (same strides as member 0's) */
+    const float* w1; const float* b1; const float* w2; const float* b2;   /* FC head */
+    float* flat_param; float* flat_grad; float* exp_avg; float* exp_avg_sq;   /* [n_param] each */
+    int32_t* step2;                                              /* the member's own int32[4], as drgnn_net_train_step's */
+    float* pred; float* readout; float* head_partials; float* partials;   /* outputs / slabs, sized for the largest mini-batch */
+    float* loss;                                                 /* [1] the member's loss word */
+    float lr, beta1, beta2, eps;
+    uint32_t seed; int32_t reserved;                             /* dropout stream seed */
+} drgnn_cohort_member;
+/* The plan of a cohort launch of K members over plan->n_graphs graphs each (training; otherwise as drgnn_ens_step_plan).
+ * Returns 1 when the fused cohort launches take these bounds, 0 otherwise (family NONE: the caller steps the members one by
+ * one; the host emulation always answers NONE). */
+int32_t drgnn_cohort_step_plan(drgnn_step_plan* plan, int32_t K);
+/* The fused step of all members.  ids: DEVICE int32, member m's graph numbers of this step at ids + m * ids_stride;
+ * counts: DEVICE int32 [K], member m's mini-batch size B_m <= n_graphs (= the largest, which sizes the grid).  A slot
+ * g >= B_m returns at once; a member with B_m = 0 is not stepped (step index, slabs, loss word untouched).  Graph numbers must
+ * lie inside the cached set (the caller checks: they are device memory here).  Targets come from cache->y.
+ * `net` / `head`: member 0's descriptors (shapes, task, dropout probability, class weights; their parameter pointers and the
+ * seed are not read).  hints->plan: the plan drgnn_cohort_step_plan returned (required).  hints->host_ids (+ set_node_ptr /
+ * set_edge_ptr): ONLY when every member steps exactly these n_graphs graphs -- the host-known sizes then travel in the launch
+ * arguments as for a single model; otherwise leave them NULL (sizes come from the workspace tables).  Never allocates or
+ * synchronises; hipGraph-capturable. */
+int drgnn_cohort_train_step_cached(const drgnn_net_desc* net, const drgnn_head_desc* head, const drgnn_cohort_member* members,
+                                   int32_t K, const drgnn_topology_cache* cache, const int32_t* ids, const int32_t* counts,
+                                   int64_t ids_stride, int64_t n_graphs, int32_t max_nodes, int32_t max_edges, int32_t max_c0,
+                                   const drgnn_step_hints* hints, void* stream);
+/* The update of all members: member m sums its counts[m] slabs in drgnn_step_update's fixed order, applies Adam with its own
+ * learning rate and step index, commits its step2[0] = step2[1] and writes its loss word.  g_conv1 / g_conv2 / head_offset:
+ * member 0's gradient destinations (member m's are those shifted by members[m].flat_grad - members[0].flat_grad).
+ * losses: optional DEVICE float [K]: a stepped member's loss goes there too (an epoch's [steps, K] record, row by row). */
+int drgnn_cohort_update(const drgnn_net_desc* net, const drgnn_cohort_member* members, int32_t K, const int32_t* counts,
+                        drgnn_conv_grads* g_conv1, drgnn_conv_grads* g_conv2, int32_t R, int32_t H, int32_t O,
+                        int64_t head_offset, int64_t n_param, float* losses /* optional */, int32_t apply_adam, void* stream);
+
 /* Data-parallel hook of the native epoch loop: called on the host once per mini-batch, after the launches that leave
  * this rank's gradient of mini-batch `batch_index` in flat_grad have been ENQUEUED on `stream`; it must enqueue the
  * exchange (one all-reduce of flat_grad, weighted n_local / n_global) on the same stream and return 0.  The loop then
