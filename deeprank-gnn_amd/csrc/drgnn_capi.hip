@@ -363,11 +363,17 @@ int drgnn_topology_status(const int32_t* ws_i32, int64_t n_nodes, int64_t n_edge
 }
 
 // ---- fused net ----------------------------------------------------------------------
+// the LDS capacities a launch's bounds ask for: room for one edge at least; max_c0 counts only where it bounds anything
+struct StepCaps { int N, E, C; };
+static StepCaps step_caps(int32_t max_nodes, int32_t max_edges, int32_t max_c0) {
+    return StepCaps{max_nodes, max_edges > 0 ? max_edges : 1, (max_c0 > 0 && max_c0 < max_nodes) ? max_c0 : max_nodes};
+}
+
 int64_t drgnn_net_lds_bytes(int32_t kind, int32_t n_feat, int32_t max_nodes, int32_t max_edges,
                             int32_t max_c0, int32_t backward) {
     if (max_nodes <= 0) return 0;
-    const int capC = (max_c0 > 0 && max_c0 < max_nodes) ? max_c0 : max_nodes;
-    return 4 * net_scratch_words(kind, n_feat, max_nodes, max_edges > 0 ? max_edges : 1, capC, backward);
+    const StepCaps c = step_caps(max_nodes, max_edges, max_c0);
+    return 4 * net_scratch_words(kind, n_feat, c.N, c.E, c.C, backward);
 }
 
 int64_t drgnn_net_partial_elems(int32_t kind, int32_t n_feat) { (void)kind; return net_partial_floats(n_feat); }
@@ -405,9 +411,8 @@ static int net_launch(NetLaunch& L, int32_t max_nodes, int32_t max_edges, int32_
     int64_t use_lds = 0;
     L.a.hf.stage = 0;
     if (lds > 0 && lds <= DRGNN_LDS_LIMIT) {
-        L.capN = max_nodes;
-        L.capE = max_edges > 0 ? max_edges : 1;
-        L.capC = (max_c0 > 0 && max_c0 < max_nodes) ? max_c0 : max_nodes;
+        const StepCaps c = step_caps(max_nodes, max_edges, max_c0);
+        L.capN = c.N; L.capE = c.E; L.capC = c.C;
         use_lds = lds;
         if (BWD && L.a.hf.enabled) {    // room to keep the head's weights in LDS as well?
             const int64_t extra = 4 * head_stage_words(L.a.hf.R, L.a.hf.H, L.a.hf.O);
@@ -645,8 +650,8 @@ static int64_t step_lds_bytes(int kind, int F, int capN, int capE, int capC, int
 int64_t drgnn_net_step_lds_bytes(int32_t kind, int32_t n_feat, int32_t max_nodes, int32_t max_edges,
                                  int32_t max_c0, int32_t R, int32_t H, int32_t O) {
     if (max_nodes <= 0 || max_nodes > 32767 || max_edges > 65535 || n_feat > 256) return 0;   // else: the launch pair
-    const int capC = (max_c0 > 0 && max_c0 < max_nodes) ? max_c0 : max_nodes;
-    return step_lds_bytes(kind, n_feat, max_nodes, max_edges > 0 ? max_edges : 1, capC, R, H, O);
+    const StepCaps c = step_caps(max_nodes, max_edges, max_c0);
+    return step_lds_bytes(kind, n_feat, c.N, c.E, c.C, R, H, O);
 }
 
 int64_t drgnn_head_compact_elems(int32_t R, int32_t H, int32_t O) { return head_compact_floats(R, H, O); }
@@ -893,6 +898,19 @@ static StepPick step_pick(const StepAsk& q) {
     return k;
 }
 
+// sGAT / FoutNet: the from-memory level of the pick (1: x rows, 2: S rows too); GINet: 1 = its S-from-memory form
+static int step_mem_level(int kind, const StepPick& k) { return kind == DRGNN_GINET ? (k.sg ? 1 : 0) : k.xg; }
+
+// The shape of a launch and the overrides of its plan; the rest as for a launch that co-builds nothing, reads an aligned x and
+// is free in its layout -- the callers fill in what they know better.
+static StepAsk step_ask(int kind, int F, const StepCaps& c, int R, int H, int O, int64_t B, bool train, const drgnn_step_plan* plan) {
+    StepAsk q;
+    q.kind = kind; q.F = F; q.capN = c.N; q.capE = c.E; q.capC = c.C; q.R = R; q.H = H; q.O = O; q.B = B;
+    q.co = 0; q.co_roles = 1; q.train = train; q.x_ok = true; q.topo_flags = 0; q.commit_wgs = 0;
+    q.ov = step_overrides_of(plan);
+    return q;
+}
+
 static bool step_bounds_ok(int32_t max_nodes, int32_t max_edges, int32_t n_feat) {
     return max_nodes > 0 && max_nodes <= 32767 && max_edges <= 65535 && n_feat <= 256;
 }
@@ -904,42 +922,36 @@ int32_t drgnn_net_step_plan(drgnn_step_plan* p) {
     if (!step_bounds_ok(p->max_nodes, p->max_edges, p->n_feat) || p->n_graphs < 0 || p->H < 1 || p->H > 512 || p->O < 1 ||
         p->O > DRGNN_MAX_OUT || p->kind < 0 || p->kind > DRGNN_FOUT)
         return 0;
-    StepAsk q;
-    q.kind = p->kind; q.F = p->n_feat; q.capN = p->max_nodes; q.capE = p->max_edges > 0 ? p->max_edges : 1;
-    q.capC = (p->max_c0 > 0 && p->max_c0 < p->max_nodes) ? p->max_c0 : p->max_nodes;
-    q.R = p->R; q.H = p->H; q.O = p->O; q.B = p->n_graphs;
+    StepAsk q = step_ask(p->kind, p->n_feat, step_caps(p->max_nodes, p->max_edges, p->max_c0), p->R, p->H, p->O, p->n_graphs,
+                         p->train != 0, p);
     q.co = p->co_built_graphs > 0 ? p->co_built_graphs : 0;
     q.co_roles = (q.co > 0 && q.co <= DRGNN_TOPO_SPLIT_MAX_GRAPHS) ? 2 : 1;
-    q.train = p->train != 0; q.x_ok = true; q.topo_flags = p->topo_flags; q.commit_wgs = 0;
-    q.ov = step_overrides_of(p);
+    q.topo_flags = p->topo_flags;
     const StepPick k = step_pick(q);
     if (k.rc) return 0;
     p->family = k.family; p->wgs_per_graph = k.wgs; p->slabs_per_graph = k.slabs; p->width = k.width; p->cls = k.cls;
     p->lean_ok = k.lean_ok; p->builder_wgs_per_graph = k.builder_roles; p->lds_bytes = k.lds; p->xchg_words = k.xchg_words;
-    p->from_memory = (k.sg || k.xg) ? 1 : 0;
+    p->from_memory = step_mem_level(p->kind, k) ? 1 : 0;
     return k.wgs;
 }
 
 int64_t drgnn_net_step_xchg_elems(int32_t kind, int32_t max_nodes, int32_t max_c0, int32_t H) {
     if (kind == DRGNN_GINET) return 2 * (int64_t)(H > DRGNN_H2 ? H : DRGNN_H2);
-    const int capC = (max_c0 > 0 && max_c0 < max_nodes) ? max_c0 : max_nodes;
+    const int capC = step_caps(max_nodes, 0, max_c0).C;
     return step2_xchg_words(capC > 0 ? capC : 1);
 }
 
 int32_t drgnn_net_step_variant(int32_t kind, const float* x, int32_t n_feat, int32_t max_nodes, int32_t max_edges,
                                int32_t max_c0, int32_t H, int32_t O) {
-    const int capC = (max_c0 > 0 && max_c0 < max_nodes) ? max_c0 : max_nodes;
-    return step_variant(kind, x, n_feat, max_nodes, max_edges > 0 ? max_edges : 1, capC, H, O);
+    const StepCaps c = step_caps(max_nodes, max_edges, max_c0);
+    return step_variant(kind, x, n_feat, c.N, c.E, c.C, H, O);
 }
 
 #ifndef DRGNN_EMU
-// One launch of a step kernel instance (+ the co-launched builder's workgroups).  These kernels use up to the whole 160 KiB of
-// LDS: the attribute is raised once per kernel instance and device (the call costs host time on every launch otherwise).
-// (ens: an ensemble instance, drgnn_kernels.h k_step3b_ens / k_step2_ens -- its member table and K follow the launch arguments;
-// coh: a cohort instance, k_step3b_cohort / k_step2_cohort -- its CohortStep follows them instead)
-static int step_launch(drgnn_step_kernel_t kern, int64_t lds_bytes, unsigned grid, hipStream_t stream, const StepCoLaunch& C,
-                       const drgnn_ens_member* ens = nullptr, int ens_K = 0, const CohortStep* coh = nullptr) {
-    if (!kern) return DRGNN_E_ARG;
+// One launch of a step kernel instance (+ the co-launched builder's workgroups) with the argument array its caller built.  These
+// kernels use up to the whole 160 KiB of LDS: the attribute is raised once per kernel instance and device (the call costs host
+// time on every launch otherwise).
+static int step_launch(const void* kern, void** args, int64_t lds_bytes, unsigned grid, hipStream_t stream) {
     if (lds_bytes > 64 * 1024) {
         struct Seen { const void* fn; int dev; };
         static Seen seen[256];
@@ -947,92 +959,126 @@ static int step_launch(drgnn_step_kernel_t kern, int64_t lds_bytes, unsigned gri
         const int dev = step_current_device();
         bool known = false;
         const int n = __atomic_load_n(&n_seen, __ATOMIC_ACQUIRE);
-        for (int i = 0; i < n && !known; ++i) known = seen[i].fn == (const void*)kern && seen[i].dev == dev;
+        for (int i = 0; i < n && !known; ++i) known = seen[i].fn == kern && seen[i].dev == dev;
         if (!known) {
-            if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DRGNN_LDS_LIMIT) != hipSuccess) {
+            if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DRGNN_LDS_LIMIT) != hipSuccess) {
                 (void)hipGetLastError();      // (profiling builds carry a static LDS word: ask for what this launch needs)
-                HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+                HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
             } else {
                 // (a cache, not state: a lost race only repeats the idempotent call above)
                 const int slot = __atomic_fetch_add(&n_seen, 0, __ATOMIC_RELAXED);
-                if (slot < 256) { seen[slot].fn = (const void*)kern; seen[slot].dev = dev; __atomic_store_n(&n_seen, slot + 1, __ATOMIC_RELEASE); }
+                if (slot < 256) { seen[slot].fn = kern; seen[slot].dev = dev; __atomic_store_n(&n_seen, slot + 1, __ATOMIC_RELEASE); }
             }
         }
     }
-    void* args[] = {const_cast<StepCoLaunch*>(&C), &ens, &ens_K};
-    if (coh) args[1] = const_cast<CohortStep*>(coh);
-    HIP_TRY(hipLaunchKernel((const void*)kern, dim3(grid), dim3(DRGNN_NTHREADS), args, (size_t)lds_bytes, stream));
+    HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(DRGNN_NTHREADS), args, (size_t)lds_bytes, stream));
     return 0;
 }
 #endif
 
-// n_graphs graphs of the launch; (n_nodes, n_edges, ws_graphs): the shape the workspace was laid out for (the
-// mini-batch itself, or a whole cached set whose graphs gather_ids[0..n_graphs) are stepped)
-static int train_step_impl(const drgnn_net_desc* net, const drgnn_head_desc* hd, const float* x,
-                           const void* target, int32_t* step2, const int32_t* ws_i32, const float* ws_f32,
-                           int64_t n_nodes, int64_t n_edges, int64_t n_graphs, int64_t ws_graphs,
-                           const int32_t* gather_ids, int32_t max_nodes,
-                           int32_t max_edges, int32_t max_c0, float* pred, float* readout,
-                           float* head_partials, float* partials, uint64_t* xchg,
-                           const drgnn_topology_request* next, const drgnn_step_hints* hints, void* stream_,
-                           const drgnn_ens_member* ens = nullptr, int ens_K = 0, const CohortStep* coh = nullptr) {
-    int rc = net_check(net);
+// The operands of one fused step launch, as its entry point (drgnn_net_train_step, drgnn_net_train_step_cached,
+// drgnn_ens_predict_cached, drgnn_cohort_train_step_cached) got them.
+struct StepOperands {
+    const drgnn_net_desc* net;
+    const drgnn_head_desc* hd;
+    const float* x;
+    const void* target;
+    int32_t* step2;
+    const int32_t* ws_i32;
+    const float* ws_f32;
+    // n_graphs graphs of the launch; (n_nodes, n_edges, ws_graphs): the shape the workspace was laid out for (the mini-batch
+    // itself, or a whole cached set whose graphs gather_ids[0..n_graphs) are stepped)
+    int64_t n_nodes, n_edges, n_graphs, ws_graphs;
+    const int32_t* gather_ids;
+    int32_t max_nodes, max_edges, max_c0;
+    float *pred, *readout, *head_partials, *partials;
+    uint64_t* xchg;
+    const drgnn_topology_request* next;
+    const drgnn_step_hints* hints;
+    void* stream;
+    const drgnn_ens_member* ens;      // an ensemble launch: its member table and K
+    int ens_K;
+    const CohortStep* coh;            // a cohort launch
+};
+// ... of a launch on a cached set's workspace (the callers have checked cache, cache->x and cache->ws_i32)
+static StepOperands step_operands_cached(const drgnn_net_desc* net, const drgnn_head_desc* hd, const drgnn_topology_cache* cache,
+                                         const int32_t* ids, int64_t n_graphs, int32_t max_nodes, int32_t max_edges, int32_t max_c0,
+                                         const drgnn_step_hints* hints, void* stream) {
+    StepOperands s = {};
+    s.net = net; s.hd = hd; s.x = cache->x; s.target = cache->y; s.ws_i32 = cache->ws_i32; s.ws_f32 = cache->ws_f32;
+    s.n_nodes = cache->n_nodes; s.n_edges = cache->n_edges; s.n_graphs = n_graphs; s.ws_graphs = cache->n_graphs;
+    s.gather_ids = ids; s.max_nodes = max_nodes; s.max_edges = max_edges; s.max_c0 = max_c0; s.hints = hints; s.stream = stream;
+    return s;
+}
+
+static int step_check(const StepOperands& s) {
+    const drgnn_net_desc* net = s.net;
+    const drgnn_head_desc* hd = s.hd;
+    const int rc = net_check(net);
     if (rc) return rc;
 #ifdef DRGNN_EMU
-    if (ens || coh) return DRGNN_E_CAPACITY;      // (the host emulation has no ensemble / cohort launch: their plans answer NONE)
+    if (s.ens || s.coh) return DRGNN_E_CAPACITY;      // (the host emulation has no ensemble / cohort launch: their plans answer NONE)
 #else
     // a cohort launch (drgnn_cohort_train_step_cached): the members' parameters, outputs, slabs and step words come from the
     // member table; what the checks below ask of a single model's are member 0's stand-ins
-    if (coh && (coh->K < 1 || !coh->members || !coh->ids || !coh->counts || !hd || hd->train != 1 || hd->task == DRGNN_TASK_GRAD ||
-                hd->drop_mask || !(hints && hints->plan) || !target || ens))
+    if (s.coh && (s.coh->K < 1 || !s.coh->members || !s.coh->ids || !s.coh->counts || !hd || hd->train != 1 ||
+                  hd->task == DRGNN_TASK_GRAD || hd->drop_mask || !(s.hints && s.hints->plan) || !s.target || s.ens))
         return DRGNN_E_ARG;
 #endif
-    if (ens && (ens_K < 1 || !gather_ids || hd->train || !(hints && hints->plan))) return DRGNN_E_ARG;
-    if (!hd || !x || !ws_i32) return DRGNN_E_ARG;
-    if (!coh && (!hd->w1 || !hd->b1 || !hd->w2 || !hd->b2 || !step2 || !pred || !readout)) return DRGNN_E_ARG;
+    if (s.ens && (s.ens_K < 1 || !s.gather_ids || hd->train || !(s.hints && s.hints->plan))) return DRGNN_E_ARG;
+    if (!hd || !s.x || !s.ws_i32) return DRGNN_E_ARG;
+    if (!s.coh && (!hd->w1 || !hd->b1 || !hd->w2 || !hd->b2 || !s.step2 || !s.pred || !s.readout)) return DRGNN_E_ARG;
     // hd->train: 1 = the whole step; 0 = inference; 2 = the forward of a training step (predictions only, dropout on)
     if (hd->train < 0 || hd->train > 2) return DRGNN_E_ARG;
-    const bool full_step = hd->train == 1;
-    if (full_step && !coh && (!target || !head_partials || !partials)) return DRGNN_E_ARG;      // inference needs neither
+    if (hd->train == 1 && !s.coh && (!s.target || !s.head_partials || !s.partials)) return DRGNN_E_ARG;      // inference needs neither
     if (hd->task != DRGNN_TASK_REG && hd->task != DRGNN_TASK_CLASS && hd->task != DRGNN_TASK_GRAD) return DRGNN_E_ARG;
-    if (hd->task == DRGNN_TASK_GRAD && gather_ids) return DRGNN_E_ARG;      // (the upstream gradient is indexed by slot)
-    if (net->n_branch > 1 && !xchg && !ens && !coh) return DRGNN_E_ARG;      // (the ensemble / cohort forms exchange nothing)
-    if (net->kind == DRGNN_SGAT && !ws_f32) return DRGNN_E_ARG;
+    if (hd->task == DRGNN_TASK_GRAD && s.gather_ids) return DRGNN_E_ARG;      // (the upstream gradient is indexed by slot)
+    if (net->n_branch > 1 && !s.xchg && !s.ens && !s.coh) return DRGNN_E_ARG;      // (the ensemble / cohort forms exchange nothing)
+    if (net->kind == DRGNN_SGAT && !s.ws_f32) return DRGNN_E_ARG;
     if (hd->R != DRGNN_H2 * net->n_branch || hd->H < 1 || hd->H > 512 || hd->O < 1 || hd->O > DRGNN_MAX_OUT)
         return DRGNN_E_WIDTH;
-    if (!step_bounds_ok(max_nodes, max_edges, net->n_feat)) return DRGNN_E_CAPACITY;
-    const int kind = net->kind, F = net->n_feat;
-    // the co-launched builder of the next mini-batch's topology
+    if (!step_bounds_ok(s.max_nodes, s.max_edges, net->n_feat)) return DRGNN_E_CAPACITY;
+    return 0;
+}
+
+// the co-launched builder of the next mini-batch's topology
+struct StepBuilder {
     TopoLaunch T;
-    int64_t tlds = 0;
-    bool co_ok = false;
-    if (next) {
-        rc = topo_prepare_req(T, &tlds, next);
-        if (rc) return rc;
-        co_ok = T.capN > 0 && T.user_nptr != nullptr && !(T.args.cluster1 != nullptr && T.args.c1_ptr == nullptr) &&
-                T.args.n_graphs > 0 && n_graphs > 0;
-        // the builder inside a GINet / FoutNet step launch is compiled without the edge-weight path: a request that wants
-        // weights (another kind's topology) gets a launch of its own
-        if (kind != DRGNN_SGAT && T.args.edge_attr != nullptr && T.tv.w0 != nullptr) co_ok = false;
-    }
-    // ---- the layout: one decision procedure for this launch and for drgnn_net_step_plan ----------------------------------
-    StepAsk q;
-    q.kind = kind; q.F = F; q.capN = max_nodes; q.capE = max_edges > 0 ? max_edges : 1;
-    q.capC = (max_c0 > 0 && max_c0 < max_nodes) ? max_c0 : max_nodes;
-    q.R = hd->R; q.H = hd->H; q.O = hd->O; q.B = n_graphs;
-    q.co = co_ok ? (int64_t)T.args.n_graphs : 0;
-    q.co_roles = co_ok ? T.roles : 1;
-    q.train = full_step;
-    q.x_ok = (((uintptr_t)x) & 15) == 0;
+    int64_t lds;
+    bool ok;      // the request can share the step's launch
+};
+static int step_builder(const StepOperands& s, StepBuilder& b) {
+    b.lds = 0; b.ok = false;
+    if (!s.next) return 0;
+    const int rc = topo_prepare_req(b.T, &b.lds, s.next);
+    if (rc) return rc;
+    const TopoLaunch& T = b.T;
+    b.ok = T.capN > 0 && T.user_nptr != nullptr && !(T.args.cluster1 != nullptr && T.args.c1_ptr == nullptr) &&
+           T.args.n_graphs > 0 && s.n_graphs > 0;
+    // the builder inside a GINet / FoutNet step launch is compiled without the edge-weight path: a request that wants
+    // weights (another kind's topology) gets a launch of its own
+    if (s.net->kind != DRGNN_SGAT && T.args.edge_attr != nullptr && T.tv.w0 != nullptr) b.ok = false;
+    return 0;
+}
+
+// the layout: one decision procedure (step_pick) for this launch and for drgnn_net_step_plan, and what the launch's plan and
+// hints commit it to
+static int step_layout(const StepOperands& s, StepBuilder& b, StepAsk& q, StepPick& k) {
+    const drgnn_head_desc* hd = s.hd;
+    const drgnn_step_hints* hints = s.hints;
+    const drgnn_step_plan* plan = hints ? hints->plan : nullptr;
+    const int kind = s.net->kind;
+    q = step_ask(kind, s.net->n_feat, step_caps(s.max_nodes, s.max_edges, s.max_c0), hd->R, hd->H, hd->O, s.n_graphs, hd->train == 1, plan);
+    q.co = b.ok ? (int64_t)b.T.args.n_graphs : 0;
+    q.co_roles = b.ok ? b.T.roles : 1;
+    q.x_ok = (((uintptr_t)s.x) & 15) == 0;
     q.topo_flags = hints ? hints->topo_flags : 0;
     // (the caller vouches for the tiles' flavour: weighted sums for sGAT, plain sums for FoutNet / GINet)
     if (!(hints && hints->tiles && ((((uintptr_t)hints->tiles) & 15) == 0))) q.topo_flags &= ~DRGNN_TOPO_TILES;
-    const drgnn_step_plan* plan = hints ? hints->plan : nullptr;
-    q.ov = step_overrides_of(plan);
     q.commit_wgs = (kind == DRGNN_GINET) ? 0 : (plan && plan->wgs_per_graph == 2) ? 2 : 1;
-    if (ens || coh) { q.ov.force_wgs = 1; q.commit_wgs = (kind == DRGNN_GINET) ? 0 : 1; }      // (the ensemble / cohort forms: one workgroup per graph)
-    if (q.commit_wgs == 2 && !xchg) return DRGNN_E_CAPACITY;
-    const StepPick k = step_pick(q);
+    if (s.ens || s.coh) { q.ov.force_wgs = 1; q.commit_wgs = (kind == DRGNN_GINET) ? 0 : 1; }      // (the ensemble / cohort forms: one workgroup per graph)
+    if (q.commit_wgs == 2 && !s.xchg) return DRGNN_E_CAPACITY;
+    k = step_pick(q);
     if (k.rc) return k.rc;
     // a workspace built with DRGNN_TOPO_LEAN holds only what the aggregation-first kernels read
     if (hints && (hints->topo_flags & DRGNN_TOPO_LEAN) && !k.lean_ok) return DRGNN_E_ARG;
@@ -1045,124 +1091,167 @@ static int train_step_impl(const drgnn_net_desc* net, const drgnn_head_desc* hd,
     if (plan && plan->family != DRGNN_STEP_FAMILY_NONE && (plan->train != 0) == q.train &&
         (plan->family != k.family || plan->width != k.width || plan->cls != k.cls || plan->slabs_per_graph != k.slabs))
         return DRGNN_E_CAPACITY;
-    if (co_ok && k.builder_roles == 0) co_ok = false;      // the builder gets a launch of its own
-    if ((ens || coh) && (k.wgs != 1 || (k.kernel != SK_AF3B && k.kernel != SK_AF2))) return DRGNN_E_CAPACITY;
-    if (co_ok) T.roles = k.builder_roles;
+    if (b.ok && k.builder_roles == 0) b.ok = false;      // the builder gets a launch of its own
+    if ((s.ens || s.coh) && (k.wgs != 1 || (k.kernel != SK_AF3B && k.kernel != SK_AF2))) return DRGNN_E_CAPACITY;
+    if (b.ok) b.T.roles = k.builder_roles;
+    return 0;
+}
 
-    StepLaunch L;
-    L.capN = k.capN; L.capE = k.capE; L.capC = k.capC;
-    L.words = k.lds / 4;
-    TopoLayout lay;
-    topo_layout(n_nodes, n_edges, ws_graphs, &lay);
-    StepArgs& a = L.a;
-    a.gather_ids = gather_ids; a.ws_graphs = (int)ws_graphs;
-    a.tiles = (q.topo_flags & DRGNN_TOPO_TILES) ? hints->tiles : nullptr; a.tile_nodes = n_nodes;
-    L.dims.count = 0;
+// The table of the launch's graphs the host knows (drgnn_kernels.h: StepDims); count = 0 where it does not.
+static int step_host_dims(const StepOperands& s, const StepAsk& q, StepDims& D) {
+    const drgnn_step_hints* hints = s.hints;
+    const int64_t n_graphs = s.n_graphs;
+    D.count = 0;
     // host-known graph numbers of a cached-topology launch are range-checked whatever the batch size: the kernel reads the
     // set's tables at gather_ids[g] as is
-    if (gather_ids && hints && hints->host_ids)
+    if (s.gather_ids && hints && hints->host_ids)
         for (int64_t g = 0; g < n_graphs; ++g)
-            if (hints->host_ids[g] < 0 || hints->host_ids[g] >= ws_graphs) return DRGNN_E_ARG;
-    if (hints && n_graphs > 0 && n_graphs <= DRGNN_STEP_DIMS_MAX) {
-        StepDims& D = L.dims;
-        bool ok = true;
-        if (!gather_ids && hints->host_node_ptr && hints->host_edge_ptr) {
-            for (int g = 0; g < (int)n_graphs; ++g) {
-                D.n0[g] = hints->host_node_ptr[g]; D.n[g] = hints->host_node_ptr[g + 1] - hints->host_node_ptr[g];
-                D.e0[g] = hints->host_edge_ptr[g]; D.e[g] = hints->host_edge_ptr[g + 1] - hints->host_edge_ptr[g];
-                D.gi[g] = g;
-                ok = ok && D.n[g] >= 0 && D.e[g] >= 0 && D.n[g] <= q.capN && D.e[g] <= q.capE;
-            }
-            if (ok && (hints->host_node_ptr[n_graphs] != n_nodes || hints->host_edge_ptr[n_graphs] != n_edges)) ok = false;
-        } else if (gather_ids && hints->host_ids && hints->set_node_ptr && hints->set_edge_ptr) {
-            for (int g = 0; g < (int)n_graphs; ++g) {
-                const int64_t id = hints->host_ids[g];
-                if (id < 0 || id >= ws_graphs) { ok = false; break; }
-                D.n0[g] = (int32_t)hints->set_node_ptr[id]; D.n[g] = (int32_t)(hints->set_node_ptr[id + 1] - hints->set_node_ptr[id]);
-                D.e0[g] = (int32_t)hints->set_edge_ptr[id]; D.e[g] = (int32_t)(hints->set_edge_ptr[id + 1] - hints->set_edge_ptr[id]);
-                D.gi[g] = (int32_t)id;
-                ok = ok && D.n[g] <= q.capN && D.e[g] <= q.capE;
-            }
-        } else {
-            ok = false;
+            if (hints->host_ids[g] < 0 || hints->host_ids[g] >= s.ws_graphs) return DRGNN_E_ARG;
+    if (!(hints && n_graphs > 0 && n_graphs <= DRGNN_STEP_DIMS_MAX)) return 0;
+    bool ok = true;
+    if (!s.gather_ids && hints->host_node_ptr && hints->host_edge_ptr) {
+        for (int g = 0; g < (int)n_graphs; ++g) {
+            D.n0[g] = hints->host_node_ptr[g]; D.n[g] = hints->host_node_ptr[g + 1] - hints->host_node_ptr[g];
+            D.e0[g] = hints->host_edge_ptr[g]; D.e[g] = hints->host_edge_ptr[g + 1] - hints->host_edge_ptr[g];
+            D.gi[g] = g;
+            ok = ok && D.n[g] >= 0 && D.e[g] >= 0 && D.n[g] <= q.capN && D.e[g] <= q.capE;
         }
-        if (ok) D.count = (int)n_graphs;       // (a table that contradicts the capacities is ignored: the device path decides)
+        if (ok && (hints->host_node_ptr[n_graphs] != s.n_nodes || hints->host_edge_ptr[n_graphs] != s.n_edges)) ok = false;
+    } else if (s.gather_ids && hints->host_ids && hints->set_node_ptr && hints->set_edge_ptr) {
+        for (int g = 0; g < (int)n_graphs; ++g) {
+            const int64_t id = hints->host_ids[g];
+            if (id < 0 || id >= s.ws_graphs) { ok = false; break; }
+            D.n0[g] = (int32_t)hints->set_node_ptr[id]; D.n[g] = (int32_t)(hints->set_node_ptr[id + 1] - hints->set_node_ptr[id]);
+            D.e0[g] = (int32_t)hints->set_edge_ptr[id]; D.e[g] = (int32_t)(hints->set_edge_ptr[id + 1] - hints->set_edge_ptr[id]);
+            D.gi[g] = (int32_t)id;
+            ok = ok && D.n[g] <= q.capN && D.e[g] <= q.capE;
+        }
+    } else {
+        ok = false;
     }
-    a.net = *net; a.x = x;
-    a.tv = topo_view(const_cast<int32_t*>(ws_i32), const_cast<float*>(ws_f32), lay);
-    a.n_nodes = n_nodes; a.n_graphs = (int)n_graphs;
-    a.partials = partials; a.n_partial = (int)net_partial_floats(F);
-    a.xchg = (unsigned long long*)xchg; a.step2 = step2;
+    if (ok) D.count = (int)n_graphs;       // (a table that contradicts the capacities is ignored: the device path decides)
+    return 0;
+}
+
+static void step_args(const StepOperands& s, const StepAsk& q, StepArgs& a) {
+    const drgnn_head_desc* hd = s.hd;
+    TopoLayout lay;
+    topo_layout(s.n_nodes, s.n_edges, s.ws_graphs, &lay);
+    a.gather_ids = s.gather_ids; a.ws_graphs = (int)s.ws_graphs;
+    a.tiles = (q.topo_flags & DRGNN_TOPO_TILES) ? s.hints->tiles : nullptr; a.tile_nodes = s.n_nodes;
+    a.net = *s.net; a.x = s.x;
+    a.tv = topo_view(const_cast<int32_t*>(s.ws_i32), const_cast<float*>(s.ws_f32), lay);
+    a.n_nodes = s.n_nodes; a.n_graphs = (int)s.n_graphs;
+    a.partials = s.partials; a.n_partial = (int)net_partial_floats(q.F);
+    a.xchg = (unsigned long long*)s.xchg; a.step2 = s.step2;
     a.xchg_stride = (int)step2_xchg_words(q.capC > 0 ? q.capC : 1);
     HeadFused& hf = a.hf;
-    hf.enabled = 1; hf.B = (int)n_graphs; hf.R = hd->R; hf.H = hd->H; hf.O = hd->O; hf.task = hd->task;
-    hf.p_drop = hd->train ? hd->p_drop : 0.0f; hf.seed = hd->seed; hf.step_bias = 0; hf.train = full_step ? 1 : 0; hf.sigmoid = hd->transform_sigmoid;
+    hf.enabled = 1; hf.B = (int)s.n_graphs; hf.R = hd->R; hf.H = hd->H; hf.O = hd->O; hf.task = hd->task;
+    hf.p_drop = hd->train ? hd->p_drop : 0.0f; hf.seed = hd->seed; hf.step_bias = 0; hf.train = q.train ? 1 : 0; hf.sigmoid = hd->transform_sigmoid;
     hf.drop_mask = hd->train ? hd->drop_mask : nullptr;
     hf.w1 = hd->w1; hf.b1 = hd->b1; hf.w2 = hd->w2; hf.b2 = hd->b2; hf.class_w = hd->class_w;
-    hf.y_reg = (hd->task != DRGNN_TASK_CLASS) ? (const float*)target : nullptr;
-    hf.y_cls = (hd->task == DRGNN_TASK_CLASS) ? (const int64_t*)target : nullptr;
-    hf.readout = readout; hf.step = step2; hf.pred = pred; hf.partials = head_partials; hf.stage = 0;
+    hf.y_reg = (hd->task != DRGNN_TASK_CLASS) ? (const float*)s.target : nullptr;
+    hf.y_cls = (hd->task == DRGNN_TASK_CLASS) ? (const int64_t*)s.target : nullptr;
+    hf.readout = s.readout; hf.step = s.step2; hf.pred = s.pred; hf.partials = s.head_partials; hf.stage = 0;
+}
 
+#ifndef DRGNN_EMU
+// What shares the grid with the step's workgroups: the builder's, or the next mini-batch's prefetchers.  Returns their number;
+// *lds: the launch's dynamic LDS.
+static int step_co_setup(const StepOperands& s, const StepBuilder& b, const StepPick& k, int blocks, StepCoLaunch& C, int64_t* lds) {
+    const drgnn_step_hints* hints = s.hints;
+    const StepArgs& a = C.step.a;
+    *lds = k.lds;
+    C.topo.pf_ids = nullptr; C.topo.pf_n = 0; C.topo.pf_graphs = 0;
+    if (b.ok) {
+        C.topo = b.T;
+        if (b.lds > *lds) *lds = b.lds;
+        return b.T.args.n_graphs * b.T.roles;
+    }
+    // (an ensemble / cohort kernel runs its own workgroups only)
+    if (s.ens || s.coh || !s.gather_ids || !(hints && hints->next_ids && hints->n_next > 0) || (blocks % 8) != 0 ||
+        blocks + hints->n_next > device_cu_count() || step_no_prefetch() || a.tiles == nullptr)
+        return 0;
+    // cached topology, CUs to spare: one extra workgroup per graph of the NEXT mini-batch warms the L2 of the XCD that
+    // will step it (prefetch_block; beyond the resident size the workgroups would only queue behind the step's)
+    const int kind = a.net.kind, F = a.net.n_feat, TF = (F + 3) & ~3;
+    TopoLaunch& Q = C.topo;
+    memset(&Q, 0, sizeof(Q));
+    Q.tv = a.tv;
+    Q.pf_ids = hints->next_ids; Q.pf_n = (int)hints->n_next; Q.pf_graphs = a.ws_graphs;
+    Q.pf_tiles = a.tiles; Q.pf_f = TF; Q.pf_tile_nodes = s.n_nodes;
+    Q.pf_x = (kind == DRGNN_GINET) ? nullptr : (F & 3) ? a.tiles + drgnn_tiles_x_off(s.n_nodes, TF) : s.x;
+    Q.pf_coef = (kind != DRGNN_GINET) ? 1 : 0;
+    Q.pf_y = s.hd->train == 1 ? s.target : nullptr; Q.pf_y_bytes = (s.hd->task == DRGNN_TASK_REG) ? 4 : 8;
+    return Q.pf_n;
+}
+
+// the kernel instance of the pick (drgnn_step_af.h) and its launch, each form with its own argument array
+static int step_run(const StepOperands& s, const StepPick& k, const StepCoLaunch& C, int64_t lds, unsigned grid) {
+    if (k.kernel == SK_EMU) return DRGNN_E_CAPACITY;      // (the host emulation's; step_pick never picks it here)
+    AfKey key;
+    key.kind = s.net->kind; key.width = k.width; key.wgs = k.wgs; key.level = step_mem_level(key.kind, k); key.cls = k.cls;
+    key.gather = s.gather_ids != nullptr; key.train = s.hd->train == 1;
+    key.axis = s.ens ? AF_AXIS_ENS : s.coh ? AF_AXIS_COHORT : AF_AXIS_NONE;
+    const void* kern = af_kernel(key);
+    if (!kern) return key.axis == AF_AXIS_NONE ? DRGNN_E_ARG : DRGNN_E_CAPACITY;
+    void* c = const_cast<StepCoLaunch*>(&C);
+    if (s.ens) {
+        const drgnn_ens_member* members = s.ens;
+        int K = s.ens_K;
+        void* args[] = {c, &members, &K};
+        return step_launch(kern, args, lds, grid, (hipStream_t)s.stream);
+    }
+    if (s.coh) {
+        void* args[] = {c, const_cast<CohortStep*>(s.coh)};
+        return step_launch(kern, args, lds, grid, (hipStream_t)s.stream);
+    }
+    void* args[] = {c};
+    return step_launch(kern, args, lds, grid, (hipStream_t)s.stream);
+}
+#endif
+
+static int train_step_impl(const StepOperands& s) {
+    int rc = step_check(s);
+    if (rc) return rc;
+    StepBuilder b;
+    if ((rc = step_builder(s, b))) return rc;
+    StepAsk q;
+    StepPick k;
+    if ((rc = step_layout(s, b, q, k))) return rc;
+#ifdef DRGNN_EMU
+    StepLaunch L;
+#else
+    StepCoLaunch C;
+    StepLaunch& L = C.step;
+#endif
+    L.capN = k.capN; L.capE = k.capE; L.capC = k.capC;
+    L.words = k.lds / 4;
+    if ((rc = step_host_dims(s, q, L.dims))) return rc;
+    step_args(s, q, L.a);
     // grid of the step part: graphs in groups of 8 x 2 when a graph has two workgroups (step2_block, step3_block)
     // (ensemble / cohort: graphs in groups of 8 x K, see ens_slot)
-    const int multi_K = ens ? ens_K : coh ? coh->K : 0;
+    const int64_t n_graphs = s.n_graphs;
+    const int multi_K = s.ens ? s.ens_K : s.coh ? s.coh->K : 0;
     const int blocks = multi_K ? (int)((n_graphs + 7) / 8) * 8 * multi_K : (k.wgs == 2) ? (int)((n_graphs + 7) / 8) * 16 : (int)n_graphs;
     if (blocks > 0) {
 #ifdef DRGNN_EMU
-        if (kind == DRGNN_GINET) emu_step<DRGNN_GINET>(a, full_step, k.capN, k.capE, k.capC);
-        else if (kind == DRGNN_SGAT) emu_step<DRGNN_SGAT>(a, full_step, k.capN, k.capE, k.capC);
-        else emu_step<DRGNN_FOUT>(a, full_step, k.capN, k.capE, k.capC);
-        if (co_ok) {
-            std::vector<int> tbuf((size_t)(tlds / 4) + 16);
-            for (int g = 0; g < T.args.n_graphs * T.roles; ++g) topo_block<true>(T, g, tbuf.data());
+        if (q.kind == DRGNN_GINET) emu_step<DRGNN_GINET>(L.a, q.train, k.capN, k.capE, k.capC);
+        else if (q.kind == DRGNN_SGAT) emu_step<DRGNN_SGAT>(L.a, q.train, k.capN, k.capE, k.capC);
+        else emu_step<DRGNN_FOUT>(L.a, q.train, k.capN, k.capE, k.capC);
+        if (b.ok) {
+            std::vector<int> tbuf((size_t)(b.lds / 4) + 16);
+            for (int g = 0; g < b.T.args.n_graphs * b.T.roles; ++g) topo_block<true>(b.T, g, tbuf.data());
         }
-        (void)stream_;
 #else
-        StepCoLaunch C;
-        C.step = L; C.n_net = blocks;
-        int64_t both = k.lds;
-        int extra = 0;
-        C.topo.pf_ids = nullptr; C.topo.pf_n = 0; C.topo.pf_graphs = 0;
-        if (co_ok) { C.topo = T; both = k.lds > tlds ? k.lds : tlds; extra = T.args.n_graphs * T.roles; }
-        else if (!coh && gather_ids && hints && hints->next_ids && hints->n_next > 0 && (blocks % 8) == 0 &&
-                 blocks + hints->n_next <= device_cu_count() && !step_no_prefetch()) {
-            // cached topology, CUs to spare: one extra workgroup per graph of the NEXT mini-batch warms the L2 of the XCD that
-            // will step it (prefetch_block; beyond the resident size the workgroups would only queue behind the step's)
-            TopoLaunch& Q = C.topo;
-            memset(&Q, 0, sizeof(Q));
-            Q.tv = a.tv;
-            Q.pf_ids = hints->next_ids; Q.pf_n = (int)hints->n_next; Q.pf_graphs = a.ws_graphs;
-            const int TF = (F + 3) & ~3;
-            Q.pf_tiles = a.tiles; Q.pf_f = TF; Q.pf_tile_nodes = n_nodes;
-            Q.pf_x = (kind == DRGNN_GINET) ? nullptr : (F & 3) ? a.tiles + drgnn_tiles_x_off(n_nodes, TF) : x;
-            Q.pf_coef = (kind != DRGNN_GINET) ? 1 : 0;
-            Q.pf_y = full_step ? target : nullptr; Q.pf_y_bytes = (hd->task == DRGNN_TASK_REG) ? 4 : 8;
-            if (Q.pf_tiles != nullptr) extra = Q.pf_n; else Q.pf_ids = nullptr;
-        }
-        if (ens) {
-            const drgnn_ens_kernel_t ek = af_ens_kernel(kind, k.width, k.cls, kind == DRGNN_GINET ? (k.sg ? 1 : 0) : k.xg);
-            if (!ek) return DRGNN_E_CAPACITY;
-            return step_launch(reinterpret_cast<drgnn_step_kernel_t>(ek), k.lds, (unsigned)blocks, (hipStream_t)stream_, C, ens, ens_K);
-        }
-        if (coh) {
-            const drgnn_cohort_kernel_t ck = af_cohort_kernel(kind, k.width, k.cls, kind == DRGNN_GINET ? (k.sg ? 1 : 0) : k.xg);
-            if (!ck) return DRGNN_E_CAPACITY;
-            return step_launch(reinterpret_cast<drgnn_step_kernel_t>(ck), k.lds, (unsigned)blocks, (hipStream_t)stream_, C, nullptr, 0, coh);
-        }
-        drgnn_step_kernel_t kern = nullptr;
-        const bool gather = gather_ids != nullptr;
-        switch (k.kernel) {
-            case SK_AF3: kern = af_step_kernel(DRGNN_AF_GINET_TWO, k.width, gather, k.cls, 1, q.train); break;
-            case SK_AF3B: kern = af_step_kernel(k.sg ? DRGNN_AF_GINET_SG : DRGNN_AF_GINET_ONE, k.width, gather, k.cls, 1, q.train); break;
-            case SK_AF2: kern = af_step_kernel(k.xg ? (kind == DRGNN_SGAT ? DRGNN_AF_SGAT_XG : DRGNN_AF_FOUT_XG)
-                                                    : (kind == DRGNN_SGAT ? DRGNN_AF_SGAT : DRGNN_AF_FOUT), k.width, gather, k.cls, k.wgs, q.train, k.xg); break;
-            default: return DRGNN_E_CAPACITY;      // (SK_EMU: the host emulation's; step_pick never picks it here)
-        }
-        if ((rc = step_launch(kern, both, (unsigned)(blocks + extra), (hipStream_t)stream_, C))) return rc;
+        C.n_net = blocks;
+        int64_t lds = 0;
+        const int extra = step_co_setup(s, b, k, blocks, C, &lds);
+        if ((rc = step_run(s, k, C, lds, (unsigned)(blocks + extra)))) return rc;
 #endif
     }
-    if (next && (!co_ok || blocks == 0))
-        return drgnn_topology_build_request(next, stream_);
+    if (s.next && (!b.ok || blocks == 0))
+        return drgnn_topology_build_request(s.next, s.stream);
     return 0;
 }
 
@@ -1172,8 +1261,13 @@ int drgnn_net_train_step(const drgnn_net_desc* net, const drgnn_head_desc* hd, c
                          int32_t max_edges, int32_t max_c0, float* pred, float* readout,
                          float* head_partials, float* partials, uint64_t* xchg,
                          const drgnn_topology_request* next, const drgnn_step_hints* hints, void* stream_) {
-    return train_step_impl(net, hd, x, target, step2, ws_i32, ws_f32, n_nodes, n_edges, n_graphs, n_graphs, nullptr,
-                           max_nodes, max_edges, max_c0, pred, readout, head_partials, partials, xchg, next, hints, stream_);
+    StepOperands s = {};
+    s.net = net; s.hd = hd; s.x = x; s.target = target; s.step2 = step2; s.ws_i32 = ws_i32; s.ws_f32 = ws_f32;
+    s.n_nodes = n_nodes; s.n_edges = n_edges; s.n_graphs = n_graphs; s.ws_graphs = n_graphs;
+    s.max_nodes = max_nodes; s.max_edges = max_edges; s.max_c0 = max_c0;
+    s.pred = pred; s.readout = readout; s.head_partials = head_partials; s.partials = partials; s.xchg = xchg;
+    s.next = next; s.hints = hints; s.stream = stream_;
+    return train_step_impl(s);
 }
 
 int drgnn_net_train_step_cached(const drgnn_net_desc* net, const drgnn_head_desc* hd,
@@ -1185,52 +1279,25 @@ int drgnn_net_train_step_cached(const drgnn_net_desc* net, const drgnn_head_desc
     if (hd && hd->train == 1) {
         if (!cache->y || cache->y_bytes != (hd->task == DRGNN_TASK_REG ? 4 : 8)) return DRGNN_E_ARG;
     }
-    return train_step_impl(net, hd, cache->x, cache->y, step2, cache->ws_i32, cache->ws_f32, cache->n_nodes,
-                           cache->n_edges, n_graphs, cache->n_graphs, ids, max_nodes, max_edges, max_c0, pred, readout,
-                           head_partials, partials, xchg, nullptr, hints, stream_);
+    StepOperands s = step_operands_cached(net, hd, cache, ids, n_graphs, max_nodes, max_edges, max_c0, hints, stream_);
+    s.step2 = step2; s.pred = pred; s.readout = readout; s.head_partials = head_partials; s.partials = partials; s.xchg = xchg;
+    return train_step_impl(s);
 }
 
-int32_t drgnn_ens_step_plan(drgnn_step_plan* p, int32_t K) {
+// the plan of a launch with a member axis (K models / members): the one-workgroup-per-graph forms, where no workgroup of the
+// launch waits for another
+static int32_t member_step_plan(drgnn_step_plan* p, int32_t K, int32_t max_K, int32_t train) {
     if (!p) return 0;
-    p->train = 0;
-    p->force_wgs = 1;      // the one-workgroup-per-graph forms: no workgroup of the launch waits for another
+    p->train = train;
+    p->force_wgs = 1;
     p->co_built_graphs = 0;
     const int32_t wgs = drgnn_net_step_plan(p);
 #ifdef DRGNN_EMU
+    (void)K; (void)max_K; (void)wgs;
     p->family = DRGNN_STEP_FAMILY_NONE;
     return 0;
 #else
-    if (K < 1 || wgs != 1 || p->family != DRGNN_STEP_FAMILY_AGGREGATE || p->lds_bytes <= 0 || p->lds_bytes > DRGNN_LDS_LIMIT ||
-        (int64_t)K * ((p->n_graphs + 7) / 8) * 8 > (int64_t)INT32_MAX) {
-        p->family = DRGNN_STEP_FAMILY_NONE;
-        return 0;
-    }
-    return 1;
-#endif
-}
-
-int drgnn_ens_predict_cached(const drgnn_net_desc* net, const drgnn_head_desc* hd, const drgnn_ens_member* members,
-                             int32_t K, const drgnn_topology_cache* cache, const int32_t* ids, int64_t n_graphs,
-                             int32_t max_nodes, int32_t max_edges, int32_t max_c0, int32_t* step2, float* pred,
-                             float* readout, const drgnn_step_hints* hints, void* stream_) {
-    if (!members || K < 1 || !hd || hd->train || !pred || !readout) return DRGNN_E_ARG;
-    if (!cache || !ids || !cache->ws_i32 || !cache->x || n_graphs < 0 || n_graphs > cache->n_graphs) return DRGNN_E_ARG;
-    return train_step_impl(net, hd, cache->x, cache->y, step2, cache->ws_i32, cache->ws_f32, cache->n_nodes,
-                           cache->n_edges, n_graphs, cache->n_graphs, ids, max_nodes, max_edges, max_c0, pred, readout,
-                           nullptr, nullptr, nullptr, nullptr, hints, stream_, members, K);
-}
-
-int32_t drgnn_cohort_step_plan(drgnn_step_plan* p, int32_t K) {
-    if (!p) return 0;
-    p->train = 1;
-    p->force_wgs = 1;      // the one-workgroup-per-graph forms: no workgroup of the launch waits for another
-    p->co_built_graphs = 0;
-    const int32_t wgs = drgnn_net_step_plan(p);
-#ifdef DRGNN_EMU
-    p->family = DRGNN_STEP_FAMILY_NONE;
-    return 0;
-#else
-    if (K < 1 || K > 65535 || wgs != 1 || p->family != DRGNN_STEP_FAMILY_AGGREGATE || p->lds_bytes <= 0 ||
+    if (K < 1 || K > max_K || wgs != 1 || p->family != DRGNN_STEP_FAMILY_AGGREGATE || p->lds_bytes <= 0 ||
         p->lds_bytes > DRGNN_LDS_LIMIT || (int64_t)K * ((p->n_graphs + 7) / 8) * 8 > (int64_t)INT32_MAX) {
         p->family = DRGNN_STEP_FAMILY_NONE;
         return 0;
@@ -1238,6 +1305,21 @@ int32_t drgnn_cohort_step_plan(drgnn_step_plan* p, int32_t K) {
     return 1;
 #endif
 }
+
+int32_t drgnn_ens_step_plan(drgnn_step_plan* p, int32_t K) { return member_step_plan(p, K, INT32_MAX, 0); }
+
+int drgnn_ens_predict_cached(const drgnn_net_desc* net, const drgnn_head_desc* hd, const drgnn_ens_member* members,
+                             int32_t K, const drgnn_topology_cache* cache, const int32_t* ids, int64_t n_graphs,
+                             int32_t max_nodes, int32_t max_edges, int32_t max_c0, int32_t* step2, float* pred,
+                             float* readout, const drgnn_step_hints* hints, void* stream_) {
+    if (!members || K < 1 || !hd || hd->train || !pred || !readout) return DRGNN_E_ARG;
+    if (!cache || !ids || !cache->ws_i32 || !cache->x || n_graphs < 0 || n_graphs > cache->n_graphs) return DRGNN_E_ARG;
+    StepOperands s = step_operands_cached(net, hd, cache, ids, n_graphs, max_nodes, max_edges, max_c0, hints, stream_);
+    s.step2 = step2; s.pred = pred; s.readout = readout; s.ens = members; s.ens_K = K;
+    return train_step_impl(s);
+}
+
+int32_t drgnn_cohort_step_plan(drgnn_step_plan* p, int32_t K) { return member_step_plan(p, K, 65535, 1); }
 
 int drgnn_cohort_train_step_cached(const drgnn_net_desc* net, const drgnn_head_desc* hd, const drgnn_cohort_member* members,
                                    int32_t K, const drgnn_topology_cache* cache, const int32_t* ids, const int32_t* counts,
@@ -1252,9 +1334,9 @@ int drgnn_cohort_train_step_cached(const drgnn_net_desc* net, const drgnn_head_d
 #else
     CohortStep coh;
     coh.members = members; coh.ids = ids; coh.counts = counts; coh.K = K; coh.stride = ids_stride;
-    return train_step_impl(net, hd, cache->x, cache->y, nullptr, cache->ws_i32, cache->ws_f32, cache->n_nodes,
-                           cache->n_edges, n_graphs, cache->n_graphs, ids, max_nodes, max_edges, max_c0, nullptr, nullptr,
-                           nullptr, nullptr, nullptr, nullptr, hints, stream_, nullptr, 0, &coh);
+    StepOperands s = step_operands_cached(net, hd, cache, ids, n_graphs, max_nodes, max_edges, max_c0, hints, stream_);
+    s.coh = &coh;
+    return train_step_impl(s);
 #endif
 }
 

@@ -1172,6 +1172,6 @@ __global__ void __launch_bounds__(256) k_topo_begin(const int32_t* node_ptr, con
 #endif  // DRGNN_KERNELS_MAIN
 // The instantiations of the aggregation-first step kernels live in drgnn_step_tu.hip (one translation unit per (family, width),
 // drgnn_step_af.h) when the library is built from several translation units (Makefile: DRGNN_SPLIT_TU); a single-unit build
-// (profiling variants) instantiates them at their lookup functions.
+// (profiling variants) instantiates them at the dispatcher's table of lookups (af_kernel).
 #endif  // !DRGNN_EMU
 #include "drgnn_step_af.h"

@@ -160,7 +160,7 @@ template <int J> DEV void burst_store_x4_rows(const BurstX<J>& b, const BurstRow
 // 128-VGPR limit of a 16-wave workgroup with 31 - 39 registers spilled to scratch memory; with the ~36 offsets in SGPRs (some of
 // which the compiler parks in lanes of a VGPR: no memory) they need 94 - 97 and spill nothing: batch 64, 32 features 21.05 ->
 // 19.70 us per step rebuilt, 20.65 -> 19.32 cached, 48 features 23.0 -> 21.07 (profiles/r05_sgat_spin_ab.txt).  NOT for the
-// one-workgroup launches that carry the one-role weighted builder (family 5 of drgnn_step_af.h): the scalar registers are what
+// one-workgroup launches that carry the one-role weighted builder (family SGAT_WHOLE of drgnn_step_af.h): the scalar registers are what
 // that builder chain lives on, 24.0 -> 24.75 us at batch 128; and not for the one-workgroup launches on a cached workspace
 // either (31 - 35 spilled, yet 19.4 -> 19.9 us at batch 128 with the scalar pin): the two-workgroup launches only.
 #ifdef DRGNN_EMU
