@@ -788,13 +788,13 @@ class NeuralNet(object):
     def save_model(self, filename='model.pth.tar'):
         if getattr(self, "world", 1) > 1 and self.rank > 0:
             return                        # data parallel: the replicas are identical, rank 0 writes the checkpoint
-        state = {'model': {k: v.detach().cpu().clone() for k, v in self.model.state_dict().items()},
-                 'optimizer': self.trainer.optimizer_state_dict(),
-                 'node': self.node_feature, 'edge': self.edge_feature, 'target': self.target, 'task': self.task,
-                 'classes': self.classes, 'class_weight': self.class_weights, 'batch_size': self.batch_size,
-                 'percent': self.percent, 'lr': self.lr, 'index': self.index, 'shuffle': self.shuffle,
-                 'threshold': self.threshold, 'cluster_nodes': self.cluster_nodes,
-                 'transform_sigmoid': self.transform_sigmoid}
+        from .members import checkpoint_state
+        state = checkpoint_state(
+            {k: v.detach().cpu().clone() for k, v in self.model.state_dict().items()}, self.trainer.optimizer_state_dict(),
+            node=self.node_feature, edge=self.edge_feature, target=self.target, task=self.task, classes=self.classes,
+            class_weight=self.class_weights, batch_size=self.batch_size, percent=self.percent, lr=self.lr, index=self.index,
+            shuffle=self.shuffle, threshold=self.threshold, cluster_nodes=self.cluster_nodes,
+            transform_sigmoid=self.transform_sigmoid)
         torch.save(state, filename)
 
     def cross_validate(self, k=10, nepoch=1, validate=True, save_model=None, seed=0, threshold=4.0):

@@ -60,7 +60,7 @@ class EnsMember(ctypes.Structure):
 
 class CohortMember(ctypes.Structure):
     """drgnn_cohort_member: one entry of a training cohort's member table (its array lives in device memory)"""
-    _fields_ = [("net", NetDesc), ("w1", _vp), ("b1", _vp), ("w2", _vp), ("b2", _vp),
+    _fields_ = EnsMember._fields_ + [
                 ("flat_param", _vp), ("flat_grad", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp),
                 ("step2", _vp), ("pred", _vp), ("readout", _vp), ("head_partials", _vp), ("partials", _vp), ("loss", _vp),
                 ("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
@@ -127,6 +127,14 @@ class StepPlan(ctypes.Structure):
 
 
 STEP_FAMILY_NONE, STEP_FAMILY_PRODUCT, STEP_FAMILY_AGGREGATE = 0, 1, 2
+
+
+def _plan_inputs(kind, n_feat, max_nodes, max_edges, max_c0, R, H, O, n_graphs, topo_flags):
+    """a StepPlan with the input members every plan query sets (an inference launch that co-builds nothing, no overrides)"""
+    p = StepPlan()
+    p.kind, p.n_feat, p.max_nodes, p.max_edges, p.max_c0 = int(kind), int(n_feat), int(max_nodes), int(max_edges), int(max_c0)
+    p.R, p.H, p.O, p.n_graphs, p.topo_flags = int(R), int(H), int(O), int(n_graphs), int(topo_flags)
+    return p
 
 
 class StepHints(ctypes.Structure):
@@ -372,11 +380,8 @@ class Api(object):
         """The launch plan (StepPlan, ``out`` members filled) of a fused step of ``n_graphs`` graphs with these bounds on a
         workspace built with ``topo_flags``, the same launch building the topology of ``co_built_graphs`` graphs.
         ``overrides``: dict over StepPlan.OVERRIDES (tests, A/B runs).  ``family == 0``: outside the fused kernels."""
-        p = StepPlan()
-        p.kind, p.n_feat, p.max_nodes, p.max_edges, p.max_c0 = int(kind), int(n_feat), int(max_nodes), int(max_edges), int(max_c0)
-        p.R, p.H, p.O = int(R), int(H), int(O)
-        p.n_graphs, p.co_built_graphs = int(n_graphs), int(co_built_graphs)
-        p.train, p.topo_flags = int(bool(train)), int(topo_flags)
+        p = _plan_inputs(kind, n_feat, max_nodes, max_edges, max_c0, R, H, O, n_graphs, topo_flags)
+        p.co_built_graphs, p.train = int(co_built_graphs), int(bool(train))
         for k, v in (overrides or {}).items():
             if k not in StepPlan.OVERRIDES:
                 raise KeyError("unknown step-plan override %r" % (k,))
@@ -423,9 +428,7 @@ class Api(object):
 
     def ens_step_plan(self, K, kind, n_feat, max_nodes, max_edges, max_c0, R, H, O, n_graphs, topo_flags=0):
         """The plan (StepPlan) of an ensemble launch of K models; ``family == 0``: no fused ensemble launch takes it."""
-        p = StepPlan()
-        p.kind, p.n_feat, p.max_nodes, p.max_edges, p.max_c0 = int(kind), int(n_feat), int(max_nodes), int(max_edges), int(max_c0)
-        p.R, p.H, p.O, p.n_graphs, p.topo_flags = int(R), int(H), int(O), int(n_graphs), int(topo_flags)
+        p = _plan_inputs(kind, n_feat, max_nodes, max_edges, max_c0, R, H, O, n_graphs, topo_flags)
         self.lib.drgnn_ens_step_plan(ctypes.byref(p), int(K))
         return p
 
@@ -438,9 +441,7 @@ class Api(object):
 
     def cohort_step_plan(self, K, kind, n_feat, max_nodes, max_edges, max_c0, R, H, O, n_graphs, topo_flags=0):
         """The plan (StepPlan) of a cohort's fused step launch of K members; ``family == 0``: the members are stepped one by one."""
-        p = StepPlan()
-        p.kind, p.n_feat, p.max_nodes, p.max_edges, p.max_c0 = int(kind), int(n_feat), int(max_nodes), int(max_edges), int(max_c0)
-        p.R, p.H, p.O, p.n_graphs, p.topo_flags = int(R), int(H), int(O), int(n_graphs), int(topo_flags)
+        p = _plan_inputs(kind, n_feat, max_nodes, max_edges, max_c0, R, H, O, n_graphs, topo_flags)
         self.lib.drgnn_cohort_step_plan(ctypes.byref(p), int(K))
         return p
 

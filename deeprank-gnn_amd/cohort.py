@@ -8,8 +8,8 @@ once per member).  Each member has its own mini-batch (folds have different trai
 have none in a step and is then left alone), its own dropout stream, step index, learning rate and loss word.  Member m's
 trajectory is that of a ``FusedTrainer`` of its own with the one-workgroup-per-graph layout, bit for bit.
 
-The members' flat buffers are rows of packed ``[K, P]`` tensors (parameters, gradients, both Adam moments); the member table
-(drgnn_cohort_member[K]) is written to the device when the buffers of a batch size are made.
+The members are a members.MemberPack: nets and trainers on rows of packed ``[K, P]`` tensors (parameters, gradients, both
+Adam moments); the member table (drgnn_cohort_member[K]) is written to the device when the buffers of a batch size are made.
 
 ``last_path`` / ``last_reason`` as ``Ensemble``: ``"fused"`` (every step in the cohort launches) or ``"separate"`` (the plan
 answered NONE -- the host emulation, a graph beyond the fused kernels, no cached topology: each member runs its own step, one
@@ -19,10 +19,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .ensemble import Ensemble, _first_difference, _load, _signature
+from .ensemble import Ensemble
 from .functional import H2
-from .launch import NetLayout, cached_flags, fused, head_desc
-from .trainer import FusedTrainer
+from .launch import fused, head_desc, wrong_targets
+from .members import MemberPack, checkpoint_state, device_table, fill_member, load_members
 
 __all__ = ["Cohort", "kfold_indices"]
 
@@ -46,78 +46,39 @@ def _per_member(value, K, what, cast):
     return [cast(value)] * K
 
 
-class Cohort(object):
+class Cohort(MemberPack):
     """K members of the net class ``Net``: ``members`` is K (fresh nets ``Net(n_feat, n_out, edge_dim)``) or a list of
     checkpoint paths / checkpoint dictionaries / state dicts to start from.  ``lr`` and ``seeds`` (dropout streams) are
     scalars or length-K lists; ``seeds=None`` gives every member a stream of its own."""
 
     def __init__(self, Net, members, n_feat=None, n_out=1, lr=0.01, task="reg", seeds=None, class_weights=None,
                  transform_sigmoid=False, device=None, api=None, edge_dim=1, betas=(0.9, 0.999), eps=1e-8):
-        self.device = torch.device(device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
         if isinstance(members, (int, np.integer)):
             if members < 1 or n_feat is None:
                 raise ValueError("Cohort: K >= 1 fresh members need n_feat")
-            states = [None] * int(members)
+            K, states = int(members), None
         else:
-            loaded = [_load(m) for m in members]
-            if not loaded:
-                raise ValueError("Cohort: no members")
-            sigs = [_signature(Net, sd, {"task": task}) for sd, _ in loaded]
-            for k, s in enumerate(sigs[1:], start=1):
-                diff = _first_difference(s, sigs[0])
-                if diff is not None:
-                    raise ValueError("Cohort: member %d differs from member 0 in %r (%r against %r)" % ((k,) + diff))
-            states = [sd for sd, _ in loaded]
-            n_feat, n_out = sigs[0]["F"], sigs[0]["O"]
-        self.Net, self.K, self.n_feat, self.O, self.task = Net, len(states), int(n_feat), int(n_out), task
+            states, sig = load_members(Net, members, "Cohort", {"task": task})
+            K, n_feat, n_out = len(states), sig["F"], sig["O"]
+        self.task, self.classes = task, None if task == "reg" else list(range(int(n_out)))
         self.transform_sigmoid = bool(transform_sigmoid) and task == "reg"
-        self.edge_dim = edge_dim
-        K = self.K
         self.lr = _per_member(lr, K, "lr", float)
         if seeds is None:
             seeds = [(torch.initial_seed() + m * 0x9E3779B1) & 0xFFFFFFFF for m in range(K)]
         self.seeds = _per_member(seeds, K, "seeds", lambda v: int(v) & 0xFFFFFFFF)
-        self.trainers = []
-        for m, sd in enumerate(states):
-            net = Net(self.n_feat, self.O, edge_dim)
-            if sd is not None:
-                net.load_state_dict(sd, strict=True)
-            tr = FusedTrainer(net.to(self.device), lr=self.lr[m], task=task, class_weights=class_weights, betas=betas, eps=eps,
-                              seed=self.seeds[m], api=api, transform_sigmoid=self.transform_sigmoid)
+        MemberPack.__init__(self, Net, K, n_feat, n_out, device, edge_dim, states=states, training=True,
+                            per_member=[{"lr": self.lr[m], "seed": self.seeds[m]} for m in range(K)], task=task,
+                            class_weights=class_weights, betas=betas, eps=eps, api=api,
+                            transform_sigmoid=self.transform_sigmoid)
+        for tr in self.trainers:
             # the one-workgroup-per-graph layout, as the cohort launch: a member stepped on its own (the separate path)
             # gives the bits the cohort launch gives
             tr.plan_overrides = {"force_wgs": 1}
-            self.trainers.append(tr)
-        tr0 = self.trainers[0]
-        lay = NetLayout(tr0.net)
-        self.kind, self.api, self.n_branch, self.R, self.H = lay.kind, tr0.api, lay.n_branch, lay.R, lay.H
-        self.head_offset, self.n_param = lay.head_offset, lay.total
-        # the members' flat buffers as rows of packed [K, P] tensors; their step words and loss words likewise
-        self.params = torch.stack([tr.flat_p for tr in self.trainers])
-        self.grads = torch.zeros_like(self.params)
-        self.exp_avg = torch.zeros_like(self.params)
-        self.exp_avg_sq = torch.zeros_like(self.params)
-        self.step2 = torch.zeros((K, 4), dtype=torch.int32, device=self.device)
-        self.losses = torch.zeros(K, dtype=torch.float32, device=self.device)
-        for m, tr in enumerate(self.trainers):
-            tr.flat_p, tr.flat_g, tr.exp_avg, tr.exp_avg_sq = self.params[m], self.grads[m], self.exp_avg[m], self.exp_avg_sq[m]
-            tr.step2 = self.step2[m]
-            tr.step = tr.step2[:1]
-            tr._loss_buf = self.losses[m:m + 1]
-            with torch.no_grad():
-                lay.bind(tr.net, tr.flat_p, tr.flat_g)
-            tr.live_grads = tuple(p.grad for p in tr.live)
-            tr._desc_cache.clear()
-        self._g1, self._g2, self._desc0 = tr0._descs(self.n_feat)
+        self._g1, self._g2, self._desc0 = self.trainers[0]._descs(self.n_feat)
         self._cap, self._table, self._bufs = 0, None, None
         self.last_pred = [None] * K
-        self.last_path, self.last_reason = None, None
 
     # -- members --------------------------------------------------------------------------------------------------------
-    @property
-    def nets(self):
-        return [tr.net for tr in self.trainers]
-
     def state_dicts(self):
         return [{k: v.detach().cpu().clone() for k, v in tr.net.state_dict().items()} for tr in self.trainers]
 
@@ -128,40 +89,18 @@ class Cohort(object):
         if len(paths) != self.K:
             raise ValueError("Cohort.save: %d paths for %d members" % (len(paths), self.K))
         cw = self.trainers[0].class_w
+        common = dict(node=None, edge=['dist'], target=None, task=self.task, classes=list(range(max(self.O, 2))),
+                      class_weight=None if cw is None else cw.cpu().tolist(), batch_size=32, percent=[1.0, 0.0], index=None,
+                      shuffle=True, threshold=0.3, cluster_nodes='mcl', transform_sigmoid=self.transform_sigmoid)
         for m, (path, sd) in enumerate(zip(paths, self.state_dicts())):
-            state = {'model': sd, 'optimizer': self.trainers[m].optimizer_state_dict(), 'node': None, 'edge': ['dist'],
-                     'target': None, 'task': self.task, 'classes': list(range(max(self.O, 2))),
-                     'class_weight': None if cw is None else cw.cpu().tolist(), 'batch_size': 32, 'percent': [1.0, 0.0],
-                     'lr': self.lr[m], 'index': None, 'shuffle': True, 'threshold': 0.3, 'cluster_nodes': 'mcl',
-                     'transform_sigmoid': self.transform_sigmoid}
-            state.update(settings)
-            torch.save(state, path)
+            torch.save(checkpoint_state(sd, self.trainers[m].optimizer_state_dict(),
+                                        **{**common, 'lr': self.lr[m], **settings}), path)
         return paths
 
     def ensemble(self):
         """An ``Ensemble`` over the members' CURRENT parameters: it shares the cohort's parameter buffer (no copy), so it
         scores with whatever the cohort has trained so far."""
-        ens = Ensemble(self.Net, [{k: v.detach() for k, v in tr.net.state_dict().items()} for tr in self.trainers],
-                       device=self.device, api=self.api, edge_dim=self.edge_dim)
-        ens.transform_sigmoid = self.transform_sigmoid
-        lay = NetLayout(ens.trainers[0].net)
-        ens.params = self.params
-        table = (_lib.EnsMember * self.K)()
-        ens._descs = []
-        for m, tr in enumerate(ens.trainers):
-            tr.flat_p = self.params[m]
-            tr.transform_sigmoid = self.transform_sigmoid
-            with torch.no_grad():
-                lay.bind(tr.net, self.params[m])
-            tr._desc_cache.clear()
-            d = tr._descs(self.n_feat)[2]
-            ens._descs.append(d)
-            table[m].net = d
-            table[m].w1, table[m].b1 = tr.net.fc1.weight.data_ptr(), tr.net.fc1.bias.data_ptr()
-            table[m].w2, table[m].b2 = tr.net.fc2.weight.data_ptr(), tr.net.fc2.bias.data_ptr()
-        ens.table = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(self.device)
-        ens._head = head_desc(ens.trainers[0].net, ens.trainers[0].task, False, 0.0, 0, self.transform_sigmoid)
-        return ens
+        return Ensemble.over(self)
 
     def faults(self):
         """the members' sticky fault words ([K] int32 view on the device)"""
@@ -176,18 +115,10 @@ class Cohort(object):
                     raise _lib.DrgnnError("cohort member %d: %s" % (m, exc))
 
     # -- one step -------------------------------------------------------------------------------------------------------
-    def _cached_ok(self, rs):
-        need_w = self.kind == _lib.SGAT
-        return bool(rs.has_c0 and rs.has_c1) and not (need_w and rs.edge_attr is None)
-
     def plan(self, cache, ids, B):
         """drgnn_cohort_step_plan of a cohort launch of ``B`` graphs per member with the bounds of the graphs ``ids`` of
         ``cache``, and (bounds, flags, tiles) of that launch"""
-        bounds = cache.bounds(ids)
-        flags, tiles = cached_flags(self.kind, cache)
-        p = self.api.cohort_step_plan(self.K, self.kind, self.n_feat, bounds[0], bounds[1], bounds[2], self.R, self.H, self.O,
-                                      B, flags)
-        return p, bounds, flags, tiles
+        return self.member_plan(self.api.cohort_step_plan, cache, ids, B)
 
     def _ensure(self, B):
         """the members' outputs and slabs for mini-batches of up to ``B`` graphs, and the member table that names them"""
@@ -200,15 +131,14 @@ class Cohort(object):
         hp = torch.empty((K, B, api.head_compact_elems(self.R, self.H, self.O)), dtype=torch.float32, device=dev)
         table = (_lib.CohortMember * K)()
         for m, tr in enumerate(self.trainers):
-            t, n = table[m], tr.net
-            t.net = tr._descs(self.n_feat)[2]
-            t.w1, t.b1, t.w2, t.b2 = n.fc1.weight.data_ptr(), n.fc1.bias.data_ptr(), n.fc2.weight.data_ptr(), n.fc2.bias.data_ptr()
+            t = table[m]
+            fill_member(t, tr, tr._descs(self.n_feat)[2])
             t.flat_param, t.flat_grad = tr.flat_p.data_ptr(), tr.flat_g.data_ptr()
             t.exp_avg, t.exp_avg_sq = tr.exp_avg.data_ptr(), tr.exp_avg_sq.data_ptr()
             t.step2, t.loss = tr.step2.data_ptr(), tr._loss_buf.data_ptr()
             t.pred, t.readout, t.head_partials, t.partials = pred[m].data_ptr(), readout[m].data_ptr(), hp[m].data_ptr(), partials[m].data_ptr()
             t.lr, t.beta1, t.beta2, t.eps, t.seed = tr.lr, tr.betas[0], tr.betas[1], tr.eps, tr.seed
-        self._table = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
+        self._table = device_table(table, dev)
         self._bufs, self._cap = (pred, readout, partials, hp), B
 
     def _tables(self, rs, batches):
@@ -259,11 +189,6 @@ class Cohort(object):
         return (p, bounds, flags, tiles, cache.desc_for(self.kind == _lib.SGAT), head,
                 _lib.step_hints(topo_flags=flags, tiles=tiles, plan=p))
 
-    def _check_targets(self, rs):
-        want = torch.float32 if self.task == "reg" else torch.int64
-        if rs.y is None or rs.y.dtype != want:
-            raise ValueError("the set's targets must be %s for this task" % want)
-
     def _separate_step(self, rs, cache, row):
         """each member's own step on its mini-batch, one after the other (a member without one is left alone)"""
         from .topology import Topology
@@ -284,7 +209,9 @@ class Cohort(object):
     def _run(self, rs, batches, cached=None):
         """``batches``: [steps][K] lists of graph numbers.  Returns the losses [steps, K] (NaN where a member had no
         mini-batch), on the device, without synchronising."""
-        self._check_targets(rs)
+        wrong = wrong_targets(self.task == "reg", rs.y)
+        if wrong:
+            raise ValueError(wrong)
         steps, K = len(batches), self.K
         out = torch.full((steps, K), float("nan"), dtype=torch.float32, device=self.device)
         if steps == 0:

@@ -4,9 +4,9 @@ The reference scores a docking set with its ten fold models by building ten Neur
 each of which reads and collates the set again.  Here the set is uploaded once (resident.ResidentGraphSet), its topology is
 cached once, and per mini-batch ONE launch runs all K members (drgnn_ens_predict_cached: one workgroup per (model, graph),
 the K models of a graph on the same XCD, so the graph's topology, tiles and node rows are read once into that L2).  The
-member table -- member m's conv parameters and head, rows of one packed [K, P] parameter buffer -- is written to the device
-once, when the ensemble is built.  Each member's outputs are those of the same model alone, bit for bit, with the
-one-workgroup-per-graph layout (the plan's force_wgs = 1).
+members are a members.MemberPack: nets and inference-only trainers on the rows of one packed [K, P] parameter buffer; the
+member table that names them is written to the device once, when the ensemble is built.  Each member's outputs are those
+of the same model alone, bit for bit, with the one-workgroup-per-graph layout (the plan's force_wgs = 1).
 
 ``last_path`` / ``last_reason`` tell which path the last ``predict`` took, as StepEngine does: ``"fused"`` (every mini-batch
 in one ensemble launch), ``"separate"`` (the members' own launches, one after the other: the plan answers NONE -- the host
@@ -16,124 +16,46 @@ import numpy as np
 import torch
 
 from . import _lib
-from .functional import _describe
-from .launch import NetLayout, cached_flags, fused, head_desc, set_hints
-from .trainer import FusedTrainer
-
-# the properties the members of an ensemble must share (the ValueError names the first that differs)
-KEYS = ("net", "F", "task", "O", "classes", "transform_sigmoid", "head")
+from .launch import fused, head_desc, set_hints
+from .members import MemberPack, device_table, fill_member, load_members
 
 
-def _load(member):
-    """(model state dict, checkpoint settings) of a checkpoint path, a checkpoint dictionary (NeuralNet.save_model's) or a
-    bare state dict."""
-    if isinstance(member, (str, bytes)) or hasattr(member, "__fspath__"):
-        member = torch.load(member, map_location="cpu", weights_only=False)
-    if not isinstance(member, dict):
-        raise TypeError("an ensemble member is a checkpoint path, a checkpoint dictionary or a state dict, not %r"
-                        % type(member).__name__)
-    if "model" in member and isinstance(member["model"], dict):
-        return member["model"], member
-    return member, {}
-
-
-def _n_feat(Net, sd):
-    """F of a state dict of one of the three nets (the in-features of its first layer)."""
-    name = Net.__name__
-    if name == "GINet":
-        return int(sd["conv1.fc.weight"].shape[1])
-    if name == "sGAT":
-        return int(sd["conv1.weight"].shape[0]) // 2
-    if name == "FoutNet":
-        return int(sd["conv1.Wc"].shape[0])
-    raise ValueError("Ensemble: unknown net class %s" % name)
-
-
-def _signature(Net, sd, ck):
-    O = int(sd["fc2.weight"].shape[0])
-    task = ck.get("task") or ("reg" if O == 1 else "class")
-    return {"net": Net.__name__, "F": _n_feat(Net, sd), "task": task, "O": O,
-            "classes": None if task == "reg" else list(ck.get("classes", range(O))),
-            "transform_sigmoid": bool(ck.get("transform_sigmoid", False)) and task == "reg",
-            "head": (tuple(sd["fc1.weight"].shape), tuple(sd["fc2.weight"].shape)),
-            "params": {k: tuple(v.shape) for k, v in sd.items()}}
-
-
-def _first_difference(a, b):
-    """the first key of the signatures a, b that differs (a parameter's name for the parameter shapes)"""
-    for key in KEYS:
-        if a[key] != b[key]:
-            return key, a[key], b[key]
-    for name in sorted(set(a["params"]) | set(b["params"])):
-        if a["params"].get(name) != b["params"].get(name):
-            return name, a["params"].get(name), b["params"].get(name)
-    return None
-
-
-class Ensemble(object):
+class Ensemble(MemberPack):
     """K members of the net class ``Net`` (checkpoint paths, checkpoint dictionaries or state dicts), inference only.
 
     ``predict`` returns ``[K, n, O]`` on the device: the members' outputs as each alone would give them (after the sigmoid
     when the checkpoints set ``transform_sigmoid``; logits for classification)."""
 
     def __init__(self, Net, checkpoints_or_state_dicts, device=None, api=None, edge_dim=1):
-        members = list(checkpoints_or_state_dicts)
-        if not members:
-            raise ValueError("Ensemble: no members")
-        self.device = torch.device(device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
-        loaded = [_load(m) for m in members]
-        sigs = [_signature(Net, sd, ck) for sd, ck in loaded]
-        for k, s in enumerate(sigs[1:], start=1):
-            diff = _first_difference(s, sigs[0])
-            if diff is not None:
-                raise ValueError("Ensemble: member %d differs from member 0 in %r (%r against %r)" % ((k,) + diff))
-        sig = sigs[0]
-        self.Net, self.K, self.n_feat, self.O = Net, len(members), sig["F"], sig["O"]
-        self.task, self.classes, self.transform_sigmoid = sig["task"], sig["classes"], sig["transform_sigmoid"]
-        self.trainers = []
-        for sd, _ in loaded:
-            net = Net(self.n_feat, self.O, edge_dim)
-            net.load_state_dict(sd, strict=True)
-            tr = FusedTrainer(net.to(self.device), task=self.task, api=api, transform_sigmoid=self.transform_sigmoid)
-            tr.exp_avg = tr.exp_avg_sq = None          # inference only: no optimiser state
-            self.trainers.append(tr)
-        tr0 = self.trainers[0]
-        lay = NetLayout(tr0.net)
-        # the K parameter sets packed in ONE device buffer [K, P] (the members' parameters are views of their rows)
-        self.params = torch.stack([tr.flat_p for tr in self.trainers])
-        for m, tr in enumerate(self.trainers):
-            tr.flat_p = self.params[m]
-            with torch.no_grad():
-                lay.bind(tr.net, self.params[m])
-        self.kind, self.api, self.n_branch = lay.kind, tr0.api, lay.n_branch
-        self.R, self.H = lay.R, lay.H
-        self._head = head_desc(tr0.net, _lib.TASK_REG if self.task == "reg" else _lib.TASK_CLASS, False, 0.0, tr0.seed,
-                               self.transform_sigmoid)
-        # the member table (drgnn_ens_member[K]) in device memory, written once; the host descriptors it was made from keep
-        # the layout the launch checks against (member 0's)
-        table = (_lib.EnsMember * self.K)()
-        self._descs = []
-        for m, tr in enumerate(self.trainers):
-            d = _describe(self.kind, self.n_feat, tr.live, self.n_branch)
-            self._descs.append(d)
-            n = tr.net
-            table[m].net = d
-            table[m].w1, table[m].b1 = n.fc1.weight.data_ptr(), n.fc1.bias.data_ptr()
-            table[m].w2, table[m].b2 = n.fc2.weight.data_ptr(), n.fc2.bias.data_ptr()
-        self.table = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(self.device)
-        self.last_path, self.last_reason = None, None
+        states, sig = load_members(Net, list(checkpoints_or_state_dicts), "Ensemble")
+        self._build(Net, len(states), sig["F"], sig["O"], sig["task"], sig["classes"], sig["transform_sigmoid"], device, api,
+                    edge_dim, states=states)
 
-    @property
-    def nets(self):
-        return [tr.net for tr in self.trainers]
+    @classmethod
+    def over(cls, pack):
+        """An ensemble over the CURRENT parameters of ``pack`` (a Cohort, another Ensemble): nets and trainers of its own
+        (their default launch plans, their own step words) on the rows of ``pack.params``, no copy."""
+        ens = cls.__new__(cls)
+        ens._build(pack.Net, pack.K, pack.n_feat, pack.O, pack.task, pack.classes, pack.transform_sigmoid, pack.device,
+                   pack.api, pack.edge_dim, params=pack.params)
+        return ens
+
+    def _build(self, Net, K, n_feat, n_out, task, classes, transform_sigmoid, device, api, edge_dim, **storage):
+        self.task, self.classes, self.transform_sigmoid = task, classes, transform_sigmoid
+        MemberPack.__init__(self, Net, K, n_feat, n_out, device, edge_dim, task=task, api=api,
+                            transform_sigmoid=transform_sigmoid, **storage)
+        tr0 = self.trainers[0]
+        self._desc0 = tr0._descs(self.n_feat)[2]       # (the launch checks the members' layout against member 0's)
+        self._head = head_desc(tr0.net, tr0.task, False, 0.0, tr0.seed, transform_sigmoid)
+        # the member table (drgnn_ens_member[K]) in device memory, written once
+        table = (_lib.EnsMember * self.K)()
+        for m, tr in enumerate(self.trainers):
+            fill_member(table[m], tr, tr._descs(self.n_feat)[2])
+        self.table = device_table(table, self.device)
 
     def _resident(self, dataset):
         from .resident import ResidentGraphSet
         return dataset if isinstance(dataset, ResidentGraphSet) else ResidentGraphSet(dataset, self.device, api=self.api)
-
-    def _cached_ok(self, rs):
-        need_w = self.kind == _lib.SGAT
-        return bool(rs.has_c0 and rs.has_c1) and not (need_w and rs.edge_attr is None)
 
     @torch.no_grad()
     def predict(self, dataset, indices=None, batch_size=64, cached=None):
@@ -183,11 +105,7 @@ class Ensemble(object):
     def plan(self, cache, ids):
         """drgnn_ens_step_plan of the ensemble launch over the graphs ``ids`` of ``cache`` (with the topology flags and tiles
         that launch reads), and those (flags, tiles)"""
-        max_nodes, max_edges, max_c0 = cache.bounds(ids)
-        flags, tiles = cached_flags(self.kind, cache)
-        p = self.api.ens_step_plan(self.K, self.kind, self.n_feat, max_nodes, max_edges, max_c0, self.R, self.H, self.O,
-                                   len(ids), flags)
-        return p, (max_nodes, max_edges, max_c0), flags, tiles
+        return self.member_plan(self.api.ens_step_plan, cache, ids, len(ids))
 
     def _launch(self, cache, ids, ids_dev):
         """[K, B, O] of ONE ensemble launch over the graphs ``ids``, or None when its plan is NONE"""
@@ -199,7 +117,7 @@ class Ensemble(object):
         pred = torch.empty((self.K, B, self.O), dtype=torch.float32, device=self.device)
         readout = torch.empty((self.K, B, self.R), dtype=torch.float32, device=self.device)
         hints = set_hints(gset, ids, flags, tiles, p)
-        self.api.ens_predict_cached(self._descs[0], self._head, self.table, self.K, cache.desc_for(self.kind == _lib.SGAT),
+        self.api.ens_predict_cached(self._desc0, self._head, self.table, self.K, cache.desc_for(self.kind == _lib.SGAT),
                                     ids_dev, B, mn, me, mc, self.trainers[0].step2, pred, readout, _lib.current_stream(gset.x),
                                     hints[0])
         return pred

@@ -1,9 +1,11 @@
-"""Launch set-up of the fused step kernels, shared by their three front ends: FusedTrainer (trainer.py), the drop-in
-``model(batch)`` boundary StepEngine (fused_autograd.py) and Ensemble (ensemble.py).
+"""Launch set-up of the fused step kernels, shared by their front ends: FusedTrainer (trainer.py), the drop-in
+``model(batch)`` boundary StepEngine (fused_autograd.py), and Ensemble / Cohort (ensemble.py, cohort.py).
 
-What a launch of drgnn_net_train_step / drgnn_net_train_step_cached / drgnn_ens_predict_cached is handed is decided here
-once: where a net's parameters sit (NetLayout), its head descriptor, which TOPO_* flags of a workspace the launch may rely
-on, the launch hints, the exchange words, and whether a plan is a fused launch at all.
+What a launch of drgnn_net_train_step / drgnn_net_train_step_cached / drgnn_ens_predict_cached /
+drgnn_cohort_train_step_cached is handed is decided here once: where a net's parameters sit (NetLayout), its head descriptor,
+which TOPO_* flags of a workspace the launch may rely on, the launch hints, the exchange words, whether a plan is a fused
+launch at all, and whether a set's targets suit the task.  What K members of one net over packed storage are (their nets,
+trainers, [K, P] buffers and member tables) lives in members.py.
 """
 import torch
 
@@ -75,6 +77,13 @@ def fused(plan, family=None):
     """True when ``plan`` is a launch of a fused step kernel of ``family`` (None: any family) within a workgroup's LDS."""
     ok = plan.family != _lib.STEP_FAMILY_NONE if family is None else plan.family == family
     return ok and 0 < plan.lds_bytes <= _lib.LDS_LIMIT
+
+
+def wrong_targets(regression, y):
+    """None when the targets ``y`` of a resident set suit the task (float32 for regression, int64 class indices), else the
+    message of the callers that raise"""
+    want = torch.float32 if regression else torch.int64
+    return None if (y is not None and y.dtype == want) else "the set's targets must be %s for this task" % want
 
 
 # -- topology flags ---------------------------------------------------------------------------------------------------------

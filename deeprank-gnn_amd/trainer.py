@@ -24,7 +24,7 @@ import torch.distributed as dist
 
 from . import _lib, hostcpu
 from .functional import H1, H2, _conv_grads, _describe
-from .launch import ExchangeWords, NetLayout, batch_hints, cached_flags, fused, head_desc, set_hints, tiles_match, usable_flags
+from .launch import ExchangeWords, NetLayout, batch_hints, cached_flags, fused, head_desc, set_hints, tiles_match, usable_flags, wrong_targets
 from .topology import Topology
 
 __all__ = ["FusedTrainer"]
@@ -55,16 +55,7 @@ class FusedTrainer(object):
         dev = params[0].device
         if self.api is _lib._API:
             _lib.require_device(*params)
-        total = lay.total
-        self.flat_p = torch.empty(total, dtype=torch.float32, device=dev)
-        self.flat_g = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.exp_avg = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.exp_avg_sq = torch.zeros(total, dtype=torch.float32, device=dev)
-        # [0] optimiser steps completed, [1] index of the step in flight (fused step launch writes it,
-        # the update launch reads it for Adam and commits [0]); `step` is the public 1-element view
-        # ([2]: sticky fault bits the fused step raises, see check_faults; [3] reserved)
-        self.step2 = torch.zeros(4, dtype=torch.int32, device=dev)
-        self.step = self.step2[:1]
+        self.layout, total = lay, lay.total
         self.fused_step = True       # one launch for fwd + head + bwd whenever a graph fits LDS
         # overrides of the fused step's launch plan (drgnn_step_plan: force_wgs / no_class / no_aggregate / no_split; tests
         # and A/B runs) -- per trainer, handed to every plan query and every launch
@@ -77,16 +68,54 @@ class FusedTrainer(object):
         self._epoch_bytes = {}        # scratch need of the native epoch loop by epoch shape (_run_epoch)
         self._ids_memo = {}           # (set, inference) -> (host order, its ids on the device) of the last such pass
         self._epoch_scratch = None
-        self._loss_buf = torch.zeros(1, dtype=torch.float32, device=dev)
+        flat_p = torch.empty(total, dtype=torch.float32, device=dev)
         with torch.no_grad():
             for name, p in net.named_parameters():
                 off = self.offset[name]
-                self.flat_p[off:off + p.numel()].copy_(p.detach().reshape(-1))
-            lay.bind(net, self.flat_p, self.flat_g)
+                flat_p[off:off + p.numel()].copy_(p.detach().reshape(-1))
+        # [0] optimiser steps completed, [1] index of the step in flight (fused step launch writes it,
+        # the update launch reads it for Adam and commits [0]); `step` is the public 1-element view
+        # ([2]: sticky fault bits the fused step raises, see check_faults; [3] reserved)
+        self.adopt_storage(flat_p, *(torch.zeros(total, dtype=torch.float32, device=dev) for _ in range(3)),
+                           step2=torch.zeros(4, dtype=torch.int32, device=dev),
+                           loss=torch.zeros(1, dtype=torch.float32, device=dev))
         self.class_w = None
         if class_weights is not None:
             self.class_w = torch.as_tensor(class_weights, dtype=torch.float32, device=dev).contiguous()
+
+    def adopt_storage(self, flat_p, flat_g=None, exp_avg=None, exp_avg_sq=None, step2=None, loss=None):
+        """Put the trainer on caller-owned buffers: the flat parameters [P], and for training the flat gradient and both
+        Adam moments [P]; optionally the step words ``step2`` (int32 [4]) and the loss word ``loss`` (float32 [1]), else
+        the trainer keeps its own.  The one supported way to do so (the constructor uses it for its own buffers, the member
+        packs of members.py for rows of [K, P] tensors).
+
+        Nothing is copied: what the buffers hold becomes the trainer's state (parameters, moments, step index), so a
+        caller that wants the current values stacks or copies them first, as members.MemberPack does.  With ``flat_p``
+        alone the trainer is inference only: it drops its gradient and moments, and its training entry points raise.
+
+        Everything here that holds an address of the storage is refreshed: the net's parameters and their ``.grad``
+        (views, NetLayout.bind), ``live_grads``, the ``step`` view of ``step2``, the ``loss`` buffer, and the descriptors
+        of ``_descs`` (dropped, rebuilt on demand).  Head descriptors, epoch plans and launch arguments read the addresses
+        at launch time.  A hipGraph the caller recorded earlier still names the old buffers."""
+        if len({flat_g is None, exp_avg is None, exp_avg_sq is None}) > 1:
+            raise ValueError("adopt_storage: training storage is flat_g, exp_avg and exp_avg_sq together")
+        self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq = flat_p, flat_g, exp_avg, exp_avg_sq
+        if step2 is not None:
+            self.step2 = step2
+        self.step = self.step2[:1]
+        if loss is not None:
+            self._loss_buf = loss
+        with torch.no_grad():
+            self.layout.bind(self.net, flat_p, flat_g)
+        if flat_g is None:
+            for p in self.net.parameters():
+                p.grad = None           # (views of the gradient buffer just released)
         self.live_grads = tuple(p.grad for p in self.live)
+        self._desc_cache.clear()
+
+    def _training_storage(self):
+        if self.flat_g is None:
+            raise _lib.DrgnnError("this trainer adopted parameters only (inference): it has no gradient or Adam buffers")
 
     # ---------------------------------------------------------------------------
     @property
@@ -144,7 +173,8 @@ class FusedTrainer(object):
         """(g_conv1, g_conv2, net descriptor) of a fused step over ``n_feat`` features (built once per width)"""
         ck = self._desc_cache.get(n_feat)
         if ck is None:
-            g1, g2 = _conv_grads(self.kind, n_feat, self.live_grads, self.n_branch)
+            # (an inference-only trainer has no gradients to describe)
+            g1, g2 = _conv_grads(self.kind, n_feat, self.live_grads, self.n_branch) if self.flat_g is not None else (None, None)
             ck = self._desc_cache[n_feat] = (g1, g2, _describe(self.kind, n_feat, self.live, self.n_branch))
         return ck
 
@@ -255,10 +285,11 @@ class FusedTrainer(object):
     def train_step_cached(self, cache, ids, ids_dev=None, apply_adam=True, next_ids_dev=None):
         """One optimisation step on the graphs ``ids`` of a cached set: the fused step launch reading the cached
         topology in place + the update launch.  Same arithmetic as ``train_step`` on the collated mini-batch."""
+        self._training_storage()
         c = self._cached_prepare(cache, ids, ids_dev, True, next_ids_dev)
-        want = torch.float32 if self.task == _lib.TASK_REG else torch.int64
-        if cache.set.y is None or cache.set.y.dtype != want:
-            raise ValueError("the set's targets must be %s for this task" % want)
+        wrong = wrong_targets(self.task == _lib.TASK_REG, cache.set.y)
+        if wrong:
+            raise ValueError(wrong)
         self._cached_launch_step(c, True)
         self._fused_launch_update(c, apply_adam)
         self.last_pred = c["pred"]
@@ -290,6 +321,7 @@ class FusedTrainer(object):
         -> fixed-order reduction of the partials, with Adam applied in the same launch when
         ``apply_adam``."""
         api = self.api
+        self._training_storage()
         if topo is None:
             topo = self._topology_of(batch, True)
         if self._can_fuse(topo, batch.x.shape[1], next_topo, True, batch.x):
@@ -394,6 +426,7 @@ class FusedTrainer(object):
 
     def apply_update(self):
         """Adam on the flat buffers (one launch)."""
+        self._training_storage()
         self.api.adam_step(self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.step, self.lr,
                            self.betas[0], self.betas[1], self.eps, self.weight_decay,
                            _lib.current_stream(self.flat_p))
@@ -460,10 +493,8 @@ class FusedTrainer(object):
         resident set) and the update launch -- no Python and no host synchronisation between mini-batches.  Returns (losses [n_batches], pred [len(order), O]) as
         device tensors, or None when this configuration needs the per-batch path (data parallel, weight decay,
         a graph too large for the fused kernels)."""
-        if self.weight_decay != 0.0:
-            return None
-        want = torch.float32 if self.task == _lib.TASK_REG else torch.int64
-        if gset.y is None or gset.y.dtype != want:
+        self._training_storage()
+        if self.weight_decay != 0.0 or wrong_targets(self.task == _lib.TASK_REG, gset.y):
             return None
         self._dp = None
         if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
@@ -519,10 +550,11 @@ class FusedTrainer(object):
         plan.batch_size, plan.need_weights = int(batch_size), int(need_w)
         plan.net = ctypes.cast(ctypes.pointer(desc), vp)
         plan.head = ctypes.cast(ctypes.pointer(head), vp)
-        plan.g_conv1, plan.g_conv2 = ctypes.cast(g1, vp), ctypes.cast(g2, vp)
         plan.head_offset = self.head_grad_offset
-        plan.flat_param, plan.flat_grad = self.flat_p.data_ptr(), self.flat_g.data_ptr()
-        plan.exp_avg, plan.exp_avg_sq, plan.n_param = self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.flat_p.numel()
+        plan.flat_param, plan.n_param = self.flat_p.data_ptr(), self.flat_p.numel()
+        if self.flat_g is not None:       # (an inference-only trainer: the loop reads none of them in an inference pass)
+            plan.g_conv1, plan.g_conv2 = ctypes.cast(g1, vp), ctypes.cast(g2, vp)
+            plan.flat_grad, plan.exp_avg, plan.exp_avg_sq = self.flat_g.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr()
         plan.step2 = self.step2.data_ptr()
         plan.lr, plan.beta1, plan.beta2, plan.eps = self.lr, self.betas[0], self.betas[1], self.eps
         if cached:
