@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("DRGNN_LIB") or os.path.join(_HERE, "csrc", "libdrgnn.
 GINET, SGAT, FOUT = 0, 1, 2
 MAX_BRANCH = 2
 LDS_LIMIT = 160 * 1024     # LDS bytes one workgroup may allocate (gfx950)
+HEAD_MAX_HIDDEN = 512      # hidden units of the FC head the launch pair takes (drgnn_net_backward_fused_head: DRGNN_E_WIDTH beyond)
 
 # enum drgnn_topo_i32 / drgnn_topo_f32 (include/drgnn.h)
 TI = {name: i for i, name in enumerate([
@@ -288,6 +289,10 @@ class Api(object):
         lib.drgnn_head_partial_elems.restype = _c_i64
         lib.drgnn_head_num_slabs.argtypes = [_c_i64]
         lib.drgnn_head_num_slabs.restype = _c_i64
+        lib.drgnn_head_pass_units.argtypes = [_c_i32] * 3 + [_c_i64]
+        lib.drgnn_head_pass_units.restype = _c_i32
+        lib.drgnn_net_head_stage_bytes.argtypes = [_c_i32] * 3
+        lib.drgnn_net_head_stage_bytes.restype = _c_i64
         lib.drgnn_head_step.argtypes = [ctypes.POINTER(HeadDesc), _vp, _vp, _c_i64] + [_vp] * 5
         lib.drgnn_head_reduce.argtypes = [_vp, _c_i64, _c_i32, _c_i32, _c_i32] + [_vp] * 4
         lib.drgnn_adam_step.argtypes = [_vp] * 5 + [_c_i64] + [ctypes.c_float] * 5 + [_vp]
@@ -616,6 +621,14 @@ class Api(object):
 
     def head_num_slabs(self, n_graphs):
         return int(self.lib.drgnn_head_num_slabs(n_graphs))
+
+    def head_pass_units(self, R, H, O, n_graphs):
+        """Hidden units an inference head_step of ``n_graphs`` keeps in LDS at a time (H: the head whole, in one pass)."""
+        return int(self.lib.drgnn_head_pass_units(R, H, O, n_graphs))
+
+    def net_head_stage_bytes(self, R, H, O):
+        """LDS bytes the backward launch needs on top of net_lds_bytes to keep the head's weights in LDS."""
+        return int(self.lib.drgnn_net_head_stage_bytes(R, H, O))
 
     def head_step(self, desc, readout, target, n_graphs, step, pred, grad_readout, partials, stream):
         _check(self.lib.drgnn_head_step(ctypes.byref(desc), _ptr(readout), _ptr(target), n_graphs,

@@ -415,7 +415,7 @@ static int net_launch(NetLaunch& L, int32_t max_nodes, int32_t max_edges, int32_
         L.capN = c.N; L.capE = c.E; L.capC = c.C;
         use_lds = lds;
         if (BWD && L.a.hf.enabled) {    // room to keep the head's weights in LDS as well?
-            const int64_t extra = 4 * head_stage_words(L.a.hf.R, L.a.hf.H, L.a.hf.O);
+            const int64_t extra = drgnn_net_head_stage_bytes(L.a.hf.R, L.a.hf.H, L.a.hf.O);
             if (use_lds + extra <= DRGNN_LDS_LIMIT) { use_lds += extra; L.a.hf.stage = 1; }
         }
     } else if (!scratch) {
@@ -1376,10 +1376,29 @@ int drgnn_net_reduce_grads(const drgnn_net_desc* net, const float* partials, int
 int64_t drgnn_head_partial_elems(int32_t R, int32_t H, int32_t O) { return head_partial_floats(R, H, O); }
 int64_t drgnn_head_num_slabs(int64_t n_graphs) { const int t = head_tile(n_graphs); return (n_graphs + t - 1) / t; }
 
+// hidden units k_head stages at a time for T graphs per workgroup: all H, or for inference the largest multiple of 16 that
+// fits LDS (the passes of head_block); 0: none does
+static int head_chunk(const drgnn_head_desc* hd, int T) {
+    if (4 * head_lds_words(hd->R, hd->H, hd->O, T) <= DRGNN_LDS_LIMIT) return hd->H;
+    if (hd->train) return 0;
+    for (int hc = (hd->H - 1) / 16 * 16; hc >= 16; hc -= 16)
+        if (4 * head_lds_words(hd->R, hc, hd->O, T) <= DRGNN_LDS_LIMIT) return hc;
+    return 0;
+}
+
+int32_t drgnn_head_pass_units(int32_t R, int32_t H, int32_t O, int64_t n_graphs) {
+    drgnn_head_desc hd = {};
+    hd.R = R; hd.H = H; hd.O = O; hd.train = 0;
+    if (R < 1 || H < 1 || O < 1 || O > DRGNN_MAX_OUT) return 0;
+    return head_chunk(&hd, head_tile(n_graphs));
+}
+int64_t drgnn_net_head_stage_bytes(int32_t R, int32_t H, int32_t O) { return 4 * head_stage_words(R, H, O); }
+
 static int head_check(const drgnn_head_desc* hd) {
     if (!hd || !hd->w1 || !hd->b1 || !hd->w2 || !hd->b2) return DRGNN_E_ARG;
     if (hd->R < 1 || hd->H < 1 || hd->O < 1 || hd->O > DRGNN_MAX_OUT) return DRGNN_E_WIDTH;
-    if (4 * head_lds_words(hd->R, hd->H, hd->O, DRGNN_HEAD_TILE_LARGE) > DRGNN_LDS_LIMIT) return DRGNN_E_WIDTH;
+    // (a training head is staged whole, whatever the batch size; an inference launch takes a wider one in passes)
+    if (head_chunk(hd, DRGNN_HEAD_TILE_LARGE) == 0) return DRGNN_E_WIDTH;
     if (hd->task != DRGNN_TASK_REG && hd->task != DRGNN_TASK_CLASS) return DRGNN_E_ARG;
     if (!(hd->p_drop >= 0.0f && hd->p_drop < 1.0f)) return DRGNN_E_ARG;
     return 0;
@@ -1404,8 +1423,9 @@ int drgnn_head_step(const drgnn_head_desc* hd, const float* readout, const void*
     a.B = (int)n_graphs; a.R = hd->R; a.H = hd->H; a.O = hd->O;
     a.task = hd->task; a.train = hd->train; a.p_drop = hd->p_drop; a.seed = hd->seed; a.sigmoid = hd->transform_sigmoid;
     a.T = head_tile(n_graphs);
+    a.HC = head_chunk(hd, a.T);
     const int blocks = (int)((n_graphs + a.T - 1) / a.T);
-    const int64_t lds = 4 * head_lds_words(hd->R, hd->H, hd->O, a.T);
+    const int64_t lds = 4 * head_lds_words(hd->R, a.HC, hd->O, a.T);
 #ifdef DRGNN_EMU
     std::vector<float> buf((size_t)(lds / 4) + 16);
     for (int b = 0; b < blocks; ++b) head_block(a, b, buf.data());

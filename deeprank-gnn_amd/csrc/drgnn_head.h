@@ -36,6 +36,7 @@ struct HeadArgs {
     float* grad_readout;      // [B, R] or null (inference)
     float* partials;          // [n_wg][P] or null
     int B, R, H, O, T;        // T = graphs per workgroup
+    int HC;                   // hidden units in LDS at a time: H, or less for an inference launch of a head too wide to stage whole
     int task;
     int train;                // apply dropout, compute gradients
     int sigmoid;              // regression: pred = sigmoid(output) before the loss
@@ -43,87 +44,104 @@ struct HeadArgs {
     uint32_t seed;
 };
 
+// (fc2's split sums are 8 per graph and output: more than DRGNN_HEAD_TMP floats from 64 graphs x 9 outputs on)
+HD int64_t head_tmp_words(int O, int T) { return 8 * T * O > DRGNN_HEAD_TMP ? 8 * T * O : DRGNN_HEAD_TMP; }
+// H: the hidden units staged at a time (HeadArgs::HC)
 HD int64_t head_lds_words(int R, int H, int O, int T) {
     return (int64_t)T * (R + 1) + (int64_t)H * (R + 1) + (int64_t)T * (H + 1) + H + (int64_t)O * H + O +
-           2 * T * DRGNN_MAX_OUT + 2 * T + DRGNN_HEAD_TMP + 64;
+           2 * T * DRGNN_MAX_OUT + 2 * T + head_tmp_words(O, T) + 64;
 }
 
 DEV void head_block(const HeadArgs& a, int blk, float* lds) {
-    const int R = a.R, H = a.H, O = a.O, T = a.T;
+    const int R = a.R, H = a.H, O = a.O, T = a.T, HC = a.HC;
     const int g0 = blk * T;
     const int G = imin(T, a.B - g0);
-    const int ldx = R + 1, ldh = H + 1;
+    const int ldx = R + 1, ldh = HC + 1;
     float* xs = lds;                                   // [T][R+1]
-    float* w1p = xs + T * ldx;                         // [H][R+1]
-    float* hid = w1p + (long)H * ldx;                  // [T][H+1]
-    float* b1s = hid + T * ldh;                        // [H]
-    float* w2s = b1s + H;                              // [O][H]
-    float* b2s = w2s + (long)O * H;                    // [O]
+    float* w1p = xs + T * ldx;                         // [HC][R+1]
+    float* hid = w1p + (long)HC * ldx;                 // [T][HC+1]
+    float* b1s = hid + T * ldh;                        // [HC]
+    float* w2s = b1s + HC;                             // [O][HC]
+    float* b2s = w2s + (long)O * HC;                   // [O]
     float* outs = b2s + O;                             // [T][MAX_OUT]   pred tile
     float* douts = outs + T * DRGNN_MAX_OUT;           // [T][MAX_OUT]   d loss / d pred
     float* red = douts + T * DRGNN_MAX_OUT;            // [T][2] per-graph (loss, weight)
-    float* tmp = red + 2 * T;                          // [DRGNN_HEAD_TMP]
+    float* tmp = red + 2 * T;                          // [head_tmp_words]
     const uint32_t step = a.step ? (uint32_t)a.step[0] : 0u;
-    const FastDiv dH = fastdiv_make(H), dO = fastdiv_make(O), dR = fastdiv_make(R);
+    const FastDiv dO = fastdiv_make(O), dR = fastdiv_make(R);
     PHASE_MARK();
 
-    // ---- stage (all loads in flight together when the sizes allow) ------------------------
-    if (H * R <= 8 * DRGNN_BCAP && T * R <= 4 * DRGNN_BCAP && O * H <= 2 * DRGNN_BCAP &&
-        H <= DRGNN_BCAP) {
-        BurstW<8> bw1;  burst_load_w(bw1, a.w1, R, 1, H, R);
-        BurstW<4> bx;   burst_load_w(bx, a.readout + (long)g0 * R, R, 1, G, R);
-        Burst<float, 1> bb1, bb2;  burst_load(bb1, a.b1, H);  burst_load(bb2, a.b2, O);
-        Burst<float, 2> bw2;       burst_load(bw2, a.w2, O * H);
-        burst_store_w(bw1, w1p, ldx);
-        burst_store_w(bx, xs, ldx);
-        burst_store(bb1, b1s); burst_store(bb2, b2s); burst_store(bw2, w2s);
-    } else {
-        FOR_TID(e, G * R) { const int g = fastdiv(dR, e); xs[g * ldx + fastmod(dR, e, g)] = a.readout[(long)g0 * R + e]; }
-        FOR_TID(e, H * R) { const int h = fastdiv(dR, e); w1p[h * ldx + fastmod(dR, e, h)] = a.w1[e]; }
-        FOR_TID(h, H) { b1s[h] = a.b1[h]; }
-        FOR_TID(e, O * H) { w2s[e] = a.w2[e]; }
-        FOR_TID(o, O) { b2s[o] = a.b2[o]; }
-    }
-    FOR_TID(e, (T - G) * R) { const int g = fastdiv(dR, e); xs[(G + g) * ldx + fastmod(dR, e, g)] = 0.0f; }   // rows beyond the batch
-    BARRIER();
-    // hid = X W1^T            B(k=r, j=h) = w1p[h*ldx + r]
-    wg_gemm(T, H, R, xs, ldx, 1, w1p, 1, ldx, hid, ldh, 1);
-    BARRIER();
-    {
-        const float keep_scale = (a.train && a.p_drop > 0.0f) ? 1.0f / (1.0f - a.p_drop) : 1.0f;
-        const double pt = (double)a.p_drop * 4294967296.0;
-        const uint32_t thresh = (a.train && a.p_drop > 0.0f) ? (uint32_t)(pt > 4294967295.0 ? 4294967295.0 : pt) : 0u;
-        FOR_TID(e, T * H) {
-            const int g = fastdiv(dH, e), h = fastmod(dH, e, g);
-            float v = hid[g * ldh + h] + b1s[h];
-            v = v > 0.0f ? v : 0.0f;
-            if (thresh) {
-                const uint32_t u = drgnn_hash(a.seed, step, (uint32_t)((g0 + g) * H + h));
-                v = (u >= thresh) ? v * keep_scale : 0.0f;
+    // The hidden units go through LDS HC at a time: all of them at once (HC == H: every training launch, and the one pass in
+    // which the sums below are what they always were), or, for inference with a head too wide for that, in passes whose fc2
+    // sums add up in `outs`.
+    for (int h0 = 0; h0 < H; h0 += HC) {
+        const int hn = imin(HC, H - h0);
+        const FastDiv dH = fastdiv_make(hn);
+        const float* w1g = a.w1 + (long)h0 * R;
+        // ---- stage (all loads in flight together when the sizes allow) --------------------
+        if (hn == H && H * R <= 8 * DRGNN_BCAP && T * R <= 4 * DRGNN_BCAP && O * H <= 2 * DRGNN_BCAP &&
+            H <= DRGNN_BCAP) {
+            BurstW<8> bw1;  burst_load_w(bw1, a.w1, R, 1, H, R);
+            BurstW<4> bx;   burst_load_w(bx, a.readout + (long)g0 * R, R, 1, G, R);
+            Burst<float, 1> bb1, bb2;  burst_load(bb1, a.b1, H);  burst_load(bb2, a.b2, O);
+            Burst<float, 2> bw2;       burst_load(bw2, a.w2, O * H);
+            burst_store_w(bw1, w1p, ldx);
+            burst_store_w(bx, xs, ldx);
+            burst_store(bb1, b1s); burst_store(bb2, b2s); burst_store(bw2, w2s);
+        } else {
+            if (h0 == 0) {
+                FOR_TID(e, G * R) { const int g = fastdiv(dR, e); xs[g * ldx + fastmod(dR, e, g)] = a.readout[(long)g0 * R + e]; }
+                FOR_TID(o, O) { b2s[o] = a.b2[o]; }
             }
-            hid[g * ldh + h] = v;
+            FOR_TID(e, hn * R) { const int h = fastdiv(dR, e); w1p[h * ldx + fastmod(dR, e, h)] = w1g[e]; }
+            FOR_TID(h, hn) { b1s[h] = a.b1[h0 + h]; }
+            FOR_TID(e, O * hn) { const int o = fastdiv(dH, e); w2s[e] = a.w2[(long)o * H + h0 + fastmod(dH, e, o)]; }
         }
+        if (h0 == 0) {
+            FOR_TID(e, (T - G) * R) { const int g = fastdiv(dR, e); xs[(G + g) * ldx + fastmod(dR, e, g)] = 0.0f; }   // rows beyond the batch
+        }
+        BARRIER();
+        // hid = X W1^T            B(k=r, j=h) = w1p[h*ldx + r]
+        wg_gemm(T, hn, R, xs, ldx, 1, w1p, 1, ldx, hid, ldh, 1);
+        BARRIER();
+        {
+            const float keep_scale = (a.train && a.p_drop > 0.0f) ? 1.0f / (1.0f - a.p_drop) : 1.0f;
+            const double pt = (double)a.p_drop * 4294967296.0;
+            const uint32_t thresh = (a.train && a.p_drop > 0.0f) ? (uint32_t)(pt > 4294967295.0 ? 4294967295.0 : pt) : 0u;
+            FOR_TID(e, T * hn) {
+                const int g = fastdiv(dH, e), h = fastmod(dH, e, g);
+                float v = hid[g * ldh + h] + b1s[h];
+                v = v > 0.0f ? v : 0.0f;
+                if (thresh) {
+                    const uint32_t u = drgnn_hash(a.seed, step, (uint32_t)((g0 + g) * H + h0 + h));
+                    v = (u >= thresh) ? v * keep_scale : 0.0f;
+                }
+                hid[g * ldh + h] = v;
+            }
+        }
+        BARRIER();
+        // fc2: 8 interleaved partial dot products per output, combined in fixed order
+        FOR_TID(e, T * O * 8) {
+            const int q = e & 7, go = e >> 3;
+            const int g = fastdiv(dO, go), o = fastmod(dO, go, g);
+            float acc = 0.0f;
+            for (int h = q; h < hn; h += 8) acc = fmaf(hid[g * ldh + h], w2s[o * hn + h], acc);
+            tmp[e] = acc;
+        }
+        BARRIER();
+        const bool last = h0 + hn >= H;
+        FOR_TID(go, T * O) {
+            const int g = fastdiv(dO, go), o = fastmod(dO, go, g);
+            float acc = h0 == 0 ? b2s[o] : outs[g * DRGNN_MAX_OUT + o];
+            for (int q = 0; q < 8; ++q) acc += tmp[go * 8 + q];
+            if (last && a.sigmoid && a.task == DRGNN_TASK_REG) acc = drgnn_sigmoid(acc);
+            outs[g * DRGNN_MAX_OUT + o] = acc;
+            if (last && g < G) a.pred[(long)(g0 + g) * O + o] = acc;
+        }
+        BARRIER();
     }
-    BARRIER();
-    // fc2: 8 interleaved partial dot products per output, combined in fixed order
-    FOR_TID(e, T * O * 8) {
-        const int q = e & 7, go = e >> 3;
-        const int g = fastdiv(dO, go), o = fastmod(dO, go, g);
-        float acc = 0.0f;
-        for (int h = q; h < H; h += 8) acc = fmaf(hid[g * ldh + h], w2s[o * H + h], acc);
-        tmp[e] = acc;
-    }
-    BARRIER();
-    FOR_TID(go, T * O) {
-        const int g = fastdiv(dO, go), o = fastmod(dO, go, g);
-        float acc = b2s[o];
-        for (int q = 0; q < 8; ++q) acc += tmp[go * 8 + q];
-        if (a.sigmoid && a.task == DRGNN_TASK_REG) acc = drgnn_sigmoid(acc);
-        outs[g * DRGNN_MAX_OUT + o] = acc;
-        if (g < G) a.pred[(long)(g0 + g) * O + o] = acc;
-    }
-    BARRIER();
     if (!a.train || a.grad_readout == nullptr) return;
+    const FastDiv dH = fastdiv_make(H);          // (training: HC == H, see drgnn_head_step)
 
     // ---- loss and d loss / d pred (mean reduction over the WHOLE batch) --------------------
     FOR_TID(g, T) {

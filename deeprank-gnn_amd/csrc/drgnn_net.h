@@ -166,7 +166,9 @@ DEV bool drgnn_keep(const HeadFused& hf, uint32_t step, int g, int H, int h, uin
 DEV float drgnn_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
 HD int64_t head_stage_words(int R, int H, int O) { return (int64_t)H * (R + 1) + H + (int64_t)O * H + O + R + 16; }
 
-// scratch `gp`: >= 1024 + H + R + 2*DRGNN_MAX_OUT floats; dr_out: this branch's 32 columns
+// scratch `gp`: >= 1024 + H + R + 2*DRGNN_MAX_OUT floats for every H the entry points accept (1632 at H = 512,
+// R = 64; the carve gives 2048): [0, 1024) split sums, then hid [H], the readout row [R], outs, douts
+// dr_out: this branch's 32 columns
 // w1/b1/w2/b2/xrow: either the model's tensors in global memory (ldw = R) or their LDS copies
 // made by the prologue burst (ldw = R + 1, padded rows)
 DEV void head_graph(const HeadFused& hf, int g, int br, float* gp, float* dr_out, const float* w1, int ldw,
@@ -190,25 +192,29 @@ DEV void head_graph(const HeadFused& hf, int g, int br, float* gp, float* dr_out
 
     FOR_TID(r, R) { xr[r] = xrow[r]; }
     BARRIER();
-    {   // fc1: 8 lanes per hidden unit, each a contiguous slice of the row (coalesced W1 read)
-        const int per = (R + 7) >> 3;
-        FOR_TID(t, H * 8) {
-            const int h = t >> 3, q = t & 7;
+    // fc1: 8 lanes per hidden unit, each a contiguous slice of the row (coalesced W1 read).  `tmp` holds the 8
+    // slice sums of 128 units, so a wider head goes in passes of 128 (H <= 128: one pass, the sums as ever)
+    const int per = (R + 7) >> 3;
+    for (int h0 = 0; h0 < H; h0 += 128) {
+        const int hn = imin(128, H - h0);
+        FOR_TID(t, hn * 8) {
+            const int h = h0 + (t >> 3), q = t & 7;
             const int lo = q * per, hi = imin(R, lo + per);
             float acc = 0.0f;
             for (int r = lo; r < hi; ++r) acc = fmaf(w1[h * ldw + r], xr[r], acc);
             tmp[t] = acc;
         }
+        BARRIER();
+        FOR_TID(hl, hn) {
+            const int h = h0 + hl;
+            float v = b1[h];
+            for (int q = 0; q < 8; ++q) v += tmp[hl * 8 + q];
+            v = v > 0.0f ? v : 0.0f;
+            if (thresh) v = drgnn_keep(hf, step, g, H, h, thresh) ? v * keep_scale : 0.0f;
+            hid[h] = v;
+        }
+        BARRIER();
     }
-    BARRIER();
-    FOR_TID(h, H) {
-        float v = b1[h];
-        for (int q = 0; q < 8; ++q) v += tmp[h * 8 + q];
-        v = v > 0.0f ? v : 0.0f;
-        if (thresh) v = drgnn_keep(hf, step, g, H, h, thresh) ? v * keep_scale : 0.0f;
-        hid[h] = v;
-    }
-    BARRIER();
     FOR_TID(t, O * 16) {
         const int o = t >> 4, q = t & 15;
         float acc = 0.0f;

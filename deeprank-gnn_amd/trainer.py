@@ -326,6 +326,9 @@ class FusedTrainer(object):
             topo = self._topology_of(batch, True)
         if self._can_fuse(topo, batch.x.shape[1], next_topo, True, batch.x):
             return self._fused(batch, topo, apply_adam, next_topo)
+        if self.H > _lib.HEAD_MAX_HIDDEN:
+            # (refused here, before the forward launch counts a step the backward launch would then refuse: DRGNN_E_WIDTH)
+            _lib._check(-3, "training step with a head of %d hidden units (at most %d)" % (self.H, _lib.HEAD_MAX_HIDDEN))
         if int(getattr(topo, "flags", 0)) & _lib.TOPO_LEAN:
             topo.rebuild()       # the launch pair reads CSC0 and the member lists a lean build leaves out
         stream = _lib.current_stream(batch.x)

@@ -381,7 +381,10 @@ int drgnn_batch_offsets(const drgnn_graph_set* set, const int32_t* ids, int64_t 
  * same launch (the head is row-wise), instead of taking grad_readout from drgnn_head_step:
  * reads readout [B,32*n_branch] (forward output) and the targets, writes pred [B,O], one head
  * partial slab per GRAPH (head_partials [B][drgnn_head_partial_elems]) and the conv partials.
- * Dropout stream id = *step - 1 (the forward launch of the same step has incremented it). */
+ * Dropout stream id = *step - 1 (the forward launch of the same step has incremented it).
+ * The launch keeps the head's weights in LDS when drgnn_net_head_stage_bytes() more than the backward's
+ * drgnn_net_lds_bytes() still fit the LDS limit, and reads them from global memory otherwise. */
+int64_t drgnn_net_head_stage_bytes(int32_t R, int32_t H, int32_t O);
 int drgnn_net_backward_fused_head(const drgnn_net_desc* net, const drgnn_head_desc* head, const float* x,
                                   const float* readout, const void* target, const int32_t* step,
                                   const int32_t* ws_i32, const float* ws_f32, int64_t n_nodes,
@@ -398,6 +401,9 @@ int drgnn_net_backward_fused_head(const drgnn_net_desc* net, const drgnn_head_de
  * `step` (device int32) selects the dropout stream; it is NOT modified here. */
 int64_t drgnn_head_partial_elems(int32_t R, int32_t H, int32_t O);
 int64_t drgnn_head_num_slabs(int64_t n_graphs);
+/* Hidden units an INFERENCE drgnn_head_step of n_graphs keeps in LDS at a time: H when the head fits whole, fewer (a multiple
+ * of 16) when the launch goes over the hidden units in passes, 0 when no pass fits.  A training launch takes a head only whole. */
+int32_t drgnn_head_pass_units(int32_t R, int32_t H, int32_t O, int64_t n_graphs);
 int drgnn_head_step(const drgnn_head_desc* head, const float* readout, const void* target,
                     int64_t n_graphs, const int32_t* step, float* pred, float* grad_readout,
                     float* partials, void* stream);

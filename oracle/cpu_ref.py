@@ -379,13 +379,15 @@ def init_params(net, n_feat, n_out=1, n_edge_feat=1, seed=0):
 def loss_and_grads(net, params, data, target, task="reg", **fw):
     """One training-step worth of math on CPU: forward, loss (MSE for regression,
     cross-entropy for classification: reference NeuralNet.py:239-263), backward.
-    Returns (pred, loss, {name: grad}).  ``fw`` goes to the forward (``trace``, ``nudge``, ``looped``, ...)."""
+    Returns (pred, loss, {name: grad}).  ``fw`` goes to the forward (``trace``, ``nudge``, ``looped``, ...), except
+    ``class_weights`` ([n_out]): the ``weight`` of CrossEntropyLoss (NeuralNet.py:246-263)."""
+    class_weights = fw.pop("class_weights", None)
     leaves = {k: v.detach().clone().requires_grad_(True) for k, v in params.items()}
     pred = FORWARD[net](leaves, data, **fw)
     if task == "reg":
         loss = F.mse_loss(pred.reshape(-1), target)
     else:
-        loss = F.cross_entropy(pred, target)
+        loss = F.cross_entropy(pred, target, weight=None if class_weights is None else class_weights.to(pred.dtype))
     loss.backward()
     grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
     return pred.detach(), loss.detach(), grads

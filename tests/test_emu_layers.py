@@ -85,6 +85,20 @@ def test_conv_layer_any_width_forward_backward_vs_oracle(kind, width):
             np.testing.assert_allclose(p.grad.numpy(), q.grad.numpy(), rtol=1e-4, atol=1e-4)
 
 
+@pytest.mark.parametrize("kind", ["ginet", "sgat", "fout"])
+@pytest.mark.parametrize("n_feat,width", [(100, 128), (70, 96), (3, 1)])
+def test_conv_layer_wide_and_narrow_shapes_vs_oracle_elementwise(kind, n_feat, width):
+    """up to DRGNN_LAYER_MAXH outputs, more than 64 inputs, 1 / 64 / 65 / 130 nodes, an isolated node, directed duplicate edges"""
+    from layer_check import check_layers
+    check_layers(kind, n_feat, width, "cpu")
+
+
+@pytest.mark.parametrize("kind", ["ginet", "sgat", "fout"])
+def test_conv_layer_wider_than_128_is_refused(kind):
+    from layer_check import check_too_wide
+    check_too_wide(kind, "cpu")
+
+
 @pytest.mark.parametrize("fname", ["fix8_GINet.npz", "fix8_sGAT.npz"])
 def test_pooling_functions_vs_reference_golden(fname):
     g = golden(fname)

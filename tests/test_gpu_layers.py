@@ -40,6 +40,8 @@ def test_conv_layer_any_width_vs_oracle(kind, width):
               lay.bias.detach().clone().requires_grad_(True)]
         ref = cpu_ref.fout_conv(xr, ei, *rp, looped=False)
         live = [lay.Wc, lay.Wn, lay.bias]
+    from elementwise import assert_arbiter_rate, check, new_stats
+    from layer_check import _oracle
     lay = lay.to(DEV)
     live = list(lay.parameters()) if kind != "ginet" else [lay.fc.weight]
     out = lay(x, ei.to(DEV)) if kind == "fout" else lay(x, ei.to(DEV), ea.to(DEV))
@@ -50,6 +52,35 @@ def test_conv_layer_any_width_vs_oracle(kind, width):
     np.testing.assert_allclose(x.grad.cpu().numpy(), xr.grad.numpy(), rtol=1e-4, atol=1e-4)
     for p, q in zip(live, rp):
         np.testing.assert_allclose(p.grad.cpu().numpy(), q.grad.numpy(), rtol=1e-4, atol=2e-4)
+    # ... and the project's element-wise rule on top (tests/elementwise.py: 1e-4 + 1e-4 |ref| per element, no scaling by the
+    # tensor; the same oracle functions in float64 as arbiter for at most 0.1 % of the elements)
+    ref64 = []
+
+    def arbiter(i):
+        if not ref64:
+            ref64.extend(_oracle(kind, lay, batch.x, ei, ea, live, wgt, torch.float64))
+        return ref64[i]
+    stats = new_stats()
+    got = [out.detach().cpu().numpy(), x.grad.cpu().numpy()] + [p.grad.cpu().numpy() for p in live]
+    want = [ref.detach().numpy(), xr.grad.numpy()] + [q.grad.numpy() for q in rp]
+    for i in range(len(got)):
+        check("%s width %d tensor %d" % (kind, width, i), got[i], want[i], lambda i=i: arbiter(i), stats)
+    assert_arbiter_rate(stats, "%s width %d" % (kind, width))
+    print("LAYER %-8s F=10  H=%-3d 900 nodes elements=%-6d arbiter=%d" % (kind, width, stats["elements"], stats["arbiter"]))
+
+
+@pytest.mark.parametrize("kind", ["ginet", "sgat", "fout"])
+@pytest.mark.parametrize("n_feat,width", [(100, 128), (70, 96), (3, 1)])
+def test_conv_layer_wide_and_narrow_shapes_vs_oracle_elementwise(kind, n_feat, width):
+    """up to DRGNN_LAYER_MAXH outputs, more than 64 inputs, 1 / 64 / 65 / 130 nodes, an isolated node, directed duplicate edges"""
+    from layer_check import check_layers
+    check_layers(kind, n_feat, width, torch.device(DEV))
+
+
+@pytest.mark.parametrize("kind", ["ginet", "sgat", "fout"])
+def test_conv_layer_wider_than_128_is_refused(kind):
+    from layer_check import check_too_wide
+    check_too_wide(kind, torch.device(DEV))
 
 
 @pytest.mark.parametrize("fname", ["fix8_GINet.npz", "fix8_sGAT.npz"])
