@@ -64,7 +64,7 @@ class CohortMember(ctypes.Structure):
     _fields_ = EnsMember._fields_ + [
                 ("flat_param", _vp), ("flat_grad", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp),
                 ("step2", _vp), ("pred", _vp), ("readout", _vp), ("head_partials", _vp), ("partials", _vp), ("loss", _vp),
-                ("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
+                ("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
                 ("seed", ctypes.c_uint32), ("reserved", _c_i32)]
 
 
@@ -104,7 +104,7 @@ class EpochPlan(ctypes.Structure):
                 ("head_offset", _c_i64),
                 ("flat_param", _vp), ("flat_grad", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp), ("n_param", _c_i64),
                 ("step2", _vp),
-                ("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
+                ("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
                 ("cache", _vp), ("exchange", _vp), ("exchange_user", _vp), ("step_overrides", _vp), ("last_loss", _vp)]
 
 
@@ -211,7 +211,7 @@ class Api(object):
         lib.drgnn_train_update.argtypes = ([ctypes.POINTER(NetDesc), _vp, _c_i64] +
                                            [ctypes.POINTER(ConvGrads)] * 2 + [_vp, _c_i64] + [_c_i32] * 3 +
                                            [_c_i64] + [_vp] * 4 + [_c_i64] + [_vp] * 2 +
-                                           [ctypes.c_float] * 4 + [_c_i32, _vp])
+                                           [ctypes.c_double] * 4 + [_c_i32, _vp])
         lib.drgnn_net_step_lds_bytes.argtypes = [_c_i32] * 8
         lib.drgnn_net_step_lds_bytes.restype = _c_i64
         lib.drgnn_net_step_variant.argtypes = [_c_i32, _vp] + [_c_i32] * 6
@@ -241,7 +241,7 @@ class Api(object):
         lib.drgnn_step_update.argtypes = ([ctypes.POINTER(NetDesc), _vp, _c_i64] +
                                           [ctypes.POINTER(ConvGrads)] * 2 + [_vp, _vp] + [_c_i32] * 3 +
                                           [_c_i64] + [_vp] * 4 + [_c_i64] + [_vp] * 2 +
-                                          [ctypes.c_float] * 4 + [_c_i32, _c_i32, _vp])
+                                          [ctypes.c_double] * 4 + [_c_i32, _c_i32, _vp])
         lib.drgnn_net_step_xchg_elems.argtypes = [_c_i32] * 4
         lib.drgnn_net_step_xchg_elems.restype = _c_i64
         lib.drgnn_net_reduce_grads.argtypes = ([ctypes.POINTER(NetDesc), _vp, _c_i64, _c_i64] +
@@ -295,11 +295,11 @@ class Api(object):
         lib.drgnn_net_head_stage_bytes.restype = _c_i64
         lib.drgnn_head_step.argtypes = [ctypes.POINTER(HeadDesc), _vp, _vp, _c_i64] + [_vp] * 5
         lib.drgnn_head_reduce.argtypes = [_vp, _c_i64, _c_i32, _c_i32, _c_i32] + [_vp] * 4
-        lib.drgnn_adam_step.argtypes = [_vp] * 5 + [_c_i64] + [ctypes.c_float] * 5 + [_vp]
+        lib.drgnn_adam_step.argtypes = [_vp] * 5 + [_c_i64] + [ctypes.c_double] * 5 + [_vp]
         lib.drgnn_step_gradients.argtypes = ([ctypes.POINTER(NetDesc), _vp, _c_i64] + [ctypes.POINTER(ConvGrads)] * 2 +
                                              [_vp, _vp] + [_c_i32] * 3 + [_vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_c_i64), _c_i32,
                                                                        _vp, _c_i32, _vp])
-        if lib.drgnn_abi_version() != 4:
+        if lib.drgnn_abi_version() != 5:
             raise DrgnnError("ABI mismatch in %s" % path)
 
     # -- topology ---------------------------------------------------------------

@@ -121,7 +121,8 @@ class Cohort(MemberPack):
         return self.member_plan(self.api.cohort_step_plan, cache, ids, B)
 
     def _ensure(self, B):
-        """the members' outputs and slabs for mini-batches of up to ``B`` graphs, and the member table that names them"""
+        """the members' outputs and slabs for mini-batches of up to ``B`` graphs, and the member table that names them
+        (it caches each member's lr / betas / eps: changing a member's hyper-parameters after its first step is not supported)"""
         if B <= self._cap:
             return
         K, dev, api, nb = self.K, self.device, self.api, self.n_branch

@@ -1458,13 +1458,13 @@ int drgnn_head_reduce(const float* partials, int64_t n_graphs, int32_t R, int32_
 }
 
 int drgnn_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
-                    const int32_t* step, int64_t n, float lr, float beta1, float beta2, float eps,
-                    float weight_decay, void* stream_) {
+                    const int32_t* step, int64_t n, double lr, double beta1, double beta2, double eps,
+                    double weight_decay, void* stream_) {
     if (!param || !grad || !exp_avg || !exp_avg_sq || !step || n < 0) return DRGNN_E_ARG;
     if (n == 0) return 0;
     AdamArgs a;
     a.param = param; a.grad = grad; a.exp_avg = exp_avg; a.exp_avg_sq = exp_avg_sq; a.step = step; a.n = n;
-    a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay;
+    adam_set_hyper(a, lr, beta1, beta2, eps, weight_decay);
 #ifdef DRGNN_EMU
     for (int64_t i = 0; i < n; ++i) adam_item(a, i);
     (void)stream_;
@@ -1565,7 +1565,7 @@ static int update_impl(int32_t slabs_per_graph, const drgnn_net_desc* net, const
                        int64_t head_slabs, const float* readout, int32_t R, int32_t H, int32_t O,
                        int64_t head_offset, float* flat_param,
                        float* flat_grad, float* exp_avg, float* exp_avg_sq, int64_t n_param,
-                       int32_t* step, float* loss, float lr, float beta1, float beta2, float eps,
+                       int32_t* step, float* loss, double lr, double beta1, double beta2, double eps,
                        int32_t apply_adam, void* stream_, float* loss2 = nullptr,
                        const drgnn_cohort_member* coh_members = nullptr, int coh_K = 0, const int32_t* coh_counts = nullptr) {
     int rc = net_check(net);
@@ -1596,7 +1596,7 @@ static int update_impl(int32_t slabs_per_graph, const drgnn_net_desc* net, const
     u.loss2 = (loss || coh_members) ? loss2 : nullptr;
     u.ad.param = flat_param; u.ad.grad = flat_grad; u.ad.exp_avg = exp_avg; u.ad.exp_avg_sq = exp_avg_sq;
     u.ad.step = (readout && step) ? step + 1 : step; u.ad.n = n_param;
-    u.ad.lr = lr; u.ad.beta1 = beta1; u.ad.beta2 = beta2; u.ad.eps = eps; u.ad.weight_decay = 0.0f;
+    adam_set_hyper(u.ad, lr, beta1, beta2, eps, 0.0);
     u.apply_adam = apply_adam ? 1 : 0;
     const int64_t pitems = (int64_t)net->n_branch * r.n_partial;
     u.blocks_per_branch = (r.n_partial + 63) / 64;
@@ -1633,7 +1633,7 @@ int drgnn_train_update(const drgnn_net_desc* net, const float* conv_partials, in
                        int64_t head_slabs, int32_t R, int32_t H, int32_t O, int64_t head_offset,
                        float* flat_param,
                        float* flat_grad, float* exp_avg, float* exp_avg_sq, int64_t n_param,
-                       const int32_t* step, float* loss, float lr, float beta1, float beta2, float eps,
+                       const int32_t* step, float* loss, double lr, double beta1, double beta2, double eps,
                        int32_t apply_adam, void* stream_) {
     if (!head_partials) return DRGNN_E_ARG;
     return update_impl(0, net, conv_partials, n_graphs, g_conv1, g_conv2, head_partials, head_slabs, nullptr, R, H, O,
@@ -1645,7 +1645,7 @@ int drgnn_step_update(const drgnn_net_desc* net, const float* conv_partials, int
                       drgnn_conv_grads* g_conv1, drgnn_conv_grads* g_conv2, const float* head_partials,
                       const float* readout, int32_t R, int32_t H, int32_t O, int64_t head_offset,
                       float* flat_param, float* flat_grad, float* exp_avg, float* exp_avg_sq, int64_t n_param,
-                      int32_t* step2, float* loss, float lr, float beta1, float beta2, float eps,
+                      int32_t* step2, float* loss, double lr, double beta1, double beta2, double eps,
                       int32_t apply_adam, int32_t slabs_per_graph, void* stream_) {
     if (!head_partials || !readout || !step2) return DRGNN_E_ARG;
     return update_impl(slabs_per_graph, net, conv_partials, n_graphs, g_conv1, g_conv2, head_partials, n_graphs, readout, R, H, O,
@@ -2259,7 +2259,7 @@ static int epoch_update(const drgnn_epoch_plan* p, const EpochCarve& c, int64_t 
     if (rc || fused) return rc;
     if ((rc = p->exchange(p->exchange_user, k, B, stream))) return rc;
     return drgnn_adam_step(p->flat_param, p->flat_grad, p->exp_avg, p->exp_avg_sq, p->step2, p->n_param, p->lr, p->beta1,
-                           p->beta2, p->eps, 0.0f, stream);
+                           p->beta2, p->eps, 0.0, stream);
 }
 
 int drgnn_train_epoch(const drgnn_epoch_plan* p, void* scratch, int64_t scratch_bytes, float* pred, float* losses,

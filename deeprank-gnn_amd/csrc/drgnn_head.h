@@ -262,8 +262,17 @@ struct AdamArgs {
     float* param; const float* grad; float* exp_avg; float* exp_avg_sq;
     const int32_t* step;      // already counts this step (>= 1)
     int64_t n;
-    float lr, beta1, beta2, eps, weight_decay;
+    // The hyper-parameters arrive as the caller's doubles (torch keeps them as Python floats) and every fp32 scalar of
+    // the update is rounded ONCE from a double expression, as the scalars torch hands its kernels are: 1 - beta formed
+    // in fp32 from an fp32 beta is off by up to 2^-24 / (1 - beta), 1.3e-5 of the gradient term of v at beta2 = 0.999.
+    double lr, beta1, beta2;                             // adam_bias_scalars
+    float beta2f, omb1, omb2, eps, weight_decay;         // (float)beta2, (float)(1 - beta1), (float)(1 - beta2)
 };
+HD void adam_set_hyper(AdamArgs& a, double lr, double beta1, double beta2, double eps, double weight_decay) {
+    a.lr = lr; a.beta1 = beta1; a.beta2 = beta2;
+    a.beta2f = (float)beta2; a.omb1 = (float)(1.0 - beta1); a.omb2 = (float)(1.0 - beta2);
+    a.eps = (float)eps; a.weight_decay = (float)weight_decay;
+}
 
 // torch.optim.Adam (no amsgrad, maximize=False): identical operation order to the reference
 // implementation (_single_tensor_adam): denom = sqrt(v)/sqrt(bc2) + eps; p -= (lr/bc1) * m/denom
@@ -283,9 +292,9 @@ DEV void adam_bias_scalars(const AdamArgs& a, float& step_size, float& sqrt_bc2)
     // bias corrections in double, as the Python-side scalars of torch's reference path; beta^t by
     // repeated squaring (t is an integer): a libm pow() in double costs more than the rest of the launch
     const int t = a.step[0];
-    const double bc1 = 1.0 - adam_ipow((double)a.beta1, t);
-    const double bc2 = 1.0 - adam_ipow((double)a.beta2, t);
-    step_size = (float)((double)a.lr / bc1);
+    const double bc1 = 1.0 - adam_ipow(a.beta1, t);
+    const double bc2 = 1.0 - adam_ipow(a.beta2, t);
+    step_size = (float)(a.lr / bc1);
     sqrt_bc2 = (float)sqrt(bc2);
 }
 // the element's state only (k_update: another wave forms the scalars meanwhile and hands them over through LDS)
@@ -310,8 +319,8 @@ DEV void adam_apply(const AdamArgs& a, int64_t i, float g, const AdamPre& r) {
 #endif
     if (!r.ok) return;
     if (a.weight_decay != 0.0f) g = fmaf(a.weight_decay, r.p, g);
-    const float m = r.m + (g - r.m) * (1.0f - a.beta1);          // lerp
-    const float v = a.beta2 * r.v + (1.0f - a.beta2) * g * g;
+    const float m = r.m + (g - r.m) * a.omb1;          // lerp
+    const float v = a.beta2f * r.v + a.omb2 * g * g;
     a.exp_avg[i] = m;
     a.exp_avg_sq[i] = v;
     const float denom = sqrtf(v) / r.sqrt_bc2 + a.eps;

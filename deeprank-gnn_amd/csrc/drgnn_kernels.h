@@ -1115,7 +1115,7 @@ __global__ void __launch_bounds__(DRGNN_UPDATE_THREADS) k_update_cohort(UpdateAr
     u.readout = mm.readout; u.step2 = mm.step2; u.loss2 = u0.loss2 ? u0.loss2 + m : nullptr;      // (losses [K] of this step)
     u.ad.param = mm.flat_param; u.ad.grad = mm.flat_grad; u.ad.exp_avg = mm.exp_avg; u.ad.exp_avg_sq = mm.exp_avg_sq;
     u.ad.step = mm.step2 + 1;
-    u.ad.lr = mm.lr; u.ad.beta1 = mm.beta1; u.ad.beta2 = mm.beta2; u.ad.eps = mm.eps;
+    adam_set_hyper(u.ad, mm.lr, mm.beta1, mm.beta2, mm.eps, 0.0);
     update_block(u, u0.r, (int)blockIdx.x, (int64_t)(mm.flat_grad - wg_uniform_words(members[0].flat_grad)), quarter, bias_scalars);
 }
 // drgnn_step_gradients: k_update's fixed-order sums without the optimiser -- the gradient of the step's slabs, each slab

@@ -284,14 +284,18 @@ class FusedTrainer(object):
 
     def train_step_cached(self, cache, ids, ids_dev=None, apply_adam=True, next_ids_dev=None):
         """One optimisation step on the graphs ``ids`` of a cached set: the fused step launch reading the cached
-        topology in place + the update launch.  Same arithmetic as ``train_step`` on the collated mini-batch."""
+        topology in place + the update launch.  Same arithmetic as ``train_step`` on the collated mini-batch: with weight
+        decay the update launch only leaves the gradient and Adam is a launch of its own (``apply_update``), as there."""
         self._training_storage()
         c = self._cached_prepare(cache, ids, ids_dev, True, next_ids_dev)
         wrong = wrong_targets(self.task == _lib.TASK_REG, cache.set.y)
         if wrong:
             raise ValueError(wrong)
         self._cached_launch_step(c, True)
-        self._fused_launch_update(c, apply_adam)
+        decay = apply_adam and self.weight_decay != 0.0        # (the update launch's Adam knows no weight decay)
+        self._fused_launch_update(c, apply_adam and not decay)
+        if decay:
+            self.apply_update()
         self.last_pred = c["pred"]
         self.last_batch_size = c["B"]
         return self.loss

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DRGNN_ABI_VERSION 4
+#define DRGNN_ABI_VERSION 5
 
 /* host-side argument errors */
 #define DRGNN_E_ARG      (-1)   /* null pointer / negative size / bad mode            */
@@ -412,10 +412,11 @@ int drgnn_head_step(const drgnn_head_desc* head, const float* readout, const voi
 int drgnn_head_reduce(const float* partials, int64_t n_graphs, int32_t R, int32_t H, int32_t O,
                       float* grad_block, float* loss, int32_t* step, void* stream);
 /* torch.optim.Adam single-tensor semantics on flat fp32 buffers; *step must already count
- * this update (>= 1). */
+ * this update (>= 1).  The hyper-parameters are doubles, as torch keeps them: the bias corrections are formed
+ * from them in double, and 1 - beta1, 1 - beta2, lr / bc1 and sqrt(bc2) reach the fp32 arithmetic rounded once. */
 int drgnn_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
-                    const int32_t* step, int64_t n, float lr, float beta1, float beta2, float eps,
-                    float weight_decay, void* stream);
+                    const int32_t* step, int64_t n, double lr, double beta1, double beta2, double eps,
+                    double weight_decay, void* stream);
 
 /* Single-launch parameter update for one process: fixed-order reduction of the conv partials
  * (as drgnn_net_reduce_grads) and of the head partials (as drgnn_head_reduce, without
@@ -429,7 +430,7 @@ int drgnn_train_update(const drgnn_net_desc* net, const float* conv_partials, in
                        const float* head_partials, int64_t head_slabs /* rows of head_partials */,
                        int32_t R, int32_t H, int32_t O, int64_t head_offset, float* flat_param, float* flat_grad, float* exp_avg,
                        float* exp_avg_sq, int64_t n_param, const int32_t* step, float* loss,
-                       float lr, float beta1, float beta2, float eps, int32_t apply_adam, void* stream);
+                       double lr, double beta1, double beta2, double eps, int32_t apply_adam, void* stream);
 
 /* ---- fused training step --------------------------------------------------------------------
  * Body forward + FC head + loss + body backward of one mini-batch in ONE launch (every workgroup
@@ -559,7 +560,7 @@ int drgnn_step_update(const drgnn_net_desc* net, const float* conv_partials, int
                       drgnn_conv_grads* g_conv1, drgnn_conv_grads* g_conv2, const float* head_partials,
                       const float* readout, int32_t R, int32_t H, int32_t O, int64_t head_offset,
                       float* flat_param, float* flat_grad, float* exp_avg, float* exp_avg_sq, int64_t n_param,
-                      int32_t* step2, float* loss, float lr, float beta1, float beta2, float eps,
+                      int32_t* step2, float* loss, double lr, double beta1, double beta2, double eps,
                       int32_t apply_adam, int32_t slabs_per_graph, void* stream);
 
 /* The gradient half of drgnn_step_update alone, for a caller whose optimiser lives outside the library (the drop-in boundary:
@@ -734,7 +735,7 @@ typedef struct drgnn_cohort_member {
     int32_t* step2;                                              /* the member's own int32[4], as drgnn_net_train_step's */
     float* pred; float* readout; float* head_partials; float* partials;   /* outputs / slabs, sized for the largest mini-batch */
     float* loss;                                                 /* [1] the member's loss word */
-    float lr, beta1, beta2, eps;
+    double lr, beta1, beta2, eps;                                /* Adam, as for drgnn_adam_step */
     uint32_t seed; int32_t reserved;                             /* dropout stream seed */
 } drgnn_cohort_member;
 /* The plan of a cohort launch of K members over plan->n_graphs graphs each (training; otherwise as drgnn_ens_step_plan).
@@ -780,7 +781,7 @@ typedef struct drgnn_epoch_plan {
     int64_t head_offset;
     float* flat_param; float* flat_grad; float* exp_avg; float* exp_avg_sq; int64_t n_param;
     int32_t* step2;
-    float lr, beta1, beta2, eps;
+    double lr, beta1, beta2, eps;
     /* cached-topology mode (non-NULL): mini-batches are stepped straight out of the cache, the loop issues no
      * offset-table, builder or gather work; `set` is then only consulted for the graphs' sizes on the host */
     const drgnn_topology_cache* cache;

@@ -42,13 +42,15 @@ def schedule(n, K, T, B):
     return rows
 
 
-def single_trajectory(Net, sd, rs, batches, lr, seed, api, task="reg", class_weights=None, O=1, dropout=None):
+def single_trajectory(Net, sd, rs, batches, lr, seed, api, task="reg", class_weights=None, O=1, dropout=None,
+                      betas=(0.9, 0.999), eps=1e-8):
     """a FusedTrainer of its own over one member's mini-batches: (trainer, losses per step with None where it had none)"""
     net = Net(rs.n_feat, O, 1)
     net.load_state_dict(sd)
     if dropout is not None:
         net.dropout = dropout
-    tr = FusedTrainer(net.to(rs.device), lr=lr, task=task, class_weights=class_weights, seed=seed, api=api)
+    tr = FusedTrainer(net.to(rs.device), lr=lr, task=task, class_weights=class_weights, seed=seed, api=api, betas=betas,
+                      eps=eps)
     tr.plan_overrides = {"force_wgs": 1}
     cache = rs.topology_cache(need_weights=Net is sGAT)
     losses = []
@@ -127,6 +129,26 @@ def test_member_equals_single_trainer(name):
     assert int(coh.step2[K - 1, 0]) == T - 1 and int(coh.step2[0, 0]) == T
     assert coh.faults().tolist() == [0] * K
     coh.raise_on_faults()
+
+
+@pytest.mark.parametrize("name", ["GINet", "sGAT"])
+def test_member_hyper_parameters(name):
+    """non-default betas / eps and a learning rate per member: 3 steps of 4 graphs, every member bit-equal to a trainer of its
+    own with those hyper-parameters (itself pinned to float64 by test_adam.py)"""
+    Net = NETS[name]
+    graphs = fixture_graphs(NODE_FEATURES)
+    rs = ResidentGraphSet(graphs, "cpu", api=emu())
+    K, betas, eps = 3, (0.5, 0.9), 1e-3
+    sds = random_states(Net, rs.n_feat, K, seed=8)
+    lrs, seeds = [0.1, 0.01, 0.001], [21, 22, 23]
+    coh = Cohort(Net, sds, lr=lrs, seeds=seeds, device="cpu", api=emu(), betas=betas, eps=eps)
+    rows = schedule(len(graphs), K, 3, 4)
+    got = torch.stack([coh.train_step(rs, row).clone() for row in rows])
+    for m in range(K):
+        tr, losses = single_trajectory(Net, sds[m], rs, [row[m] for row in rows], lrs[m], seeds[m], emu(), betas=betas, eps=eps)
+        assert (tr.lr, tuple(tr.betas), tr.eps) == (lrs[m], betas, eps)
+        assert_member_equals(coh, m, tr, losses, got, words=True)
+    assert not torch.equal(coh.exp_avg_sq[0], torch.zeros_like(coh.exp_avg_sq[0]))
 
 
 def test_learning_rates_and_seeds():

@@ -51,13 +51,14 @@ def schedule(n, K, T, B, seed=3):
     return rows
 
 
-def single(Net, sd, rs, batches, lr, seed, task="reg", class_weights=None, O=1, dropout=None, overrides={"force_wgs": 1}):
+def single(Net, sd, rs, batches, lr, seed, task="reg", class_weights=None, O=1, dropout=None, overrides={"force_wgs": 1},
+           betas=(0.9, 0.999), eps=1e-8):
     """a FusedTrainer of its own over one member's mini-batches: (trainer, its loss per step, None where it had none)"""
     net = Net(rs.n_feat, O, 1)
     net.load_state_dict(sd)
     if dropout is not None:
         net.dropout = dropout
-    tr = FusedTrainer(net.to(DEV), lr=lr, task=task, class_weights=class_weights, seed=seed)
+    tr = FusedTrainer(net.to(DEV), lr=lr, task=task, class_weights=class_weights, seed=seed, betas=betas, eps=eps)
     tr.plan_overrides = dict(overrides)
     cache = rs.topology_cache(need_weights=Net is sGAT)
     losses = [tr.train_step_cached(cache, ids).clone() if len(ids) else None for ids in batches]
@@ -65,7 +66,8 @@ def single(Net, sd, rs, batches, lr, seed, task="reg", class_weights=None, O=1, 
     return tr, losses
 
 
-def check_cohort(Net, sds, graphs, rows, lrs=0.01, seeds=None, task="reg", class_weights=None, O=1, y=None):
+def check_cohort(Net, sds, graphs, rows, lrs=0.01, seeds=None, task="reg", class_weights=None, O=1, y=None,
+                 betas=(0.9, 0.999), eps=1e-8):
     """cohort steps over ``rows`` ([T][K] mini-batches) == per member a single trainer on that member's mini-batches"""
     K = len(sds)
     rs = ResidentGraphSet(graphs, DEV)
@@ -73,7 +75,7 @@ def check_cohort(Net, sds, graphs, rows, lrs=0.01, seeds=None, task="reg", class
         rs.set_targets(y)
     seeds = list(range(40, 40 + K)) if seeds is None else seeds
     lrs = [lrs] * K if not isinstance(lrs, list) else lrs
-    coh = Cohort(Net, sds, lr=lrs, seeds=seeds, task=task, class_weights=class_weights, device=DEV)
+    coh = Cohort(Net, sds, lr=lrs, seeds=seeds, task=task, class_weights=class_weights, device=DEV, betas=betas, eps=eps)
     cache = rs.topology_cache(need_weights=Net is sGAT)
     got = torch.stack([coh.train_step(cache, row).clone() for row in rows])
     assert coh.last_path == "fused", coh.last_reason
@@ -82,7 +84,8 @@ def check_cohort(Net, sds, graphs, rows, lrs=0.01, seeds=None, task="reg", class
     assert coh.faults().cpu().tolist() == [0] * K
     coh.raise_on_faults()
     for m in range(K):
-        tr, losses = single(Net, sds[m], rs, [row[m] for row in rows], lrs[m], seeds[m], task, class_weights, O)
+        tr, losses = single(Net, sds[m], rs, [row[m] for row in rows], lrs[m], seeds[m], task, class_weights, O,
+                            betas=betas, eps=eps)
         assert torch.equal(coh.params[m], tr.flat_p), (Net.__name__, m, "parameters")
         assert torch.equal(coh.exp_avg[m], tr.exp_avg) and torch.equal(coh.exp_avg_sq[m], tr.exp_avg_sq), (Net.__name__, m)
         assert torch.equal(coh.step2[m, :2], tr.step2[:2]), (Net.__name__, m, "step words")
@@ -109,6 +112,15 @@ def test_member_equals_single_trainer(name, width, K):
                           schedule(24, K, 6, 16))
     if K > 1:
         assert int(coh.step2[K - 1, 0]) == 5 and int(coh.step2[0, 0]) == 6
+
+
+@pytest.mark.parametrize("name", ["GINet", "sGAT"])
+def test_member_hyper_parameters(name):
+    """non-default betas / eps and a learning rate per member reach the member table: 3 steps of 4 graphs, every member
+    bit-equal to a trainer of its own with those hyper-parameters (itself pinned to float64 by test_gpu_adam.py)"""
+    coh, _ = check_cohort(NETS[name], states(NETS[name], 28, 3, seed=17), graphs_of(8, 28), schedule(8, 3, 3, 4),
+                          lrs=[0.1, 0.01, 0.001], betas=(0.5, 0.9), eps=1e-3)
+    assert not torch.equal(coh.exp_avg_sq[0], torch.zeros_like(coh.exp_avg_sq[0]))
 
 
 # 2 -------------------------------------------------------------------------------------------------------------------------
