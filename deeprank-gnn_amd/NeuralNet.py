@@ -151,7 +151,12 @@ class NeuralNet(object):
                  target='irmsd', lr=0.01, batch_size=32, percent=[1.0, 0.0], database_eval=None, index=None,
                  class_weights=None, task=None, classes=[0, 1], threshold=None, pretrained_model=None,
                  shuffle=True, outdir='./', cluster_nodes='mcl', transform_sigmoid=False, device=None,
-                 _api=None):
+                 _api=None, weight_decay=0.0, decoupled_weight_decay=False, max_grad_norm=None, lr_schedule=None):
+        """``weight_decay`` / ``decoupled_weight_decay`` / ``max_grad_norm``: FusedTrainer's (torch's AdamW param group and
+        ``clip_grad_norm_``); ``lr_schedule``: one learning rate PER EPOCH (the last one holds for every later epoch;
+        ``trainer.schedule_from_torch`` makes one from a torch scheduler), expanded to the trainer's per-step table with the
+        number of mini-batches per epoch (``batch_size`` is the global one under data parallel).  All four are stored in
+        the checkpoint when one of them is on; a checkpoint without them loads as the defaults."""
         self._api = _api
         hostcpu.fit_torch_threads()
         self.device = torch.device(device if device is not None else ('cuda' if torch.cuda.is_available() else 'cpu'))
@@ -172,6 +177,9 @@ class NeuralNet(object):
                     raise ValueError("User target detected -> The task argument is required ('class' or 'reg').")
             if self.threshold is None:
                 self.threshold = self.classes[1] if self.task == 'class' else 0.3
+            self.weight_decay, self.decoupled_weight_decay = float(weight_decay), bool(decoupled_weight_decay)
+            self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+            self.lr_schedule = None if lr_schedule is None else [float(v) for v in lr_schedule]
             opt_state = model_state = None
         else:
             # a list of checkpoints: an ensemble of them (inference only, ensemble.py); the settings are the first one's
@@ -185,6 +193,10 @@ class NeuralNet(object):
                              ('threshold', 'threshold'), ('shuffle', 'shuffle'), ('cluster_nodes', 'cluster_nodes'),
                              ('transform_sigmoid', 'transform_sigmoid')):
                 setattr(self, dst, state[src])
+            # (absent in checkpoints written before these settings existed, and in the reference's: the defaults)
+            self.weight_decay = float(state.get('weight_decay', 0.0))
+            self.decoupled_weight_decay = bool(state.get('decoupled_weight_decay', False))
+            self.max_grad_norm, self.lr_schedule = state.get('max_grad_norm'), state.get('lr_schedule')
             opt_state, model_state = state['optimizer'], state['model']
         self.pretrained = pretrained_model is not None
         ensemble_members = members if pretrained_model is not None else None
@@ -240,8 +252,11 @@ class NeuralNet(object):
             self.model = Net(first.num_features, n_out, len(self.edge_feature)).to(self.device)
             if model_state is not None:
                 self.model.load_state_dict(model_state)
+            # (a checkpoint's optimiser state carries the per-step table itself: load_optimizer_state_dict restores it)
             self.trainer = FusedTrainer(self.model, lr=self.lr, task=self.task, class_weights=weights, api=_api,
-                                        transform_sigmoid=bool(self.transform_sigmoid))
+                                        transform_sigmoid=bool(self.transform_sigmoid), weight_decay=self.weight_decay,
+                                        decoupled_weight_decay=self.decoupled_weight_decay, max_grad_norm=self.max_grad_norm,
+                                        lr_schedule=None if self.pretrained else self._step_schedule(len(self.train_index)))
             if opt_state is not None:
                 self.trainer.load_optimizer_state_dict(opt_state)
             # data parallel: the replicas start as ONE model -- rank 0's parameters, Adam moments and step counter -- whatever
@@ -785,6 +800,21 @@ class NeuralNet(object):
         self.exported.append(fname)
         return fname
 
+    def _step_schedule(self, n_graphs):
+        """``lr_schedule`` (per epoch) as the per-step table of a trainer whose epoch has ``n_graphs`` graphs"""
+        if not self.lr_schedule:
+            return None
+        per_epoch = max(1, (int(n_graphs) + int(self.batch_size) - 1) // int(self.batch_size))
+        return [lr for lr in self.lr_schedule for _ in range(per_epoch)]
+
+    def _optim_settings(self):
+        """the checkpoint entries of the optimiser options, present only when one is on: a default run's checkpoint keeps the
+        reference's schema key for key"""
+        if self.weight_decay == 0.0 and self.max_grad_norm is None and not self.lr_schedule:
+            return {}
+        return dict(weight_decay=self.weight_decay, decoupled_weight_decay=self.decoupled_weight_decay,
+                    max_grad_norm=self.max_grad_norm, lr_schedule=self.lr_schedule)
+
     def save_model(self, filename='model.pth.tar'):
         if getattr(self, "world", 1) > 1 and self.rank > 0:
             return                        # data parallel: the replicas are identical, rank 0 writes the checkpoint
@@ -794,7 +824,7 @@ class NeuralNet(object):
             node=self.node_feature, edge=self.edge_feature, target=self.target, task=self.task, classes=self.classes,
             class_weight=self.class_weights, batch_size=self.batch_size, percent=self.percent, lr=self.lr, index=self.index,
             shuffle=self.shuffle, threshold=self.threshold, cluster_nodes=self.cluster_nodes,
-            transform_sigmoid=self.transform_sigmoid)
+            transform_sigmoid=self.transform_sigmoid, **self._optim_settings())
         torch.save(state, filename)
 
     def cross_validate(self, k=10, nepoch=1, validate=True, save_model=None, seed=0, threshold=4.0):
@@ -819,7 +849,9 @@ class NeuralNet(object):
         train_sets = [np.setdiff1d(np.arange(n, dtype=np.int64), f) for f in folds]
         coh = Cohort(type(self.model), int(k), n_feat=rs.n_feat, n_out=self.trainer.O, lr=self.lr, task=self.task,
                      class_weights=self.trainer.class_w, transform_sigmoid=bool(self.transform_sigmoid), device=self.device,
-                     api=self._api, edge_dim=len(self.edge_feature))
+                     api=self._api, edge_dim=len(self.edge_feature), weight_decay=self.weight_decay,
+                     decoupled_weight_decay=self.decoupled_weight_decay, max_grad_norm=self.max_grad_norm,
+                     lr_schedule=None if not self.lr_schedule else [self._step_schedule(len(t)) for t in train_sets])
         if hasattr(self.model, "dropout"):
             for net in coh.nets:
                 net.dropout = self.model.dropout
@@ -855,7 +887,8 @@ class NeuralNet(object):
             out['paths'] = coh.save(paths, node=self.node_feature, edge=self.edge_feature, target=self.target,
                                     classes=self.classes, class_weight=self.class_weights, batch_size=self.batch_size,
                                     percent=self.percent, index=self.index, shuffle=self.shuffle, threshold=self.threshold,
-                                    cluster_nodes=self.cluster_nodes, transform_sigmoid=self.transform_sigmoid)
+                                    cluster_nodes=self.cluster_nodes, transform_sigmoid=self.transform_sigmoid,
+                                    **self._optim_settings())
         return out
 
     def _fold_loss(self, pred, y):

@@ -108,6 +108,17 @@ class EpochPlan(ctypes.Structure):
                 ("cache", _vp), ("exchange", _vp), ("exchange_user", _vp), ("step_overrides", _vp), ("last_loss", _vp)]
 
 
+class Optim(ctypes.Structure):
+    """drgnn_optim (include/drgnn.h): Adam's scalars and the options of the ``_opt`` entry points (AdamW, clipping,
+    learning-rate table); pointer members are device addresses."""
+    _fields_ = [("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+                ("weight_decay", ctypes.c_double), ("max_grad_norm", ctypes.c_double),
+                ("lr_table", _vp), ("norm_words", _vp), ("norm_out", _vp),
+                ("lr_n", _c_i32), ("decoupled", _c_i32), ("clip", _c_i32), ("norm_cap", _c_i32),
+                ("n_dead", _c_i32), ("reserved", _c_i32),
+                ("dead_off", _c_i64 * 8), ("dead_len", _c_i64 * 8)]
+
+
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p)
 
 
@@ -299,6 +310,20 @@ class Api(object):
         lib.drgnn_step_gradients.argtypes = ([ctypes.POINTER(NetDesc), _vp, _c_i64] + [ctypes.POINTER(ConvGrads)] * 2 +
                                              [_vp, _vp] + [_c_i32] * 3 + [_vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_c_i64), _c_i32,
                                                                        _vp, _c_i32, _vp])
+        lib.drgnn_optim_norm_words.argtypes = [_c_i64]
+        lib.drgnn_optim_norm_words.restype = _c_i64
+        lib.drgnn_adam_step_opt.argtypes = [_vp] * 5 + [_c_i64, ctypes.POINTER(Optim), _vp]
+        lib.drgnn_train_update_opt.argtypes = ([ctypes.POINTER(NetDesc), _vp, _c_i64] +
+                                               [ctypes.POINTER(ConvGrads)] * 2 + [_vp, _c_i64] + [_c_i32] * 3 +
+                                               [_c_i64] + [_vp] * 4 + [_c_i64] + [_vp] * 2 +
+                                               [ctypes.POINTER(Optim), _c_i32, _vp])
+        lib.drgnn_step_update_opt.argtypes = ([ctypes.POINTER(NetDesc), _vp, _c_i64] +
+                                              [ctypes.POINTER(ConvGrads)] * 2 + [_vp, _vp] + [_c_i32] * 3 +
+                                              [_c_i64] + [_vp] * 4 + [_c_i64] + [_vp] * 2 +
+                                              [ctypes.POINTER(Optim), _c_i32, _c_i32, _vp])
+        lib.drgnn_cohort_update_opt.argtypes = ([ctypes.POINTER(NetDesc), _vp, _vp, _c_i32, _vp] + [ctypes.POINTER(ConvGrads)] * 2 +
+                                                [_c_i32] * 3 + [_c_i64, _c_i64, _vp, _c_i32, _c_i32, _vp])
+        lib.drgnn_train_epoch_opt.argtypes = [ctypes.POINTER(EpochPlan), ctypes.POINTER(Optim), _vp, _c_i64, _vp, _vp, _vp]
         if lib.drgnn_abi_version() != 5:
             raise DrgnnError("ABI mismatch in %s" % path)
 
@@ -368,6 +393,15 @@ class Api(object):
             ctypes.byref(desc), _ptr(x), _ptr(grad_readout), _ptr(ws_i32), _ptr(ws_f32), n_nodes,
             n_edges, n_graphs, max_nodes, max_edges, max_c0, _ptr(xp), _ptr(arg0), _ptr(arg1),
             _ptr(grad_x), _ptr(partials), _ptr(scratch), _ptr(step_inc), stream), "drgnn_net_backward")
+
+    def train_update_opt(self, desc, conv_partials, n_graphs, g1, g2, head_partials, R, H, O, head_offset,
+                         flat_p, flat_g, exp_avg, exp_avg_sq, step, loss, optim, stream, apply_adam=True):
+        """drgnn_train_update under the options of ``optim`` (an Optim record)"""
+        _check(self.lib.drgnn_train_update_opt(
+            ctypes.byref(desc), _ptr(conv_partials), n_graphs, g1, g2, _ptr(head_partials),
+            head_partials.shape[0], R, H, O, head_offset, _ptr(flat_p), _ptr(flat_g), _ptr(exp_avg),
+            _ptr(exp_avg_sq), flat_p.numel(), _ptr(step), _ptr(loss), ctypes.byref(optim),
+            1 if apply_adam else 0, stream), "drgnn_train_update_opt")
 
     def train_update(self, desc, conv_partials, n_graphs, g1, g2, head_partials, R, H, O, head_offset,
                      flat_p, flat_g, exp_avg, exp_avg_sq, step, loss, lr, beta1, beta2, eps, stream,
@@ -462,6 +496,13 @@ class Api(object):
         _check(self.lib.drgnn_cohort_update(ctypes.byref(desc), _ptr(members), int(K), counts, g1, g2, R, H, O, int(head_offset),
                                             int(n_param), losses, 1 if apply_adam else 0, stream), "drgnn_cohort_update")
 
+    def cohort_update_opt(self, desc, members, optims, K, counts, g1, g2, R, H, O, head_offset, n_param, stream, losses=None,
+                          apply_adam=True, any_clip=False):
+        """drgnn_cohort_update with ``optims``, the device table of the members' Optim records"""
+        _check(self.lib.drgnn_cohort_update_opt(ctypes.byref(desc), _ptr(members), _ptr(optims), int(K), counts, g1, g2, R, H, O,
+                                                int(head_offset), int(n_param), losses, 1 if apply_adam else 0,
+                                                1 if any_clip else 0, stream), "drgnn_cohort_update_opt")
+
     def step_update(self, desc, conv_partials, n_graphs, g1, g2, head_partials, readout, R, H, O, head_offset,
                     flat_p, flat_g, exp_avg, exp_avg_sq, step2, loss, lr, beta1, beta2, eps, stream,
                     apply_adam=True, slabs_per_graph=0):
@@ -470,6 +511,15 @@ class Api(object):
             R, H, O, head_offset, _ptr(flat_p), _ptr(flat_g), _ptr(exp_avg), _ptr(exp_avg_sq), flat_p.numel(),
             _ptr(step2), _ptr(loss), lr, beta1, beta2, eps, 1 if apply_adam else 0, int(slabs_per_graph), stream),
             "drgnn_step_update")
+
+    def step_update_opt(self, desc, conv_partials, n_graphs, g1, g2, head_partials, readout, R, H, O, head_offset,
+                        flat_p, flat_g, exp_avg, exp_avg_sq, step2, loss, optim, stream, apply_adam=True, slabs_per_graph=0):
+        """drgnn_step_update under the options of ``optim`` (an Optim record)"""
+        _check(self.lib.drgnn_step_update_opt(
+            ctypes.byref(desc), _ptr(conv_partials), n_graphs, g1, g2, _ptr(head_partials), _ptr(readout),
+            R, H, O, head_offset, _ptr(flat_p), _ptr(flat_g), _ptr(exp_avg), _ptr(exp_avg_sq), flat_p.numel(),
+            _ptr(step2), _ptr(loss), ctypes.byref(optim), 1 if apply_adam else 0, int(slabs_per_graph), stream),
+            "drgnn_step_update_opt")
 
     def step_gradients(self, desc, conv_partials, n_graphs, g1, g2, head_partials, readout, R, H, O, head_grad,
                        graph_weight, zero_ptr, zero_len, n_zero, step2, slabs_per_graph, stream):
@@ -615,6 +665,11 @@ class Api(object):
         _check(self.lib.drgnn_train_epoch(ctypes.byref(plan), _ptr(scratch), scratch.numel() * scratch.element_size(),
                                           _ptr(pred), _ptr(losses), stream), "drgnn_train_epoch")
 
+    def train_epoch_opt(self, plan, optim, scratch, pred, losses, stream):
+        _check(self.lib.drgnn_train_epoch_opt(ctypes.byref(plan), ctypes.byref(optim), _ptr(scratch),
+                                              scratch.numel() * scratch.element_size(), _ptr(pred), _ptr(losses), stream),
+               "drgnn_train_epoch_opt")
+
     # -- head / loss / optimiser ------------------------------------------------
     def head_partial_elems(self, R, H, O):
         return int(self.lib.drgnn_head_partial_elems(R, H, O))
@@ -644,6 +699,15 @@ class Api(object):
         _check(self.lib.drgnn_adam_step(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq),
                                         _ptr(step), param.numel(), lr, beta1, beta2, eps, weight_decay,
                                         stream), "drgnn_adam_step")
+
+
+    def optim_norm_words(self, n_param):
+        """doubles of ``Optim.norm_words`` scratch a clipping step over ``n_param`` parameters needs"""
+        return int(self.lib.drgnn_optim_norm_words(int(n_param)))
+
+    def adam_step_opt(self, param, grad, exp_avg, exp_avg_sq, step, optim, stream):
+        _check(self.lib.drgnn_adam_step_opt(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(step),
+                                            param.numel(), ctypes.byref(optim), stream), "drgnn_adam_step_opt")
 
 
 _API = None

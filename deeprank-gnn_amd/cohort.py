@@ -15,6 +15,8 @@ Adam moments); the member table (drgnn_cohort_member[K]) is written to the devic
 answered NONE -- the host emulation, a graph beyond the fused kernels, no cached topology: each member runs its own step, one
 after the other, with the same results).
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -46,13 +48,27 @@ def _per_member(value, K, what, cast):
     return [cast(value)] * K
 
 
+def _per_member_tables(value, K):
+    """``lr_schedule``: None, one table for all members, or K tables ([K, n]; an entry may be None)"""
+    if value is None:
+        return [None] * K
+    if len(value) and isinstance(value[0], (list, tuple, np.ndarray, type(None))):
+        if len(value) != K:
+            raise ValueError("Cohort: lr_schedule has %d tables for %d members" % (len(value), K))
+        return [None if t is None else [float(v) for v in t] for t in value]
+    return [[float(v) for v in value]] * K
+
+
 class Cohort(MemberPack):
     """K members of the net class ``Net``: ``members`` is K (fresh nets ``Net(n_feat, n_out, edge_dim)``) or a list of
     checkpoint paths / checkpoint dictionaries / state dicts to start from.  ``lr`` and ``seeds`` (dropout streams) are
-    scalars or length-K lists; ``seeds=None`` gives every member a stream of its own."""
+    scalars or length-K lists; ``seeds=None`` gives every member a stream of its own.  ``weight_decay`` and
+    ``max_grad_norm`` (None: off) likewise, ``lr_schedule`` one table or K of them; ``decoupled_weight_decay`` is the
+    cohort's (FusedTrainer's options: they run inside the two cohort launches, a clipping member's Adam step in a third)."""
 
     def __init__(self, Net, members, n_feat=None, n_out=1, lr=0.01, task="reg", seeds=None, class_weights=None,
-                 transform_sigmoid=False, device=None, api=None, edge_dim=1, betas=(0.9, 0.999), eps=1e-8):
+                 transform_sigmoid=False, device=None, api=None, edge_dim=1, betas=(0.9, 0.999), eps=1e-8,
+                 weight_decay=0.0, decoupled_weight_decay=False, max_grad_norm=None, lr_schedule=None):
         if isinstance(members, (int, np.integer)):
             if members < 1 or n_feat is None:
                 raise ValueError("Cohort: K >= 1 fresh members need n_feat")
@@ -66,10 +82,20 @@ class Cohort(MemberPack):
         if seeds is None:
             seeds = [(torch.initial_seed() + m * 0x9E3779B1) & 0xFFFFFFFF for m in range(K)]
         self.seeds = _per_member(seeds, K, "seeds", lambda v: int(v) & 0xFFFFFFFF)
+        self.weight_decay = _per_member(weight_decay, K, "weight_decay", float)
+        self.max_grad_norm = _per_member(max_grad_norm, K, "max_grad_norm", lambda v: None if v is None else float(v))
+        self.lr_schedule = _per_member_tables(lr_schedule, K)
         MemberPack.__init__(self, Net, K, n_feat, n_out, device, edge_dim, states=states, training=True,
-                            per_member=[{"lr": self.lr[m], "seed": self.seeds[m]} for m in range(K)], task=task,
+                            per_member=[{"lr": self.lr[m], "seed": self.seeds[m], "weight_decay": self.weight_decay[m],
+                                         "max_grad_norm": self.max_grad_norm[m], "lr_schedule": self.lr_schedule[m]}
+                                        for m in range(K)], task=task,
                             class_weights=class_weights, betas=betas, eps=eps, api=api,
-                            transform_sigmoid=self.transform_sigmoid)
+                            transform_sigmoid=self.transform_sigmoid, decoupled_weight_decay=decoupled_weight_decay)
+        # [K] the members' gradient norms before clipping (each trainer's grad_norm word is its entry)
+        self.grad_norm = torch.zeros(K, dtype=torch.float32, device=self.device)
+        for m, tr in enumerate(self.trainers):
+            tr._grad_norm = self.grad_norm[m:m + 1]
+        self._optims, self._any_clip = None, False
         for tr in self.trainers:
             # the one-workgroup-per-graph layout, as the cohort launch: a member stepped on its own (the separate path)
             # gives the bits the cohort launch gives
@@ -141,6 +167,14 @@ class Cohort(MemberPack):
             t.lr, t.beta1, t.beta2, t.eps, t.seed = tr.lr, tr.betas[0], tr.betas[1], tr.eps, tr.seed
         self._table = device_table(table, dev)
         self._bufs, self._cap = (pred, readout, partials, hp), B
+        # the members' option records (drgnn_optim[K]) next to it, when any member has an option on
+        self._optims = None
+        if any(tr._optim() is not None for tr in self.trainers):
+            records = (_lib.Optim * K)()
+            for m, tr in enumerate(self.trainers):
+                ctypes.memmove(ctypes.addressof(records[m]), ctypes.addressof(tr._optim(always=True)), ctypes.sizeof(_lib.Optim))
+            self._optims = device_table(records, dev)
+            self._any_clip = any(tr.max_grad_norm is not None for tr in self.trainers)
 
     def _tables(self, rs, batches):
         """``batches``: [steps][K] lists of graph numbers -> (ids [steps, K, B] int32, counts [steps, K] int32) on the
@@ -174,6 +208,11 @@ class Cohort(MemberPack):
         api = self.api
         api.cohort_train_step_cached(self._desc0, head, self._table, self.K, desc, ids_ptr, counts_ptr, B, B,
                                      bounds[0], bounds[1], bounds[2], stream, hints)
+        if self._optims is not None:
+            api.cohort_update_opt(self._desc0, self._table, self._optims, self.K, counts_ptr, self._g1, self._g2, self.R,
+                                  self.H, self.O, self.head_offset, self.n_param, stream, losses=losses_ptr,
+                                  any_clip=self._any_clip)
+            return
         api.cohort_update(self._desc0, self._table, self.K, counts_ptr, self._g1, self._g2, self.R, self.H, self.O,
                           self.head_offset, self.n_param, stream, losses=losses_ptr)
 
@@ -244,6 +283,8 @@ class Cohort(MemberPack):
             cached = self._cached_ok(rs)
         if not cached:
             return None, "no cached topology", None
+        if any(tr._coupled() for tr in self.trainers):
+            return None, "coupled L2 weight decay (the flat Adam launch alone knows it)", rs.topology_cache(need_weights=self.kind == _lib.SGAT)
         cache = rs.topology_cache(need_weights=self.kind == _lib.SGAT)
         dev_ids, dev_counts, B, ids, counts = self._tables(rs, batches)
         used = np.unique(ids[np.arange(B)[None, None, :] < counts[:, :, None]])

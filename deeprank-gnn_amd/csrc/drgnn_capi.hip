@@ -1477,6 +1477,73 @@ int drgnn_adam_step(float* param, const float* grad, float* exp_avg, float* exp_
 
 }  // extern "C"
 
+// ---- the options of drgnn_optim ------------------------------------------------------------------------------------
+static int optim_check(const drgnn_optim* o) {
+    if (!o) return DRGNN_E_ARG;
+    if (o->lr_n < 0 || (o->lr_n > 0 && !o->lr_table)) return DRGNN_E_ARG;
+    if (o->n_dead < 0 || o->n_dead > DRGNN_ZERO_RANGES) return DRGNN_E_ARG;
+    for (int r = 0; r < o->n_dead; ++r) if (o->dead_off[r] < 0 || o->dead_len[r] < 0) return DRGNN_E_ARG;
+    if (o->clip && (!o->norm_words || o->norm_cap < 1)) return DRGNN_E_ARG;
+    return 0;
+}
+// coupled L2 is the flat kernel's alone (drgnn_adam_step): the update launches then only leave the gradient
+static bool optim_coupled(const drgnn_optim* o) { return !o->decoupled && o->weight_decay != 0.0; }
+static void optim_adam_args(AdamArgs& a, const drgnn_optim* o) {
+    adam_set_hyper(a, o->lr, o->beta1, o->beta2, o->eps, optim_coupled(o) ? o->weight_decay : 0.0);
+}
+// the Adam launch of the flat route; n_words > 0: norm_words[0, n_words) already hold the per-block sums of this gradient
+static int adam_opt_impl(AdamArgs a, float* grad, const drgnn_optim* o, int n_words, void* stream_) {
+    if (a.n == 0) return 0;
+    const int64_t flat_words = (a.n + 255) / 256;
+    if (o->clip && n_words == 0 && flat_words > o->norm_cap) return DRGNN_E_CAPACITY;
+#ifdef DRGNN_EMU
+    AdamOptScalars sc;
+    adam_bias_scalars<true>(a, sc.step_size, sc.sqrt_bc2, o, &sc.decay);
+    sc.clip = 1.0f;
+    if (o->clip) {
+        if (n_words == 0) {
+            for (int64_t w = 0; w < flat_words; ++w) o->norm_words[w] = adam_norm_word(*o, grad, a.n, w * 256);
+            n_words = (int)flat_words;
+        }
+        double norm;
+        sc.clip = adam_clip_scale(*o, n_words, &norm);
+        if (o->norm_out) o->norm_out[0] = (float)norm;
+    }
+    for (int64_t i = 0; i < a.n; ++i) adam_opt_item(a, *o, grad, i, sc);
+    (void)stream_;
+#else
+    if (o->clip && n_words == 0) {
+        hipLaunchKernelGGL(k_grad_norm_words, dim3((unsigned)flat_words), dim3(256), 0, (hipStream_t)stream_, grad, a.n, *o);
+        HIP_TRY(hipGetLastError());
+        n_words = (int)flat_words;
+    }
+    hipLaunchKernelGGL(k_adam_opt, dim3((unsigned)flat_words), dim3(256), 0, (hipStream_t)stream_, a, *o, grad, n_words);
+    HIP_TRY(hipGetLastError());
+#endif
+    return 0;
+}
+
+extern "C" {
+
+int64_t drgnn_optim_norm_words(int64_t n_param) {
+    // update blocks: 64 gradient elements each, a branch's and the head's last block partly filled, slots of the conv partials
+    // that are no parameter (at most as many again); flat route: one word per 256 elements
+    return n_param < 0 ? (int64_t)DRGNN_E_ARG : n_param / 16 + 64;
+}
+
+int drgnn_adam_step_opt(float* param, float* grad, float* exp_avg, float* exp_avg_sq, const int32_t* step, int64_t n,
+                        const drgnn_optim* optim, void* stream_) {
+    if (!param || !grad || !exp_avg || !exp_avg_sq || !step || n < 0) return DRGNN_E_ARG;
+    const int rc = optim_check(optim);
+    if (rc) return rc;
+    AdamArgs a;
+    a.param = param; a.grad = grad; a.exp_avg = exp_avg; a.exp_avg_sq = exp_avg_sq; a.step = step; a.n = n;
+    optim_adam_args(a, optim);
+    return adam_opt_impl(a, grad, optim, 0, stream_);
+}
+
+}  // extern "C"
+
 extern "C" {
 
 int64_t drgnn_p2p_bytes(int64_t n_floats) { return n_floats < 0 ? (int64_t)DRGNN_E_ARG : p2p_bytes(n_floats); }
@@ -1567,9 +1634,11 @@ static int update_impl(int32_t slabs_per_graph, const drgnn_net_desc* net, const
                        float* flat_grad, float* exp_avg, float* exp_avg_sq, int64_t n_param,
                        int32_t* step, float* loss, double lr, double beta1, double beta2, double eps,
                        int32_t apply_adam, void* stream_, float* loss2 = nullptr,
-                       const drgnn_cohort_member* coh_members = nullptr, int coh_K = 0, const int32_t* coh_counts = nullptr) {
+                       const drgnn_cohort_member* coh_members = nullptr, int coh_K = 0, const int32_t* coh_counts = nullptr,
+                       const drgnn_optim* opt = nullptr, const drgnn_optim* coh_optims = nullptr, int coh_clip = 0) {
     int rc = net_check(net);
     if (rc) return rc;
+    if (opt && (coh_members || (rc = optim_check(opt)))) return rc ? rc : DRGNN_E_ARG;
     // (a cohort launch, drgnn_cohort_update: sources, flat buffers, step words and Adam's scalars come from the member table)
     if (!coh_members && (!conv_partials || !head_partials || !flat_grad)) return DRGNN_E_ARG;
     if (!g_conv1 || !g_conv2) return DRGNN_E_ARG;
@@ -1598,6 +1667,14 @@ static int update_impl(int32_t slabs_per_graph, const drgnn_net_desc* net, const
     u.ad.step = (readout && step) ? step + 1 : step; u.ad.n = n_param;
     adam_set_hyper(u.ad, lr, beta1, beta2, eps, 0.0);
     u.apply_adam = apply_adam ? 1 : 0;
+    // the options: AdamW / the learning-rate table inside this launch; a clipping step (and coupled L2) as the sums launch,
+    // Adam off, + the flat Adam launch.  Without Adam (data parallel) the launch is today's.
+    const bool opt_flat = opt && apply_adam && (opt->clip || optim_coupled(opt));
+    if (opt) {
+        optim_adam_args(u.ad, opt);
+        if (opt_flat) u.apply_adam = 0;
+        if (!apply_adam) opt = nullptr;
+    }
     const int64_t pitems = (int64_t)net->n_branch * r.n_partial;
     u.blocks_per_branch = (r.n_partial + 63) / 64;
     u.conv_blocks = net->n_branch * u.blocks_per_branch;
@@ -1606,6 +1683,7 @@ static int update_impl(int32_t slabs_per_graph, const drgnn_net_desc* net, const
     const int head_blocks = (head_items + 63) / 64;
 #ifdef DRGNN_EMU
     if (coh_members) return DRGNN_E_CAPACITY;
+    if (opt) u.apply_adam = 0;           // (host loop: the sums here, then the flat loop with the options)
     for (int64_t i = 0; i < pitems; ++i) {
         const int br = (int)(i / r.n_partial), p = (int)(i % r.n_partial);
         if (!reduce_live(r, p)) continue;
@@ -1615,7 +1693,32 @@ static int update_impl(int32_t slabs_per_graph, const drgnn_net_desc* net, const
     for (int i = 0; i < head_items; ++i) update_head_store(u, i, update_head_sum(u, i, 0, 1));
     if (u.step2) u.step2[0] = u.step2[1];
     (void)stream_; (void)head_blocks;
+    if (opt) return adam_opt_impl(u.ad, flat_grad, opt, 0, stream_);
 #else
+    if (opt) {
+        const int n_blocks = u.conv_blocks + head_blocks;
+        const bool words = opt->clip && !optim_coupled(opt);     // (coupled L2: the flat route's own words)
+        if (words && n_blocks > opt->norm_cap) return DRGNN_E_CAPACITY;
+        hipLaunchKernelGGL(k_update_opt, dim3((unsigned)n_blocks), dim3(DRGNN_UPDATE_THREADS), 0, (hipStream_t)stream_, u, *opt,
+                           words ? opt->norm_words : (double*)nullptr);
+        HIP_TRY(hipGetLastError());
+        return opt_flat ? adam_opt_impl(u.ad, flat_grad, opt, words ? n_blocks : 0, stream_) : 0;
+    }
+    if (coh_members && coh_optims) {
+        // (the records live in device memory: their norm_cap is the caller's promise, drgnn_optim_norm_words, checked here
+        // against this launch's blocks and guarded in the kernel)
+        const int n_blocks = u.conv_blocks + head_blocks;
+        if (coh_clip && n_blocks > drgnn_optim_norm_words(n_param)) return DRGNN_E_CAPACITY;
+        hipLaunchKernelGGL(k_update_cohort_opt, dim3((unsigned)n_blocks, (unsigned)coh_K), dim3(DRGNN_UPDATE_THREADS), 0,
+                           (hipStream_t)stream_, u, coh_members, coh_optims, coh_counts, head_offset);
+        HIP_TRY(hipGetLastError());
+        if (coh_clip && apply_adam) {
+            hipLaunchKernelGGL(k_adam_cohort_opt, dim3((unsigned)((n_param + 255) / 256), (unsigned)coh_K), dim3(256), 0,
+                               (hipStream_t)stream_, coh_members, coh_optims, coh_counts, n_param, n_blocks);
+            HIP_TRY(hipGetLastError());
+        }
+        return 0;
+    }
     if (coh_members)
         hipLaunchKernelGGL(k_update_cohort, dim3((unsigned)(u.conv_blocks + head_blocks), (unsigned)coh_K), dim3(DRGNN_UPDATE_THREADS), 0,
                            (hipStream_t)stream_, u, coh_members, coh_counts, head_offset);
@@ -1653,6 +1756,29 @@ int drgnn_step_update(const drgnn_net_desc* net, const float* conv_partials, int
                        beta2, eps, apply_adam, stream_);
 }
 
+int drgnn_train_update_opt(const drgnn_net_desc* net, const float* conv_partials, int64_t n_graphs,
+                           drgnn_conv_grads* g_conv1, drgnn_conv_grads* g_conv2, const float* head_partials,
+                           int64_t head_slabs, int32_t R, int32_t H, int32_t O, int64_t head_offset, float* flat_param,
+                           float* flat_grad, float* exp_avg, float* exp_avg_sq, int64_t n_param, const int32_t* step, float* loss,
+                           const drgnn_optim* optim, int32_t apply_adam, void* stream_) {
+    if (!head_partials || !optim) return DRGNN_E_ARG;
+    return update_impl(0, net, conv_partials, n_graphs, g_conv1, g_conv2, head_partials, head_slabs, nullptr, R, H, O,
+                       head_offset, flat_param, flat_grad, exp_avg, exp_avg_sq, n_param, const_cast<int32_t*>(step), loss,
+                       optim->lr, optim->beta1, optim->beta2, optim->eps, apply_adam, stream_, nullptr, nullptr, 0, nullptr, optim);
+}
+
+int drgnn_step_update_opt(const drgnn_net_desc* net, const float* conv_partials, int64_t n_graphs,
+                          drgnn_conv_grads* g_conv1, drgnn_conv_grads* g_conv2, const float* head_partials,
+                          const float* readout, int32_t R, int32_t H, int32_t O, int64_t head_offset,
+                          float* flat_param, float* flat_grad, float* exp_avg, float* exp_avg_sq, int64_t n_param,
+                          int32_t* step2, float* loss, const drgnn_optim* optim, int32_t apply_adam, int32_t slabs_per_graph,
+                          void* stream_) {
+    if (!head_partials || !readout || !step2 || !optim) return DRGNN_E_ARG;
+    return update_impl(slabs_per_graph, net, conv_partials, n_graphs, g_conv1, g_conv2, head_partials, n_graphs, readout, R, H, O,
+                       head_offset, flat_param, flat_grad, exp_avg, exp_avg_sq, n_param, step2, loss, optim->lr, optim->beta1,
+                       optim->beta2, optim->eps, apply_adam, stream_, nullptr, nullptr, 0, nullptr, optim);
+}
+
 int drgnn_cohort_update(const drgnn_net_desc* net, const drgnn_cohort_member* members, int32_t K, const int32_t* counts,
                         drgnn_conv_grads* g_conv1, drgnn_conv_grads* g_conv2, int32_t R, int32_t H, int32_t O,
                         int64_t head_offset, int64_t n_param, float* losses, int32_t apply_adam, void* stream_) {
@@ -1664,6 +1790,20 @@ int drgnn_cohort_update(const drgnn_net_desc* net, const drgnn_cohort_member* me
     return update_impl(0, net, nullptr, 0, g_conv1, g_conv2, nullptr, 0, &stand_in_f, R, H, O, head_offset, nullptr, nullptr,
                        nullptr, nullptr, n_param, stand_in_i, nullptr, 0.0f, 0.0f, 0.0f, 0.0f, apply_adam, stream_, losses,
                        members, K, counts);
+}
+
+int drgnn_cohort_update_opt(const drgnn_net_desc* net, const drgnn_cohort_member* members, const drgnn_optim* optims, int32_t K,
+                            const int32_t* counts, drgnn_conv_grads* g_conv1, drgnn_conv_grads* g_conv2, int32_t R, int32_t H,
+                            int32_t O, int64_t head_offset, int64_t n_param, float* losses, int32_t apply_adam, int32_t any_clip,
+                            void* stream_) {
+    if (!members || !optims || K < 1 || K > 65535 || !counts || n_param < 1 || head_offset < 0 || head_offset >= n_param)
+        return DRGNN_E_ARG;
+    if (!net || R != DRGNN_H2 * net->n_branch || H < 1 || H > 512 || O < 1 || O > DRGNN_MAX_OUT) return DRGNN_E_WIDTH;
+    static float stand_in_f;
+    static int32_t stand_in_i[2];
+    return update_impl(0, net, nullptr, 0, g_conv1, g_conv2, nullptr, 0, &stand_in_f, R, H, O, head_offset, nullptr, nullptr,
+                       nullptr, nullptr, n_param, stand_in_i, nullptr, 0.0f, 0.0f, 0.0f, 0.0f, apply_adam, stream_, losses,
+                       members, K, counts, nullptr, optims, any_clip);
 }
 
 int drgnn_step_gradients(const drgnn_net_desc* net, const float* conv_partials, int64_t n_graphs,
@@ -2247,23 +2387,35 @@ int64_t drgnn_train_epoch_scratch_bytes(const drgnn_epoch_plan* plan) {
 // reduction of the step's slabs + optimiser update of mini-batch k: one launch, or (data parallel) gradient launch ->
 // the caller's exchange -> Adam launch
 static int epoch_update(const drgnn_epoch_plan* p, const EpochCarve& c, int64_t B, int64_t k, float* losses, void* stream,
-                        int slabs_per_graph = 0) {
+                        int slabs_per_graph, const drgnn_optim* o) {
     const drgnn_head_desc* hd = p->head;
     const int fused = p->exchange ? 0 : 1;
     // (the last mini-batch of the call also writes the caller's loss word, drgnn_epoch_plan.last_loss)
     const int64_t nb = (p->n_ids + p->batch_size - 1) / p->batch_size;
     int rc = update_impl(slabs_per_graph, p->net, c.partials, B, p->g_conv1, p->g_conv2, c.head_partials, B, c.readout, hd->R, hd->H,
                          hd->O, p->head_offset, p->flat_param, p->flat_grad, p->exp_avg, p->exp_avg_sq, p->n_param,
-                         p->step2, losses + k, p->lr, p->beta1, p->beta2, p->eps, fused, stream,
-                         (k == nb - 1) ? p->last_loss : nullptr);
+                         p->step2, losses + k, o ? o->lr : p->lr, o ? o->beta1 : p->beta1, o ? o->beta2 : p->beta2,
+                         o ? o->eps : p->eps, fused, stream, (k == nb - 1) ? p->last_loss : nullptr, nullptr, 0, nullptr, o);
     if (rc || fused) return rc;
     if ((rc = p->exchange(p->exchange_user, k, B, stream))) return rc;
+    if (o) return drgnn_adam_step_opt(p->flat_param, p->flat_grad, p->exp_avg, p->exp_avg_sq, p->step2, p->n_param, o, stream);
     return drgnn_adam_step(p->flat_param, p->flat_grad, p->exp_avg, p->exp_avg_sq, p->step2, p->n_param, p->lr, p->beta1,
                            p->beta2, p->eps, 0.0, stream);
 }
 
+static int train_epoch_impl(const drgnn_epoch_plan* p, const drgnn_optim* optim, void* scratch, int64_t scratch_bytes, float* pred,
+                            float* losses, void* stream);
 int drgnn_train_epoch(const drgnn_epoch_plan* p, void* scratch, int64_t scratch_bytes, float* pred, float* losses,
                       void* stream) {
+    return train_epoch_impl(p, nullptr, scratch, scratch_bytes, pred, losses, stream);
+}
+int drgnn_train_epoch_opt(const drgnn_epoch_plan* p, const drgnn_optim* optim, void* scratch, int64_t scratch_bytes, float* pred,
+                          float* losses, void* stream) {
+    const int rc = optim_check(optim);
+    return rc ? rc : train_epoch_impl(p, optim, scratch, scratch_bytes, pred, losses, stream);
+}
+static int train_epoch_impl(const drgnn_epoch_plan* p, const drgnn_optim* optim, void* scratch, int64_t scratch_bytes, float* pred,
+                            float* losses, void* stream) {
     EpochCarve c;
     int rc = epoch_carve(p, (char*)scratch, &c);
     if (rc) return rc;
@@ -2301,7 +2453,7 @@ int drgnn_train_epoch(const drgnn_epoch_plan* p, void* scratch, int64_t scratch_
                                              train ? c.partials : nullptr, c.xchg, &hints, stream);
             if (rc) return rc;
             if (!train) continue;
-            if ((rc = epoch_update(p, c, b.B, k, losses, stream, split ? 2 : 0))) return rc;
+            if ((rc = epoch_update(p, c, b.B, k, losses, stream, split ? 2 : 0, optim))) return rc;
         }
         return 0;
     }
@@ -2363,7 +2515,7 @@ int drgnn_train_epoch(const drgnn_epoch_plan* p, void* scratch, int64_t scratch_
         if (rc) return rc;
         if (more) cur_flags = req.flags;
         if (!train) { if (more) cur = nxt; continue; }
-        if ((rc = epoch_update(p, c, cur.B, k, losses, stream, split ? 2 : 0))) return rc;
+        if ((rc = epoch_update(p, c, cur.B, k, losses, stream, split ? 2 : 0, optim))) return rc;
         if (more) cur = nxt;
     }
     return 0;

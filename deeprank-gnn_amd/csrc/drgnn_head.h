@@ -286,22 +286,37 @@ DEV double adam_ipow(double b, int t) {
 }
 // adam_item split in two so that a caller can have the element's state and the step-dependent scalars in flight
 // while it is still computing the gradient (same arithmetic, same order -> same bits)
-struct AdamPre { float p, m, v, step_size, sqrt_bc2; bool ok; };
+// (decay: the decoupled weight-decay factor of this step, read by adam_apply<true> only)
+struct AdamPre { float p, m, v, step_size, sqrt_bc2; bool ok; float decay; };
 // the step-dependent scalars: ~35 dependent double-precision operations behind the load of the step index
-DEV void adam_bias_scalars(const AdamArgs& a, float& step_size, float& sqrt_bc2) {
+// OPT (the drgnn_optim entry points): the learning rate of step t comes from the record's device table, entry min(t, n) - 1,
+// and the decoupled weight-decay factor (float)(1 - lr_t w) is formed next to it, in double as torch.optim.AdamW forms it
+template <bool OPT = false>
+DEV void adam_bias_scalars(const AdamArgs& a, float& step_size, float& sqrt_bc2, const drgnn_optim* o = nullptr,
+                           float* decay = nullptr) {
     // bias corrections in double, as the Python-side scalars of torch's reference path; beta^t by
     // repeated squaring (t is an integer): a libm pow() in double costs more than the rest of the launch
     const int t = a.step[0];
     const double bc1 = 1.0 - adam_ipow(a.beta1, t);
     const double bc2 = 1.0 - adam_ipow(a.beta2, t);
-    step_size = (float)(a.lr / bc1);
+    if constexpr (OPT) {
+        double lr = a.lr;
+        if (o->lr_table && o->lr_n > 0) {
+            const int e = (t < o->lr_n ? t : o->lr_n) - 1;
+            lr = o->lr_table[e > 0 ? e : 0];
+        }
+        *decay = (float)(1.0 - lr * (o->decoupled ? o->weight_decay : 0.0));
+        step_size = (float)(lr / bc1);
+    } else {
+        step_size = (float)(a.lr / bc1);
+    }
     sqrt_bc2 = (float)sqrt(bc2);
 }
 // the element's state only (k_update: another wave forms the scalars meanwhile and hands them over through LDS)
 DEV AdamPre adam_prefetch_state(const AdamArgs& a, int64_t i) {
     AdamPre r;
     r.ok = i >= 0 && i < a.n;
-    r.p = r.m = r.v = 0.0f; r.step_size = 0.0f; r.sqrt_bc2 = 1.0f;
+    r.p = r.m = r.v = 0.0f; r.step_size = 0.0f; r.sqrt_bc2 = 1.0f; r.decay = 1.0f;
     if (!r.ok) return r;
     r.p = a.param[i];
     r.m = a.exp_avg[i];
@@ -313,6 +328,7 @@ DEV AdamPre adam_prefetch(const AdamArgs& a, int64_t i) {
     if (r.ok) adam_bias_scalars(a, r.step_size, r.sqrt_bc2);
     return r;
 }
+template <bool OPT = false>
 DEV void adam_apply(const AdamArgs& a, int64_t i, float g, const AdamPre& r) {
 #ifndef DRGNN_EMU
 #pragma clang fp contract(off)      // every product and sum rounded on its own: the same bits wherever this is inlined
@@ -324,11 +340,54 @@ DEV void adam_apply(const AdamArgs& a, int64_t i, float g, const AdamPre& r) {
     a.exp_avg[i] = m;
     a.exp_avg_sq[i] = v;
     const float denom = sqrtf(v) / r.sqrt_bc2 + a.eps;
-    a.param[i] = r.p - r.step_size * (m / denom);
+    // decoupled weight decay: ONE product in front of the step (a factor of exactly 1 without decay: the same bits)
+    const float p = OPT ? r.p * r.decay : r.p;
+    a.param[i] = p - r.step_size * (m / denom);
 }
 DEV void adam_item(const AdamArgs& a, int64_t i) {
     if (i >= a.n) return;
     const float g = a.grad[i];
     const AdamPre r = adam_prefetch(a, i);
     adam_apply(a, i, g, r);          // ONE statement of the arithmetic for every caller: identical bits
+}
+
+// ---- the flat update with the options of drgnn_optim ------------------------------------------------------------------------
+// the scalars one launch shares: Adam's two, the decay factor, the clipping scale
+struct AdamOptScalars { float step_size, sqrt_bc2, decay, clip; };
+// s = (float)min(1, c / (N + 1e-6)), N = sqrt of the per-block words summed in index order, all in double
+// (torch.nn.utils.clip_grad_norm_; a NaN norm gives a NaN scale, as there: no special case)
+DEV float adam_clip_from_sum(const drgnn_optim& o, double sum_sq, double* norm) {
+    const double N = sqrt(sum_sq);
+    *norm = N;
+    const double q = o.max_grad_norm / (N + 1e-6);
+    return (float)(q > 1.0 ? 1.0 : q);
+}
+DEV float adam_clip_scale(const drgnn_optim& o, int n_words, double* norm) {
+    double acc = 0.0;
+    for (int w = 0; w < n_words; ++w) acc += o.norm_words[w];
+    return adam_clip_from_sum(o, acc, norm);
+}
+DEV bool adam_dead(const drgnn_optim& o, int64_t i) {
+    for (int r = 0; r < o.n_dead; ++r)
+        if (i >= o.dead_off[r] && i < o.dead_off[r] + o.dead_len[r]) return true;
+    return false;
+}
+// grad: the flat gradient, written back when the step clips (p.grad holds the clipped gradient, as after clip_grad_norm_)
+DEV void adam_opt_item(const AdamArgs& a, const drgnn_optim& o, float* grad, int64_t i, const AdamOptScalars& sc) {
+#ifndef DRGNN_EMU
+#pragma clang fp contract(off)      // g * s rounds on its own wherever this is inlined (adam_apply)
+#endif
+    if (i >= a.n || adam_dead(o, i)) return;
+    float g = grad[i];
+    if (o.clip) { g = g * sc.clip; grad[i] = g; }
+    AdamPre r = adam_prefetch_state(a, i);
+    r.step_size = sc.step_size; r.sqrt_bc2 = sc.sqrt_bc2; r.decay = sc.decay;
+    adam_apply<true>(a, i, g, r);
+}
+// one word of the norm: the squares of up to 256 consecutive elements, each formed in double (exact), summed in index order
+DEV double adam_norm_word(const drgnn_optim& o, const float* grad, int64_t n, int64_t first) {
+    double acc = 0.0;
+    for (int64_t i = first; i < n && i < first + 256; ++i)
+        if (!adam_dead(o, i)) acc += (double)grad[i] * (double)grad[i];
+    return acc;
 }

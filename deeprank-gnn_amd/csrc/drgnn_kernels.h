@@ -1026,7 +1026,13 @@ __global__ void __launch_bounds__(256) k_head_reduce(HeadReduceArgs a) {
 // buffers and scalars (k_update: the kernel arguments; the cohort: a per-member copy whose descriptor arrays are never indexed).
 // dst: the conv gradient descriptors (strides, destinations) -- always the kernel arguments, so that the run-time branch index
 // stays a scalar load; gshift: added to every conv destination (the cohort: member m's flat gradient relative to member 0's).
-DEV void update_block(const UpdateArgs& u, const ReduceArgs& dst, int blk_id, int64_t gshift, float (*quarter)[64], float* bias_scalars) {
+// OPT (k_update_opt, k_update_cohort_opt): Adam's scalars follow the drgnn_optim record o (learning-rate table, decoupled decay;
+// bias_scalars then has a third word, the decay factor); words_out non-null: the block also leaves the sum of the squares of
+// the gradient elements it stored in words_out[blk_id] -- each square formed in double, the 64 lanes' combined by a fixed
+// butterfly -- for the Adam launch that clips (the sums launch of a clipping step runs with apply_adam = 0).
+template <bool OPT>
+DEV void update_block_t(const UpdateArgs& u, const ReduceArgs& dst, int blk_id, int64_t gshift, float (*quarter)[64], float* bias_scalars,
+                        const drgnn_optim* o, double* words_out) {
     const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
     const bool conv = blk_id < u.conv_blocks;
     // ONE textual barrier for all five waves: before it the four quarter waves issue their loads and sums and the
@@ -1040,8 +1046,10 @@ DEV void update_block(const UpdateArgs& u, const ReduceArgs& dst, int blk_id, in
     if (q == 4) {
         if (lane == 0) {
             float step_size = 0.0f, sqrt_bc2 = 1.0f;
-            if (u.apply_adam) adam_bias_scalars(u.ad, step_size, sqrt_bc2);
+            float decay = 1.0f;
+            if (u.apply_adam) adam_bias_scalars<OPT>(u.ad, step_size, sqrt_bc2, o, &decay);
             bias_scalars[0] = step_size; bias_scalars[1] = sqrt_bc2;
+            if (OPT) bias_scalars[2] = decay;
         }
     } else if (conv) {
         const ReduceArgs& a = u.r;
@@ -1075,10 +1083,16 @@ DEV void update_block(const UpdateArgs& u, const ReduceArgs& dst, int blk_id, in
     __syncthreads();
     if (q == 0) {
         pre.step_size = bias_scalars[0]; pre.sqrt_bc2 = bias_scalars[1];
+        if (OPT) pre.decay = bias_scalars[2];
         const float g = (quarter[0][lane] + quarter[1][lane]) + (quarter[2][lane] + quarter[3][lane]);
+        if (OPT && words_out) {
+            double sq = d ? (double)g * (double)g : 0.0;
+            for (int mask = 32; mask > 0; mask >>= 1) sq += __shfl_xor(sq, mask, 64);
+            if (lane == 0) words_out[blk_id] = sq;
+        }
         if (d) {
             *d = g;                                   // keep p.grad inspectable
-            if (upd) adam_apply(u.ad, idx, g, pre);
+            if (upd) adam_apply<OPT>(u.ad, idx, g, pre);
         } else if (!conv && live && item == n_grad && u.h.loss) {
             u.h.loss[0] = g;
             if (u.loss2) u.loss2[0] = g;
@@ -1087,11 +1101,21 @@ DEV void update_block(const UpdateArgs& u, const ReduceArgs& dst, int blk_id, in
     // nobody reads step2[0] in this launch (Adam reads step2[1]): safe to commit it here
     if (u.step2 && blk_id == 0 && threadIdx.x == 0) u.step2[0] = u.step2[1];
 }
+DEV void update_block(const UpdateArgs& u, const ReduceArgs& dst, int blk_id, int64_t gshift, float (*quarter)[64], float* bias_scalars) {
+    update_block_t<false>(u, dst, blk_id, gshift, quarter, bias_scalars, nullptr, nullptr);
+}
 __global__ void __launch_bounds__(DRGNN_UPDATE_THREADS) k_update(UpdateArgs u) {
     kernarg_touch_lines<DRGNN_KA_LINES(0, (int)sizeof(UpdateArgs))>(0);
     __shared__ float quarter[4][64];
     __shared__ float bias_scalars[2];
     update_block(u, u.r, (int)blockIdx.x, 0, quarter, bias_scalars);
+}
+// k_update under a drgnn_optim record (AdamW, learning-rate table: still ONE launch); with words_out the sums launch of a
+// clipping step, k_adam_opt follows
+__global__ void __launch_bounds__(DRGNN_UPDATE_THREADS) k_update_opt(UpdateArgs u, drgnn_optim o, double* words_out) {
+    __shared__ float quarter[4][64];
+    __shared__ float bias_scalars[3];
+    update_block_t<true>(u, u.r, (int)blockIdx.x, 0, quarter, bias_scalars, &o, words_out);
 }
 // The update of a cohort (include/drgnn.h: drgnn_cohort_update): k_update's block once per member, the member from the second
 // grid dimension.  u: member 0's launch (shapes, strides, conv destinations); what differs per member comes from entry m of the
@@ -1117,6 +1141,91 @@ __global__ void __launch_bounds__(DRGNN_UPDATE_THREADS) k_update_cohort(UpdateAr
     u.ad.step = mm.step2 + 1;
     adam_set_hyper(u.ad, mm.lr, mm.beta1, mm.beta2, mm.eps, 0.0);
     update_block(u, u0.r, (int)blockIdx.x, (int64_t)(mm.flat_grad - wg_uniform_words(members[0].flat_grad)), quarter, bias_scalars);
+}
+// The scalars of a flat Adam launch under drgnn_optim, formed once per 256-thread block (all threads call this): thread 0 the
+// bias corrections, learning rate and decay factor; the per-block norm words are fetched by all threads at once (one memory
+// round trip: a single thread walking them paid one per word, 12 us for GINet's 167), staged in LDS 256 at a time and added up
+// by thread 64 in index order -- the order adam_clip_scale states.  Block 0 publishes the norm.
+DEV void adam_opt_block_scalars(const AdamArgs& a, const drgnn_optim& o, int n_words, AdamOptScalars& sc, double* stage) {
+    const int tid = (int)threadIdx.x;
+    double acc = 0.0;
+    if (o.clip) {
+        for (int base = 0; base < n_words; base += 256) {
+            const double mine = base + tid < n_words ? o.norm_words[base + tid] : 0.0;
+            if (base == 0 && tid == 0) adam_bias_scalars<true>(a, sc.step_size, sc.sqrt_bc2, &o, &sc.decay);
+            stage[tid] = mine;
+            __syncthreads();
+            if (tid == 64) {
+                const int m = n_words - base < 256 ? n_words - base : 256;
+                int k = 0;
+                for (; k + 8 <= m; k += 8) {
+                    double v[8];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) v[j] = stage[k + j];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) acc += v[j];
+                }
+                for (; k < m; ++k) acc += stage[k];
+            }
+            __syncthreads();
+        }
+        if (n_words <= 0 && tid == 0) adam_bias_scalars<true>(a, sc.step_size, sc.sqrt_bc2, &o, &sc.decay);
+        if (tid == 64) {
+            double norm;
+            sc.clip = adam_clip_from_sum(o, acc, &norm);
+            if (blockIdx.x == 0 && o.norm_out) o.norm_out[0] = (float)norm;
+        }
+    } else {
+        if (tid == 0) adam_bias_scalars<true>(a, sc.step_size, sc.sqrt_bc2, &o, &sc.decay);
+        if (tid == 64) sc.clip = 1.0f;
+    }
+    __syncthreads();
+}
+// k_update_cohort under a device table of K drgnn_optim records (drgnn_cohort_update_opt): Adam's scalars and the options of
+// member m come from optims[m].  A member that clips only sums here (its words in its own norm_words) and takes its Adam step
+// in k_adam_cohort_opt; the others finish in this launch.
+__global__ void __launch_bounds__(DRGNN_UPDATE_THREADS) k_update_cohort_opt(UpdateArgs u_by_value, const drgnn_cohort_member* members,
+                                                                             const drgnn_optim* optims, const int32_t* counts,
+                                                                             int64_t head_offset) {
+    __shared__ float quarter[4][64];
+    __shared__ float bias_scalars[3];
+    const UpdateArgs& u0 = *reinterpret_cast<const UpdateArgs*>((const char*)__builtin_amdgcn_kernarg_segment_ptr());
+    const int m = (int)blockIdx.y;
+    const int B = __builtin_amdgcn_readfirstlane(counts[m]);
+    if (B <= 0) return;
+    const drgnn_cohort_member mm = wg_uniform_words(members[m]);
+    const drgnn_optim* o = optims + m;
+    const bool clip = __builtin_amdgcn_readfirstlane(o->clip) != 0;
+    UpdateArgs u = u0;
+    u.r.partials = mm.partials; u.r.n_graphs = B;
+    u.h.partials = mm.head_partials; u.h.n_wg = B;
+    u.h.grad = mm.flat_grad + head_offset; u.h.loss = mm.loss;
+    u.readout = mm.readout; u.step2 = mm.step2; u.loss2 = u0.loss2 ? u0.loss2 + m : nullptr;
+    u.ad.param = mm.flat_param; u.ad.grad = mm.flat_grad; u.ad.exp_avg = mm.exp_avg; u.ad.exp_avg_sq = mm.exp_avg_sq;
+    u.ad.step = mm.step2 + 1;
+    adam_set_hyper(u.ad, o->lr, o->beta1, o->beta2, o->eps, 0.0);
+    if (clip) u.apply_adam = 0;
+    double* words = (clip && (int)blockIdx.x < o->norm_cap) ? o->norm_words : nullptr;
+    update_block_t<true>(u, u0.r, (int)blockIdx.x, (int64_t)(mm.flat_grad - wg_uniform_words(members[0].flat_grad)), quarter,
+                         bias_scalars, o, words);
+}
+// the Adam launch of the cohort's clipping members: k_adam_opt once per member (second grid dimension) over the n_words
+// per-block words k_update_cohort_opt left; a member that does not clip, or without a mini-batch this step, is left alone
+__global__ void __launch_bounds__(256) k_adam_cohort_opt(const drgnn_cohort_member* members, const drgnn_optim* optims,
+                                                         const int32_t* counts, int64_t n_param, int n_words) {
+    __shared__ AdamOptScalars sc;
+    __shared__ double stage[256];
+    const int m = (int)blockIdx.y;
+    if (__builtin_amdgcn_readfirstlane(counts[m]) <= 0) return;
+    // (read in place: a private copy of the record, indexed by adam_dead at run time, went to scratch -- 232 bytes per lane)
+    const drgnn_optim& o = optims[m];
+    if (!__builtin_amdgcn_readfirstlane(o.clip)) return;
+    AdamArgs a;
+    a.param = members[m].flat_param; a.grad = members[m].flat_grad; a.exp_avg = members[m].exp_avg;
+    a.exp_avg_sq = members[m].exp_avg_sq; a.step = members[m].step2 + 1; a.n = n_param;
+    adam_set_hyper(a, o.lr, o.beta1, o.beta2, o.eps, 0.0);
+    adam_opt_block_scalars(a, o, n_words < o.norm_cap ? n_words : o.norm_cap, sc, stage);
+    adam_opt_item(a, o, members[m].flat_grad, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, sc);
 }
 // drgnn_step_gradients: k_update's fixed-order sums without the optimiser -- the gradient of the step's slabs, each slab
 // optionally weighted by its graph's d loss / d pred (the autograd boundary, include/drgnn.h), plus one block that clears the
@@ -1158,6 +1267,29 @@ __global__ void __launch_bounds__(256) k_gradients(GradArgs ga) {
 __global__ void __launch_bounds__(DRGNN_P2P_THREADS) k_allreduce_oneshot(P2PArgs a) { p2p_block(a, blockIdx.x); }
 __global__ void __launch_bounds__(256) k_adam(AdamArgs a) {
     adam_item(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+// drgnn_adam_step_opt.  Wave 0 forms Adam's scalars and the decay factor, wave 1 meanwhile the clipping scale from the n_words
+// per-block words (adam_opt_block_scalars), then every thread takes its element.
+__global__ void __launch_bounds__(256) k_adam_opt(AdamArgs a, drgnn_optim o, float* grad, int n_words) {
+    __shared__ AdamOptScalars sc;
+    __shared__ double stage[256];
+    adam_opt_block_scalars(a, o, n_words, sc, stage);
+    adam_opt_item(a, o, grad, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, sc);
+}
+// one word of the gradient norm per 256 elements of the flat gradient (the flat route of a clipping step): each thread's
+// square in double, the block's 256 combined by a fixed tree
+__global__ void __launch_bounds__(256) k_grad_norm_words(const float* grad, int64_t n, drgnn_optim o) {
+    __shared__ double part[256];
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    double sq = 0.0;
+    if (i < n && !adam_dead(o, i)) sq = (double)grad[i] * (double)grad[i];
+    part[threadIdx.x] = sq;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) o.norm_words[blockIdx.x] = part[0];
 }
 // topology prologue when the caller supplies the per-graph offsets: copy them into the
 // workspace and clear the status words (one launch instead of two copies and a fill)

@@ -16,7 +16,8 @@ from .trainer import FusedTrainer
 KEYS = ("net", "F", "task", "O", "classes", "transform_sigmoid", "head")
 # a checkpoint's entries besides 'model' and 'optimizer' (NeuralNet reads every one of them back)
 SETTINGS = ("node", "edge", "target", "task", "classes", "class_weight", "batch_size", "percent", "lr", "index", "shuffle",
-            "threshold", "cluster_nodes", "transform_sigmoid")
+            "threshold", "cluster_nodes", "transform_sigmoid", "weight_decay", "decoupled_weight_decay", "max_grad_norm",
+            "lr_schedule")
 
 
 def checkpoint_state(model_sd, optimizer_sd, **settings):

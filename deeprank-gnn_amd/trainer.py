@@ -27,7 +27,26 @@ from .functional import H1, H2, _conv_grads, _describe
 from .launch import ExchangeWords, NetLayout, batch_hints, cached_flags, fused, head_desc, set_hints, tiles_match, usable_flags, wrong_targets
 from .topology import Topology
 
-__all__ = ["FusedTrainer"]
+__all__ = ["FusedTrainer", "schedule_from_torch"]
+
+
+def schedule_from_torch(make_scheduler, lr, n_steps, every=1):
+    """A learning-rate table for ``FusedTrainer(lr_schedule=...)`` from any torch scheduler: ``make_scheduler(optimizer)``
+    is run on a dummy CPU parameter whose group starts at ``lr``; entry t is the group's rate before optimiser step t + 1,
+    and ``scheduler.step()`` is called every ``every`` optimiser steps (``every`` = mini-batches per epoch: the usual
+    epoch-wise use).  The last entry then holds for every later step."""
+    import warnings
+    opt = torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=float(lr))
+    sched = make_scheduler(opt)
+    table = []
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        for t in range(int(n_steps)):
+            table.append(float(opt.param_groups[0]["lr"]))
+            opt.step()
+            if (t + 1) % int(every) == 0:
+                sched.step()
+    return table
 
 
 class FusedTrainer(object):
@@ -35,7 +54,13 @@ class FusedTrainer(object):
     _dp_first_batch = 0
 
     def __init__(self, net, lr=0.01, task="reg", class_weights=None, betas=(0.9, 0.999), eps=1e-8,
-                 weight_decay=0.0, seed=None, api=None, transform_sigmoid=False):
+                 weight_decay=0.0, seed=None, api=None, transform_sigmoid=False, decoupled_weight_decay=False,
+                 max_grad_norm=None, lr_schedule=None):
+        """``weight_decay`` with ``decoupled_weight_decay`` as in torch's param group (AdamW: p <- p (1 - lr_t w) before the
+        Adam step, parameters without a gradient untouched); ``max_grad_norm``: ``clip_grad_norm_(params, c)`` on the summed
+        mini-batch gradient (data parallel: the all-reduced one) before Adam, the norm before clipping in ``grad_norm``;
+        ``lr_schedule``: one learning rate per optimiser step, the last one held for ever (``schedule_from_torch``).  All
+        three run inside the native launches of every training path; with all of them off the launches are unchanged."""
         hostcpu.fit_torch_threads()                           # the launching thread must not lose its CPU quota to idle pool threads
         self.net = net
         self.transform_sigmoid = bool(transform_sigmoid)      # regression: sigmoid on the output before the loss
@@ -45,6 +70,9 @@ class FusedTrainer(object):
         self.head_grad_offset, self.R, self.H, self.O = lay.head_offset, lay.R, lay.H, lay.O
         self.task = _lib.TASK_REG if task == "reg" else _lib.TASK_CLASS
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), betas, float(eps), float(weight_decay)
+        self.decoupled_weight_decay = bool(decoupled_weight_decay)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self._lr_schedule = self._lr_table = self._norm_words = self._optim_key = self._optim_rec = None
         if seed is None:
             # dropout stream: follows torch.manual_seed (like the reference's F.dropout) and differs per rank, so that
             # data-parallel ranks do not draw the same masks for their different graphs
@@ -79,6 +107,9 @@ class FusedTrainer(object):
         self.adopt_storage(flat_p, *(torch.zeros(total, dtype=torch.float32, device=dev) for _ in range(3)),
                            step2=torch.zeros(4, dtype=torch.int32, device=dev),
                            loss=torch.zeros(1, dtype=torch.float32, device=dev))
+        # [1] the 2-norm of the last step's gradient before clipping (written by the Adam launch of a clipping step)
+        self._grad_norm = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.lr_schedule = lr_schedule
         self.class_w = None
         if class_weights is not None:
             self.class_w = torch.as_tensor(class_weights, dtype=torch.float32, device=dev).contiguous()
@@ -124,6 +155,68 @@ class FusedTrainer(object):
         reference to it stays current).  Every update launch writes it -- ``train_step`` directly, ``train_epoch`` through its
         last mini-batch's update launch (drgnn_epoch_plan.last_loss) -- on the stream of that launch: no lazy state."""
         return self._loss_buf
+
+    # -- optimiser options --------------------------------------------------------------------------------------------
+    @property
+    def grad_norm(self):
+        """[1] device tensor: ||g||_2 of the last clipping step's gradient BEFORE it was clipped (ONE fixed buffer; reading it
+        is the caller's synchronisation, the step never waits for it)."""
+        return self._grad_norm
+
+    @property
+    def lr_schedule(self):
+        return self._lr_schedule
+
+    @lr_schedule.setter
+    def lr_schedule(self, table):
+        """the table lives in device memory (float64): the update launch loads its entry by the step index it reads anyway"""
+        self._optim_key = None        # (a new table can land at the old one's address: never reuse a record across a change)
+        if table is None or len(table) == 0:
+            self._lr_schedule = self._lr_table = None
+            return
+        self._lr_schedule = [float(v) for v in table]
+        self._lr_table = torch.tensor(self._lr_schedule, dtype=torch.float64).to(self.flat_p.device)
+
+    def lr_at(self, t):
+        """the learning rate optimiser step ``t`` (>= 1) uses"""
+        if self._lr_schedule is None:
+            return self.lr
+        return self._lr_schedule[max(min(int(t), len(self._lr_schedule)), 1) - 1]
+
+    def _coupled(self):
+        return self.weight_decay != 0.0 and not self.decoupled_weight_decay
+
+    def _optim(self, always=False):
+        """The drgnn_optim record of this trainer's options, or None with all of them off (weight decay 0 or coupled, no
+        clipping, no schedule): the launches are then the plain ones.  ``always``: the record even then (a cohort's table
+        has one per member)."""
+        if not always and self.max_grad_norm is None and self._lr_table is None and (
+                self.weight_decay == 0.0 or not self.decoupled_weight_decay):
+            return None
+        key = (self.lr, tuple(self.betas), self.eps, self.weight_decay, self.decoupled_weight_decay, self.max_grad_norm,
+               None if self._lr_table is None else self._lr_table.data_ptr())
+        if key != self._optim_key:
+            o = _lib.Optim()
+            o.lr, o.beta1, o.beta2, o.eps = self.lr, self.betas[0], self.betas[1], self.eps
+            o.weight_decay, o.decoupled = self.weight_decay, int(self.decoupled_weight_decay)
+            if self._lr_table is not None:
+                o.lr_table, o.lr_n = self._lr_table.data_ptr(), self._lr_table.numel()
+            if self.max_grad_norm is not None:
+                if self._norm_words is None:
+                    self._norm_words = torch.zeros(self.api.optim_norm_words(self.flat_p.numel()), dtype=torch.float64,
+                                                   device=self.flat_p.device)
+                o.clip, o.max_grad_norm = 1, self.max_grad_norm
+                o.norm_words, o.norm_cap = self._norm_words.data_ptr(), self._norm_words.numel()
+                o.norm_out = self._grad_norm.data_ptr()
+            if not self._coupled():       # (coupled L2 decays the parameters without a gradient too, as drgnn_adam_step does)
+                dead = sorted(self.layout.dead)
+                if len(dead) > len(o.dead_off):
+                    raise _lib.DrgnnError("more than %d parameter ranges without a gradient" % len(o.dead_off))
+                o.n_dead = len(dead)
+                for i, (off, n) in enumerate(dead):
+                    o.dead_off[i], o.dead_len[i] = int(off), int(n)
+            self._optim_key, self._optim_rec = key, o
+        return self._optim_rec
 
     def _head_desc(self, train):
         return head_desc(self.net, self.task, train, getattr(self.net, "dropout", 0.0) if train else 0.0, self.seed,
@@ -235,6 +328,13 @@ class FusedTrainer(object):
 
     def _fused_launch_update(self, c, apply_adam=True, lr=None):
         """Second launch: fixed-order reduction of the slabs (+ dW_fc1 = dhid^T readout) and Adam."""
+        o = self._optim() if (apply_adam and lr is None) else None      # (an explicit lr: the plain launch with that rate)
+        if o is not None:
+            self.api.step_update_opt(c["desc"], c["partials"], c["B"], c["g1"], c["g2"], c["hp"], c["readout"], self.R,
+                                     self.H, self.O, self.head_grad_offset, self.flat_p, self.flat_g, self.exp_avg,
+                                     self.exp_avg_sq, self.step2, self.loss, o, c["stream"], apply_adam=True,
+                                     slabs_per_graph=c.get("slabs", 0))
+            return
         self.api.step_update(c["desc"], c["partials"], c["B"], c["g1"], c["g2"], c["hp"], c["readout"], self.R,
                              self.H, self.O, self.head_grad_offset, self.flat_p, self.flat_g, self.exp_avg,
                              self.exp_avg_sq, self.step2, self.loss, self.lr if lr is None else lr,
@@ -292,7 +392,8 @@ class FusedTrainer(object):
         if wrong:
             raise ValueError(wrong)
         self._cached_launch_step(c, True)
-        decay = apply_adam and self.weight_decay != 0.0        # (the update launch's Adam knows no weight decay)
+        # (the plain update launch's Adam knows no weight decay; with an option on, drgnn_step_update_opt takes it all)
+        decay = apply_adam and self.weight_decay != 0.0 and self._optim() is None
         self._fused_launch_update(c, apply_adam and not decay)
         if decay:
             self.apply_update()
@@ -352,9 +453,14 @@ class FusedTrainer(object):
                                     topo.ws_f32, n_nodes, topo.n_edges, B, topo.max_nodes, topo.max_edges,
                                     topo.max_c0, xp, arg0, arg1, pred, hp, None, partials, scratch, stream,
                                     next_topology=None if next_topo is None else next_topo.request(self.topo_flags))
-        api.train_update(desc, partials, B, g1, g2, hp, self.R, self.H, self.O, self.head_grad_offset,
-                         self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.step, self.loss,
-                         self.lr, self.betas[0], self.betas[1], self.eps, stream, apply_adam=apply_adam)
+        o = self._optim() if apply_adam else None
+        if o is not None:
+            api.train_update_opt(desc, partials, B, g1, g2, hp, self.R, self.H, self.O, self.head_grad_offset,
+                                 self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.step, self.loss, o, stream)
+        else:
+            api.train_update(desc, partials, B, g1, g2, hp, self.R, self.H, self.O, self.head_grad_offset,
+                             self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.step, self.loss,
+                             self.lr, self.betas[0], self.betas[1], self.eps, stream, apply_adam=apply_adam)
         self.last_pred = pred
         self.last_batch_size = B
         return self.loss
@@ -432,8 +538,14 @@ class FusedTrainer(object):
         return self._oneshot
 
     def apply_update(self):
-        """Adam on the flat buffers (one launch)."""
+        """Adam on the flat buffers (one launch; with clipping, a small launch for the norm of what ``flat_g`` holds now --
+        in data parallel the all-reduced gradient -- in front of it)."""
         self._training_storage()
+        o = self._optim()
+        if o is not None:
+            self.api.adam_step_opt(self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.step, o,
+                                   _lib.current_stream(self.flat_p))
+            return
         self.api.adam_step(self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.step, self.lr,
                            self.betas[0], self.betas[1], self.eps, self.weight_decay,
                            _lib.current_stream(self.flat_p))
@@ -448,7 +560,7 @@ class FusedTrainer(object):
         body fwd, body bwd incl. head + loss, reduce+Adam.  With torch.distributed initialised:
         reduce, ONE all-reduce of the flat gradient, Adam."""
         distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
-        if not distributed and self.weight_decay == 0.0:
+        if not distributed and (self.weight_decay == 0.0 or self._optim() is not None):
             return self._backward(batch, topo, True, next_topo)
         loss = self.compute_gradients(batch, topo, next_topo)
         # n_local: this rank's weight in the global mini-batch when it differs from the batch it stepped (0 for a rank
@@ -498,10 +610,11 @@ class FusedTrainer(object):
         (graph numbers), driven by the native loop ``drgnn_train_epoch``: per mini-batch the fused step launch
         (whose extra workgroups build the next mini-batch's topology and gather its node rows straight from the
         resident set) and the update launch -- no Python and no host synchronisation between mini-batches.  Returns (losses [n_batches], pred [len(order), O]) as
-        device tensors, or None when this configuration needs the per-batch path (data parallel, weight decay,
-        a graph too large for the fused kernels)."""
+        device tensors, or None when this configuration needs the per-batch path (coupled L2 weight decay,
+        a graph too large for the fused kernels).  Decoupled weight decay, clipping and a learning-rate table run inside
+        the loop (drgnn_train_epoch_opt): the table is indexed by the step words on the device, no host work per step."""
         self._training_storage()
-        if self.weight_decay != 0.0 or wrong_targets(self.task == _lib.TASK_REG, gset.y):
+        if self._coupled() or wrong_targets(self.task == _lib.TASK_REG, gset.y):
             return None
         self._dp = None
         if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
@@ -615,6 +728,8 @@ class FusedTrainer(object):
         # two pieces back), never the device.
         chunk = self.EPOCH_CHUNK
         in_flight = []
+        optim = None if inference else self._optim()
+        run_epoch = self.api.train_epoch if optim is None else (lambda *a: self.api.train_epoch_opt(a[0], optim, *a[1:]))
         try:
             for c0 in range(0, nb, chunk):
                 c1 = min(nb, c0 + chunk)
@@ -629,7 +744,7 @@ class FusedTrainer(object):
                 if dev.type == "cuda" and len(in_flight) >= 2:
                     in_flight.pop(0).synchronize()
                 try:
-                    self.api.train_epoch(plan, scratch, pred[lo:], losses[c0:], stream)
+                    run_epoch(plan, scratch, pred[lo:], losses[c0:], stream)
                 except _lib.DrgnnError:
                     if known is None or self._dp_error is not None:
                         raise
@@ -648,7 +763,7 @@ class FusedTrainer(object):
                     self._epoch_bytes[shape_key] = nbytes
                     if scratch.numel() < nbytes:
                         scratch = self._epoch_scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                    self.api.train_epoch(plan, scratch, pred[lo:], losses[c0:], stream)
+                    run_epoch(plan, scratch, pred[lo:], losses[c0:], stream)
                 if dev.type == "cuda" and c1 < nb:
                     ev = torch.cuda.Event()
                     ev.record()
@@ -680,12 +795,25 @@ class FusedTrainer(object):
         group = {'lr': self.lr, 'betas': tuple(self.betas), 'eps': self.eps, 'weight_decay': self.weight_decay,
                  'amsgrad': False, 'maximize': False, 'foreach': None, 'capturable': False, 'differentiable': False,
                  'fused': None, 'params': list(range(len(self.offset)))}
+        # the options, only when on (a default trainer's dictionary is torch.optim.Adam's, key for key)
+        if self.decoupled_weight_decay:
+            group['decoupled_weight_decay'] = True
+        if self.max_grad_norm is not None:
+            group['max_grad_norm'] = self.max_grad_norm
+        if self._lr_schedule is not None:
+            # 'lr': the rate the next step will use, as a torch scheduler leaves it in the group
+            group['lr_schedule'], group['initial_lr'], group['lr'] = list(self._lr_schedule), self.lr, self.lr_at(step + 1)
         return {'state': state, 'param_groups': [group]}
 
     def load_optimizer_state_dict(self, sd):
         group = sd['param_groups'][0]
         self.lr, self.betas, self.eps = float(group['lr']), tuple(group['betas']), float(group['eps'])
         self.weight_decay = float(group.get('weight_decay', 0.0))
+        self.decoupled_weight_decay = bool(group.get('decoupled_weight_decay', False))
+        self.max_grad_norm = None if group.get('max_grad_norm') is None else float(group['max_grad_norm'])
+        self.lr_schedule = group.get('lr_schedule')
+        if self._lr_schedule is not None:
+            self.lr = float(group.get('initial_lr', group['lr']))
         steps = set()
         with torch.no_grad():
             for i, (name, p) in enumerate(self.net.named_parameters()):

@@ -424,7 +424,7 @@ int drgnn_adam_step(float* param, const float* grad, float* exp_avg, float* exp_
  * g_conv1/g_conv2 must point INTO flat_grad; head_offset = element offset of fc1.weight in
  * the flat buffers; *step must already count this update (the forward launch's step_inc).
  * apply_adam = 0 only produces the flat gradient + loss (data parallel: all-reduce, then
- * drgnn_adam_step).  weight_decay is not supported here (use drgnn_adam_step). */
+ * drgnn_adam_step).  weight_decay is not supported here (coupled L2: drgnn_adam_step; decoupled: drgnn_train_update_opt). */
 int drgnn_train_update(const drgnn_net_desc* net, const float* conv_partials, int64_t n_graphs,
                        drgnn_conv_grads* g_conv1, drgnn_conv_grads* g_conv2,
                        const float* head_partials, int64_t head_slabs /* rows of head_partials */,
@@ -797,6 +797,70 @@ typedef struct drgnn_epoch_plan {
 int64_t drgnn_train_epoch_scratch_bytes(const drgnn_epoch_plan* plan);
 int drgnn_train_epoch(const drgnn_epoch_plan* plan, void* scratch, int64_t scratch_bytes, float* pred,
                       float* losses, void* stream);
+
+/* ---- optimiser options: decoupled weight decay (AdamW), gradient-norm clipping, learning-rate table ----------
+ * The `_opt` siblings below take Adam's scalars from this record instead of their argument lists and otherwise do what
+ * the entry point they are named after does; with every option off they compute the same bits.
+ *   weight_decay / decoupled   decoupled != 0: before the Adam step, p <- p * (float)(1 - lr_t * weight_decay), the factor
+ *                  formed in double (torch.optim.AdamW); the gradient is not touched.  decoupled == 0: the coupled L2 term of
+ *                  drgnn_adam_step (g + weight_decay * p), which only the flat kernel knows: the update siblings then leave
+ *                  the gradient and run the flat kernel behind it.
+ *   lr_table       NULL, or DEVICE double [lr_n]: optimiser step t >= 1 uses entry min(t, lr_n) - 1 in place of lr, loaded
+ *                  by the step index the kernel reads anyway -- nothing of a schedule is a kernel argument, so a recorded
+ *                  step advances through it on replay.
+ *   clip / max_grad_norm   clip != 0: torch.nn.utils.clip_grad_norm_(params, max_grad_norm), norm_type 2.  N = ||g||_2 over
+ *                  the whole flat gradient, every square formed and summed in double in a fixed order (per block, then the
+ *                  per-block words in index order); s = (float)min(1, max_grad_norm / (N + 1e-6)); g <- g * s is stored back
+ *                  to the flat gradient and consumed by Adam.  Two launches, no workgroup waits for another: the sums launch
+ *                  (Adam off) leaves one double per block in norm_words, the Adam launch adds them up in every block.
+ *                  norm_words: DEVICE scratch of norm_cap doubles, at least max(update blocks, ceil(n_param / 256)): see
+ *                  drgnn_optim_norm_words.  norm_out: optional DEVICE float [1], receives N (before clipping).
+ *   dead_off / dead_len   element ranges of the flat buffers that belong to parameters without a gradient (GINet's
+ *                  fc_attention / fc_edge_attr): the flat kernel leaves parameter, moments and gradient there untouched, as
+ *                  torch skips a parameter whose grad is None.  (The update launches never visit them.)  A caller that wants
+ *                  coupled L2 to decay them, as drgnn_adam_step does, passes n_dead = 0. */
+typedef struct drgnn_optim {
+    double lr, beta1, beta2, eps;
+    double weight_decay;
+    double max_grad_norm;
+    const double* lr_table;
+    double* norm_words;
+    float* norm_out;
+    int32_t lr_n, decoupled, clip, norm_cap;
+    int32_t n_dead, reserved;
+    int64_t dead_off[DRGNN_ZERO_RANGES], dead_len[DRGNN_ZERO_RANGES];
+} drgnn_optim;
+/* doubles of norm_words scratch that any `_opt` call over a net of n_param parameters needs */
+int64_t drgnn_optim_norm_words(int64_t n_param);
+/* drgnn_adam_step with the options; with clip it first leaves one word per 256 elements of grad (one more small launch),
+ * then scales grad in place. */
+int drgnn_adam_step_opt(float* param, float* grad, float* exp_avg, float* exp_avg_sq, const int32_t* step, int64_t n,
+                        const drgnn_optim* optim, void* stream);
+int drgnn_train_update_opt(const drgnn_net_desc* net, const float* conv_partials, int64_t n_graphs,
+                           drgnn_conv_grads* g_conv1, drgnn_conv_grads* g_conv2,
+                           const float* head_partials, int64_t head_slabs, int32_t R, int32_t H, int32_t O,
+                           int64_t head_offset, float* flat_param, float* flat_grad, float* exp_avg, float* exp_avg_sq,
+                           int64_t n_param, const int32_t* step, float* loss, const drgnn_optim* optim,
+                           int32_t apply_adam, void* stream);
+int drgnn_step_update_opt(const drgnn_net_desc* net, const float* conv_partials, int64_t n_graphs,
+                          drgnn_conv_grads* g_conv1, drgnn_conv_grads* g_conv2, const float* head_partials,
+                          const float* readout, int32_t R, int32_t H, int32_t O, int64_t head_offset,
+                          float* flat_param, float* flat_grad, float* exp_avg, float* exp_avg_sq, int64_t n_param,
+                          int32_t* step2, float* loss, const drgnn_optim* optim,
+                          int32_t apply_adam, int32_t slabs_per_graph, void* stream);
+/* drgnn_cohort_update with a DEVICE table of K records next to the member table: member m's Adam scalars and options are
+ * optims[m] (members[m].lr / beta1 / beta2 / eps are not read; decoupled decay only: a coupled weight_decay is ignored, as
+ * drgnn_cohort_update knows none).  any_clip: non-zero when any record clips -- the clipping members then take their Adam
+ * step in a second launch (once per member, second grid dimension); every record's norm_cap must be at least
+ * drgnn_optim_norm_words(n_param).  A member without a mini-batch (counts[m] == 0) is left alone, norm_out included.
+ * Member m's result is what drgnn_step_update_opt gives for that member alone, bit for bit. */
+int drgnn_cohort_update_opt(const drgnn_net_desc* net, const drgnn_cohort_member* members, const drgnn_optim* optims, int32_t K,
+                            const int32_t* counts, drgnn_conv_grads* g_conv1, drgnn_conv_grads* g_conv2, int32_t R, int32_t H,
+                            int32_t O, int64_t head_offset, int64_t n_param, float* losses /* optional */, int32_t apply_adam,
+                            int32_t any_clip, void* stream);
+/* drgnn_train_epoch with the options (plan->lr / beta1 / beta2 / eps are not read) */
+int drgnn_train_epoch_opt(const drgnn_epoch_plan* plan, const drgnn_optim* optim, void* scratch, int64_t scratch_bytes,
+                          float* pred, float* losses, void* stream);
 
 /* ---- one-shot all-reduce over peer-mapped exchange buffers (csrc/drgnn_p2p.h) ------------------------------
  * Data-parallel exchange of the flat gradient without a ring: each rank owns a fine-grained exchange buffer
