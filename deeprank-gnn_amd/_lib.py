@@ -119,6 +119,18 @@ class Optim(ctypes.Structure):
                 ("dead_off", _c_i64 * 8), ("dead_len", _c_i64 * 8)]
 
 
+class IfaceRequest(ctypes.Structure):
+    """drgnn_iface_request (include/drgnn.h): one ragged batch of complexes for drgnn_iface_count / drgnn_iface_fill;
+    ``host_*`` are addresses of host copies of the three offset tables."""
+    _fields_ = [("xyz", _vp), ("atom_ptr", _vp), ("res_ptr", _vp), ("res_split", _vp), ("res_type", _vp),
+                ("host_atom_ptr", _vp), ("host_res_ptr", _vp), ("host_res_split", _vp),
+                ("n_atoms", _c_i64), ("n_residues", _c_i64), ("n_complexes", _c_i64),
+                ("contact_distance", ctypes.c_double), ("internal_contact_distance", ctypes.c_double),
+                ("tile_atoms", _c_i32), ("reserved", _c_i32),
+                ("workspace", _vp), ("workspace_bytes", _c_i64),
+                ("node_ptr", _vp), ("edge_ptr", _vp), ("iedge_ptr", _vp)]
+
+
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p)
 
 
@@ -324,6 +336,10 @@ class Api(object):
         lib.drgnn_cohort_update_opt.argtypes = ([ctypes.POINTER(NetDesc), _vp, _vp, _c_i32, _vp] + [ctypes.POINTER(ConvGrads)] * 2 +
                                                 [_c_i32] * 3 + [_c_i64, _c_i64, _vp, _c_i32, _c_i32, _vp])
         lib.drgnn_train_epoch_opt.argtypes = [ctypes.POINTER(EpochPlan), ctypes.POINTER(Optim), _vp, _c_i64, _vp, _vp, _vp]
+        lib.drgnn_iface_workspace_bytes.argtypes = [_c_i64] * 4
+        lib.drgnn_iface_workspace_bytes.restype = _c_i64
+        lib.drgnn_iface_count.argtypes = [ctypes.POINTER(IfaceRequest), _vp]
+        lib.drgnn_iface_fill.argtypes = [ctypes.POINTER(IfaceRequest)] + [_c_i64] * 3 + [_vp] * 9
         if lib.drgnn_abi_version() != 5:
             raise DrgnnError("ABI mismatch in %s" % path)
 
@@ -597,6 +613,18 @@ class Api(object):
         _check(self.lib.drgnn_metrics(_ptr(pred), _ptr(y), n, what, direction, float(threshold), label_lo, n_labels,
                                       _ptr(workspace), workspace.numel() * workspace.element_size(), _ptr(counts),
                                       _ptr(scores), _ptr(order), _ptr(hits), stream), "drgnn_metrics")
+
+    def iface_workspace_bytes(self, n_complexes, max_res_a, max_res_b, n_residues):
+        return int(self.lib.drgnn_iface_workspace_bytes(int(n_complexes), int(max_res_a), int(max_res_b), int(n_residues)))
+
+    def iface_count(self, request, stream):
+        _check(self.lib.drgnn_iface_count(ctypes.byref(request), stream), "drgnn_iface_count")
+
+    def iface_fill(self, request, n_nodes, n_edges, n_iedges, node_residue, pos, chain, type_, edge_index, dist,
+                   internal_edge_index, internal_dist, stream):
+        _check(self.lib.drgnn_iface_fill(ctypes.byref(request), int(n_nodes), int(n_edges), int(n_iedges), _ptr(node_residue),
+                                         _ptr(pos), _ptr(chain), _ptr(type_), _ptr(edge_index), _ptr(dist),
+                                         _ptr(internal_edge_index), _ptr(internal_dist), stream), "drgnn_iface_fill")
 
     def collate(self, gset, ids, n_graphs, n_nodes, n_edges, x, edge_index, edge_attr, batch, cluster0, cluster1,
                 y, node_ptr, edge_ptr, c1_ptr, stream):

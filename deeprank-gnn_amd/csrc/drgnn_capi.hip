@@ -8,6 +8,7 @@
 #include "drgnn_kernels.h"
 
 #include <vector>
+#include <algorithm>
 #include <memory>
 #include <string.h>
 #include <stdlib.h>
@@ -2085,6 +2086,138 @@ int drgnn_louvain(const int64_t* edge_index, int64_t n_edges, const int32_t* nod
     if (words * 4 > 64 * 1024)
         HIP_TRY(hipFuncSetAttribute((const void*)k_louvain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(words * 4)));
     hipLaunchKernelGGL(k_louvain, dim3((unsigned)n_graphs), dim3(LV_W), (size_t)(words * 4), (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+#endif
+    return 0;
+}
+
+// ---- interface graphs from atom coordinates (drgnn_iface.h) ------------------------------------------
+int64_t drgnn_iface_workspace_bytes(int64_t n_complexes, int64_t max_res_a, int64_t max_res_b, int64_t n_residues) {
+    if (n_complexes < 0 || max_res_a < 0 || max_res_b < 0 || n_residues < 0) return -1;
+    int64_t off[8];
+    iface_layout(n_complexes, max_res_a, max_res_b, n_residues, off);
+    return off[7];
+}
+
+// checks the request on the host and fills the launch record; *max_res: the longest complex
+static int iface_prepare(const drgnn_iface_request* q, IfaceArgs& a, int* max_res) {
+    if (!q || !q->host_atom_ptr || !q->host_res_ptr || !q->node_ptr || !q->edge_ptr || !q->iedge_ptr) return DRGNN_E_ARG;
+    const int64_t T = q->n_atoms, R = q->n_residues, M = q->n_complexes;
+    if (T < 0 || R < 0 || M < 0 || T > INT32_MAX / 3 || R >= INT32_MAX) return DRGNN_E_ARG;
+    if (M > 0 && (!q->host_res_split || !q->res_ptr || !q->res_split)) return DRGNN_E_ARG;
+    if (R > 0 && (!q->atom_ptr || !q->res_type || !q->workspace)) return DRGNN_E_ARG;
+    if (T > 0 && !q->xyz) return DRGNN_E_ARG;
+    if (!(q->contact_distance >= 0.0) || !(q->internal_contact_distance >= 0.0) || q->tile_atoms < 0) return DRGNN_E_ARG;
+    const int32_t *ap = q->host_atom_ptr, *rp = q->host_res_ptr, *sp = q->host_res_split;
+    if (ap[0] != 0 || ap[R] != T || rp[0] != 0 || rp[M] != R) return DRGNN_E_ARG;
+    int max_atoms = 0, maxA = 0, maxB = 0, maxR = 0, maxB_atoms = 0;
+    for (int64_t r = 0; r < R; ++r) {
+        if (ap[r + 1] < ap[r]) return DRGNN_E_ARG;
+        max_atoms = std::max(max_atoms, ap[r + 1] - ap[r]);
+    }
+    // the residue tables whole, before anything is indexed through them: 0 = rp[0] <= rp[c] <= sp[c] <= rp[c + 1] <= R
+    for (int64_t c = 0; c < M; ++c)
+        if (rp[c + 1] < rp[c] || rp[c + 1] > R || sp[c] < rp[c] || sp[c] > rp[c + 1]) return DRGNN_E_ARG;
+    for (int64_t c = 0; c < M; ++c) {
+        maxA = std::max(maxA, sp[c] - rp[c]);
+        maxB = std::max(maxB, rp[c + 1] - sp[c]);
+        maxR = std::max(maxR, rp[c + 1] - rp[c]);
+        maxB_atoms = std::max(maxB_atoms, ap[rp[c + 1]] - ap[sp[c]]);
+    }
+    if (M > 65535) return DRGNN_E_CAPACITY;
+    if (M * (int64_t)maxA * maxB > INT32_MAX) return DRGNN_E_CAPACITY;      // (the edge counts and their prefix sums are int32)
+    int tile = q->tile_atoms > 0 ? q->tile_atoms : IF_TILE_DEFAULT;
+    tile = std::max(std::max(std::min(tile, maxB_atoms), max_atoms), 1);
+    if (iface_pairs_lds_bytes(tile) > DRGNN_LDS_LIMIT) return DRGNN_E_CAPACITY;
+    int64_t off[8];
+    iface_layout(M, maxA, maxB, R, off);
+    if (q->workspace_bytes < off[7]) return DRGNN_E_CAPACITY;
+    if (off[7] > 0 && ((uintptr_t)q->workspace & 15) != 0) return DRGNN_E_ARG;
+    char* ws = (char*)q->workspace;
+    memset(&a, 0, sizeof(a));
+    a.xyz = q->xyz; a.atom_ptr = q->atom_ptr; a.res_ptr = q->res_ptr; a.res_split = q->res_split; a.res_type = q->res_type;
+    a.n_complexes = (int)M; a.n_residues = (int)R; a.maxA = maxA; a.maxB = maxB; a.tile_atoms = tile;
+    a.cut = (float)q->contact_distance; a.cut2 = (float)(q->contact_distance * q->contact_distance);
+    a.icut = (float)q->internal_contact_distance;
+    a.icut2 = (float)(q->internal_contact_distance * q->internal_contact_distance);
+    a.D = (float*)(ws + off[0]); a.sphere = (float*)(ws + off[1]); a.flag = (int*)(ws + off[2]); a.nloc = (int*)(ws + off[3]);
+    a.eoff = (int*)(ws + off[4]); a.ioff = (int*)(ws + off[5]); a.cnt = (int*)(ws + off[6]);
+    a.node_ptr = q->node_ptr; a.edge_ptr = q->edge_ptr; a.iedge_ptr = q->iedge_ptr;
+    *max_res = maxR;
+    return 0;
+}
+
+#ifdef DRGNN_EMU
+static void iface_rows_emu(const IfaceArgs& a, int max_res, bool write) {
+    for (int c = 0; c < a.n_complexes; ++c)
+        for (int blk = 0; blk * IF_AB < max_res; ++blk) iface_rows_block(a, c, blk, write);
+}
+#endif
+
+int drgnn_iface_count(const drgnn_iface_request* req, void* stream) {
+    IfaceArgs a;
+    int max_res = 0;
+    const int rc = iface_prepare(req, a, &max_res);
+    if (rc) return rc;
+    const int M = a.n_complexes, R = a.n_residues;
+#ifdef DRGNN_EMU
+    (void)stream;
+    std::vector<float> lds((size_t)(iface_pairs_lds_bytes(a.tile_atoms) / 4) + 4);
+    std::vector<int> part(DRGNN_NTHREADS + 1);
+    for (int r = 0; r < R; ++r) iface_sphere_item(a, r);
+    for (int c = 0; c < M; ++c)
+        for (int blk = 0; blk * IF_AB < a.maxA; ++blk) iface_pairs_block(a, c, blk, lds.data());
+    iface_rows_emu(a, max_res, false);
+    for (int c = 0; c < M; ++c) iface_scan_block(a, c, part.data());
+    iface_offsets_block(a, part.data());
+#else
+    hipStream_t st = (hipStream_t)stream;
+    if (R > 0) {
+        hipLaunchKernelGGL(k_iface_sphere, dim3((unsigned)((R + IF_NT - 1) / IF_NT)), dim3(IF_NT), 0, st, a);
+        HIP_TRY(hipGetLastError());
+    }
+    if (M > 0 && a.maxA > 0) {
+        const int64_t lds = iface_pairs_lds_bytes(a.tile_atoms);
+        if (lds > 64 * 1024)
+            HIP_TRY(hipFuncSetAttribute((const void*)k_iface_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(k_iface_pairs, dim3((unsigned)((a.maxA + IF_AB - 1) / IF_AB), (unsigned)M), dim3(IF_NT), (size_t)lds, st, a);
+        HIP_TRY(hipGetLastError());
+    }
+    if (M > 0 && max_res > 0) {
+        hipLaunchKernelGGL(k_iface_rows, dim3((unsigned)((max_res + IF_AB - 1) / IF_AB), (unsigned)M), dim3(IF_NT), 0, st, a, 0);
+        HIP_TRY(hipGetLastError());
+    }
+    if (M > 0) {
+        hipLaunchKernelGGL(k_iface_scan, dim3((unsigned)M), dim3(DRGNN_NTHREADS), 0, st, a);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_iface_offsets, dim3(1), dim3(DRGNN_NTHREADS), 0, st, a);
+    HIP_TRY(hipGetLastError());
+#endif
+    return 0;
+}
+
+int drgnn_iface_fill(const drgnn_iface_request* req, int64_t n_nodes, int64_t n_edges, int64_t n_iedges,
+                     int32_t* node_residue, float* pos, int32_t* chain, int32_t* type, int64_t* edge_index, float* dist,
+                     int64_t* internal_edge_index, float* internal_dist, void* stream) {
+    IfaceArgs a;
+    int max_res = 0;
+    const int rc = iface_prepare(req, a, &max_res);
+    if (rc) return rc;
+    if (n_nodes < 0 || n_edges < 0 || n_iedges < 0) return DRGNN_E_ARG;
+    if (n_nodes > 0 && (!node_residue || !pos || !chain || !type)) return DRGNN_E_ARG;
+    if (n_edges > 0 && (!edge_index || !dist)) return DRGNN_E_ARG;
+    if (n_iedges > 0 && (!internal_edge_index || !internal_dist)) return DRGNN_E_ARG;
+    a.node_residue = node_residue; a.pos = pos; a.chain = chain; a.type = type;
+    a.edge_index = edge_index; a.dist = dist; a.iedge_index = internal_edge_index; a.idist = internal_dist;
+    a.n_nodes = n_nodes; a.n_edges = n_edges; a.n_iedges = n_iedges;
+    if (a.n_complexes == 0 || max_res == 0 || n_nodes == 0) return 0;
+#ifdef DRGNN_EMU
+    (void)stream;
+    iface_rows_emu(a, max_res, true);
+#else
+    hipLaunchKernelGGL(k_iface_rows, dim3((unsigned)((max_res + IF_AB - 1) / IF_AB), (unsigned)a.n_complexes), dim3(IF_NT), 0,
+                       (hipStream_t)stream, a, 1);
     HIP_TRY(hipGetLastError());
 #endif
     return 0;

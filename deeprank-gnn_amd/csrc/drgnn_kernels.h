@@ -11,6 +11,7 @@
 #include "drgnn_layers.h"
 #include "drgnn_mcl.h"
 #include "drgnn_louvain.h"
+#include "drgnn_iface.h"
 #include "drgnn_metrics.h"
 #include "drgnn_collate.h"
 #include "drgnn_p2p.h"
@@ -966,6 +967,24 @@ __global__ void __launch_bounds__(DRGNN_NTHREADS) k_mcl(MclArgs a) {
 __global__ void __launch_bounds__(LV_W) k_louvain(LouvainArgs a) {
     extern __shared__ __attribute__((aligned(16))) int smem_lv[];
     louvain_graph(a, blockIdx.x, smem_lv);
+}
+// interface graphs from atom coordinates (drgnn_iface.h)
+__global__ void __launch_bounds__(IF_NT) k_iface_sphere(IfaceArgs a) {
+    const int r = blockIdx.x * IF_NT + threadIdx.x;
+    if (r < a.n_residues) iface_sphere_item(a, r);
+}
+__global__ void __launch_bounds__(IF_NT) k_iface_pairs(IfaceArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem_if[];
+    iface_pairs_block(a, blockIdx.y, blockIdx.x, smem_if);
+}
+__global__ void __launch_bounds__(IF_NT) k_iface_rows(IfaceArgs a, int write) { iface_rows_block(a, blockIdx.y, blockIdx.x, write != 0); }
+__global__ void __launch_bounds__(DRGNN_NTHREADS) k_iface_scan(IfaceArgs a) {
+    __shared__ int part[DRGNN_NTHREADS + 1];
+    iface_scan_block(a, blockIdx.x, part);
+}
+__global__ void __launch_bounds__(DRGNN_NTHREADS) k_iface_offsets(IfaceArgs a) {
+    __shared__ int part[DRGNN_NTHREADS + 1];
+    iface_offsets_block(a, part);
 }
 // evaluation scores (drgnn_metrics.h)
 __global__ void __launch_bounds__(MT_NT) k_mt_reduce(MetricsArgs a, int centred) {

@@ -69,6 +69,18 @@ class GraphStore(object):
                     f[mol].visititems(visit)
                     self._mols[mol] = tree
 
+    @classmethod
+    def from_trees(cls, mols, trees, path=None):
+        """A store built in memory: ``trees[i]`` is the ``{dataset path: ndarray}`` tree of molecule ``mols[i]``
+        (what interface_graphs returns; save_npz / save_native write it out)."""
+        mols = [str(m) for m in mols]
+        if len(mols) != len(trees) or len(set(mols)) != len(mols):
+            raise ValueError("from_trees needs one tree per molecule name, names unique")
+        self = cls.__new__(cls)
+        self.path = path
+        self._mols = {m: {k: np.asarray(v) for k, v in t.items()} for m, t in zip(mols, trees)}
+        return self
+
     def save_native(self, path):
         """Write the whole tree as a native container (lossless: names, dtypes, shapes, byte strings)."""
         from .container import write_container

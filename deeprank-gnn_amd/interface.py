@@ -1,0 +1,271 @@
+"""Interface graphs from atom coordinates, built on the device: the geometric half of the reference's graph
+generation (``ResidueGraph`` / ``GraphGenMP``: ResidueGraph.py:108-145, 207-245, 272-316, 364-381).
+
+    chain, res_seq, res_name, xyz = read_pdb_atoms("1ATN_1w.pdb")
+    table = AtomTable(chain, res_seq, res_name, xyz)
+    store = interface_graphs([table], ["1ATN_1w"])           # a GraphStore: GraphDataSet / PreCluster / NeuralNet take it
+
+    poses = AtomTable.poses(table, xyz_of_all_poses)         # docking: one topology, M coordinate sets
+    store = interface_graphs(poses, names)
+
+Covered: nodes, interface and internal edges with their ``dist``, and the node features that come from the
+coordinates or from a table (``pos``, ``chain``, ``type``, ``polarity``, ``charge``).  Not covered: ``bsa`` (needs a
+SASA program), ``depth`` / ``hse`` (Biopython), PSSM file parsing (``pssm``, ``cons``, ``ic``) and the scores
+(``irmsd``, ``dockQ`` ...).  For those every graph carries ``node_data/residue``, each node's index among the
+residues of its ``AtomTable``: a per-residue array the caller holds is attached with ``attach_residue_features``.
+
+Order (fixed here; the reference's is networkx insertion order): nodes by (chain, position of the residue in the
+input), interface edges (A node, B node) and internal edges (i < j) sorted by their pair.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+
+# this reference version's tables (ResidueGraph.py:43-60): index = the `type` of the residue
+RESIDUE_NAMES = ("CYS", "HIS", "ASN", "GLN", "SER", "THR", "TYR", "TRP", "ALA", "PHE",
+                 "GLY", "ILE", "VAL", "MET", "PRO", "LEU", "GLU", "ASP", "LYS", "ARG")
+RESIDUE_CHARGE = np.array([-0.64, -0.29, -1.22, -1.22, -0.80, -0.80, -0.80, -0.79, -0.37, -0.37,
+                           -0.37, -0.37, -0.37, -0.37, 0.0, -0.37, -1.37, -1.37, -0.36, -1.65])
+# 0 apolar, 1 polar, 2 negatively charged, 3 positively charged (LYS is listed as negatively charged there)
+RESIDUE_POLARITY = np.array([1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 2, 2, 2, 3])
+_TYPE_OF = {n: i for i, n in enumerate(RESIDUE_NAMES)}
+WORKSPACE_BUDGET = 256 << 20       # bytes of dense min-d^2 workspace one call may ask for (sets the default chunk)
+
+
+def read_pdb_atoms(path):
+    """(chain str [T], res_seq int32 [T], res_name str [T], xyz float64 [T,3]) of the ``ATOM`` records of a PDB file,
+    by the fixed columns of the format, hydrogens included, in file order.  Host-side plumbing."""
+    chain, seq, name, xyz = [], [], [], []
+    with open(path) as f:
+        for line in f:
+            if line.startswith("ATOM  "):
+                name.append(line[17:20].strip())
+                chain.append(line[21])
+                seq.append(int(line[22:26]))
+                xyz.append((float(line[30:38]), float(line[38:46]), float(line[46:54])))
+    return (np.array(chain, dtype="U1"), np.array(seq, dtype=np.int32), np.array(name, dtype="U3"),
+            np.array(xyz, dtype=np.float64).reshape(-1, 3))
+
+
+class AtomTable(object):
+    """The atoms of one two-chain complex grouped for the kernels: atoms sorted by residue, residues of chain A
+    (in order of first appearance in the input) before those of chain B.  A residue is (chain, res_seq).
+
+    ``order`` [T] input position of each kept atom; ``atom_ptr`` int32 [R+1]; ``split`` = number of chain-A residues;
+    ``res_chain`` / ``res_seq`` / ``res_name`` / ``res_type`` per residue (type -1: not one of the 20 standard names);
+    ``xyz`` float32 [T,3] in the grouped order."""
+
+    def __init__(self, chain, res_seq, res_name, xyz, chains=("A", "B")):
+        chain = np.asarray(chain).astype("U")
+        res_seq = np.asarray(res_seq).astype(np.int64)
+        res_name = np.asarray(res_name).astype("U")
+        xyz = np.asarray(xyz)
+        if not (chain.shape == res_seq.shape == res_name.shape == xyz.shape[:1]) or xyz.shape[1:] != (3,):
+            raise ValueError("chain, res_seq, res_name [T] and xyz [T,3] must describe the same atoms")
+        side = np.full(chain.shape, -1, dtype=np.int64)
+        side[chain == chains[0]] = 0
+        side[chain == chains[1]] = 1
+        kept = np.flatnonzero(side >= 0)
+        # residue of every kept atom: rank of (side, first appearance of its (side, res_seq))
+        span = int(res_seq.max() - res_seq.min() + 1) if kept.size else 1
+        key = side[kept] * span + (res_seq[kept] - (res_seq.min() if kept.size else 0))
+        uniq, first, inv = np.unique(key, return_index=True, return_inverse=True)
+        rank_of_uniq = np.empty(len(uniq), dtype=np.int64)
+        rank_of_uniq[np.lexsort((first, uniq // span))] = np.arange(len(uniq))
+        res_of_atom = rank_of_uniq[inv]
+        grouped = np.argsort(res_of_atom, kind="stable")
+        self.order = kept[grouped]
+        counts = np.bincount(res_of_atom, minlength=len(uniq))
+        self.atom_ptr = np.concatenate(([0], np.cumsum(counts))).astype(np.int32)
+        head = self.order[self.atom_ptr[:-1]] if len(uniq) else np.zeros(0, dtype=np.int64)
+        self.res_chain = side[head].astype(np.int32)
+        self.res_seq = res_seq[head].astype(np.int32)
+        self.res_name = res_name[head]
+        self.res_type = np.array([_TYPE_OF.get(n, -1) for n in self.res_name], dtype=np.int32)
+        self.split = int((self.res_chain == 0).sum())
+        self.chains = tuple(chains)
+        self.n_input_atoms = int(chain.shape[0])
+        self.xyz = np.ascontiguousarray(xyz[self.order], dtype=np.float32)
+
+    @property
+    def n_residues(self):
+        return int(self.res_type.shape[0])
+
+    @property
+    def n_atoms(self):
+        return int(self.order.shape[0])
+
+    @staticmethod
+    def poses(table, xyz):
+        """M coordinate sets xyz [M, T, 3] (atoms in the order the table was made from) of one topology: the
+        grouping of ``table`` is applied to all of them with one gather."""
+        return Poses(table, xyz)
+
+
+class Poses(object):
+    """``AtomTable.poses``: ``table`` and ``xyz`` float32 [M, T', 3] in the table's grouped atom order."""
+
+    def __init__(self, table, xyz):
+        xyz = np.asarray(xyz)
+        if xyz.ndim != 3 or xyz.shape[1:] != (table.n_input_atoms, 3):
+            raise ValueError("poses need xyz [M, %d, 3]" % table.n_input_atoms)
+        self.table = table
+        self.xyz = np.ascontiguousarray(xyz[:, table.order], dtype=np.float32)
+
+    def __len__(self):
+        return int(self.xyz.shape[0])
+
+
+def _complexes(items):
+    """[(table, xyz float32 [T,3])] of a Poses, an AtomTable or a sequence of either"""
+    if isinstance(items, Poses):
+        return [(items.table, items.xyz[m]) for m in range(len(items))]
+    if isinstance(items, AtomTable):
+        return [(items, items.xyz)]
+    out = []
+    for it in items:
+        out += _complexes(it)
+    return out
+
+
+def _ragged(part):
+    """(xyz, atom_ptr, res_ptr, res_split, res_type) of a list of (table, xyz); the offset tables int32"""
+    tables = [t for t, _ in part]
+    m = len(part)
+    xyz = np.concatenate([x for _, x in part]).astype(np.float32, copy=False) if m else np.zeros((0, 3), np.float32)
+    if m and all(t is tables[0] for t in tables):                      # poses of one topology: no per-complex work
+        t = tables[0]
+        atom_ptr = np.append((t.atom_ptr[None, :-1].astype(np.int64) + t.n_atoms * np.arange(m)[:, None]).ravel(), m * t.n_atoms)
+        res_ptr = t.n_residues * np.arange(m + 1)
+        res_type = np.tile(t.res_type, m)
+        split = res_ptr[:-1] + t.split
+    else:
+        n_at = np.array([t.n_atoms for t in tables], dtype=np.int64)
+        n_res = np.array([t.n_residues for t in tables], dtype=np.int64)
+        a0 = np.concatenate(([0], np.cumsum(n_at)))
+        res_ptr = np.concatenate(([0], np.cumsum(n_res)))
+        atom_ptr = np.concatenate([t.atom_ptr[:-1].astype(np.int64) + a0[k] for k, t in enumerate(tables)] + [a0[-1:]])
+        res_type = np.concatenate([t.res_type for t in tables]) if m else np.zeros(0, np.int32)
+        split = res_ptr[:-1] + np.array([t.split for t in tables], dtype=np.int64)
+    if xyz.shape[0] * 3 >= 2 ** 31:
+        raise ValueError("a chunk of %d complexes holds too many atoms for int32 offsets; lower `chunk`" % m)
+    return (np.ascontiguousarray(xyz), atom_ptr.astype(np.int32), np.asarray(res_ptr).astype(np.int32),
+            np.asarray(split).astype(np.int32), res_type.astype(np.int32))
+
+
+def build_ragged(api, xyz, atom_ptr, res_ptr, res_split, res_type, contact_distance=8.5, internal_contact_distance=3.0,
+                 device="cpu", tile_atoms=0, workspace_bytes=None):
+    """One drgnn_iface_count + drgnn_iface_fill over a ragged batch given as numpy arrays (include/drgnn.h).  Returns a
+    dict of numpy arrays: node_ptr / edge_ptr / iedge_ptr int32 [M+1] and the eight outputs of drgnn_iface_fill."""
+    dev = torch.device(device)
+    M, R = len(res_ptr) - 1, len(atom_ptr) - 1
+    host = [np.ascontiguousarray(a, dtype=np.int32) for a in (atom_ptr, res_ptr, res_split)]
+    d_xyz = torch.from_numpy(np.ascontiguousarray(xyz, dtype=np.float32)).to(dev)
+    d_ap, d_rp, d_rs = [torch.from_numpy(h).to(dev) for h in host]
+    d_rt = torch.from_numpy(np.ascontiguousarray(res_type, dtype=np.int32)).to(dev)
+    if api is _lib._API:
+        _lib.require_device(d_xyz)
+    if workspace_bytes is None:
+        rp, rs = host[1].astype(np.int64), host[2].astype(np.int64)
+        workspace_bytes = api.iface_workspace_bytes(M, int((rs - rp[:-1]).max()) if M else 0,
+                                                    int((rp[1:] - rs).max()) if M else 0, R)
+    ws = torch.empty(max(int(workspace_bytes), 16), dtype=torch.uint8, device=dev)
+    ptrs = torch.zeros((3, M + 1), dtype=torch.int32, device=dev)
+    q = _lib.IfaceRequest()
+    q.xyz, q.atom_ptr, q.res_ptr, q.res_split, q.res_type = (d_xyz.data_ptr(), d_ap.data_ptr(), d_rp.data_ptr(),
+                                                            d_rs.data_ptr(), d_rt.data_ptr())
+    q.host_atom_ptr, q.host_res_ptr, q.host_res_split = [h.ctypes.data for h in host]
+    q.n_atoms, q.n_residues, q.n_complexes = int(d_xyz.shape[0]), R, M
+    q.contact_distance, q.internal_contact_distance = float(contact_distance), float(internal_contact_distance)
+    q.tile_atoms = int(tile_atoms)
+    q.workspace, q.workspace_bytes = ws.data_ptr(), int(workspace_bytes)
+    q.node_ptr, q.edge_ptr, q.iedge_ptr = ptrs[0].data_ptr(), ptrs[1].data_ptr(), ptrs[2].data_ptr()
+    stream = _lib.current_stream(d_xyz)
+    api.iface_count(q, stream)
+    N, E, Ei = (int(v) for v in ptrs[:, -1].cpu())                 # the one synchronisation of the build
+    out = {"node_residue": torch.empty(N, dtype=torch.int32, device=dev), "pos": torch.empty((N, 3), dtype=torch.float32, device=dev),
+           "chain": torch.empty(N, dtype=torch.int32, device=dev), "type": torch.empty(N, dtype=torch.int32, device=dev),
+           "edge_index": torch.empty((E, 2), dtype=torch.int64, device=dev), "dist": torch.empty(E, dtype=torch.float32, device=dev),
+           "internal_edge_index": torch.empty((Ei, 2), dtype=torch.int64, device=dev),
+           "internal_dist": torch.empty(Ei, dtype=torch.float32, device=dev)}
+    api.iface_fill(q, N, E, Ei, out["node_residue"], out["pos"], out["chain"], out["type"], out["edge_index"], out["dist"],
+                   out["internal_edge_index"], out["internal_dist"], stream)
+    res = {k: v.cpu().numpy() for k, v in out.items()}
+    p = ptrs.cpu().numpy()
+    res["node_ptr"], res["edge_ptr"], res["iedge_ptr"] = p[0], p[1], p[2]
+    return res
+
+
+def default_chunk(api, max_res_a, max_res_b, max_atoms, budget=WORKSPACE_BUDGET):
+    """the largest number of complexes of these bounds whose workspace stays within ``budget`` bytes (at least 1; the
+    grid and the int32 offsets bound it too)"""
+    lo, hi = 1, 65535
+    hi = min(hi, max(1, (2 ** 31 - 1) // (3 * max(max_atoms, 1))))
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        if api.iface_workspace_bytes(mid, max_res_a, max_res_b, mid * (max_res_a + max_res_b)) <= budget:
+            lo = mid
+        else:
+            hi = mid - 1
+    return lo
+
+
+def interface_graphs(tables_or_poses, names, contact_distance=8.5, internal_contact_distance=3.0, device=None, chunk=None,
+                     api=None):
+    """Interface graphs of complexes (a sequence of ``AtomTable``, an ``AtomTable.poses`` batch, or a mix) as a
+    ``GraphStore`` with one molecule per name, in the reference's tree: ``edge_index``, ``edge_data/dist``,
+    ``internal_edge_index``, ``internal_edge_data/dist``, ``nodes`` and, under ``node_data/``, ``pos``, ``chain``,
+    ``type`` (one-hot 20), ``polarity`` (one-hot 4), ``charge`` and ``residue`` (index into the table's residues).
+    ``chunk``: complexes per kernel call, which bounds the dense workspace (default: what fits WORKSPACE_BUDGET
+    bytes); it changes no bit of the result.  ``api`` / ``device``: the product library on the GPU unless given."""
+    from .dataset import GraphStore
+    api = api or _lib.get()
+    if device is None:
+        device = "cuda" if api is _lib._API else "cpu"
+    cx = _complexes(tables_or_poses)
+    names = [str(n) for n in names]
+    if len(names) != len(cx):
+        raise ValueError("%d names for %d complexes" % (len(names), len(cx)))
+    if chunk is None:
+        chunk = default_chunk(api, max([t.split for t, _ in cx] + [0]), max([t.n_residues - t.split for t, _ in cx] + [0]),
+                              max([t.n_atoms for t, _ in cx] + [0]))
+    chunk = max(1, int(chunk))
+    trees = []
+    for lo in range(0, len(cx), chunk):
+        part = cx[lo:lo + chunk]
+        xyz, atom_ptr, res_ptr, split, res_type = _ragged(part)
+        r = build_ragged(api, xyz, atom_ptr, res_ptr, split, res_type, contact_distance, internal_contact_distance, device)
+        for k, (t, _) in enumerate(part):
+            n0, n1 = r["node_ptr"][k:k + 2]
+            e0, e1 = r["edge_ptr"][k:k + 2]
+            i0, i1 = r["iedge_ptr"][k:k + 2]
+            residue = r["node_residue"][n0:n1].astype(np.int64) - int(res_ptr[k])
+            typ = r["type"][n0:n1].astype(np.int64)
+            trees.append({
+                "nodes": np.stack((np.asarray(t.chains)[t.res_chain[residue]], t.res_seq[residue].astype("U"),
+                                   t.res_name[residue]), axis=1).astype("S") if n1 > n0 else np.zeros((0, 3), "S1"),
+                "edge_index": r["edge_index"][e0:e1].copy(),
+                "edge_data/dist": r["dist"][e0:e1].copy(),
+                "internal_edge_index": r["internal_edge_index"][i0:i1].copy(),
+                "internal_edge_data/dist": r["internal_dist"][i0:i1].copy(),
+                "node_data/pos": r["pos"][n0:n1].copy(),
+                "node_data/chain": r["chain"][n0:n1].astype(np.int64),
+                "node_data/type": np.eye(20, dtype=np.float32)[typ],
+                "node_data/polarity": np.eye(4, dtype=np.float32)[RESIDUE_POLARITY[typ]],
+                "node_data/charge": RESIDUE_CHARGE[typ].astype(np.float64),
+                "node_data/residue": residue,
+            })
+    return GraphStore.from_trees(names, trees)
+
+
+def attach_residue_features(store, name, per_residue_array):
+    """``node_data/<name>`` of every molecule of ``store`` = ``per_residue_array[node_data/residue]``: a table with
+    one row per residue of the ``AtomTable`` (pssm, ic, cons ... constant across rigid-body poses), or a dict
+    ``{mol: table}``."""
+    for mol in store.mols():
+        table = per_residue_array[mol] if isinstance(per_residue_array, dict) else per_residue_array
+        store.set(mol, "node_data/" + name, np.asarray(table)[store.get(mol, "node_data/residue")])
+    return store

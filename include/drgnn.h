@@ -643,6 +643,64 @@ int drgnn_metrics(const double* pred, const double* y, int64_t n, int32_t what, 
                   int32_t label_lo, int32_t n_labels, void* workspace, int64_t workspace_bytes, int64_t* counts,
                   double* scores, int32_t* order, int64_t* hits, void* stream);
 
+/* ---- interface graphs from atom coordinates (drgnn_iface.h) ------------------------------------------
+ * The geometric half of the reference's graph generation (ResidueGraph.get_graph, ResidueGraph.py:108-145; the contact
+ * search, :272-316; the edge distance, :364-381) for a ragged batch of M complexes of two chains.  Atoms are sorted
+ * by residue, residues by complex with chain A before chain B:
+ *   xyz f32 [T,3]; atom_ptr i32 [R+1] atom range of each residue; res_ptr i32 [M+1] residue range of each complex;
+ *   res_split i32 [M] first chain-B residue of each complex; res_type i32 [R] 0..19, or -1: non-standard residue.
+ * The three offset tables are also given as HOST arrays (host_*): the grid, the tile and the argument checks come from
+ * them, so nothing is read back from the device.
+ * Rule: residues a of A and b of B are an interface pair when an atom pair has d^2 < contact_distance^2 (strict),
+ * its dist the smallest atom distance; nodes are the standard residues of the pairs whose two residues are standard;
+ * two nodes i < j of one chain with an atom pair at d^2 < internal_contact_distance^2 form an internal edge.
+ * Order: nodes by (chain, residue), interface edges (A node, B node) and internal edges (i < j) sorted by their pair;
+ * node ids are local to the complex.  d^2 comes from fp32 coordinate differences; results repeat bit for bit and do
+ * not depend on the other complexes of the batch, on tile_atoms or on the workspace's size.
+ * tile_atoms: B-chain atoms staged in LDS at a time (0: 4 096; raised to the largest residue, DRGNN_E_CAPACITY when
+ * that is beyond 160 KiB).  workspace: drgnn_iface_workspace_bytes() of (M, the largest chain A, the largest chain B, R)
+ * or more, 16-byte aligned: the dense min-d^2 matrix [M, max_res_a, max_res_b] f32, 16 + 16 bytes per residue, 12 per
+ * complex.  M <= 65 535 and M * max_res_a * max_res_b <= 2^31 - 1 (the edge offsets are int32): split larger batches. */
+typedef struct drgnn_iface_request {
+    const float* xyz;
+    const int32_t* atom_ptr;
+    const int32_t* res_ptr;
+    const int32_t* res_split;
+    const int32_t* res_type;
+    const int32_t* host_atom_ptr;      /* the same tables in host memory */
+    const int32_t* host_res_ptr;
+    const int32_t* host_res_split;
+    int64_t n_atoms, n_residues, n_complexes;
+    double contact_distance, internal_contact_distance;
+    int32_t tile_atoms, reserved;
+    void* workspace;
+    int64_t workspace_bytes;
+    int32_t* node_ptr;                 /* device i32 [M+1] each: written by drgnn_iface_count, read by drgnn_iface_fill */
+    int32_t* edge_ptr;
+    int32_t* iedge_ptr;
+} drgnn_iface_request;
+
+/* bytes of workspace for n_complexes complexes whose chains have at most max_res_a / max_res_b residues, n_residues
+ * in all; -1: a negative argument.  Pure host. */
+int64_t drgnn_iface_workspace_bytes(int64_t n_complexes, int64_t max_res_a, int64_t max_res_b, int64_t n_residues);
+
+/* Spheres, interface pairs, node flags, internal pairs and the scans (five launches): leaves the prefix sums of the
+ * complexes' node / interface-edge / internal-edge counts in node_ptr / edge_ptr / iedge_ptr.  The caller reads their
+ * last entries to size the outputs of drgnn_iface_fill: the only synchronisation of a build.
+ * DRGNN_E_ARG: a null pointer, an offset table that does not start at 0, decreases or ends elsewhere than n_atoms /
+ * n_residues, a split outside its complex, a negative cut-off; DRGNN_E_CAPACITY: workspace_bytes too small, M beyond
+ * 65 535, a dense matrix beyond 2^31 - 1 entries, a residue beyond the LDS tile.  Both without a launch.  No allocation, no synchronisation. */
+int drgnn_iface_count(const drgnn_iface_request* req, void* stream);
+
+/* The graphs, after drgnn_iface_count on the same request and workspace (one launch):
+ *   node_residue i32 [N] residue index (into res_type) of each node; pos f32 [N,3] mean of the residue's atoms (an
+ *   fp64 sum rounded once); chain i32 [N] 0 / 1; type i32 [N] res_type of the node;
+ *   edge_index i64 [E,2], dist f32 [E]; internal_edge_index i64 [Ei,2], internal_dist f32 [Ei].
+ * n_nodes / n_edges / n_iedges: the totals read from the ptr arrays (capacities: nothing is written beyond them). */
+int drgnn_iface_fill(const drgnn_iface_request* req, int64_t n_nodes, int64_t n_edges, int64_t n_iedges,
+                     int32_t* node_residue, float* pos, int32_t* chain, int32_t* type, int64_t* edge_index, float* dist,
+                     int64_t* internal_edge_index, float* internal_dist, void* stream);
+
 /* ---- device-resident graph set and mini-batch assembly --------------------
  * Replaces the host collate of every mini-batch: torch_geometric DataLoader -> Batch.from_data_list over
  * HDF5DataSet.load_one_graph's Data objects (NeuralNet.py:153-154, DataSet.py:231-366).  The set is the
