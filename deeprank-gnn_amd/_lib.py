@@ -131,6 +131,16 @@ class IfaceRequest(ctypes.Structure):
                 ("node_ptr", _vp), ("edge_ptr", _vp), ("iedge_ptr", _vp)]
 
 
+class ScoreRequest(ctypes.Structure):
+    """drgnn_score_request (include/drgnn.h): M poses of one topology for drgnn_dock_scores; ``host_*`` are addresses of
+    host copies of the index tables (``host_zone_ptr`` exists on the host only)."""
+    _fields_ = [("xyz", _vp), ("zone_atom", _vp), ("zone_ref", _vp), ("pair_res", _vp), ("atom_ptr", _vp),
+                ("host_zone_atom", _vp), ("host_zone_ptr", _vp), ("host_pair_res", _vp), ("host_atom_ptr", _vp),
+                ("n_poses", _c_i64), ("n_atoms", _c_i64), ("n_residues", _c_i64), ("n_pairs", _c_i64),
+                ("n_ref_pairs", _c_i64), ("fnat_cutoff", ctypes.c_double),
+                ("scores", _vp), ("classes", _vp), ("n_preserved", _vp)]
+
+
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p)
 
 
@@ -340,6 +350,7 @@ class Api(object):
         lib.drgnn_iface_workspace_bytes.restype = _c_i64
         lib.drgnn_iface_count.argtypes = [ctypes.POINTER(IfaceRequest), _vp]
         lib.drgnn_iface_fill.argtypes = [ctypes.POINTER(IfaceRequest)] + [_c_i64] * 3 + [_vp] * 9
+        lib.drgnn_dock_scores.argtypes = [ctypes.POINTER(ScoreRequest), _vp]
         if lib.drgnn_abi_version() != 5:
             raise DrgnnError("ABI mismatch in %s" % path)
 
@@ -619,6 +630,9 @@ class Api(object):
 
     def iface_count(self, request, stream):
         _check(self.lib.drgnn_iface_count(ctypes.byref(request), stream), "drgnn_iface_count")
+
+    def dock_scores(self, request, stream):
+        _check(self.lib.drgnn_dock_scores(ctypes.byref(request), stream), "drgnn_dock_scores")
 
     def iface_fill(self, request, n_nodes, n_edges, n_iedges, node_residue, pos, chain, type_, edge_index, dist,
                    internal_edge_index, internal_dist, stream):

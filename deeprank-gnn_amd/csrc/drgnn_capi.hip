@@ -2223,6 +2223,51 @@ int drgnn_iface_fill(const drgnn_iface_request* req, int64_t n_nodes, int64_t n_
     return 0;
 }
 
+// ---- docking scores of pose batches (drgnn_score.h) -------------------------------------------------
+int drgnn_dock_scores(const drgnn_score_request* q, void* stream) {
+    if (!q || !q->host_zone_ptr || !q->host_zone_atom || !q->host_atom_ptr || !q->zone_atom || !q->zone_ref ||
+        !q->atom_ptr || !q->xyz || !q->scores || !q->classes || !q->n_preserved)
+        return DRGNN_E_ARG;
+    const int64_t M = q->n_poses, T = q->n_atoms, R = q->n_residues, P = q->n_pairs;
+    if (M < 0 || T < 1 || R < 1 || P < 0 || q->n_ref_pairs < 1 || P > q->n_ref_pairs || !(q->fnat_cutoff >= 0.0))
+        return DRGNN_E_ARG;
+    if (P > 0 && (!q->pair_res || !q->host_pair_res)) return DRGNN_E_ARG;
+    if (M > INT32_MAX || T > INT32_MAX / 3 || R >= INT32_MAX || q->n_ref_pairs > INT32_MAX) return DRGNN_E_CAPACITY;
+    const int32_t *zp = q->host_zone_ptr, *za = q->host_zone_atom, *ap = q->host_atom_ptr, *pr = q->host_pair_res;
+    if (zp[0] != 0) return DRGNN_E_ARG;
+    for (int z = 0; z < 3; ++z)
+        if (zp[z + 1] < zp[z] || zp[z + 1] - zp[z] < 3) return DRGNN_E_ARG;
+    for (int64_t i = 0; i < zp[3]; ++i)
+        if (za[i] < 0 || za[i] >= T) return DRGNN_E_ARG;
+    if (ap[0] != 0 || ap[R] != T) return DRGNN_E_ARG;
+    for (int64_t r = 0; r < R; ++r)
+        if (ap[r + 1] < ap[r]) return DRGNN_E_ARG;
+    int amax = 1;
+    for (int64_t p = 0; p < P; ++p) {
+        const int32_t ra = pr[2 * p], rb = pr[2 * p + 1];
+        if (ra < 0 || ra >= R || rb < 0 || rb >= R) return DRGNN_E_ARG;
+        amax = std::max(amax, ap[ra + 1] - ap[ra]);
+    }
+    if ((int64_t)amax * SC_PCHUNK > INT32_MAX) return DRGNN_E_CAPACITY;
+    if (M == 0) return 0;
+    ScoreArgs a;
+    memset(&a, 0, sizeof(a));
+    a.xyz = q->xyz; a.zone_atom = q->zone_atom; a.zone_ref = q->zone_ref; a.pair_res = q->pair_res; a.atom_ptr = q->atom_ptr;
+    for (int z = 0; z < 4; ++z) a.zp[z] = zp[z];
+    a.n_atoms = (int)T; a.n_pairs = (int)P; a.n_ref_pairs = (int)q->n_ref_pairs; a.amax = amax;
+    a.cut2 = (float)(q->fnat_cutoff * q->fnat_cutoff);
+    a.scores = q->scores; a.classes = q->classes; a.n_preserved = q->n_preserved;
+#ifdef DRGNN_EMU
+    (void)stream;
+    std::vector<double> lds(SC_LDS_BYTES / 8 + 1);
+    for (int64_t m = 0; m < M; ++m) score_pose(a, m, lds.data());
+#else
+    hipLaunchKernelGGL(k_dock_scores, dim3((unsigned)M), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+#endif
+    return 0;
+}
+
 // ---- evaluation scores (drgnn_metrics.h) ---------------------------------------------------------
 int64_t drgnn_metrics_workspace_bytes(int64_t n) {
     if (n < 0 || n > INT32_MAX) return -1;

@@ -12,6 +12,7 @@
 #include "drgnn_mcl.h"
 #include "drgnn_louvain.h"
 #include "drgnn_iface.h"
+#include "drgnn_score.h"
 #include "drgnn_metrics.h"
 #include "drgnn_collate.h"
 #include "drgnn_p2p.h"
@@ -985,6 +986,11 @@ __global__ void __launch_bounds__(DRGNN_NTHREADS) k_iface_scan(IfaceArgs a) {
 __global__ void __launch_bounds__(DRGNN_NTHREADS) k_iface_offsets(IfaceArgs a) {
     __shared__ int part[DRGNN_NTHREADS + 1];
     iface_offsets_block(a, part);
+}
+// docking scores (drgnn_score.h): one workgroup per pose
+__global__ void __launch_bounds__(DRGNN_NTHREADS) k_dock_scores(ScoreArgs a) {
+    __shared__ double smem_sc[SC_LDS_BYTES / 8];
+    score_pose(a, (int64_t)blockIdx.x, smem_sc);
 }
 // evaluation scores (drgnn_metrics.h)
 __global__ void __launch_bounds__(MT_NT) k_mt_reduce(MetricsArgs a, int centred) {

@@ -9,10 +9,20 @@ generation (``ResidueGraph`` / ``GraphGenMP``: ResidueGraph.py:108-145, 207-245,
     store = interface_graphs(poses, names)
 
 Covered: nodes, interface and internal edges with their ``dist``, and the node features that come from the
-coordinates or from a table (``pos``, ``chain``, ``type``, ``polarity``, ``charge``).  Not covered: ``bsa`` (needs a
-SASA program), ``depth`` / ``hse`` (Biopython), PSSM file parsing (``pssm``, ``cons``, ``ic``) and the scores
-(``irmsd``, ``dockQ`` ...).  For those every graph carries ``node_data/residue``, each node's index among the
-residues of its ``AtomTable``: a per-residue array the caller holds is attached with ``attach_residue_features``.
+coordinates or from a table (``pos``, ``chain``, ``type``, ``polarity``, ``charge``), and the scores against a
+reference structure (``irmsd``, ``lrmsd``, ``fnat``, ``dockQ``, ``binclass``, ``capri_class``: Graph.get_score,
+Graph.py:27-59):
+
+    names = read_pdb_atom_names("1ATN_1w.pdb")
+    table = AtomTable(chain, res_seq, res_name, xyz, atom_name=names)
+    rc, rs, _, rx = read_pdb_atoms("1ATN.pdb"); rn = read_pdb_atom_names("1ATN.pdb")
+    ref = ScoreReference(table, rc, rs, rn, rx)                # once per complex, on the host
+    scores = docking_scores(poses, ref)                        # dict of arrays [M], one launch per chunk of poses
+    store = interface_graphs(poses, names, reference=ref)      # the graphs with score/<target> on every molecule
+
+Not covered: ``bsa`` (needs a SASA program), ``depth`` / ``hse`` (Biopython) and PSSM file parsing (``pssm``,
+``cons``, ``ic``).  For those every graph carries ``node_data/residue``, each node's index among the residues of its
+``AtomTable``: a per-residue array the caller holds is attached with ``attach_residue_features``.
 
 Order (fixed here; the reference's is networkx insertion order): nodes by (chain, position of the residue in the
 input), interface edges (A node, B node) and internal edges (i < j) sorted by their pair.
@@ -50,15 +60,27 @@ def read_pdb_atoms(path):
             np.array(xyz, dtype=np.float64).reshape(-1, 3))
 
 
+def read_pdb_atom_names(path):
+    """atom names str [T] (columns 13-16, stripped) of the ``ATOM`` records of a PDB file: the records and the order
+    of ``read_pdb_atoms``."""
+    names = []
+    with open(path) as f:
+        for line in f:
+            if line.startswith("ATOM  "):
+                names.append(line[12:16].strip())
+    return np.array(names, dtype="U4")
+
+
 class AtomTable(object):
     """The atoms of one two-chain complex grouped for the kernels: atoms sorted by residue, residues of chain A
     (in order of first appearance in the input) before those of chain B.  A residue is (chain, res_seq).
 
     ``order`` [T] input position of each kept atom; ``atom_ptr`` int32 [R+1]; ``split`` = number of chain-A residues;
     ``res_chain`` / ``res_seq`` / ``res_name`` / ``res_type`` per residue (type -1: not one of the 20 standard names);
-    ``xyz`` float32 [T,3] in the grouped order."""
+    ``xyz`` float32 [T,3] in the grouped order; ``atom_name`` [T] in the grouped order when given (the scores match
+    atoms by it), else None."""
 
-    def __init__(self, chain, res_seq, res_name, xyz, chains=("A", "B")):
+    def __init__(self, chain, res_seq, res_name, xyz, chains=("A", "B"), atom_name=None):
         chain = np.asarray(chain).astype("U")
         res_seq = np.asarray(res_seq).astype(np.int64)
         res_name = np.asarray(res_name).astype("U")
@@ -89,6 +111,12 @@ class AtomTable(object):
         self.chains = tuple(chains)
         self.n_input_atoms = int(chain.shape[0])
         self.xyz = np.ascontiguousarray(xyz[self.order], dtype=np.float32)
+        self.atom_name = None
+        if atom_name is not None:
+            atom_name = np.asarray(atom_name).astype("U")
+            if atom_name.shape != chain.shape:
+                raise ValueError("atom_name [T] must describe the same atoms")
+            self.atom_name = atom_name[self.order]
 
     @property
     def n_residues(self):
@@ -214,13 +242,15 @@ def default_chunk(api, max_res_a, max_res_b, max_atoms, budget=WORKSPACE_BUDGET)
 
 
 def interface_graphs(tables_or_poses, names, contact_distance=8.5, internal_contact_distance=3.0, device=None, chunk=None,
-                     api=None):
+                     api=None, reference=None):
     """Interface graphs of complexes (a sequence of ``AtomTable``, an ``AtomTable.poses`` batch, or a mix) as a
     ``GraphStore`` with one molecule per name, in the reference's tree: ``edge_index``, ``edge_data/dist``,
     ``internal_edge_index``, ``internal_edge_data/dist``, ``nodes`` and, under ``node_data/``, ``pos``, ``chain``,
     ``type`` (one-hot 20), ``polarity`` (one-hot 4), ``charge`` and ``residue`` (index into the table's residues).
     ``chunk``: complexes per kernel call, which bounds the dense workspace (default: what fits WORKSPACE_BUDGET
-    bytes); it changes no bit of the result.  ``api`` / ``device``: the product library on the GPU unless given."""
+    bytes); it changes no bit of the result.  ``api`` / ``device``: the product library on the GPU unless given.
+    ``reference``: a ``ScoreReference``; every complex must then be a pose of its table, and every molecule also gets
+    ``score/irmsd``, ``score/lrmsd``, ``score/fnat``, ``score/dockQ``, ``score/binclass``, ``score/capri_class``."""
     from .dataset import GraphStore
     api = api or _lib.get()
     if device is None:
@@ -229,6 +259,8 @@ def interface_graphs(tables_or_poses, names, contact_distance=8.5, internal_cont
     names = [str(n) for n in names]
     if len(names) != len(cx):
         raise ValueError("%d names for %d complexes" % (len(names), len(cx)))
+    if reference is not None and not all(t is reference.table for t, _ in cx):
+        raise ValueError("with `reference`, every complex must be a pose of the reference's AtomTable")
     if chunk is None:
         chunk = default_chunk(api, max([t.split for t, _ in cx] + [0]), max([t.n_residues - t.split for t, _ in cx] + [0]),
                               max([t.n_atoms for t, _ in cx] + [0]))
@@ -258,7 +290,10 @@ def interface_graphs(tables_or_poses, names, contact_distance=8.5, internal_cont
                 "node_data/charge": RESIDUE_CHARGE[typ].astype(np.float64),
                 "node_data/residue": residue,
             })
-    return GraphStore.from_trees(names, trees)
+    store = GraphStore.from_trees(names, trees)
+    if reference is not None and cx:
+        attach_scores(store, names, docking_scores(np.stack([x for _, x in cx]), reference, device=device, api=api))
+    return store
 
 
 def attach_residue_features(store, name, per_residue_array):
@@ -268,4 +303,176 @@ def attach_residue_features(store, name, per_residue_array):
     for mol in store.mols():
         table = per_residue_array[mol] if isinstance(per_residue_array, dict) else per_residue_array
         store.set(mol, "node_data/" + name, np.asarray(table)[store.get(mol, "node_data/residue")])
+    return store
+
+
+# ---- docking scores (csrc/drgnn_score.h) -------------------------------------------------------------------------------
+BACKBONE = ("CA", "C", "N", "O")
+SCORE_KEYS = ("irmsd", "lrmsd", "fnat", "dockQ", "binclass", "capri_class")
+SCORE_XYZ_BUDGET = 256 << 20       # bytes of pose coordinates one call uploads (sets the default chunk)
+
+
+def _residue_pairs(xyz_a, res_a, xyz_b, res_b, n_res_b, cutoff, rows=256):
+    """sorted unique res_a * n_res_b + res_b over the atom pairs at d <= cutoff (float64), ``rows`` atoms of A at a
+    time"""
+    found = []
+    for lo in range(0, xyz_a.shape[0], rows):
+        d = xyz_a[lo:lo + rows, None, :] - xyz_b[None, :, :]
+        i, j = np.nonzero(np.sqrt((d * d).sum(axis=2)) <= cutoff)
+        found.append(np.unique(res_a[lo + i] * n_res_b + res_b[j]))
+    return np.unique(np.concatenate(found)) if found else np.zeros(0, dtype=np.int64)
+
+
+class ScoreReference(object):
+    """The once-per-complex half of the scores, on the host: the reference structure's residue pairs (an atom pair at
+    d <= ``fnat_cutoff``, all atoms) and interface zone (the residues of the pairs at d <= ``izone_cutoff``), the
+    matching of the table's atoms to the reference's by (chain, res_seq, atom name), the long chain (more residues in
+    the reference, the first chain on a tie) and the four tables ``drgnn_dock_scores`` takes (include/drgnn.h).
+
+    ``ref_chain`` / ``ref_res_seq`` / ``ref_atom_name`` [N] and ``ref_xyz`` [N,3]: the reference's atoms in any order;
+    it may hold other atoms, residues and numbering than the decoy: what does not match is ignored on both sides.
+    ``n_ref_pairs``: the reference's residue pairs (fnat's denominator); ``n_pairs``: those whose two residues the
+    decoy has; ``zone_sizes``: matched backbone atoms of (interface zone, long chain, short chain); ``long_chain``."""
+
+    def __init__(self, table, ref_chain, ref_res_seq, ref_atom_name, ref_xyz, izone_cutoff=10.0, fnat_cutoff=5.0):
+        if table.atom_name is None:
+            raise ValueError("the scores match atoms by name: build the AtomTable with atom_name=")
+        ref_chain = np.asarray(ref_chain).astype("U")
+        seq = np.asarray(ref_res_seq).astype(np.int64)
+        name = np.asarray(ref_atom_name).astype("U")
+        xyz = np.asarray(ref_xyz, dtype=np.float64)
+        if not (ref_chain.shape == seq.shape == name.shape == xyz.shape[:1]) or xyz.shape[1:] != (3,):
+            raise ValueError("ref_chain, ref_res_seq, ref_atom_name [N] and ref_xyz [N,3] must describe the same atoms")
+        self.table = table
+        self.izone_cutoff, self.fnat_cutoff = float(izone_cutoff), float(fnat_cutoff)
+        side = np.full(ref_chain.shape, -1, dtype=np.int64)
+        side[ref_chain == table.chains[0]] = 0
+        side[ref_chain == table.chains[1]] = 1
+        at = [np.flatnonzero(side == s) for s in (0, 1)]
+        useq, inv = zip(*[np.unique(seq[a], return_inverse=True) for a in at])       # residues of each chain by res_seq
+        if len(useq[0]) == 0 or len(useq[1]) == 0:
+            raise ValueError("the reference has no atoms of chain %r or %r" % tuple(table.chains))
+        nb = len(useq[1])
+        near = [_residue_pairs(xyz[at[0]], inv[0], xyz[at[1]], inv[1], nb, c) for c in (self.fnat_cutoff, self.izone_cutoff)]
+        self.n_ref_pairs = int(near[0].shape[0])
+        if self.n_ref_pairs == 0:
+            raise ValueError("the reference has no residue pair within %g" % self.fnat_cutoff)
+        zone = (set(useq[0][near[1] // nb].tolist()), set(useq[1][near[1] % nb].tolist()))
+        self.long_chain = 0 if len(useq[0]) >= len(useq[1]) else 1
+        # the table's residues by (side, res_seq); the reference pairs whose two residues the decoy has
+        res_of = {(int(c), int(q)): r for r, (c, q) in enumerate(zip(table.res_chain, table.res_seq))}
+        pairs = [(res_of.get((0, int(useq[0][k // nb]))), res_of.get((1, int(useq[1][k % nb])))) for k in near[0]]
+        pairs = [p for p in pairs if p[0] is not None and p[1] is not None]
+        self.pair_res = np.array(pairs, dtype=np.int32).reshape(-1, 2)
+        # matching: the first reference atom of every (side, res_seq, name)
+        ref_of = {}
+        for k in np.flatnonzero(side >= 0)[::-1]:
+            ref_of[(int(side[k]), int(seq[k]), str(name[k]))] = int(k)
+        res_of_atom = np.repeat(np.arange(table.n_residues), np.diff(table.atom_ptr))
+        zones = ([], [], [])
+        for i in np.flatnonzero(np.isin(table.atom_name, BACKBONE)):
+            r = res_of_atom[i]
+            c, q = int(table.res_chain[r]), int(table.res_seq[r])
+            k = ref_of.get((c, q, str(table.atom_name[i])))
+            if k is None:
+                continue
+            if q in zone[c]:
+                zones[0].append((i, k))
+            zones[1 if c == self.long_chain else 2].append((i, k))
+        self.zone_sizes = tuple(len(z) for z in zones)
+        if min(self.zone_sizes) < 3:
+            raise ValueError("a zone of fewer than 3 matched backbone atoms (interface, long chain, short chain: %d, %d, %d)"
+                             % self.zone_sizes)
+        both = np.array(zones[0] + zones[1] + zones[2], dtype=np.int64)
+        self.zone_atom = np.ascontiguousarray(both[:, 0], dtype=np.int32)
+        self.zone_ref = np.ascontiguousarray(xyz[both[:, 1]], dtype=np.float64)
+        self.zone_ptr = np.concatenate(([0], np.cumsum(self.zone_sizes))).astype(np.int32)
+        self.atom_ptr = np.ascontiguousarray(table.atom_ptr, dtype=np.int32)
+        self._device = {}
+
+    @property
+    def n_pairs(self):
+        return int(self.pair_res.shape[0])
+
+    def device_tables(self, device):
+        """(zone_atom, zone_ref, pair_res, atom_ptr) on ``device``, uploaded once"""
+        key = str(torch.device(device))
+        if key not in self._device:
+            self._device[key] = tuple(torch.from_numpy(a).to(device) for a in
+                                      (self.zone_atom, self.zone_ref, self.pair_res.reshape(-1), self.atom_ptr))
+        return self._device[key]
+
+
+def dock_scores_raw(api, xyz, zone_atom, zone_ptr, zone_ref, pair_res, atom_ptr, n_ref_pairs, fnat_cutoff=5.0, device="cpu",
+                    tables=None):
+    """One drgnn_dock_scores call (include/drgnn.h) over numpy arrays: xyz float32 [M,T,3].  Returns (scores float64
+    [M,4], classes int32 [M,2], n_preserved int32 [M]) as numpy arrays.  ``tables``: the four index tables already on
+    the device."""
+    dev = torch.device(device)
+    xyz = np.ascontiguousarray(xyz, dtype=np.float32)
+    host = [np.ascontiguousarray(zone_atom, dtype=np.int32), np.ascontiguousarray(zone_ptr, dtype=np.int32),
+            np.ascontiguousarray(np.asarray(pair_res).reshape(-1), dtype=np.int32), np.ascontiguousarray(atom_ptr, dtype=np.int32)]
+    if host[1].shape != (4,) or xyz.ndim != 3 or xyz.shape[2] != 3:
+        raise ValueError("zone_ptr [4] and xyz [M,T,3]")
+    if tables is None:
+        tables = (torch.from_numpy(host[0]).to(dev), torch.from_numpy(np.ascontiguousarray(zone_ref, dtype=np.float64)).to(dev),
+                  torch.from_numpy(host[2]).to(dev), torch.from_numpy(host[3]).to(dev))
+    d_xyz = torch.from_numpy(xyz).to(dev)
+    if api is _lib._API:
+        _lib.require_device(d_xyz)
+    M = int(xyz.shape[0])
+    scores = torch.empty((M, 4), dtype=torch.float64, device=dev)
+    classes = torch.empty((M, 2), dtype=torch.int32, device=dev)
+    kept = torch.empty(M, dtype=torch.int32, device=dev)
+    q = _lib.ScoreRequest()
+    q.xyz = d_xyz.data_ptr()
+    q.zone_atom, q.zone_ref, q.pair_res, q.atom_ptr = [t.data_ptr() if t.numel() else None for t in tables]
+    q.host_zone_atom, q.host_zone_ptr, q.host_pair_res, q.host_atom_ptr = [h.ctypes.data if h.size else None for h in host]
+    q.n_poses, q.n_atoms, q.n_residues, q.n_pairs = M, int(xyz.shape[1]), len(host[3]) - 1, host[2].shape[0] // 2
+    q.n_ref_pairs, q.fnat_cutoff = int(n_ref_pairs), float(fnat_cutoff)
+    q.scores, q.classes, q.n_preserved = scores.data_ptr(), classes.data_ptr(), kept.data_ptr()
+    api.dock_scores(q, _lib.current_stream(d_xyz))
+    return scores.cpu().numpy(), classes.cpu().numpy(), kept.cpu().numpy()
+
+
+def docking_scores(poses_or_table, reference, device=None, api=None, chunk=None):
+    """The scores of M poses of ``reference.table`` (an ``AtomTable.poses`` batch, the table itself, or xyz float32
+    [M,T,3] already in the table's grouped atom order) against ``reference``: a dict of numpy arrays [M], ``irmsd``,
+    ``lrmsd`` (A), ``fnat``, ``dockQ`` float64, ``binclass``, ``capri_class``, ``n_preserved`` int64.  One launch per
+    ``chunk`` poses (default: what keeps the uploaded coordinates within SCORE_XYZ_BUDGET bytes); a pose's result does
+    not depend on the chunk, on its place in the batch or on the run."""
+    api = api or _lib.get()
+    if device is None:
+        device = "cuda" if api is _lib._API else "cpu"
+    t = reference.table
+    if isinstance(poses_or_table, (Poses, AtomTable)):
+        if (poses_or_table.table if isinstance(poses_or_table, Poses) else poses_or_table) is not t:
+            raise ValueError("the poses must be of the reference's AtomTable")
+        xyz = poses_or_table.xyz if isinstance(poses_or_table, Poses) else poses_or_table.xyz[None]
+    else:
+        xyz = np.asarray(poses_or_table)
+    if xyz.ndim != 3 or xyz.shape[1:] != (t.n_atoms, 3):
+        raise ValueError("poses need xyz [M, %d, 3]" % t.n_atoms)
+    if chunk is None:
+        chunk = SCORE_XYZ_BUDGET // (12 * max(t.n_atoms, 1))
+    chunk = max(1, int(chunk))
+    tables = reference.device_tables(device)
+    parts = [dock_scores_raw(api, xyz[lo:lo + chunk], reference.zone_atom, reference.zone_ptr, reference.zone_ref,
+                             reference.pair_res, reference.atom_ptr, reference.n_ref_pairs, reference.fnat_cutoff, device, tables)
+             for lo in range(0, xyz.shape[0], chunk)]
+    sc = np.concatenate([p[0] for p in parts]) if parts else np.zeros((0, 4))
+    cl = np.concatenate([p[1] for p in parts]) if parts else np.zeros((0, 2), np.int32)
+    kept = np.concatenate([p[2] for p in parts]) if parts else np.zeros(0, np.int32)
+    return {"irmsd": sc[:, 0].copy(), "lrmsd": sc[:, 1].copy(), "fnat": sc[:, 2].copy(), "dockQ": sc[:, 3].copy(),
+            "binclass": cl[:, 0].astype(np.int64), "capri_class": cl[:, 1].astype(np.int64), "n_preserved": kept.astype(np.int64)}
+
+
+def attach_scores(store, names, scores):
+    """``score/<key>`` of molecule ``names[i]`` of ``store`` = ``scores[key][i]`` for the keys of SCORE_KEYS that
+    ``scores`` (what ``docking_scores`` returns) holds; ``binclass`` is stored as a bool, as the reference does."""
+    for i, mol in enumerate(names):
+        for k in SCORE_KEYS:
+            if k in scores:
+                v = scores[k][i]
+                store.set(str(mol), "score/" + k, np.asarray(bool(v)) if k == "binclass" else np.asarray(v))
     return store

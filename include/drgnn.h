@@ -701,6 +701,55 @@ int drgnn_iface_fill(const drgnn_iface_request* req, int64_t n_nodes, int64_t n_
                      int32_t* node_residue, float* pos, int32_t* chain, int32_t* type, int64_t* edge_index, float* dist,
                      int64_t* internal_edge_index, float* internal_dist, void* stream);
 
+/* ---- docking scores of pose batches (drgnn_score.h) ---------------------------------------------------
+ * The targets the reference writes in Graph.get_score (Graph.py:27-59, through pdb2sql's StructureSimilarity) for M
+ * poses of one topology against one reference structure: irmsd, lrmsd, fnat, dockQ, bin_class, capri_class.  The
+ * once-per-complex work is the caller's (deeprank_gnn_amd.interface.ScoreReference); its rules:
+ *   matching   a decoy atom and a reference atom correspond when (chain, res_seq, atom name) are equal; unmatched
+ *              atoms are ignored on both sides.  Backbone atoms: CA, C, N, O.
+ *   fnat       a reference residue pair (a in A, b in B) exists when an atom pair of the reference lies at d <= 5.0 A,
+ *              over all atoms; it is preserved in a pose when an atom pair of the pose's residues a, b lies at
+ *              d^2 <= fnat_cutoff^2 (d^2 from fp32 coordinate differences, no contraction).  fnat = n_preserved /
+ *              n_ref_pairs; pair_res lists the P <= n_ref_pairs pairs whose two residues exist in the decoy, as residue
+ *              indices into atom_ptr: the others stay in the denominator.
+ *   irmsd      zone 0: the matched backbone atoms of the residues of the reference pairs found at d <= 10.0 A.  The
+ *              decoy is fitted onto the reference with the optimal proper rotation + translation; RMSD over the zone.
+ *   lrmsd      zone 1: the matched backbone atoms of the long chain (more residues in the reference; A on a tie), zone 2:
+ *              those of the short chain.  The fit is on zone 1, the RMSD over zone 2 under that transform.
+ *   dockQ      (fnat + 1 / (1 + (irmsd / 1.5)^2) + 1 / (1 + (lrmsd / 8.5)^2)) / 3
+ *   binclass   irmsd < 4.0;  capri_class: 5, lowered to 4, 3, 2, 1 while irmsd < 6.0, 4.0, 2.0, 1.0
+ * Inputs (device unless host_*): xyz f32 [M,T,3] the poses, atoms in one order; zone_atom i32 [Z] atom indices of the
+ * three zones back to back, zone_ptr i32 [4] (host only); zone_ref f64 [Z,3] the matched reference coordinates;
+ * pair_res i32 [P,2]; atom_ptr i32 [R+1] atom range of each residue.  The index tables are also given as HOST arrays:
+ * every check comes from them.  Outputs: scores f64 [M,4] irmsd, lrmsd (A), fnat, dockQ; classes i32 [M,2] binclass,
+ * capri_class; n_preserved i32 [M].  Distances are in the unit of the coordinates (A).
+ * Arithmetic: one pass over the zones' atoms gathers fp64 moments (sum p, sum q, sum |p|^2, sum |q|^2, sum p q^T) in a
+ * fixed slot order, reduced by a fixed tree; the rotation is the largest eigenpair of Horn's 4 x 4 matrix (cyclic
+ * Jacobi, fp64), the residual E0 - 2 lambda.  No floating-point atomics: a pose's result repeats bit for bit and does
+ * not depend on M, on its place in the batch or on the run.  One workgroup per pose, one launch. */
+typedef struct drgnn_score_request {
+    const float* xyz;
+    const int32_t* zone_atom;
+    const double* zone_ref;
+    const int32_t* pair_res;
+    const int32_t* atom_ptr;
+    const int32_t* host_zone_atom;     /* the index tables in host memory */
+    const int32_t* host_zone_ptr;      /* [4], host only */
+    const int32_t* host_pair_res;
+    const int32_t* host_atom_ptr;
+    int64_t n_poses, n_atoms, n_residues, n_pairs, n_ref_pairs;
+    double fnat_cutoff;
+    double* scores;
+    int32_t* classes;
+    int32_t* n_preserved;
+} drgnn_score_request;
+
+/* DRGNN_E_ARG, before any launch: a null pointer, an atom index outside [0, T) or a residue index outside [0, R), an
+ * atom_ptr that does not start at 0, decreases or ends elsewhere than T, a zone_ptr that does not start at 0 or
+ * decreases, a zone of fewer than 3 atoms, n_ref_pairs < 1, P > n_ref_pairs, a negative cut-off or count.
+ * DRGNN_E_CAPACITY: M or 3 T beyond 2^31 - 1.  No allocation, no synchronisation. */
+int drgnn_dock_scores(const drgnn_score_request* req, void* stream);
+
 /* ---- device-resident graph set and mini-batch assembly --------------------
  * Replaces the host collate of every mini-batch: torch_geometric DataLoader -> Batch.from_data_list over
  * HDF5DataSet.load_one_graph's Data objects (NeuralNet.py:153-154, DataSet.py:231-366).  The set is the
