@@ -7,7 +7,13 @@ unweighted INTERNAL-contact graph of every complex, pools that graph with the re
 clusters the pooled graph again, and stores both label vectors with the dataset
 (``clustering/mcl/depth_0`` and ``depth_1``); training only reads them back.  ``precluster`` does the
 same for a ``Batch``: one workgroup per graph, dense fp64 (``drgnn_mcl``), pooling through the
-topology builder.  Pinned on the fixture's stored labels (all graphs, both depths, exact).
+topology builder.  Pinned on the fixture's stored labels (all graphs, both depths, exact) and, against
+``oracle/mcl_ref.py``, on the named and random graphs of ``tests/mcl_check.py`` (labels and iteration count).
+Markov clustering is not a stable function of its input: on symmetric graphs (cycles, for one) rounding
+decides ties, so labels and iteration count there depend on the summation order and are only checked to be in
+range and the same on every launch.  ``mcl_labels`` returns ``info`` (iterations used, negative when a graph
+did not converge within 100), but neither ``precluster`` nor ``PreCluster`` nor ``community_detection`` looks at
+it: a graph that did not converge gets the labels of its last iterate, silently.
 
 ``method='louvain'`` (the reference's python-louvain ``best_partition``) runs a deterministic Louvain
 (``drgnn_louvain``, one 64-lane workgroup per graph, exact int64 arithmetic) through the same pooling path.  It
