@@ -141,6 +141,18 @@ class ScoreRequest(ctypes.Structure):
                 ("scores", _vp), ("classes", _vp), ("n_preserved", _vp)]
 
 
+class BsaRequest(ctypes.Structure):
+    """drgnn_bsa_request (include/drgnn.h): K target residues of a ragged batch of complexes for drgnn_bsa_residues;
+    ``host_*`` are addresses of host copies of the offset and target tables."""
+    _fields_ = [("xyz", _vp), ("atom_ptr", _vp), ("res_ptr", _vp), ("res_split", _vp), ("rad_complex", _vp),
+                ("rad_unbound", _vp), ("target_res", _vp), ("target_complex", _vp),
+                ("host_atom_ptr", _vp), ("host_res_ptr", _vp), ("host_res_split", _vp), ("host_target_res", _vp),
+                ("host_target_complex", _vp),
+                ("n_atoms", _c_i64), ("n_residues", _c_i64), ("n_complexes", _c_i64), ("n_targets", _c_i64),
+                ("n_radii", _c_i64), ("probe", ctypes.c_double), ("n_slices", _c_i32), ("reserved", _c_i32),
+                ("out", _vp), ("status", _vp)]
+
+
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p)
 
 
@@ -351,6 +363,9 @@ class Api(object):
         lib.drgnn_iface_count.argtypes = [ctypes.POINTER(IfaceRequest), _vp]
         lib.drgnn_iface_fill.argtypes = [ctypes.POINTER(IfaceRequest)] + [_c_i64] * 3 + [_vp] * 9
         lib.drgnn_dock_scores.argtypes = [ctypes.POINTER(ScoreRequest), _vp]
+        lib.drgnn_bsa_capacity.argtypes = [_c_i32]
+        lib.drgnn_bsa_capacity.restype = _c_i32
+        lib.drgnn_bsa_residues.argtypes = [ctypes.POINTER(BsaRequest), _vp]
         if lib.drgnn_abi_version() != 5:
             raise DrgnnError("ABI mismatch in %s" % path)
 
@@ -633,6 +648,12 @@ class Api(object):
 
     def dock_scores(self, request, stream):
         _check(self.lib.drgnn_dock_scores(ctypes.byref(request), stream), "drgnn_dock_scores")
+
+    def bsa_capacity(self, what):
+        return int(self.lib.drgnn_bsa_capacity(int(what)))
+
+    def bsa_residues(self, request, stream):
+        _check(self.lib.drgnn_bsa_residues(ctypes.byref(request), stream), "drgnn_bsa_residues")
 
     def iface_fill(self, request, n_nodes, n_edges, n_iedges, node_residue, pos, chain, type_, edge_index, dist,
                    internal_edge_index, internal_dist, stream):

@@ -2268,6 +2268,49 @@ int drgnn_dock_scores(const drgnn_score_request* q, void* stream) {
     return 0;
 }
 
+// ---- buried surface area of residues (drgnn_bsa.h) ---------------------------------------------------
+int32_t drgnn_bsa_capacity(int32_t what) { return what == 0 ? BS_NCAP : what == 1 ? BS_CCAP : what == 2 ? BS_MAX_SLICES : what == 3 ? BS_MAX_TARGETS : -1; }
+
+int drgnn_bsa_residues(const drgnn_bsa_request* q, void* stream) {
+    if (!q || !q->host_atom_ptr || !q->host_res_ptr || !q->status) return DRGNN_E_ARG;
+    const int64_t T = q->n_atoms, R = q->n_residues, M = q->n_complexes, K = q->n_targets, NR = q->n_radii;
+    if (T < 0 || R < 0 || M < 0 || K < 0 || NR < 0 || T > INT32_MAX / 3 || R >= INT32_MAX || K > INT32_MAX) return DRGNN_E_ARG;
+    if (M > 0 && (!q->host_res_split || !q->res_ptr || !q->res_split)) return DRGNN_E_ARG;
+    if (R > 0 && !q->atom_ptr) return DRGNN_E_ARG;
+    if (T > 0 && (!q->xyz || !q->rad_complex || !q->rad_unbound || NR < 1 || T % NR != 0)) return DRGNN_E_ARG;
+    if (K > 0 && (!q->host_target_res || !q->host_target_complex || !q->target_res || !q->target_complex || !q->out)) return DRGNN_E_ARG;
+    if (!(q->probe >= 0.0) || q->n_slices < 1) return DRGNN_E_ARG;
+    if (q->n_slices > BS_MAX_SLICES || K > BS_MAX_TARGETS) return DRGNN_E_CAPACITY;
+    const int32_t *ap = q->host_atom_ptr, *rp = q->host_res_ptr, *sp = q->host_res_split;
+    if (ap[0] != 0 || ap[R] != T || rp[0] != 0 || rp[M] != R) return DRGNN_E_ARG;
+    for (int64_t r = 0; r < R; ++r)
+        if (ap[r + 1] < ap[r]) return DRGNN_E_ARG;
+    for (int64_t c = 0; c < M; ++c)
+        if (rp[c + 1] < rp[c] || rp[c + 1] > R || sp[c] < rp[c] || sp[c] > rp[c + 1]) return DRGNN_E_ARG;
+    for (int64_t k = 0; k < K; ++k) {
+        const int32_t c = q->host_target_complex[k], r = q->host_target_res[k];
+        if (c < 0 || c >= M || r < rp[c] || r >= rp[c + 1]) return DRGNN_E_ARG;
+    }
+    if (K == 0) return 0;
+    BsaArgs a;
+    memset(&a, 0, sizeof(a));
+    a.xyz = q->xyz; a.atom_ptr = q->atom_ptr; a.res_ptr = q->res_ptr; a.res_split = q->res_split;
+    a.rad_c = q->rad_complex; a.rad_u = q->rad_unbound; a.tgt_res = q->target_res; a.tgt_cx = q->target_complex;
+    a.n_radii = (int)NR; a.n_slices = q->n_slices; a.probe = (float)q->probe; a.probe_d = q->probe;
+    a.out = q->out; a.status = q->status;
+#ifdef DRGNN_EMU
+    (void)stream;
+    std::unique_ptr<BsaShared> lds(new BsaShared);
+    for (int64_t k = 0; k < K; ++k) bsa_residue(a, k, *lds);
+#else
+    static_assert(sizeof(BsaShared) <= DRGNN_LDS_LIMIT, "the workgroup's lists fit the LDS");
+    HIP_TRY(hipFuncSetAttribute((const void*)k_bsa_residues, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(BsaShared)));
+    hipLaunchKernelGGL(k_bsa_residues, dim3((unsigned)K), dim3(DRGNN_NTHREADS), sizeof(BsaShared), (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+#endif
+    return 0;
+}
+
 // ---- evaluation scores (drgnn_metrics.h) ---------------------------------------------------------
 int64_t drgnn_metrics_workspace_bytes(int64_t n) {
     if (n < 0 || n > INT32_MAX) return -1;

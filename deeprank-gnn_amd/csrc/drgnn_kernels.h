@@ -13,6 +13,7 @@
 #include "drgnn_louvain.h"
 #include "drgnn_iface.h"
 #include "drgnn_score.h"
+#include "drgnn_bsa.h"
 #include "drgnn_metrics.h"
 #include "drgnn_collate.h"
 #include "drgnn_p2p.h"
@@ -991,6 +992,12 @@ __global__ void __launch_bounds__(DRGNN_NTHREADS) k_iface_offsets(IfaceArgs a) {
 __global__ void __launch_bounds__(DRGNN_NTHREADS) k_dock_scores(ScoreArgs a) {
     __shared__ double smem_sc[SC_LDS_BYTES / 8];
     score_pose(a, (int64_t)blockIdx.x, smem_sc);
+}
+// buried surface area (drgnn_bsa.h): one workgroup per target residue
+// (8 waves per SIMD: two workgroups per CU; the fp64 path of nearly tangent circles must not cost the others their registers)
+__global__ void __launch_bounds__(DRGNN_NTHREADS, 8) k_bsa_residues(BsaArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem_bs[];
+    bsa_residue(a, (int64_t)blockIdx.x, *(BsaShared*)smem_bs);
 }
 // evaluation scores (drgnn_metrics.h)
 __global__ void __launch_bounds__(MT_NT) k_mt_reduce(MetricsArgs a, int centred) {

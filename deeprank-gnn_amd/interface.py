@@ -20,8 +20,14 @@ Graph.py:27-59):
     scores = docking_scores(poses, ref)                        # dict of arrays [M], one launch per chunk of poses
     store = interface_graphs(poses, names, reference=ref)      # the graphs with score/<target> on every molecule
 
-Not covered: ``bsa`` (needs a SASA program), ``depth`` / ``hse`` (Biopython) and PSSM file parsing (``pssm``,
-``cons``, ``ic``).  For those every graph carries ``node_data/residue``, each node's index among the residues of its
+and the buried surface area of the interface residues (``bsa``: tools/BSA.py through freesasa's Lee-Richards
+method, with the reference's radii), which needs the atom names:
+
+    areas = residue_bsa(poses)                                 # float64 [M, R]: every residue of every pose
+    store = interface_graphs(poses, names, bsa=True)           # the graphs with node_data/bsa on every molecule
+
+Not covered: ``depth`` / ``hse`` (Biopython) and PSSM file parsing (``pssm``, ``cons``, ``ic``).  For those every
+graph carries ``node_data/residue``, each node's index among the residues of its
 ``AtomTable``: a per-residue array the caller holds is attached with ``attach_residue_features``.
 
 Order (fixed here; the reference's is networkx insertion order): nodes by (chain, position of the residue in the
@@ -242,7 +248,7 @@ def default_chunk(api, max_res_a, max_res_b, max_atoms, budget=WORKSPACE_BUDGET)
 
 
 def interface_graphs(tables_or_poses, names, contact_distance=8.5, internal_contact_distance=3.0, device=None, chunk=None,
-                     api=None, reference=None):
+                     api=None, reference=None, bsa=False):
     """Interface graphs of complexes (a sequence of ``AtomTable``, an ``AtomTable.poses`` batch, or a mix) as a
     ``GraphStore`` with one molecule per name, in the reference's tree: ``edge_index``, ``edge_data/dist``,
     ``internal_edge_index``, ``internal_edge_data/dist``, ``nodes`` and, under ``node_data/``, ``pos``, ``chain``,
@@ -250,7 +256,9 @@ def interface_graphs(tables_or_poses, names, contact_distance=8.5, internal_cont
     ``chunk``: complexes per kernel call, which bounds the dense workspace (default: what fits WORKSPACE_BUDGET
     bytes); it changes no bit of the result.  ``api`` / ``device``: the product library on the GPU unless given.
     ``reference``: a ``ScoreReference``; every complex must then be a pose of its table, and every molecule also gets
-    ``score/irmsd``, ``score/lrmsd``, ``score/fnat``, ``score/dockQ``, ``score/binclass``, ``score/capri_class``."""
+    ``score/irmsd``, ``score/lrmsd``, ``score/fnat``, ``score/dockQ``, ``score/binclass``, ``score/capri_class``.
+    ``bsa``: True, or a ``radii`` value of ``residue_bsa`` ("reference", "protor", a pair of arrays): every molecule also
+    gets ``node_data/bsa``, float64 [n,1], the buried surface area of exactly its nodes (one more launch per chunk)."""
     from .dataset import GraphStore
     api = api or _lib.get()
     if device is None:
@@ -261,6 +269,9 @@ def interface_graphs(tables_or_poses, names, contact_distance=8.5, internal_cont
         raise ValueError("%d names for %d complexes" % (len(names), len(cx)))
     if reference is not None and not all(t is reference.table for t, _ in cx):
         raise ValueError("with `reference`, every complex must be a pose of the reference's AtomTable")
+    bsa_mode = None if bsa is False or bsa is None else ("reference" if bsa is True else bsa)
+    if bsa_mode is not None:                                           # the radius tables refuse before any launch
+        bsa_radii_of = _radii_lookup([t for t, _ in cx], bsa_mode)
     if chunk is None:
         chunk = default_chunk(api, max([t.split for t, _ in cx] + [0]), max([t.n_residues - t.split for t, _ in cx] + [0]),
                               max([t.n_atoms for t, _ in cx] + [0]))
@@ -270,6 +281,10 @@ def interface_graphs(tables_or_poses, names, contact_distance=8.5, internal_cont
         part = cx[lo:lo + chunk]
         xyz, atom_ptr, res_ptr, split, res_type = _ragged(part)
         r = build_ragged(api, xyz, atom_ptr, res_ptr, split, res_type, contact_distance, internal_contact_distance, device)
+        if bsa_mode is not None:
+            node_res = [r["node_residue"][r["node_ptr"][k]:r["node_ptr"][k + 1]].astype(np.int64) - int(res_ptr[k])
+                        for k in range(len(part))]
+            buried = _bsa_chunk(api, part, node_res, bsa_radii_of, 1.4, 20, device, ragged=(xyz, atom_ptr, res_ptr, split))
         for k, (t, _) in enumerate(part):
             n0, n1 = r["node_ptr"][k:k + 2]
             e0, e1 = r["edge_ptr"][k:k + 2]
@@ -290,6 +305,8 @@ def interface_graphs(tables_or_poses, names, contact_distance=8.5, internal_cont
                 "node_data/charge": RESIDUE_CHARGE[typ].astype(np.float64),
                 "node_data/residue": residue,
             })
+            if bsa_mode is not None:
+                trees[-1]["node_data/bsa"] = buried[k][:, 2:3].copy()
     store = GraphStore.from_trees(names, trees)
     if reference is not None and cx:
         attach_scores(store, names, docking_scores(np.stack([x for _, x in cx]), reference, device=device, api=api))
@@ -476,3 +493,193 @@ def attach_scores(store, names, scores):
                 v = scores[k][i]
                 store.set(str(mol), "score/" + k, np.asarray(bool(v)) if k == "binclass" else np.asarray(v))
     return store
+
+
+# ---- buried surface area (csrc/drgnn_bsa.h) ----------------------------------------------------------------------------
+# ProtOr radii of the heavy atoms (the classifier freesasa applies to a PDB file): backbone, then the side chains
+BSA_BACKBONE = {"N": 1.64, "CA": 1.88, "C": 1.61, "O": 1.42, "OXT": 1.46}
+_C, _N, _O1, _O2, _S, _CT, _CR = 1.88, 1.64, 1.42, 1.46, 1.77, 1.61, 1.76          # _CT trigonal, _CR aromatic CH carbon
+BSA_SIDE_CHAIN = {
+    "ALA": {"CB": _C},
+    "ARG": {"CB": _C, "CG": _C, "CD": _C, "NE": _N, "CZ": _CT, "NH1": _N, "NH2": _N},
+    "ASN": {"CB": _C, "CG": _CT, "OD1": _O1, "ND2": _N},
+    "ASP": {"CB": _C, "CG": _CT, "OD1": _O1, "OD2": _O2},
+    "CYS": {"CB": _C, "SG": _S},
+    "GLN": {"CB": _C, "CG": _C, "CD": _CT, "OE1": _O1, "NE2": _N},
+    "GLU": {"CB": _C, "CG": _C, "CD": _CT, "OE1": _O1, "OE2": _O2},
+    "GLY": {},
+    "HIS": {"CB": _C, "CG": _CT, "ND1": _N, "CD2": _CR, "CE1": _CR, "NE2": _N},
+    "ILE": {"CB": _C, "CG1": _C, "CG2": _C, "CD1": _C},
+    "LEU": {"CB": _C, "CG": _C, "CD1": _C, "CD2": _C},
+    "LYS": {"CB": _C, "CG": _C, "CD": _C, "CE": _C, "NZ": _N},
+    "MET": {"CB": _C, "CG": _C, "SD": _S, "CE": _C},
+    "PHE": {"CB": _C, "CG": _CT, "CD1": _CR, "CD2": _CR, "CE1": _CR, "CE2": _CR, "CZ": _CR},
+    "PRO": {"CB": _C, "CG": _C, "CD": _C},
+    "SER": {"CB": _C, "OG": _O2},
+    "THR": {"CB": _C, "OG1": _O2, "CG2": _C},
+    "TRP": {"CB": _C, "CG": _CT, "CD1": _CR, "CD2": _CT, "NE1": _N, "CE2": _CT, "CE3": _CR, "CZ2": _CR, "CZ3": _CR, "CH2": _CR},
+    "TYR": {"CB": _C, "CG": _CT, "CD1": _CR, "CD2": _CR, "CE1": _CR, "CE2": _CR, "CZ": _CT, "OH": _O2},
+    "VAL": {"CB": _C, "CG1": _C, "CG2": _C},
+}
+# the unbound chains of the reference: it hands freesasa only the first character of the atom name
+BSA_FIRST_LETTER = {"C": 1.61, "N": 1.64, "O": 1.42, "S": 1.80, "H": 1.10}
+BSA_XYZ_BUDGET = 256 << 20         # bytes of coordinates one call uploads (sets the default chunk)
+
+
+def bsa_radii(table, radii="reference"):
+    """(complex_r, unbound_r) float64 [T] in the table's grouped atom order; 0: the atom is absent from that state.
+
+    "reference": what the reference's ``bsa`` feature uses.  Complex: heavy atoms only (the name does not start with
+    H) with ProtOr radii by (residue, atom name); a heavy atom outside the table or a non-standard residue raises
+    ValueError.  Unbound: every atom, hydrogens included, the radius from the first character of its name (C 1.61, N
+    1.64, O 1.42, S 1.80, H 1.10; any other raises ValueError).  "protor": the complex radii for both states.
+    A pair ``(complex_r, unbound_r)`` of arrays [n_input_atoms] in input atom order is taken as it is."""
+    if isinstance(radii, str):
+        if radii not in ("reference", "protor"):
+            raise ValueError("radii must be 'reference', 'protor' or a pair of arrays, not %r" % radii)
+        if table.atom_name is None:
+            raise ValueError("the radius tables go by atom name: build the AtomTable with atom_name=")
+        bad = np.flatnonzero(table.res_type < 0)
+        if bad.size:
+            r = int(bad[0])
+            raise ValueError("no radii for the non-standard residue %s %s%d" % (table.res_name[r], table.chains[table.res_chain[r]],
+                                                                               table.res_seq[r]))
+        res_of_atom = np.repeat(np.arange(table.n_residues), np.diff(table.atom_ptr))
+        cr = np.zeros(table.n_atoms)
+        ur = np.zeros(table.n_atoms)
+        for i, nm in enumerate(table.atom_name):
+            nm = str(nm)
+            if radii == "reference":
+                if nm[:1] not in BSA_FIRST_LETTER:
+                    raise ValueError("no radius for an atom whose name starts with %r (%s)" % (nm[:1], nm))
+                ur[i] = BSA_FIRST_LETTER[nm[0]]
+            if not nm.startswith("H"):
+                res = str(table.res_name[res_of_atom[i]])
+                rad = BSA_BACKBONE.get(nm, BSA_SIDE_CHAIN[res].get(nm))
+                if rad is None:
+                    raise ValueError("no ProtOr radius for the heavy atom %s of %s" % (nm, res))
+                cr[i] = rad
+        return (cr, cr.copy()) if radii == "protor" else (cr, ur)
+    try:
+        cr, ur = radii
+    except (TypeError, ValueError):
+        raise ValueError("radii must be 'reference', 'protor' or a pair (complex_r, unbound_r)")
+    out = []
+    for a in (cr, ur):
+        a = np.asarray(a, dtype=np.float64)
+        if a.shape != (table.n_input_atoms,):
+            raise ValueError("radius arrays need %d entries, one per input atom" % table.n_input_atoms)
+        if not np.all(a >= 0.0):                                       # (NaN fails too)
+            raise ValueError("radii must be >= 0 (0: the atom is absent)")
+        out.append(a[table.order])
+    return tuple(out)
+
+
+def _radii_lookup(tables, radii):
+    """{id(table): (complex_r, unbound_r)}: each distinct table's radii, made once"""
+    found = {}
+    for t in tables:
+        if id(t) not in found:
+            found[id(t)] = bsa_radii(t, radii)
+    return found
+
+
+def bsa_raw(api, xyz, atom_ptr, res_ptr, res_split, rad_complex, rad_unbound, target_res, target_complex, probe=1.4,
+            n_slices=20, device="cpu"):
+    """One drgnn_bsa_residues call (include/drgnn.h) over numpy arrays.  Returns (out float64 [K,3]: sasa_unbound,
+    sasa_complex, bsa; status int): bit 0 of status says a list overflowed (those residues are NaN)."""
+    dev = torch.device(device)
+    host = [np.ascontiguousarray(a, dtype=np.int32) for a in (atom_ptr, res_ptr, res_split, target_res, target_complex)]
+    rad = [np.ascontiguousarray(a, dtype=np.float32) for a in (rad_complex, rad_unbound)]
+    if rad[0].shape != rad[1].shape or rad[0].ndim != 1 or host[3].shape != host[4].shape:
+        raise ValueError("the two radius arrays, and the two target arrays, must have one length each")
+    d_xyz = torch.from_numpy(np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)).to(dev)
+    if api is _lib._API:
+        _lib.require_device(d_xyz)
+    d_host = [torch.from_numpy(h).to(dev) for h in host]
+    d_rad = [torch.from_numpy(a).to(dev) for a in rad]
+    K = int(host[3].shape[0])
+    out = torch.empty((K, 3), dtype=torch.float64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    q = _lib.BsaRequest()
+    q.xyz = d_xyz.data_ptr()
+    q.atom_ptr, q.res_ptr, q.res_split, q.target_res, q.target_complex = [t.data_ptr() for t in d_host]
+    q.rad_complex, q.rad_unbound = [t.data_ptr() for t in d_rad]
+    (q.host_atom_ptr, q.host_res_ptr, q.host_res_split, q.host_target_res,
+     q.host_target_complex) = [h.ctypes.data for h in host]
+    q.n_atoms, q.n_residues, q.n_complexes = int(d_xyz.shape[0]), len(host[0]) - 1, len(host[1]) - 1
+    q.n_targets, q.n_radii = K, int(rad[0].shape[0])
+    q.probe, q.n_slices = float(probe), int(n_slices)
+    q.out, q.status = out.data_ptr(), status.data_ptr()
+    api.bsa_residues(q, _lib.current_stream(d_xyz))
+    return out.cpu().numpy(), int(status.cpu()[0])
+
+
+def _bsa_chunk(api, part, residues, radii_of, probe, n_slices, device, ragged=None):
+    """[out float64 [K_c,3]] for the complexes of ``part`` ([(table, xyz)]) and their residue lists (local indices)"""
+    if len(part) > 1 and sum(len(r) for r in residues) > api.bsa_capacity(3):      # one workgroup per target: the grid's limit
+        half = len(part) // 2
+        return (_bsa_chunk(api, part[:half], residues[:half], radii_of, probe, n_slices, device) +
+                _bsa_chunk(api, part[half:], residues[half:], radii_of, probe, n_slices, device))
+    xyz, atom_ptr, res_ptr, split = ragged if ragged is not None else _ragged(part)[:4]
+    tables = [t for t, _ in part]
+    if all(t is tables[0] for t in tables):                              # poses of one topology: one radius table
+        cr, ur = radii_of[id(tables[0])]
+    else:
+        cr = np.concatenate([radii_of[id(t)][0] for t in tables])
+        ur = np.concatenate([radii_of[id(t)][1] for t in tables])
+    sizes = [len(r) for r in residues]
+    tgt_res = np.concatenate([np.asarray(r, dtype=np.int64) + int(res_ptr[k]) for k, r in enumerate(residues)]
+                             + [np.zeros(0, np.int64)])
+    tgt_cx = np.repeat(np.arange(len(part)), sizes)
+    out, status = bsa_raw(api, xyz, atom_ptr, res_ptr, split, cr, ur, tgt_res, tgt_cx, probe, n_slices, device)
+    if status & 1:
+        _lib._check(-2, "drgnn_bsa_residues")
+    ends = np.cumsum(sizes)
+    return [out[e - n:e] for n, e in zip(sizes, ends)]
+
+
+def residue_bsa(tables_or_poses, residues=None, radii="reference", probe=1.4, n_slices=20, device=None, chunk=None, api=None,
+                parts=False):
+    """Buried surface area (A^2) of residues, on the device: SASA of the residue in its chain alone minus its SASA in
+    the complex, each by the Lee-Richards slice method (``probe`` 1.4 A, ``n_slices`` 20: what the reference's ``bsa``
+    node feature records, negative values included; see ``bsa_radii`` for ``radii``).
+
+    An ``AtomTable`` gives float64 [R], an ``AtomTable.poses`` batch [M, R], a sequence of either a list of [R_k], with
+    NaN for the residues not asked for.  ``residues``: None (all), an index array applied to every complex, or one
+    index array per complex.  Only the atoms of the residues asked for are evaluated.  ``chunk``: complexes per
+    launch; a residue's bits do not depend on it, on the batch or on ``residues``.  ``parts``: return (bsa,
+    sasa_unbound, sasa_complex) instead.  More than 256 neighbours of one atom is refused (DrgnnError, capacity)."""
+    api = api or _lib.get()
+    if device is None:
+        device = "cuda" if api is _lib._API else "cpu"
+    cx = _complexes(tables_or_poses)
+    if int(n_slices) < 1:
+        raise ValueError("n_slices must be at least 1")
+    if not float(probe) >= 0.0:
+        raise ValueError("probe must be >= 0")
+    radii_of = _radii_lookup([t for t, _ in cx], radii)
+    if residues is None:
+        wanted = [np.arange(t.n_residues) for t, _ in cx]
+    else:
+        per_complex = (isinstance(residues, (list, tuple)) and len(residues) == len(cx) and
+                       all(np.ndim(r) == 1 for r in residues))
+        wanted = [np.asarray(residues[k] if per_complex else residues, dtype=np.int64).reshape(-1) for k in range(len(cx))]
+        for (t, _), w in zip(cx, wanted):
+            if w.size and (w.min() < 0 or w.max() >= t.n_residues):
+                raise ValueError("a residue index outside [0, %d)" % t.n_residues)
+    if chunk is None:
+        chunk = BSA_XYZ_BUDGET // (12 * max([t.n_atoms for t, _ in cx] + [1]))
+    chunk = max(1, int(chunk))
+    full = [np.full((3, t.n_residues), np.nan) for t, _ in cx]
+    for lo in range(0, len(cx), chunk):
+        part = cx[lo:lo + chunk]
+        for k, o in enumerate(_bsa_chunk(api, part, wanted[lo:lo + chunk], radii_of, probe, n_slices, device)):
+            full[lo + k][:, wanted[lo + k]] = o.T
+    pick = (lambda f: (f[2], f[0], f[1])) if parts else (lambda f: f[2])
+    if isinstance(tables_or_poses, AtomTable):
+        return pick(full[0])
+    if isinstance(tables_or_poses, Poses):
+        stacked = np.stack(full) if full else np.zeros((0, 3, tables_or_poses.table.n_residues))
+        return pick(stacked.transpose(1, 0, 2))
+    return [pick(f) for f in full]

@@ -750,6 +750,57 @@ typedef struct drgnn_score_request {
  * DRGNN_E_CAPACITY: M or 3 T beyond 2^31 - 1.  No allocation, no synchronisation. */
 int drgnn_dock_scores(const drgnn_score_request* req, void* stream);
 
+/* ---- buried surface area of residues (drgnn_bsa.h) -----------------------------------------------------
+ * The reference's `bsa` node feature (tools/BSA.py, through freesasa's Lee-Richards method) for K chosen residues of a
+ * ragged batch of M two-chain complexes laid out as for drgnn_iface_count: xyz f32 [T,3], atom_ptr i32 [R+1], res_ptr
+ * i32 [M+1], res_split i32 [M].
+ *   bsa(residue) = SASA_unbound(residue) - SASA_complex(residue); a SASA is the sum of the Lee-Richards areas of the
+ *   residue's atoms: n_slices planes through the atom's expanded sphere (R = r + probe), slice k at z_i - R_i + delta
+ *   (k + 1/2), delta = 2 R_i / n_slices, contributing R_i delta (2 pi - the union of the arcs its neighbours bury).
+ * Two radius arrays f32 [n_radii] say who takes part: rad_complex in the complex (both chains), rad_unbound in the
+ * residue's chain alone; 0: the atom is absent from that state.  Atom t reads entry t % n_radii (n_radii divides T:
+ * poses of one topology share one table).  The radius tables of the reference are the caller's
+ * (deeprank_gnn_amd.interface.bsa_radii).  Targets: target_res i32 [K] residue indices into atom_ptr, target_complex i32
+ * [K] their complexes; only their atoms are evaluated, every atom of the state acts as a neighbour.
+ * Outputs: out f64 [K,3] sasa_unbound, sasa_complex, bsa (A^2); status i32 [1], to be zeroed by the caller: bit 0 is
+ * set when a residue met more than drgnn_bsa_capacity(1) candidate atoms around its bounding box or an atom more than
+ * drgnn_bsa_capacity(0) neighbours; that residue's three outputs are NaN (DRGNN_E_CAPACITY, reported through status
+ * because the call does not synchronise).
+ * One workgroup per target, one launch.  Arc arithmetic fp32 (fp64 for nearly tangent circles), gaps summed as 2^-40 rad integers, areas and residue
+ * sums fp64 in atom order: no floating-point atomics, a residue's bits do not depend on the batch, the target list, its
+ * place or the run.  The offset and target tables are also given as HOST arrays: every check comes from them. */
+typedef struct drgnn_bsa_request {
+    const float* xyz;
+    const int32_t* atom_ptr;
+    const int32_t* res_ptr;
+    const int32_t* res_split;
+    const float* rad_complex;
+    const float* rad_unbound;
+    const int32_t* target_res;
+    const int32_t* target_complex;
+    const int32_t* host_atom_ptr;      /* the tables in host memory */
+    const int32_t* host_res_ptr;
+    const int32_t* host_res_split;
+    const int32_t* host_target_res;
+    const int32_t* host_target_complex;
+    int64_t n_atoms, n_residues, n_complexes, n_targets, n_radii;
+    double probe;
+    int32_t n_slices, reserved;
+    double* out;
+    int32_t* status;
+} drgnn_bsa_request;
+
+/* the documented capacities: what = 0 neighbours of one atom (256), 1 candidate atoms of one residue, 2 the most
+ * slices, 3 the most targets of one call (one workgroup each: the grid's limit); -1 otherwise.  Pure host. */
+int32_t drgnn_bsa_capacity(int32_t what);
+
+/* DRGNN_E_ARG, before any launch: a null pointer, an offset table that does not start at 0, decreases or ends elsewhere
+ * than n_atoms / n_residues, a split outside its complex, a target outside its complex, n_radii that does not divide
+ * n_atoms, a negative probe, n_slices < 1.  DRGNN_E_CAPACITY: n_slices beyond drgnn_bsa_capacity(2), n_targets beyond
+ * drgnn_bsa_capacity(3) (split the call).  No allocation, no
+ * workspace, no synchronisation. */
+int drgnn_bsa_residues(const drgnn_bsa_request* req, void* stream);
+
 /* ---- device-resident graph set and mini-batch assembly --------------------
  * Replaces the host collate of every mini-batch: torch_geometric DataLoader -> Batch.from_data_list over
  * HDF5DataSet.load_one_graph's Data objects (NeuralNet.py:153-154, DataSet.py:231-366).  The set is the
