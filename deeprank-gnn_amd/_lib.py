@@ -436,24 +436,18 @@ class Api(object):
             n_edges, n_graphs, max_nodes, max_edges, max_c0, _ptr(xp), _ptr(arg0), _ptr(arg1),
             _ptr(grad_x), _ptr(partials), _ptr(scratch), _ptr(step_inc), stream), "drgnn_net_backward")
 
-    def train_update_opt(self, desc, conv_partials, n_graphs, g1, g2, head_partials, R, H, O, head_offset,
-                         flat_p, flat_g, exp_avg, exp_avg_sq, step, loss, optim, stream, apply_adam=True):
-        """drgnn_train_update under the options of ``optim`` (an Optim record)"""
-        _check(self.lib.drgnn_train_update_opt(
-            ctypes.byref(desc), _ptr(conv_partials), n_graphs, g1, g2, _ptr(head_partials),
-            head_partials.shape[0], R, H, O, head_offset, _ptr(flat_p), _ptr(flat_g), _ptr(exp_avg),
-            _ptr(exp_avg_sq), flat_p.numel(), _ptr(step), _ptr(loss), ctypes.byref(optim),
-            1 if apply_adam else 0, stream), "drgnn_train_update_opt")
-
     def train_update(self, desc, conv_partials, n_graphs, g1, g2, head_partials, R, H, O, head_offset,
                      flat_p, flat_g, exp_avg, exp_avg_sq, step, loss, lr, beta1, beta2, eps, stream,
-                     apply_adam=True):
-        _check(self.lib.drgnn_train_update(
-            ctypes.byref(desc), _ptr(conv_partials), n_graphs, g1, g2, _ptr(head_partials),
-            head_partials.size(0), R, H, O,
-            head_offset, _ptr(flat_p), _ptr(flat_g), _ptr(exp_avg), _ptr(exp_avg_sq), flat_p.numel(),
-            _ptr(step), _ptr(loss), lr, beta1, beta2, eps, 1 if apply_adam else 0, stream),
-            "drgnn_train_update")
+                     apply_adam=True, optim=None):
+        """``optim`` (an Optim record): drgnn_train_update_opt, Adam's scalars and the options from the record"""
+        args = (ctypes.byref(desc), _ptr(conv_partials), n_graphs, g1, g2, _ptr(head_partials), head_partials.size(0), R, H, O,
+                head_offset, _ptr(flat_p), _ptr(flat_g), _ptr(exp_avg), _ptr(exp_avg_sq), flat_p.numel(), _ptr(step), _ptr(loss))
+        if optim is None:
+            _check(self.lib.drgnn_train_update(*(args + (lr, beta1, beta2, eps, 1 if apply_adam else 0, stream))),
+                   "drgnn_train_update")
+        else:
+            _check(self.lib.drgnn_train_update_opt(*(args + (ctypes.byref(optim), 1 if apply_adam else 0, stream))),
+                   "drgnn_train_update_opt")
 
     # -- fused training step ------------------------------------------------------
     def step_plan(self, kind, n_feat, max_nodes, max_edges, max_c0, R, H, O, n_graphs, co_built_graphs=0, train=True,
@@ -533,35 +527,29 @@ class Api(object):
             ctypes.byref(desc), ctypes.byref(head), _ptr(members), int(K), ctypes.byref(cache), ids, counts, int(ids_stride),
             int(n_graphs), max_nodes, max_edges, max_c0, ctypes.byref(hints), stream), "drgnn_cohort_train_step_cached")
 
-    def cohort_update(self, desc, members, K, counts, g1, g2, R, H, O, head_offset, n_param, stream, losses=None, apply_adam=True):
-        """``counts`` / ``losses``: raw device addresses (this step's rows of the epoch's tables; ``losses`` may be None)"""
-        _check(self.lib.drgnn_cohort_update(ctypes.byref(desc), _ptr(members), int(K), counts, g1, g2, R, H, O, int(head_offset),
-                                            int(n_param), losses, 1 if apply_adam else 0, stream), "drgnn_cohort_update")
-
-    def cohort_update_opt(self, desc, members, optims, K, counts, g1, g2, R, H, O, head_offset, n_param, stream, losses=None,
-                          apply_adam=True, any_clip=False):
-        """drgnn_cohort_update with ``optims``, the device table of the members' Optim records"""
-        _check(self.lib.drgnn_cohort_update_opt(ctypes.byref(desc), _ptr(members), _ptr(optims), int(K), counts, g1, g2, R, H, O,
-                                                int(head_offset), int(n_param), losses, 1 if apply_adam else 0,
-                                                1 if any_clip else 0, stream), "drgnn_cohort_update_opt")
+    def cohort_update(self, desc, members, K, counts, g1, g2, R, H, O, head_offset, n_param, stream, losses=None, apply_adam=True,
+                      optims=None, any_clip=False):
+        """``counts`` / ``losses``: raw device addresses (this step's rows of the epoch's tables; ``losses`` may be None);
+        ``optims``: the device table of the members' Optim records (drgnn_cohort_update_opt)"""
+        head = (ctypes.byref(desc), _ptr(members))
+        tail = (int(K), counts, g1, g2, R, H, O, int(head_offset), int(n_param), losses, 1 if apply_adam else 0)
+        if optims is None:
+            _check(self.lib.drgnn_cohort_update(*(head + tail + (stream,))), "drgnn_cohort_update")
+        else:
+            _check(self.lib.drgnn_cohort_update_opt(*(head + (_ptr(optims),) + tail + (1 if any_clip else 0, stream))),
+                   "drgnn_cohort_update_opt")
 
     def step_update(self, desc, conv_partials, n_graphs, g1, g2, head_partials, readout, R, H, O, head_offset,
                     flat_p, flat_g, exp_avg, exp_avg_sq, step2, loss, lr, beta1, beta2, eps, stream,
-                    apply_adam=True, slabs_per_graph=0):
-        _check(self.lib.drgnn_step_update(
-            ctypes.byref(desc), _ptr(conv_partials), n_graphs, g1, g2, _ptr(head_partials), _ptr(readout),
-            R, H, O, head_offset, _ptr(flat_p), _ptr(flat_g), _ptr(exp_avg), _ptr(exp_avg_sq), flat_p.numel(),
-            _ptr(step2), _ptr(loss), lr, beta1, beta2, eps, 1 if apply_adam else 0, int(slabs_per_graph), stream),
-            "drgnn_step_update")
-
-    def step_update_opt(self, desc, conv_partials, n_graphs, g1, g2, head_partials, readout, R, H, O, head_offset,
-                        flat_p, flat_g, exp_avg, exp_avg_sq, step2, loss, optim, stream, apply_adam=True, slabs_per_graph=0):
-        """drgnn_step_update under the options of ``optim`` (an Optim record)"""
-        _check(self.lib.drgnn_step_update_opt(
-            ctypes.byref(desc), _ptr(conv_partials), n_graphs, g1, g2, _ptr(head_partials), _ptr(readout),
-            R, H, O, head_offset, _ptr(flat_p), _ptr(flat_g), _ptr(exp_avg), _ptr(exp_avg_sq), flat_p.numel(),
-            _ptr(step2), _ptr(loss), ctypes.byref(optim), 1 if apply_adam else 0, int(slabs_per_graph), stream),
-            "drgnn_step_update_opt")
+                    apply_adam=True, slabs_per_graph=0, optim=None):
+        """``optim`` (an Optim record): drgnn_step_update_opt, Adam's scalars and the options from the record"""
+        args = (ctypes.byref(desc), _ptr(conv_partials), n_graphs, g1, g2, _ptr(head_partials), _ptr(readout), R, H, O,
+                head_offset, _ptr(flat_p), _ptr(flat_g), _ptr(exp_avg), _ptr(exp_avg_sq), flat_p.numel(), _ptr(step2), _ptr(loss))
+        tail = (1 if apply_adam else 0, int(slabs_per_graph), stream)
+        if optim is None:
+            _check(self.lib.drgnn_step_update(*(args + (lr, beta1, beta2, eps) + tail)), "drgnn_step_update")
+        else:
+            _check(self.lib.drgnn_step_update_opt(*(args + (ctypes.byref(optim),) + tail)), "drgnn_step_update_opt")
 
     def step_gradients(self, desc, conv_partials, n_graphs, g1, g2, head_partials, readout, R, H, O, head_grad,
                        graph_weight, zero_ptr, zero_len, n_zero, step2, slabs_per_graph, stream):

@@ -208,13 +208,9 @@ class Cohort(MemberPack):
         api = self.api
         api.cohort_train_step_cached(self._desc0, head, self._table, self.K, desc, ids_ptr, counts_ptr, B, B,
                                      bounds[0], bounds[1], bounds[2], stream, hints)
-        if self._optims is not None:
-            api.cohort_update_opt(self._desc0, self._table, self._optims, self.K, counts_ptr, self._g1, self._g2, self.R,
-                                  self.H, self.O, self.head_offset, self.n_param, stream, losses=losses_ptr,
-                                  any_clip=self._any_clip)
-            return
         api.cohort_update(self._desc0, self._table, self.K, counts_ptr, self._g1, self._g2, self.R, self.H, self.O,
-                          self.head_offset, self.n_param, stream, losses=losses_ptr)
+                          self.head_offset, self.n_param, stream, losses=losses_ptr, optims=self._optims,
+                          any_clip=self._any_clip)
 
     def _prepare(self, cache, all_ids, B):
         """(plan, bounds, flags, tiles, cache descriptor, head descriptor, hints) of cohort launches of ``B`` graphs

@@ -1341,38 +1341,6 @@ int drgnn_cohort_train_step_cached(const drgnn_net_desc* net, const drgnn_head_d
 #endif
 }
 
-int drgnn_net_reduce_grads(const drgnn_net_desc* net, const float* partials, int64_t n_nodes,
-                           int64_t n_graphs, drgnn_conv_grads* g_conv1, drgnn_conv_grads* g_conv2,
-                           float* grad_x, void* stream_) {
-    int rc = net_check(net);
-    if (rc) return rc;
-    if (!partials || !g_conv1 || !g_conv2) return DRGNN_E_ARG;
-    ReduceArgs r;
-    r.partials = partials; r.n_graphs = (int)n_graphs; r.n_branch = net->n_branch;
-    r.n_feat = net->n_feat; r.n_partial = (int)net_partial_floats(net->n_feat); r.kind = net->kind;
-    for (int b = 0; b < DRGNN_MAX_BRANCH; ++b) {
-        r.lay1[b] = net->conv1[b]; r.lay2[b] = net->conv2[b];
-        if (b < net->n_branch) { r.g1[b] = g_conv1[b]; r.g2[b] = g_conv2[b]; }
-        else { r.g1[b] = drgnn_conv_grads{nullptr, nullptr, nullptr}; r.g2[b] = r.g1[b]; }
-    }
-    r.grad_x = grad_x; r.n_nodes = n_nodes;
-    int64_t items = (int64_t)net->n_branch * r.n_partial;
-    if (grad_x && net->n_branch > 1 && n_nodes * net->n_feat > items) items = n_nodes * net->n_feat;
-#ifdef DRGNN_EMU
-    for (int64_t i = 0; i < (int64_t)net->n_branch * r.n_partial; ++i) {
-        const int br = (int)(i / r.n_partial), p = (int)(i % r.n_partial);
-        if (reduce_live(r, p)) reduce_write(r, br, p, reduce_sum(r, br, p, 0, 1));
-    }
-    for (int64_t i = 0; grad_x && i < n_nodes * net->n_feat; ++i) reduce_grad_x(r, i);
-    (void)stream_; (void)items;
-#else
-    const int reduce_blocks = net->n_branch * ((r.n_partial + 63) / 64);      // (blocks do not straddle branches)
-    hipLaunchKernelGGL(k_reduce, dim3((unsigned)reduce_blocks), dim3(256), 0, (hipStream_t)stream_, r, items);
-    HIP_TRY(hipGetLastError());
-#endif
-    return 0;
-}
-
 // ---- dense head + loss + optimiser ----------------------------------------------------------
 int64_t drgnn_head_partial_elems(int32_t R, int32_t H, int32_t O) { return head_partial_floats(R, H, O); }
 int64_t drgnn_head_num_slabs(int64_t n_graphs) { const int t = head_tile(n_graphs); return (n_graphs + t - 1) / t; }
@@ -1624,68 +1592,102 @@ int drgnn_allreduce_oneshot(float* grad, int64_t n, void* const* peer_bufs, int3
 
 }  // extern "C"
 
-// `readout` null: legacy head slabs [head_slabs][head_partial_floats] (dW_fc1 inside), Adam reads step[0].
-// `readout` given (fused step): compact slabs [n_graphs][head_compact_floats] + readout [n_graphs][R];
-// `step` is then the 2-word counter of drgnn_net_train_step: Adam reads step[1], step[0] is committed.
-// slabs_per_graph: conv slabs per graph (0: n_branch; 2 for the split layout of a single-branch net, drgnn_step2.h)
-static int update_impl(int32_t slabs_per_graph, const drgnn_net_desc* net, const float* conv_partials, int64_t n_graphs,
-                       drgnn_conv_grads* g_conv1, drgnn_conv_grads* g_conv2, const float* head_partials,
-                       int64_t head_slabs, const float* readout, int32_t R, int32_t H, int32_t O,
-                       int64_t head_offset, float* flat_param,
-                       float* flat_grad, float* exp_avg, float* exp_avg_sq, int64_t n_param,
-                       int32_t* step, float* loss, double lr, double beta1, double beta2, double eps,
-                       int32_t apply_adam, void* stream_, float* loss2 = nullptr,
-                       const drgnn_cohort_member* coh_members = nullptr, int coh_K = 0, const int32_t* coh_counts = nullptr,
-                       const drgnn_optim* opt = nullptr, const drgnn_optim* coh_optims = nullptr, int coh_clip = 0) {
-    int rc = net_check(net);
-    if (rc) return rc;
-    if (opt && (coh_members || (rc = optim_check(opt)))) return rc ? rc : DRGNN_E_ARG;
-    // (a cohort launch, drgnn_cohort_update: sources, flat buffers, step words and Adam's scalars come from the member table)
-    if (!coh_members && (!conv_partials || !head_partials || !flat_grad)) return DRGNN_E_ARG;
-    if (!g_conv1 || !g_conv2) return DRGNN_E_ARG;
-    if (!coh_members && apply_adam && (!flat_param || !exp_avg || !exp_avg_sq || !step)) return DRGNN_E_ARG;
-    UpdateArgs u;
-    ReduceArgs& r = u.r;
-    if (slabs_per_graph != 0 && slabs_per_graph != net->n_branch && !(net->n_branch == 1 && slabs_per_graph == 2)) return DRGNN_E_ARG;
-    // (a single-branch net's two half-graph slabs are two more "graphs" to the fixed-order sum)
-    const int64_t conv_rows = (net->n_branch == 1 && slabs_per_graph == 2) ? 2 * n_graphs : n_graphs;
-    r.partials = conv_partials; r.n_graphs = (int)conv_rows; r.n_branch = net->n_branch;
+// ---- the update launches: the slabs' fixed-order sums, dW_fc1, Adam, the step word ---------------------------------------------
+// Where a call's sums go.  compact: the head slabs are the fused step's, [head_slabs][head_compact_floats] + readout
+// [head_slabs][R], and dW_fc1 is formed here; otherwise the launch pair's [head_slabs][head_partial_floats] with dW_fc1 inside.
+struct UpdateDst { const drgnn_net_desc* net; drgnn_conv_grads* g_conv1; drgnn_conv_grads* g_conv2; int32_t R, H, O; bool compact; };
+// What they read.  slabs_per_graph: conv slabs per graph, 0 = n_branch; 2: the split layout of a single-branch net (drgnn_step2.h)
+struct UpdateSlabs {
+    const float* conv_partials; int64_t n_graphs; const float* head_partials; int64_t head_slabs; const float* readout;
+    int32_t slabs_per_graph;
+};
+struct UpdateFlat { float* param; float* grad; float* exp_avg; float* exp_avg_sq; int64_t n_param, head_offset; };
+// One update call (zero-initialised by update_call).  A cohort call (its slabs are the fused step's: compact) takes the slabs, flat
+// buffers, step words and Adam's scalars of every member from the member table: `slabs` and the buffers of `flat` stay empty.
+struct UpdateCall {
+    UpdateDst dst; UpdateSlabs slabs; UpdateFlat flat;      // (flat.head_offset: of the head's gradient block in the flat gradient)
+    const int32_t* step;               // legacy layout: the step word Adam reads
+    int32_t* step2;                    // compact layout: the 2-word counter of drgnn_net_train_step, Adam reads [1], [0] is committed
+    float* loss; float* loss2;         // the batch loss and its optional second destination (cohort: loss2 = losses [K])
+    double lr, beta1, beta2, eps;      // Adam's scalars, or the record(s) of an _opt form: optim, a cohort's optims
+    const drgnn_optim* optim; bool options;      // (options: an _opt form, the record(s) must be given)
+    bool cohort; const drgnn_cohort_member* members; const drgnn_optim* optims; const int32_t* counts; int32_t K, any_clip;
+    int32_t apply_adam; void* stream;
+};
+static UpdateCall update_call(const UpdateDst& dst, const UpdateSlabs& slabs, const UpdateFlat& flat, float* loss, int32_t apply_adam,
+                              void* stream) {
+    UpdateCall c = {};
+    c.dst = dst; c.slabs = slabs; c.flat = flat; c.loss = loss; c.apply_adam = apply_adam; c.stream = stream;
+    return c;
+}
+// (a single-branch net's two half-graph slabs are two more "graphs" to the fixed-order sum)
+static bool slabs_split(const drgnn_net_desc* net, int32_t slabs_per_graph) { return net->n_branch == 1 && slabs_per_graph == 2; }
+static int slabs_check(const drgnn_net_desc* net, int32_t slabs_per_graph) {
+    return (slabs_per_graph == 0 || slabs_per_graph == net->n_branch || slabs_split(net, slabs_per_graph)) ? 0 : DRGNN_E_ARG;
+}
+static int head_width_check(const UpdateDst& d) {
+    return (d.R != DRGNN_H2 * d.net->n_branch || d.H < 1 || d.H > 512 || d.O < 1 || d.O > DRGNN_MAX_OUT) ? DRGNN_E_WIDTH : 0;
+}
+// every refusal of the update launches (but the capacity of the norm words: update_run, where the blocks are counted)
+static int update_check(const UpdateCall& c) {
+    const UpdateDst& d = c.dst;
+    if (c.cohort) {
+        if (!c.members || c.K < 1 || c.K > 65535 || !c.counts || (c.options && !c.optims)) return DRGNN_E_ARG;
+        if (c.flat.n_param < 1 || c.flat.head_offset < 0 || c.flat.head_offset >= c.flat.n_param) return DRGNN_E_ARG;
+        if (!d.net) return DRGNN_E_WIDTH;      // (not E_ARG: what a cohort call without a net has always answered)
+        if (int rc = head_width_check(d)) return rc;
+    }
+    if (int rc = net_check(d.net)) return rc;
+    if (!d.g_conv1 || !d.g_conv2 || slabs_check(d.net, c.slabs.slabs_per_graph)) return DRGNN_E_ARG;
+    if (c.cohort) return 0;
+    if (c.options) { if (int rc = optim_check(c.optim)) return rc; }
+    if (!c.slabs.conv_partials || !c.slabs.head_partials || !c.flat.grad) return DRGNN_E_ARG;
+    if (d.compact && (!c.slabs.readout || !c.step2)) return DRGNN_E_ARG;
+    if (c.apply_adam && (!c.flat.param || !c.flat.exp_avg || !c.flat.exp_avg_sq || (!d.compact && !c.step))) return DRGNN_E_ARG;
+    return 0;
+}
+// the conv sums: `rows` slabs [n_branch][net_partial_floats] into the model's own gradient tensors
+static void reduce_fill(ReduceArgs& r, const drgnn_net_desc* net, const float* partials, int64_t rows, const drgnn_conv_grads* g1,
+                        const drgnn_conv_grads* g2) {
+    r = ReduceArgs{};             // (no grad_x; no destinations beyond the net's branches)
+    r.partials = partials; r.n_graphs = (int)rows; r.n_branch = net->n_branch;
     r.n_feat = net->n_feat; r.n_partial = (int)net_partial_floats(net->n_feat); r.kind = net->kind;
-    for (int b = 0; b < DRGNN_MAX_BRANCH; ++b) {
-        r.lay1[b] = net->conv1[b]; r.lay2[b] = net->conv2[b];
-        if (b < net->n_branch) { r.g1[b] = g_conv1[b]; r.g2[b] = g_conv2[b]; }
-        else { r.g1[b] = drgnn_conv_grads{nullptr, nullptr, nullptr}; r.g2[b] = r.g1[b]; }
-    }
-    r.grad_x = nullptr; r.n_nodes = 0;
-    u.h.partials = head_partials;
-    u.h.n_wg = (int)head_slabs;
-    u.h.P = (int)(readout ? head_compact_floats(R, H, O) : head_partial_floats(R, H, O));
-    u.h.grad = flat_grad + head_offset; u.h.loss = loss; u.h.step = nullptr;
-    u.readout = readout; u.hR = R; u.hH = H;
-    u.step2 = readout ? step : nullptr;
-    u.loss2 = (loss || coh_members) ? loss2 : nullptr;
-    u.ad.param = flat_param; u.ad.grad = flat_grad; u.ad.exp_avg = exp_avg; u.ad.exp_avg_sq = exp_avg_sq;
-    u.ad.step = (readout && step) ? step + 1 : step; u.ad.n = n_param;
-    adam_set_hyper(u.ad, lr, beta1, beta2, eps, 0.0);
-    u.apply_adam = apply_adam ? 1 : 0;
+    for (int b = 0; b < DRGNN_MAX_BRANCH; ++b) { r.lay1[b] = net->conv1[b]; r.lay2[b] = net->conv2[b]; }
+    for (int b = 0; b < net->n_branch; ++b) { r.g1[b] = g1[b]; r.g2[b] = g2[b]; }
+}
+// the sums of an UpdateArgs: the conv sums, the head's sources, dW_fc1's operands, the conv block counts.  Returns the head items of
+// the launch: a slab's floats (+ dW_fc1) without its last `n_tail` slots.
+static int update_sums_fill(UpdateArgs& u, const UpdateDst& d, const UpdateSlabs& s, int n_tail) {
+    reduce_fill(u.r, d.net, s.conv_partials, slabs_split(d.net, s.slabs_per_graph) ? 2 * s.n_graphs : s.n_graphs, d.g_conv1, d.g_conv2);
+    u.h.partials = s.head_partials; u.h.n_wg = (int)s.head_slabs;
+    u.h.P = (int)(d.compact ? head_compact_floats(d.R, d.H, d.O) : head_partial_floats(d.R, d.H, d.O));
+    u.readout = s.readout; u.hR = d.R; u.hH = d.H;
+    u.blocks_per_branch = (u.r.n_partial + 63) / 64;
+    u.conv_blocks = d.net->n_branch * u.blocks_per_branch;
+    return (d.compact ? d.H * d.R : 0) + u.h.P - n_tail;
+}
+
+static int update_run(const UpdateCall& c) {
+    if (int rc = update_check(c)) return rc;
+    UpdateArgs u = {};
+    const int head_items = update_sums_fill(u, c.dst, c.slabs, 1);       // the gradient block + the loss (1: not the weight slot)
+    const int n_blocks = u.conv_blocks + (head_items + 63) / 64;
+    if (!c.cohort) { u.h.grad = c.flat.grad + c.flat.head_offset; u.ad.step = c.dst.compact ? c.step2 + 1 : c.step; }
+    u.h.loss = c.loss; u.loss2 = (c.loss || c.cohort) ? c.loss2 : nullptr; u.step2 = c.dst.compact ? c.step2 : nullptr;
+    u.ad.param = c.flat.param; u.ad.grad = c.flat.grad; u.ad.exp_avg = c.flat.exp_avg; u.ad.exp_avg_sq = c.flat.exp_avg_sq;
+    u.ad.n = c.flat.n_param;
     // the options: AdamW / the learning-rate table inside this launch; a clipping step (and coupled L2) as the sums launch,
-    // Adam off, + the flat Adam launch.  Without Adam (data parallel) the launch is today's.
-    const bool opt_flat = opt && apply_adam && (opt->clip || optim_coupled(opt));
-    if (opt) {
-        optim_adam_args(u.ad, opt);
-        if (opt_flat) u.apply_adam = 0;
-        if (!apply_adam) opt = nullptr;
-    }
-    const int64_t pitems = (int64_t)net->n_branch * r.n_partial;
-    u.blocks_per_branch = (r.n_partial + 63) / 64;
-    u.conv_blocks = net->n_branch * u.blocks_per_branch;
-    (void)pitems;
-    const int head_items = (readout ? H * R : 0) + u.h.P - 1;
-    const int head_blocks = (head_items + 63) / 64;
+    // Adam off, + the flat Adam launch.  Without Adam (data parallel) the launch is the plain one.
+    const drgnn_optim* opt = c.apply_adam ? c.optim : nullptr;
+    const bool opt_flat = opt && (opt->clip || optim_coupled(opt));
+    if (c.optim) optim_adam_args(u.ad, c.optim);
+    else adam_set_hyper(u.ad, c.lr, c.beta1, c.beta2, c.eps, 0.0);
+    u.apply_adam = (c.apply_adam && !opt_flat) ? 1 : 0;
 #ifdef DRGNN_EMU
-    if (coh_members) return DRGNN_E_CAPACITY;
+    if (c.cohort) return DRGNN_E_CAPACITY;
     if (opt) u.apply_adam = 0;           // (host loop: the sums here, then the flat loop with the options)
-    for (int64_t i = 0; i < pitems; ++i) {
+    const ReduceArgs& r = u.r;
+    for (int64_t i = 0; i < (int64_t)r.n_branch * r.n_partial; ++i) {
         const int br = (int)(i / r.n_partial), p = (int)(i % r.n_partial);
         if (!reduce_live(r, p)) continue;
         float* d = reduce_dst(r, br, p);
@@ -1693,38 +1695,31 @@ static int update_impl(int32_t slabs_per_graph, const drgnn_net_desc* net, const
     }
     for (int i = 0; i < head_items; ++i) update_head_store(u, i, update_head_sum(u, i, 0, 1));
     if (u.step2) u.step2[0] = u.step2[1];
-    (void)stream_; (void)head_blocks;
-    if (opt) return adam_opt_impl(u.ad, flat_grad, opt, 0, stream_);
+    if (opt) return adam_opt_impl(u.ad, c.flat.grad, opt, 0, c.stream);
 #else
+    const dim3 grid((unsigned)n_blocks, c.cohort ? (unsigned)c.K : 1u), threads(DRGNN_UPDATE_THREADS);
+    hipStream_t stream = (hipStream_t)c.stream;
     if (opt) {
-        const int n_blocks = u.conv_blocks + head_blocks;
         const bool words = opt->clip && !optim_coupled(opt);     // (coupled L2: the flat route's own words)
         if (words && n_blocks > opt->norm_cap) return DRGNN_E_CAPACITY;
-        hipLaunchKernelGGL(k_update_opt, dim3((unsigned)n_blocks), dim3(DRGNN_UPDATE_THREADS), 0, (hipStream_t)stream_, u, *opt,
-                           words ? opt->norm_words : (double*)nullptr);
+        hipLaunchKernelGGL(k_update_opt, grid, threads, 0, stream, u, *opt, words ? opt->norm_words : (double*)nullptr);
         HIP_TRY(hipGetLastError());
-        return opt_flat ? adam_opt_impl(u.ad, flat_grad, opt, words ? n_blocks : 0, stream_) : 0;
+        return opt_flat ? adam_opt_impl(u.ad, c.flat.grad, opt, words ? n_blocks : 0, c.stream) : 0;
     }
-    if (coh_members && coh_optims) {
+    if (c.optims) {
         // (the records live in device memory: their norm_cap is the caller's promise, drgnn_optim_norm_words, checked here
         // against this launch's blocks and guarded in the kernel)
-        const int n_blocks = u.conv_blocks + head_blocks;
-        if (coh_clip && n_blocks > drgnn_optim_norm_words(n_param)) return DRGNN_E_CAPACITY;
-        hipLaunchKernelGGL(k_update_cohort_opt, dim3((unsigned)n_blocks, (unsigned)coh_K), dim3(DRGNN_UPDATE_THREADS), 0,
-                           (hipStream_t)stream_, u, coh_members, coh_optims, coh_counts, head_offset);
+        if (c.any_clip && n_blocks > drgnn_optim_norm_words(c.flat.n_param)) return DRGNN_E_CAPACITY;
+        hipLaunchKernelGGL(k_update_cohort_opt, grid, threads, 0, stream, u, c.members, c.optims, c.counts, c.flat.head_offset);
         HIP_TRY(hipGetLastError());
-        if (coh_clip && apply_adam) {
-            hipLaunchKernelGGL(k_adam_cohort_opt, dim3((unsigned)((n_param + 255) / 256), (unsigned)coh_K), dim3(256), 0,
-                               (hipStream_t)stream_, coh_members, coh_optims, coh_counts, n_param, n_blocks);
-            HIP_TRY(hipGetLastError());
-        }
-        return 0;
+        if (!c.any_clip || !c.apply_adam) return 0;
+        hipLaunchKernelGGL(k_adam_cohort_opt, dim3((unsigned)((c.flat.n_param + 255) / 256), (unsigned)c.K), dim3(256), 0, stream,
+                           c.members, c.optims, c.counts, c.flat.n_param, n_blocks);
+    } else if (c.cohort) {
+        hipLaunchKernelGGL(k_update_cohort, grid, threads, 0, stream, u, c.members, c.counts, c.flat.head_offset);
+    } else {
+        hipLaunchKernelGGL(k_update, grid, threads, 0, stream, u);
     }
-    if (coh_members)
-        hipLaunchKernelGGL(k_update_cohort, dim3((unsigned)(u.conv_blocks + head_blocks), (unsigned)coh_K), dim3(DRGNN_UPDATE_THREADS), 0,
-                           (hipStream_t)stream_, u, coh_members, coh_counts, head_offset);
-    else
-        hipLaunchKernelGGL(k_update, dim3((unsigned)(u.conv_blocks + head_blocks)), dim3(DRGNN_UPDATE_THREADS), 0, (hipStream_t)stream_, u);
     HIP_TRY(hipGetLastError());
 #endif
     return 0;
@@ -1732,118 +1727,122 @@ static int update_impl(int32_t slabs_per_graph, const drgnn_net_desc* net, const
 
 extern "C" {
 
-int drgnn_train_update(const drgnn_net_desc* net, const float* conv_partials, int64_t n_graphs,
-                       drgnn_conv_grads* g_conv1, drgnn_conv_grads* g_conv2, const float* head_partials,
-                       int64_t head_slabs, int32_t R, int32_t H, int32_t O, int64_t head_offset,
-                       float* flat_param,
-                       float* flat_grad, float* exp_avg, float* exp_avg_sq, int64_t n_param,
-                       const int32_t* step, float* loss, double lr, double beta1, double beta2, double eps,
-                       int32_t apply_adam, void* stream_) {
-    if (!head_partials) return DRGNN_E_ARG;
-    return update_impl(0, net, conv_partials, n_graphs, g_conv1, g_conv2, head_partials, head_slabs, nullptr, R, H, O,
-                       head_offset, flat_param, flat_grad, exp_avg, exp_avg_sq, n_param,
-                       const_cast<int32_t*>(step), loss, lr, beta1, beta2, eps, apply_adam, stream_);
+int drgnn_net_reduce_grads(const drgnn_net_desc* net, const float* partials, int64_t n_nodes, int64_t n_graphs,
+                           drgnn_conv_grads* g_conv1, drgnn_conv_grads* g_conv2, float* grad_x, void* stream_) {
+    if (int rc = net_check(net)) return rc;
+    if (!partials || !g_conv1 || !g_conv2) return DRGNN_E_ARG;
+    ReduceArgs r;
+    reduce_fill(r, net, partials, n_graphs, g_conv1, g_conv2);
+    r.grad_x = grad_x; r.n_nodes = n_nodes;
+    int64_t items = (int64_t)net->n_branch * r.n_partial;
+    if (grad_x && net->n_branch > 1 && n_nodes * net->n_feat > items) items = n_nodes * net->n_feat;
+#ifdef DRGNN_EMU
+    for (int64_t i = 0; i < (int64_t)net->n_branch * r.n_partial; ++i) {
+        const int br = (int)(i / r.n_partial), p = (int)(i % r.n_partial);
+        if (reduce_live(r, p)) reduce_write(r, br, p, reduce_sum(r, br, p, 0, 1));
+    }
+    for (int64_t i = 0; grad_x && i < n_nodes * net->n_feat; ++i) reduce_grad_x(r, i);
+    (void)stream_; (void)items;
+#else
+    const int reduce_blocks = net->n_branch * ((r.n_partial + 63) / 64);      // (blocks do not straddle branches)
+    hipLaunchKernelGGL(k_reduce, dim3((unsigned)reduce_blocks), dim3(256), 0, (hipStream_t)stream_, r, items);
+    HIP_TRY(hipGetLastError());
+#endif
+    return 0;
 }
 
-int drgnn_step_update(const drgnn_net_desc* net, const float* conv_partials, int64_t n_graphs,
-                      drgnn_conv_grads* g_conv1, drgnn_conv_grads* g_conv2, const float* head_partials,
-                      const float* readout, int32_t R, int32_t H, int32_t O, int64_t head_offset,
-                      float* flat_param, float* flat_grad, float* exp_avg, float* exp_avg_sq, int64_t n_param,
-                      int32_t* step2, float* loss, double lr, double beta1, double beta2, double eps,
-                      int32_t apply_adam, int32_t slabs_per_graph, void* stream_) {
-    if (!head_partials || !readout || !step2) return DRGNN_E_ARG;
-    return update_impl(slabs_per_graph, net, conv_partials, n_graphs, g_conv1, g_conv2, head_partials, n_graphs, readout, R, H, O,
-                       head_offset, flat_param, flat_grad, exp_avg, exp_avg_sq, n_param, step2, loss, lr, beta1,
-                       beta2, eps, apply_adam, stream_);
+int drgnn_train_update(const drgnn_net_desc* net, const float* conv_partials, int64_t n_graphs, drgnn_conv_grads* g_conv1,
+                       drgnn_conv_grads* g_conv2, const float* head_partials, int64_t head_slabs, int32_t R, int32_t H, int32_t O,
+                       int64_t head_offset, float* flat_param, float* flat_grad, float* exp_avg, float* exp_avg_sq, int64_t n_param,
+                       const int32_t* step, float* loss, double lr, double beta1, double beta2, double eps, int32_t apply_adam,
+                       void* stream_) {
+    UpdateCall c = update_call({net, g_conv1, g_conv2, R, H, O, false}, {conv_partials, n_graphs, head_partials, head_slabs, nullptr, 0},
+                               {flat_param, flat_grad, exp_avg, exp_avg_sq, n_param, head_offset}, loss, apply_adam, stream_);
+    c.step = step; c.lr = lr; c.beta1 = beta1; c.beta2 = beta2; c.eps = eps;
+    return update_run(c);
 }
 
-int drgnn_train_update_opt(const drgnn_net_desc* net, const float* conv_partials, int64_t n_graphs,
-                           drgnn_conv_grads* g_conv1, drgnn_conv_grads* g_conv2, const float* head_partials,
-                           int64_t head_slabs, int32_t R, int32_t H, int32_t O, int64_t head_offset, float* flat_param,
-                           float* flat_grad, float* exp_avg, float* exp_avg_sq, int64_t n_param, const int32_t* step, float* loss,
-                           const drgnn_optim* optim, int32_t apply_adam, void* stream_) {
-    if (!head_partials || !optim) return DRGNN_E_ARG;
-    return update_impl(0, net, conv_partials, n_graphs, g_conv1, g_conv2, head_partials, head_slabs, nullptr, R, H, O,
-                       head_offset, flat_param, flat_grad, exp_avg, exp_avg_sq, n_param, const_cast<int32_t*>(step), loss,
-                       optim->lr, optim->beta1, optim->beta2, optim->eps, apply_adam, stream_, nullptr, nullptr, 0, nullptr, optim);
+int drgnn_step_update(const drgnn_net_desc* net, const float* conv_partials, int64_t n_graphs, drgnn_conv_grads* g_conv1,
+                      drgnn_conv_grads* g_conv2, const float* head_partials, const float* readout, int32_t R, int32_t H, int32_t O,
+                      int64_t head_offset, float* flat_param, float* flat_grad, float* exp_avg, float* exp_avg_sq, int64_t n_param,
+                      int32_t* step2, float* loss, double lr, double beta1, double beta2, double eps, int32_t apply_adam,
+                      int32_t slabs_per_graph, void* stream_) {
+    UpdateCall c = update_call({net, g_conv1, g_conv2, R, H, O, true},
+                               {conv_partials, n_graphs, head_partials, n_graphs, readout, slabs_per_graph},
+                               {flat_param, flat_grad, exp_avg, exp_avg_sq, n_param, head_offset}, loss, apply_adam, stream_);
+    c.step2 = step2; c.lr = lr; c.beta1 = beta1; c.beta2 = beta2; c.eps = eps;
+    return update_run(c);
 }
 
-int drgnn_step_update_opt(const drgnn_net_desc* net, const float* conv_partials, int64_t n_graphs,
-                          drgnn_conv_grads* g_conv1, drgnn_conv_grads* g_conv2, const float* head_partials,
-                          const float* readout, int32_t R, int32_t H, int32_t O, int64_t head_offset,
-                          float* flat_param, float* flat_grad, float* exp_avg, float* exp_avg_sq, int64_t n_param,
-                          int32_t* step2, float* loss, const drgnn_optim* optim, int32_t apply_adam, int32_t slabs_per_graph,
-                          void* stream_) {
-    if (!head_partials || !readout || !step2 || !optim) return DRGNN_E_ARG;
-    return update_impl(slabs_per_graph, net, conv_partials, n_graphs, g_conv1, g_conv2, head_partials, n_graphs, readout, R, H, O,
-                       head_offset, flat_param, flat_grad, exp_avg, exp_avg_sq, n_param, step2, loss, optim->lr, optim->beta1,
-                       optim->beta2, optim->eps, apply_adam, stream_, nullptr, nullptr, 0, nullptr, optim);
+int drgnn_train_update_opt(const drgnn_net_desc* net, const float* conv_partials, int64_t n_graphs, drgnn_conv_grads* g_conv1,
+                           drgnn_conv_grads* g_conv2, const float* head_partials, int64_t head_slabs, int32_t R, int32_t H, int32_t O,
+                           int64_t head_offset, float* flat_param, float* flat_grad, float* exp_avg, float* exp_avg_sq,
+                           int64_t n_param, const int32_t* step, float* loss, const drgnn_optim* optim, int32_t apply_adam,
+                           void* stream_) {
+    UpdateCall c = update_call({net, g_conv1, g_conv2, R, H, O, false}, {conv_partials, n_graphs, head_partials, head_slabs, nullptr, 0},
+                               {flat_param, flat_grad, exp_avg, exp_avg_sq, n_param, head_offset}, loss, apply_adam, stream_);
+    c.step = step; c.optim = optim; c.options = true;
+    return update_run(c);
 }
 
+int drgnn_step_update_opt(const drgnn_net_desc* net, const float* conv_partials, int64_t n_graphs, drgnn_conv_grads* g_conv1,
+                          drgnn_conv_grads* g_conv2, const float* head_partials, const float* readout, int32_t R, int32_t H,
+                          int32_t O, int64_t head_offset, float* flat_param, float* flat_grad, float* exp_avg, float* exp_avg_sq,
+                          int64_t n_param, int32_t* step2, float* loss, const drgnn_optim* optim, int32_t apply_adam,
+                          int32_t slabs_per_graph, void* stream_) {
+    UpdateCall c = update_call({net, g_conv1, g_conv2, R, H, O, true},
+                               {conv_partials, n_graphs, head_partials, n_graphs, readout, slabs_per_graph},
+                               {flat_param, flat_grad, exp_avg, exp_avg_sq, n_param, head_offset}, loss, apply_adam, stream_);
+    c.step2 = step2; c.optim = optim; c.options = true;
+    return update_run(c);
+}
+
+static UpdateCall cohort_call(const UpdateDst& dst, const UpdateFlat& flat, const drgnn_cohort_member* members, int32_t K,
+                              const int32_t* counts, float* losses, int32_t apply_adam, void* stream) {
+    UpdateCall c = update_call(dst, UpdateSlabs{}, flat, nullptr, apply_adam, stream);
+    c.cohort = true; c.members = members; c.K = K; c.counts = counts; c.loss2 = losses;
+    return c;
+}
 int drgnn_cohort_update(const drgnn_net_desc* net, const drgnn_cohort_member* members, int32_t K, const int32_t* counts,
                         drgnn_conv_grads* g_conv1, drgnn_conv_grads* g_conv2, int32_t R, int32_t H, int32_t O,
                         int64_t head_offset, int64_t n_param, float* losses, int32_t apply_adam, void* stream_) {
-    if (!members || K < 1 || K > 65535 || !counts || n_param < 1 || head_offset < 0 || head_offset >= n_param) return DRGNN_E_ARG;
-    if (!net || R != DRGNN_H2 * net->n_branch || H < 1 || H > 512 || O < 1 || O > DRGNN_MAX_OUT) return DRGNN_E_WIDTH;
-    // (readout / step: non-null stand-ins select the fused-step slab layout; the kernel takes every member's own from the table)
-    static float stand_in_f;
-    static int32_t stand_in_i[2];
-    return update_impl(0, net, nullptr, 0, g_conv1, g_conv2, nullptr, 0, &stand_in_f, R, H, O, head_offset, nullptr, nullptr,
-                       nullptr, nullptr, n_param, stand_in_i, nullptr, 0.0f, 0.0f, 0.0f, 0.0f, apply_adam, stream_, losses,
-                       members, K, counts);
+    return update_run(cohort_call({net, g_conv1, g_conv2, R, H, O, true}, {nullptr, nullptr, nullptr, nullptr, n_param, head_offset},
+                                  members, K, counts, losses, apply_adam, stream_));
 }
 
 int drgnn_cohort_update_opt(const drgnn_net_desc* net, const drgnn_cohort_member* members, const drgnn_optim* optims, int32_t K,
                             const int32_t* counts, drgnn_conv_grads* g_conv1, drgnn_conv_grads* g_conv2, int32_t R, int32_t H,
                             int32_t O, int64_t head_offset, int64_t n_param, float* losses, int32_t apply_adam, int32_t any_clip,
                             void* stream_) {
-    if (!members || !optims || K < 1 || K > 65535 || !counts || n_param < 1 || head_offset < 0 || head_offset >= n_param)
-        return DRGNN_E_ARG;
-    if (!net || R != DRGNN_H2 * net->n_branch || H < 1 || H > 512 || O < 1 || O > DRGNN_MAX_OUT) return DRGNN_E_WIDTH;
-    static float stand_in_f;
-    static int32_t stand_in_i[2];
-    return update_impl(0, net, nullptr, 0, g_conv1, g_conv2, nullptr, 0, &stand_in_f, R, H, O, head_offset, nullptr, nullptr,
-                       nullptr, nullptr, n_param, stand_in_i, nullptr, 0.0f, 0.0f, 0.0f, 0.0f, apply_adam, stream_, losses,
-                       members, K, counts, nullptr, optims, any_clip);
+    UpdateCall c = cohort_call({net, g_conv1, g_conv2, R, H, O, true}, {nullptr, nullptr, nullptr, nullptr, n_param, head_offset},
+                               members, K, counts, losses, apply_adam, stream_);
+    c.optims = optims; c.options = true; c.any_clip = any_clip;
+    return update_run(c);
 }
 
-int drgnn_step_gradients(const drgnn_net_desc* net, const float* conv_partials, int64_t n_graphs,
-                         drgnn_conv_grads* g_conv1, drgnn_conv_grads* g_conv2, const float* head_partials,
-                         const float* readout, int32_t R, int32_t H, int32_t O, float* head_grad,
-                         const float* graph_weight, float* const* zero_ptr, const int64_t* zero_len, int32_t n_zero,
+int drgnn_step_gradients(const drgnn_net_desc* net, const float* conv_partials, int64_t n_graphs, drgnn_conv_grads* g_conv1,
+                         drgnn_conv_grads* g_conv2, const float* head_partials, const float* readout, int32_t R, int32_t H, int32_t O,
+                         float* head_grad, const float* graph_weight, float* const* zero_ptr, const int64_t* zero_len, int32_t n_zero,
                          int32_t* step2, int32_t slabs_per_graph, void* stream_) {
-    int rc = net_check(net);
-    if (rc) return rc;
+    const UpdateDst dst = {net, g_conv1, g_conv2, R, H, O, true};
+    int rc;
+    if ((rc = net_check(net))) return rc;
     if (!conv_partials || !g_conv1 || !g_conv2 || !head_partials || !readout || !head_grad || n_graphs < 0) return DRGNN_E_ARG;
     if (n_zero < 0 || n_zero > DRGNN_ZERO_RANGES || (n_zero > 0 && (!zero_ptr || !zero_len))) return DRGNN_E_ARG;
-    if (slabs_per_graph != 0 && slabs_per_graph != net->n_branch && !(net->n_branch == 1 && slabs_per_graph == 2)) return DRGNN_E_ARG;
-    if (R != DRGNN_H2 * net->n_branch || H < 1 || H > 512 || O < 1 || O > DRGNN_MAX_OUT) return DRGNN_E_WIDTH;
-    GradArgs ga;
-    memset(&ga, 0, sizeof(ga));
+    if ((rc = slabs_check(net, slabs_per_graph)) || (rc = head_width_check(dst))) return rc;
+    GradArgs ga = {};
     UpdateArgs& u = ga.u;
-    ReduceArgs& r = u.r;
-    const bool split = net->n_branch == 1 && slabs_per_graph == 2;
-    r.partials = conv_partials; r.n_graphs = (int)(split ? 2 * n_graphs : n_graphs); r.n_branch = net->n_branch;
-    r.n_feat = net->n_feat; r.n_partial = (int)net_partial_floats(net->n_feat); r.kind = net->kind;
-    for (int b = 0; b < DRGNN_MAX_BRANCH; ++b) {
-        r.lay1[b] = net->conv1[b]; r.lay2[b] = net->conv2[b];
-        if (b < net->n_branch) { r.g1[b] = g_conv1[b]; r.g2[b] = g_conv2[b]; }
-        else { r.g1[b] = drgnn_conv_grads{nullptr, nullptr, nullptr}; r.g2[b] = r.g1[b]; }
-    }
-    r.grad_x = nullptr; r.n_nodes = 0;
-    u.h.partials = head_partials; u.h.n_wg = (int)n_graphs; u.h.P = (int)head_compact_floats(R, H, O);
-    u.h.grad = head_grad; u.h.loss = nullptr; u.h.step = nullptr;
-    u.readout = readout; u.hR = R; u.hH = H; u.step2 = step2; u.apply_adam = 0;
-    u.blocks_per_branch = (r.n_partial + 63) / 64;
-    u.conv_blocks = net->n_branch * u.blocks_per_branch;
-    ga.graph_weight = graph_weight; ga.wshift = split ? 1 : 0; ga.n_zero = n_zero;
+    // the gradient block (2: neither the loss nor the weight slot is a gradient)
+    const int head_items = update_sums_fill(u, dst, {conv_partials, n_graphs, head_partials, n_graphs, readout, slabs_per_graph}, 2);
+    const int head_blocks = (head_items + 63) / 64;
+    u.h.grad = head_grad; u.step2 = step2;
+    ga.graph_weight = graph_weight; ga.wshift = slabs_split(net, slabs_per_graph) ? 1 : 0; ga.n_zero = n_zero;
     for (int i = 0; i < n_zero; ++i) {
         if (!zero_ptr[i] || zero_len[i] < 0) return DRGNN_E_ARG;
         ga.zero_ptr[i] = zero_ptr[i]; ga.zero_len[i] = zero_len[i];
     }
-    const int head_items = H * R + u.h.P - 2;             // the gradient block (the loss / weight slots are not gradients)
-    const int head_blocks = (head_items + 63) / 64;
 #ifdef DRGNN_EMU
+    const ReduceArgs& r = u.r;
     for (int64_t i = 0; i < (int64_t)net->n_branch * r.n_partial; ++i) {
         const int br = (int)(i / r.n_partial), p = (int)(i % r.n_partial);
         if (!reduce_live(r, p)) continue;
@@ -2613,10 +2612,13 @@ static int epoch_update(const drgnn_epoch_plan* p, const EpochCarve& c, int64_t 
     const int fused = p->exchange ? 0 : 1;
     // (the last mini-batch of the call also writes the caller's loss word, drgnn_epoch_plan.last_loss)
     const int64_t nb = (p->n_ids + p->batch_size - 1) / p->batch_size;
-    int rc = update_impl(slabs_per_graph, p->net, c.partials, B, p->g_conv1, p->g_conv2, c.head_partials, B, c.readout, hd->R, hd->H,
-                         hd->O, p->head_offset, p->flat_param, p->flat_grad, p->exp_avg, p->exp_avg_sq, p->n_param,
-                         p->step2, losses + k, o ? o->lr : p->lr, o ? o->beta1 : p->beta1, o ? o->beta2 : p->beta2,
-                         o ? o->eps : p->eps, fused, stream, (k == nb - 1) ? p->last_loss : nullptr, nullptr, 0, nullptr, o);
+    UpdateCall u = update_call({p->net, p->g_conv1, p->g_conv2, hd->R, hd->H, hd->O, true},
+                               {c.partials, B, c.head_partials, B, c.readout, slabs_per_graph},
+                               {p->flat_param, p->flat_grad, p->exp_avg, p->exp_avg_sq, p->n_param, p->head_offset}, losses + k, fused,
+                               stream);
+    u.step2 = p->step2; u.loss2 = (k == nb - 1) ? p->last_loss : nullptr;
+    u.lr = p->lr; u.beta1 = p->beta1; u.beta2 = p->beta2; u.eps = p->eps; u.optim = o; u.options = o != nullptr;
+    int rc = update_run(u);
     if (rc || fused) return rc;
     if ((rc = p->exchange(p->exchange_user, k, B, stream))) return rc;
     if (o) return drgnn_adam_step_opt(p->flat_param, p->flat_grad, p->exp_avg, p->exp_avg_sq, p->step2, p->n_param, o, stream);

@@ -329,17 +329,11 @@ class FusedTrainer(object):
     def _fused_launch_update(self, c, apply_adam=True, lr=None):
         """Second launch: fixed-order reduction of the slabs (+ dW_fc1 = dhid^T readout) and Adam."""
         o = self._optim() if (apply_adam and lr is None) else None      # (an explicit lr: the plain launch with that rate)
-        if o is not None:
-            self.api.step_update_opt(c["desc"], c["partials"], c["B"], c["g1"], c["g2"], c["hp"], c["readout"], self.R,
-                                     self.H, self.O, self.head_grad_offset, self.flat_p, self.flat_g, self.exp_avg,
-                                     self.exp_avg_sq, self.step2, self.loss, o, c["stream"], apply_adam=True,
-                                     slabs_per_graph=c.get("slabs", 0))
-            return
         self.api.step_update(c["desc"], c["partials"], c["B"], c["g1"], c["g2"], c["hp"], c["readout"], self.R,
                              self.H, self.O, self.head_grad_offset, self.flat_p, self.flat_g, self.exp_avg,
                              self.exp_avg_sq, self.step2, self.loss, self.lr if lr is None else lr,
                              self.betas[0], self.betas[1], self.eps, c["stream"], apply_adam=apply_adam,
-                             slabs_per_graph=c.get("slabs", 0))
+                             slabs_per_graph=c.get("slabs", 0), optim=o)
 
     def _fused(self, batch, topo, apply_adam, next_topo):
         c = self._fused_prepare(batch, topo, True, next_topo)
@@ -453,14 +447,10 @@ class FusedTrainer(object):
                                     topo.ws_f32, n_nodes, topo.n_edges, B, topo.max_nodes, topo.max_edges,
                                     topo.max_c0, xp, arg0, arg1, pred, hp, None, partials, scratch, stream,
                                     next_topology=None if next_topo is None else next_topo.request(self.topo_flags))
-        o = self._optim() if apply_adam else None
-        if o is not None:
-            api.train_update_opt(desc, partials, B, g1, g2, hp, self.R, self.H, self.O, self.head_grad_offset,
-                                 self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.step, self.loss, o, stream)
-        else:
-            api.train_update(desc, partials, B, g1, g2, hp, self.R, self.H, self.O, self.head_grad_offset,
-                             self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.step, self.loss,
-                             self.lr, self.betas[0], self.betas[1], self.eps, stream, apply_adam=apply_adam)
+        api.train_update(desc, partials, B, g1, g2, hp, self.R, self.H, self.O, self.head_grad_offset,
+                         self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.step, self.loss,
+                         self.lr, self.betas[0], self.betas[1], self.eps, stream, apply_adam=apply_adam,
+                         optim=self._optim() if apply_adam else None)
         self.last_pred = pred
         self.last_batch_size = B
         return self.loss
