@@ -153,6 +153,19 @@ class BsaRequest(ctypes.Structure):
                 ("out", _vp), ("status", _vp)]
 
 
+class HseRequest(ctypes.Structure):
+    """drgnn_hse_request (include/drgnn.h): K target residues, in tiles of one complex each, of a ragged batch of
+    complexes for drgnn_hse_residues; ``host_*`` are addresses of host copies of the offset, target, tile and bb tables."""
+    _fields_ = [("xyz", _vp), ("atom_ptr", _vp), ("res_ptr", _vp), ("bb", _vp), ("target_res", _vp), ("target_complex", _vp),
+                ("tile_ptr", _vp),
+                ("host_atom_ptr", _vp), ("host_res_ptr", _vp), ("host_bb", _vp), ("host_target_res", _vp),
+                ("host_target_complex", _vp), ("host_tile_ptr", _vp),
+                ("n_atoms", _c_i64), ("n_residues", _c_i64), ("n_complexes", _c_i64), ("n_targets", _c_i64),
+                ("n_tiles", _c_i64), ("n_rows", _c_i64), ("radius", ctypes.c_double), ("connect_cutoff", ctypes.c_double),
+                ("offset", _c_i32), ("connect_a", _c_i32), ("connect_b", _c_i32), ("direction", _c_i32),
+                ("out", _vp), ("status", _vp)]
+
+
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p)
 
 
@@ -366,6 +379,9 @@ class Api(object):
         lib.drgnn_bsa_capacity.argtypes = [_c_i32]
         lib.drgnn_bsa_capacity.restype = _c_i32
         lib.drgnn_bsa_residues.argtypes = [ctypes.POINTER(BsaRequest), _vp]
+        lib.drgnn_hse_capacity.argtypes = [_c_i32]
+        lib.drgnn_hse_capacity.restype = _c_i32
+        lib.drgnn_hse_residues.argtypes = [ctypes.POINTER(HseRequest), _vp]
         if lib.drgnn_abi_version() != 5:
             raise DrgnnError("ABI mismatch in %s" % path)
 
@@ -642,6 +658,12 @@ class Api(object):
 
     def bsa_residues(self, request, stream):
         _check(self.lib.drgnn_bsa_residues(ctypes.byref(request), stream), "drgnn_bsa_residues")
+
+    def hse_capacity(self, what):
+        return int(self.lib.drgnn_hse_capacity(int(what)))
+
+    def hse_residues(self, request, stream):
+        _check(self.lib.drgnn_hse_residues(ctypes.byref(request), stream), "drgnn_hse_residues")
 
     def iface_fill(self, request, n_nodes, n_edges, n_iedges, node_residue, pos, chain, type_, edge_index, dist,
                    internal_edge_index, internal_dist, stream):

@@ -2310,6 +2310,65 @@ int drgnn_bsa_residues(const drgnn_bsa_request* q, void* stream) {
     return 0;
 }
 
+// ---- half-sphere exposure of residues (drgnn_hse.h) --------------------------------------------------
+int32_t drgnn_hse_capacity(int32_t what) { return what == 0 ? HS_RCAP : what == 1 ? HS_MAX_TILES : -1; }
+
+int drgnn_hse_residues(const drgnn_hse_request* q, void* stream) {
+    if (!q || !q->host_atom_ptr || !q->host_res_ptr || !q->host_tile_ptr || !q->status) return DRGNN_E_ARG;
+    const int64_t T = q->n_atoms, R = q->n_residues, M = q->n_complexes, K = q->n_targets, NT = q->n_tiles, NB = q->n_rows;
+    if (T < 0 || R < 0 || M < 0 || K < 0 || NT < 0 || NB < 0 || T > INT32_MAX / 3 || R >= INT32_MAX || K > INT32_MAX / 3)
+        return DRGNN_E_ARG;
+    if (M > 0 && !q->res_ptr) return DRGNN_E_ARG;
+    if (R > 0 && (!q->atom_ptr || !q->bb || !q->host_bb || NB < 1 || R % NB != 0)) return DRGNN_E_ARG;
+    if (T > 0 && !q->xyz) return DRGNN_E_ARG;
+    if (K > 0 && (!q->host_target_res || !q->host_target_complex || !q->target_res || !q->target_complex || !q->tile_ptr ||
+                  !q->out || NT < 1))
+        return DRGNN_E_ARG;
+    if (!(q->radius > 0.0) || !(q->radius < 1.0e150) || !(q->connect_cutoff > 0.0) || !(q->connect_cutoff < 1.0e150) ||
+        q->offset < 0)
+        return DRGNN_E_ARG;
+    if (q->connect_a < 0 || q->connect_a > 3 || q->connect_b < 0 || q->connect_b > 3 || q->direction < 0 || q->direction > 1)
+        return DRGNN_E_ARG;
+    if (NT > HS_MAX_TILES) return DRGNN_E_CAPACITY;
+    const int32_t *ap = q->host_atom_ptr, *rp = q->host_res_ptr, *tp = q->host_tile_ptr, *hb = q->host_bb;
+    if (ap[0] != 0 || ap[R] != T || rp[0] != 0 || rp[M] != R || tp[0] != 0 || tp[NT] != K) return DRGNN_E_ARG;
+    for (int64_t r = 0; r < R; ++r) {
+        if (ap[r + 1] < ap[r]) return DRGNN_E_ARG;
+        const int32_t* row = hb + 5 * (r % NB);                       // every offset the kernel may add lies in its residue
+        for (int j = 0; j < 4; ++j)
+            if (row[j] < -1 || row[j] >= ap[r + 1] - ap[r]) return DRGNN_E_ARG;
+    }
+    for (int64_t c = 0; c < M; ++c)
+        if (rp[c + 1] < rp[c] || rp[c + 1] > R) return DRGNN_E_ARG;
+    for (int64_t k = 0; k < K; ++k) {
+        const int32_t c = q->host_target_complex[k], r = q->host_target_res[k];
+        if (c < 0 || c >= M || r < rp[c] || r >= rp[c + 1]) return DRGNN_E_ARG;
+    }
+    for (int64_t t = 0; t < NT; ++t) {
+        if (tp[t + 1] < tp[t] || tp[t + 1] > K) return DRGNN_E_ARG;
+        for (int64_t k = tp[t] + 1; k < tp[t + 1]; ++k)               // a tile serves one complex
+            if (q->host_target_complex[k] != q->host_target_complex[tp[t]]) return DRGNN_E_ARG;
+    }
+    if (K == 0) return 0;
+    HseArgs a;
+    memset(&a, 0, sizeof(a));
+    a.xyz = q->xyz; a.atom_ptr = q->atom_ptr; a.res_ptr = q->res_ptr; a.bb = q->bb;
+    a.tgt_res = q->target_res; a.tgt_cx = q->target_complex; a.tile_ptr = q->tile_ptr;
+    a.n_rows = (int)NB; a.offset = q->offset; a.con_a = q->connect_a; a.con_b = q->connect_b; a.direction = q->direction;
+    a.radius2 = q->radius * q->radius; a.cut2 = q->connect_cutoff * q->connect_cutoff;
+    a.out = q->out; a.status = q->status;
+#ifdef DRGNN_EMU
+    (void)stream;
+    std::unique_ptr<HseShared> lds(new HseShared);
+    for (int64_t t = 0; t < NT; ++t) hse_tile(a, (int)t, *lds);
+#else
+    static_assert(sizeof(HseShared) <= 64 * 1024, "the staged CAs fit the static LDS of a workgroup");
+    hipLaunchKernelGGL(k_hse_residues, dim3((unsigned)NT), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+#endif
+    return 0;
+}
+
 // ---- evaluation scores (drgnn_metrics.h) ---------------------------------------------------------
 int64_t drgnn_metrics_workspace_bytes(int64_t n) {
     if (n < 0 || n > INT32_MAX) return -1;

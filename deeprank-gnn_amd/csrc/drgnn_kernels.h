@@ -14,6 +14,7 @@
 #include "drgnn_iface.h"
 #include "drgnn_score.h"
 #include "drgnn_bsa.h"
+#include "drgnn_hse.h"
 #include "drgnn_metrics.h"
 #include "drgnn_collate.h"
 #include "drgnn_p2p.h"
@@ -998,6 +999,11 @@ __global__ void __launch_bounds__(DRGNN_NTHREADS) k_dock_scores(ScoreArgs a) {
 __global__ void __launch_bounds__(DRGNN_NTHREADS, 8) k_bsa_residues(BsaArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem_bs[];
     bsa_residue(a, (int64_t)blockIdx.x, *(BsaShared*)smem_bs);
+}
+// half-sphere exposure (drgnn_hse.h): one workgroup per tile of targets of one complex
+__global__ void __launch_bounds__(DRGNN_NTHREADS) k_hse_residues(HseArgs a) {
+    __shared__ HseShared smem_hs;
+    hse_tile(a, (int)blockIdx.x, smem_hs);
 }
 // evaluation scores (drgnn_metrics.h)
 __global__ void __launch_bounds__(MT_NT) k_mt_reduce(MetricsArgs a, int centred) {

@@ -26,7 +26,16 @@ method, with the reference's radii), which needs the atom names:
     areas = residue_bsa(poses)                                 # float64 [M, R]: every residue of every pose
     store = interface_graphs(poses, names, bsa=True)           # the graphs with node_data/bsa on every molecule
 
-Not covered: ``depth`` / ``hse`` (Biopython) and PSSM file parsing (``pssm``, ``cons``, ``ic``).  For those every
+and the half-sphere exposure of the residues (``hse``: Biopython's HSExposureCA, radius 12 A, as up, down, angle),
+which needs the atom names too:
+
+    exposure = residue_hse(poses)                              # float64 [M, R, 3]; NaN rows: residues without a value
+    store = interface_graphs(poses, names, hse=True)           # the graphs with node_data/hse on every molecule
+
+``AtomTable`` keeps two chains and merges insertion codes into their residue number, so ``hse`` equals the
+reference's on two-chain complexes without insertion codes.
+
+Not covered: ``depth`` (Biopython through the MSMS program) and PSSM file parsing (``pssm``, ``cons``, ``ic``).  For those every
 graph carries ``node_data/residue``, each node's index among the residues of its
 ``AtomTable``: a per-residue array the caller holds is attached with ``attach_residue_features``.
 
@@ -248,7 +257,7 @@ def default_chunk(api, max_res_a, max_res_b, max_atoms, budget=WORKSPACE_BUDGET)
 
 
 def interface_graphs(tables_or_poses, names, contact_distance=8.5, internal_contact_distance=3.0, device=None, chunk=None,
-                     api=None, reference=None, bsa=False):
+                     api=None, reference=None, bsa=False, hse=False):
     """Interface graphs of complexes (a sequence of ``AtomTable``, an ``AtomTable.poses`` batch, or a mix) as a
     ``GraphStore`` with one molecule per name, in the reference's tree: ``edge_index``, ``edge_data/dist``,
     ``internal_edge_index``, ``internal_edge_data/dist``, ``nodes`` and, under ``node_data/``, ``pos``, ``chain``,
@@ -258,7 +267,10 @@ def interface_graphs(tables_or_poses, names, contact_distance=8.5, internal_cont
     ``reference``: a ``ScoreReference``; every complex must then be a pose of its table, and every molecule also gets
     ``score/irmsd``, ``score/lrmsd``, ``score/fnat``, ``score/dockQ``, ``score/binclass``, ``score/capri_class``.
     ``bsa``: True, or a ``radii`` value of ``residue_bsa`` ("reference", "protor", a pair of arrays): every molecule also
-    gets ``node_data/bsa``, float64 [n,1], the buried surface area of exactly its nodes (one more launch per chunk)."""
+    gets ``node_data/bsa``, float64 [n,1], the buried surface area of exactly its nodes (one more launch per chunk).
+    ``hse``: True, or a dict of ``residue_hse`` options (radius, offset, connect, direction): every molecule also gets
+    ``node_data/hse``, float64 [n,3], the half-sphere exposure (up, down, angle) of exactly its nodes (one more launch
+    per chunk); a node without a value has the row (0, 0, 0), as in the reference."""
     from .dataset import GraphStore
     api = api or _lib.get()
     if device is None:
@@ -272,6 +284,9 @@ def interface_graphs(tables_or_poses, names, contact_distance=8.5, internal_cont
     bsa_mode = None if bsa is False or bsa is None else ("reference" if bsa is True else bsa)
     if bsa_mode is not None:                                           # the radius tables refuse before any launch
         bsa_radii_of = _radii_lookup([t for t, _ in cx], bsa_mode)
+    hse_opt = None if hse is False or hse is None else _hse_options(**({} if hse is True else dict(hse)))
+    if hse_opt is not None:                                            # a table without atom names refuses before any launch
+        hse_bb_of = _bb_lookup([t for t, _ in cx])
     if chunk is None:
         chunk = default_chunk(api, max([t.split for t, _ in cx] + [0]), max([t.n_residues - t.split for t, _ in cx] + [0]),
                               max([t.n_atoms for t, _ in cx] + [0]))
@@ -285,6 +300,10 @@ def interface_graphs(tables_or_poses, names, contact_distance=8.5, internal_cont
             node_res = [r["node_residue"][r["node_ptr"][k]:r["node_ptr"][k + 1]].astype(np.int64) - int(res_ptr[k])
                         for k in range(len(part))]
             buried = _bsa_chunk(api, part, node_res, bsa_radii_of, 1.4, 20, device, ragged=(xyz, atom_ptr, res_ptr, split))
+        if hse_opt is not None:
+            node_res = [r["node_residue"][r["node_ptr"][k]:r["node_ptr"][k + 1]].astype(np.int64) - int(res_ptr[k])
+                        for k in range(len(part))]
+            exposed = _hse_chunk(api, part, node_res, hse_bb_of, hse_opt, device, ragged=(xyz, atom_ptr, res_ptr))
         for k, (t, _) in enumerate(part):
             n0, n1 = r["node_ptr"][k:k + 2]
             e0, e1 = r["edge_ptr"][k:k + 2]
@@ -307,6 +326,10 @@ def interface_graphs(tables_or_poses, names, contact_distance=8.5, internal_cont
             })
             if bsa_mode is not None:
                 trees[-1]["node_data/bsa"] = buried[k][:, 2:3].copy()
+            if hse_opt is not None:
+                rows = exposed[k].copy()
+                rows[np.isnan(rows[:, 0])] = 0.0
+                trees[-1]["node_data/hse"] = rows
     store = GraphStore.from_trees(names, trees)
     if reference is not None and cx:
         attach_scores(store, names, docking_scores(np.stack([x for _, x in cx]), reference, device=device, api=api))
@@ -683,3 +706,174 @@ def residue_bsa(tables_or_poses, residues=None, radii="reference", probe=1.4, n_
         stacked = np.stack(full) if full else np.zeros((0, 3, tables_or_poses.table.n_residues))
         return pick(stacked.transpose(1, 0, 2))
     return [pick(f) for f in full]
+
+
+# ---- half-sphere exposure (csrc/drgnn_hse.h) ---------------------------------------------------------------------------
+HSE_CONNECT = {"CA": (1, 1, 4.3), "CN": (2, 0, 1.8)}      # (column of bb in r, column in r + 1, cutoff in A)
+HSE_DIRECTION = {"CA": 0, "CB": 1}
+HSE_BACKBONE = ("N", "CA", "C", "CB")                     # the columns of the bb table
+HSE_TILE = (4, 64)                                        # targets per workgroup: the fewest and the most
+HSE_WORKGROUPS = 512                                      # a call aims at this many workgroups (two per compute unit)
+
+
+def hse_table(table):
+    """bb int32 [R,5] of an ``AtomTable`` made with ``atom_name``: the offsets of the first atoms named N, CA, C, CB
+    inside every residue (-1: absent) and flags: bit 0 one of the 20 standard residue names, bit 1 GLY, bit 2 the first
+    residue of its chain."""
+    if table.atom_name is None:
+        raise ValueError("hse finds the backbone by atom name: build the AtomTable with atom_name=")
+    R = table.n_residues
+    bb = np.full((R, 5), -1, dtype=np.int32)
+    res_of_atom = np.repeat(np.arange(R), np.diff(table.atom_ptr))
+    inside = np.arange(table.n_atoms) - table.atom_ptr[:-1][res_of_atom]
+    for col, name in enumerate(HSE_BACKBONE):
+        hit = np.flatnonzero(table.atom_name == name)[::-1]                # reversed: the first atom of a name wins
+        bb[res_of_atom[hit], col] = inside[hit]
+    start = np.ones(R, dtype=bool)
+    start[1:] = table.res_chain[1:] != table.res_chain[:-1]
+    bb[:, 4] = (table.res_type >= 0) * 1 + (table.res_name == "GLY") * 2 + start * 4
+    return bb
+
+
+def hse_tile(n_targets):
+    """targets per workgroup for a call of ``n_targets``: small calls spread over many workgroups (1 pose of 1ATN, all
+    residues: 8.0 us at 4 against 32.1 us at 64), large ones stage a complex fewer times (1024 poses: 2.46 ms at 64 against
+    3.57 ms at 4); profiles/hse_ab.txt.  It changes no bit of the result."""
+    return max(HSE_TILE[0], min(HSE_TILE[1], int(n_targets) // HSE_WORKGROUPS))
+
+
+def _bb_lookup(tables):
+    """{id(table): bb}: each distinct table's backbone table, made once"""
+    found = {}
+    for t in tables:
+        if id(t) not in found:
+            found[id(t)] = hse_table(t)
+    return found
+
+
+def _hse_options(radius=12.0, offset=0, connect="CA", direction="CA"):
+    if connect not in HSE_CONNECT:
+        raise ValueError("connect must be 'CA' or 'CN', not %r" % (connect,))
+    if direction not in HSE_DIRECTION:
+        raise ValueError("direction must be 'CA' or 'CB', not %r" % (direction,))
+    if not float(radius) > 0.0:
+        raise ValueError("radius must be > 0")
+    if int(offset) != offset or int(offset) < 0:
+        raise ValueError("offset must be an integer >= 0")
+    return {"radius": float(radius), "offset": int(offset), "connect": connect, "direction": direction}
+
+
+def hse_raw(api, xyz, atom_ptr, res_ptr, bb, target_res, target_complex, radius=12.0, offset=0, connect="CA",
+            direction="CA", device="cpu", tile=None):
+    """One drgnn_hse_residues call (include/drgnn.h) over numpy arrays; the targets in any order (they are grouped by
+    complex and cut into tiles of ``tile``, default ``hse_tile``, here, and the rows come back in the order asked for).
+    ``connect``: "CA", "CN" or (column, column, cutoff).  Returns (out float64 [K,3]: up, down, angle, NaN rows for no value; status int): bit 0
+    of status says a complex was beyond the capacity (its rows are NaN)."""
+    dev = torch.device(device)
+    con = HSE_CONNECT[connect] if isinstance(connect, str) else connect
+    tgt_res = np.asarray(target_res, dtype=np.int64).reshape(-1)
+    tgt_cx = np.asarray(target_complex, dtype=np.int64).reshape(-1)
+    if tgt_res.shape != tgt_cx.shape:
+        raise ValueError("the two target arrays must have one length")
+    K = int(tgt_res.shape[0])
+    tile = max(1, int(tile or hse_tile(K)))
+    order = np.argsort(tgt_cx, kind="stable")
+    sorted_cx = tgt_cx[order]
+    first = np.flatnonzero(np.concatenate(([True], sorted_cx[1:] != sorted_cx[:-1]))) if K else np.zeros(0, np.int64)
+    ends = np.append(first[1:], K)
+    cuts = [np.arange(lo, hi, tile) for lo, hi in zip(first, ends)]
+    tile_ptr = np.concatenate(cuts + [np.array([K])])
+    bb = np.ascontiguousarray(bb, dtype=np.int32).reshape(-1, 5)
+    host = [np.ascontiguousarray(a, dtype=np.int32) for a in (atom_ptr, res_ptr, bb, tgt_res[order], sorted_cx, tile_ptr)]
+    d_xyz = torch.from_numpy(np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)).to(dev)
+    if api is _lib._API:
+        _lib.require_device(d_xyz)
+    d_host = [torch.from_numpy(h).to(dev) for h in host]
+    out = torch.empty((K, 3), dtype=torch.float64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    q = _lib.HseRequest()
+    q.xyz = d_xyz.data_ptr()
+    q.atom_ptr, q.res_ptr, q.bb, q.target_res, q.target_complex, q.tile_ptr = [t.data_ptr() for t in d_host]
+    (q.host_atom_ptr, q.host_res_ptr, q.host_bb, q.host_target_res, q.host_target_complex,
+     q.host_tile_ptr) = [h.ctypes.data for h in host]
+    q.n_atoms, q.n_residues, q.n_complexes = int(d_xyz.shape[0]), len(host[0]) - 1, len(host[1]) - 1
+    q.n_targets, q.n_tiles, q.n_rows = K, len(tile_ptr) - 1, int(bb.shape[0])
+    q.radius, q.offset, q.direction = float(radius), int(offset), HSE_DIRECTION.get(direction, direction)
+    q.connect_a, q.connect_b, q.connect_cutoff = int(con[0]), int(con[1]), float(con[2])
+    q.out, q.status = out.data_ptr(), status.data_ptr()
+    api.hse_residues(q, _lib.current_stream(d_xyz))
+    rows = np.empty((K, 3))
+    rows[order] = out.cpu().numpy()
+    return rows, int(status.cpu()[0])
+
+
+def _hse_chunk(api, part, residues, bb_of, opt, device, ragged=None, tile=None):
+    """[out float64 [K_c,3]] for the complexes of ``part`` ([(table, xyz)]) and their residue lists (local indices)"""
+    if len(part) > 1 and sum(len(r) // (tile or HSE_TILE[0]) + 1 for r in residues) > api.hse_capacity(1):    # one workgroup per tile
+        half = len(part) // 2
+        return (_hse_chunk(api, part[:half], residues[:half], bb_of, opt, device, tile=tile) +
+                _hse_chunk(api, part[half:], residues[half:], bb_of, opt, device, tile=tile))
+    xyz, atom_ptr, res_ptr = ragged if ragged is not None else _ragged(part)[:3]
+    tables = [t for t, _ in part]
+    if all(t is tables[0] for t in tables):                              # poses of one topology: one backbone table
+        bb = bb_of[id(tables[0])]
+    else:
+        bb = np.concatenate([bb_of[id(t)] for t in tables])
+    sizes = [len(r) for r in residues]
+    tgt_res = np.concatenate([np.asarray(r, dtype=np.int64) + int(res_ptr[k]) for k, r in enumerate(residues)]
+                             + [np.zeros(0, np.int64)])
+    tgt_cx = np.repeat(np.arange(len(part)), sizes)
+    out, status = hse_raw(api, xyz, atom_ptr, res_ptr, bb, tgt_res, tgt_cx, device=device, tile=tile, **opt)
+    if status & 1:
+        _lib._check(-2, "drgnn_hse_residues")
+    ends = np.cumsum(sizes)
+    return [out[e - n:e] for n, e in zip(sizes, ends)]
+
+
+def residue_hse(tables_or_poses, residues=None, radius=12.0, offset=0, connect="CA", direction="CA", device=None, chunk=None,
+                api=None):
+    """Half-sphere exposure of residues, on the device: (up, down, angle) as the reference's ``hse`` node feature
+    records it from Biopython's ``HSExposureCA(model)`` (``radius`` 12 A, ``offset`` 0).  The CA trace is cut into
+    peptides: consecutive standard residues of a chain are linked when their CAs are closer than 4.3 A (``connect``
+    "CA", Biopython's CaPPBuilder) or the C of one and the N of the next closer than 1.8 A ("CN", its PPBuilder).  A
+    residue linked on both sides has a value: ``up`` / ``down`` count the CAs of the other linked residues within
+    ``radius`` on either side of the plane through its CA whose normal is the sum of the unit vectors from its two
+    neighbours' CAs; ``angle`` (rad) lies between that normal and CA -> CB (a GLY: the N turned by -120 degrees about CA
+    -> C).  ``offset`` k also leaves out the residues of the same peptide at most k positions away.
+    ``direction`` "CB" is Biopython's ``HSExposureCB``: the normal is CA -> CB itself, every linked residue with that
+    vector has a value and the angle is 0 (the reference records nothing for it: it is held to the written rule of
+    tests/hse_ref.py alone).
+
+    An ``AtomTable`` gives float64 [R,3], an ``AtomTable.poses`` batch [M,R,3], a sequence of either a list of [R_k,3];
+    NaN rows mark residues without a value and residues not asked for.  ``residues``: None (all), an index array
+    applied to every complex, or one index array per complex.  ``chunk``: complexes per launch; a residue's bits do
+    not depend on it, on the batch or on ``residues``.  The tables must have been made with ``atom_name``.  A complex of
+    more than 4096 residues is refused (DrgnnError, capacity)."""
+    api = api or _lib.get()
+    if device is None:
+        device = "cuda" if api is _lib._API else "cpu"
+    cx = _complexes(tables_or_poses)
+    opt = _hse_options(radius, offset, connect, direction)
+    bb_of = _bb_lookup([t for t, _ in cx])
+    if residues is None:
+        wanted = [np.arange(t.n_residues) for t, _ in cx]
+    else:
+        per_complex = (isinstance(residues, (list, tuple)) and len(residues) == len(cx) and
+                       all(np.ndim(r) == 1 for r in residues))
+        wanted = [np.asarray(residues[k] if per_complex else residues, dtype=np.int64).reshape(-1) for k in range(len(cx))]
+        for (t, _), w in zip(cx, wanted):
+            if w.size and (w.min() < 0 or w.max() >= t.n_residues):
+                raise ValueError("a residue index outside [0, %d)" % t.n_residues)
+    if chunk is None:
+        chunk = BSA_XYZ_BUDGET // (12 * max([t.n_atoms for t, _ in cx] + [1]))
+    chunk = max(1, int(chunk))
+    full = [np.full((t.n_residues, 3), np.nan) for t, _ in cx]
+    for lo in range(0, len(cx), chunk):
+        part = cx[lo:lo + chunk]
+        for k, o in enumerate(_hse_chunk(api, part, wanted[lo:lo + chunk], bb_of, opt, device)):
+            full[lo + k][wanted[lo + k]] = o
+    if isinstance(tables_or_poses, AtomTable):
+        return full[0]
+    if isinstance(tables_or_poses, Poses):
+        return np.stack(full) if full else np.zeros((0, tables_or_poses.table.n_residues, 3))
+    return full

@@ -801,6 +801,61 @@ int32_t drgnn_bsa_capacity(int32_t what);
  * workspace, no synchronisation. */
 int drgnn_bsa_residues(const drgnn_bsa_request* req, void* stream);
 
+/* ---- half-sphere exposure of residues (drgnn_hse.h) ---------------------------------------------------
+ * The reference's `hse` node feature (Biopython's HSExposureCA, radius 12 A, offset 0: up, down, angle) for K chosen
+ * residues of a ragged batch of M complexes laid out as for drgnn_bsa_residues: xyz f32 [T,3], atom_ptr i32 [R+1],
+ * res_ptr i32 [M+1].  Atoms are found through bb i32 [n_rows,5]: the offsets of N, CA, C, CB inside the residue (-1:
+ * absent) and flags (bit 0 a standard amino acid, bit 1 GLY, bit 2 the first residue of its chain); residue r reads row
+ * r % n_rows (n_rows divides R: poses of one topology share one table; deeprank_gnn_amd.interface.hse_table).
+ *   Links: residues r, r+1 are linked iff both are standard and have a CA, r+1 does not start a chain, and atom
+ *   connect_a of r (a column of bb) and atom connect_b of r+1 exist and lie closer than connect_cutoff: (1, 1, 4.3) is
+ *   Biopython's CaPPBuilder, (2, 0, 1.8) its PPBuilder.  Members: the residues linked on at least one side.
+ *   direction 0: a residue linked on both sides has a value; b = unit(unit(c2 - c1) + unit(c2 - c3)) over the CAs of
+ *   r-1, r, r+1; every other member o (with offset k > 0: outside the stretch of r's peptide within k positions of r)
+ *   with |CA(o) - c2| < radius counts up when (CA(o) - c2).b > 0, else down; angle: between b and CB - CA, or for a GLY
+ *   with N and C the N turned by -120 degrees about C - CA, else 0.  direction 1 (HSExposureCB): every member with that
+ *   side-chain vector has a value, b is the vector itself, angle 0.
+ * Targets: target_res i32 [K] residue indices into atom_ptr, target_complex i32 [K] their complexes, grouped into
+ * n_tiles tiles by tile_ptr i32 [n_tiles+1]; the targets of a tile belong to ONE complex (one workgroup per tile: it
+ * stages that complex's CAs once; the tile size changes no bit).
+ * Outputs: out f64 [K,3] up, down, angle, a NaN row for a residue without a value; status i32 [1], to be zeroed by the
+ * caller: bit 0 is set when a complex with targets has more than drgnn_hse_capacity(0) residues; its targets are NaN
+ * rows (DRGNN_E_CAPACITY, reported through status because the call does not synchronise).
+ * All decisions and the angle in fp64 on the fp32 coordinates, counts by integer popcounts: no floating-point atomics,
+ * a residue's bits do not depend on the batch, the tiles, the target list, its place or the run.  The offset, target,
+ * tile and bb tables are also given as HOST arrays: every check comes from them. */
+typedef struct drgnn_hse_request {
+    const float* xyz;
+    const int32_t* atom_ptr;
+    const int32_t* res_ptr;
+    const int32_t* bb;
+    const int32_t* target_res;
+    const int32_t* target_complex;
+    const int32_t* tile_ptr;
+    const int32_t* host_atom_ptr;      /* the tables in host memory */
+    const int32_t* host_res_ptr;
+    const int32_t* host_bb;
+    const int32_t* host_target_res;
+    const int32_t* host_target_complex;
+    const int32_t* host_tile_ptr;
+    int64_t n_atoms, n_residues, n_complexes, n_targets, n_tiles, n_rows;
+    double radius, connect_cutoff;
+    int32_t offset, connect_a, connect_b, direction;
+    double* out;
+    int32_t* status;
+} drgnn_hse_request;
+
+/* the documented capacities: what = 0 residues of one complex (4096), 1 the most tiles of one call (one workgroup
+ * each: the grid's limit); -1 otherwise.  Pure host. */
+int32_t drgnn_hse_capacity(int32_t what);
+
+/* DRGNN_E_ARG, before any launch: a null pointer, an offset table that does not start at 0, decreases or ends elsewhere
+ * than n_atoms / n_residues / n_targets, a target outside its complex, a tile over two complexes, n_rows that does not
+ * divide n_residues, a bb offset outside its residue, connect_a / connect_b outside 0..3, direction outside 0..1,
+ * radius or connect_cutoff <= 0, offset < 0.  DRGNN_E_CAPACITY: n_tiles beyond drgnn_hse_capacity(1) (split the call).
+ * No allocation, no workspace, no synchronisation. */
+int drgnn_hse_residues(const drgnn_hse_request* req, void* stream);
+
 /* ---- device-resident graph set and mini-batch assembly --------------------
  * Replaces the host collate of every mini-batch: torch_geometric DataLoader -> Batch.from_data_list over
  * HDF5DataSet.load_one_graph's Data objects (NeuralNet.py:153-154, DataSet.py:231-366).  The set is the
