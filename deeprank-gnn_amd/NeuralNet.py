@@ -262,6 +262,7 @@ class NeuralNet(object):
             # data parallel: the replicas start as ONE model -- rank 0's parameters, Adam moments and step counter -- whatever
             # each rank's RNG produced at construction
             self.trainer.broadcast_state(src=0)
+        self.n_feat = int(first.num_features)     # the width of x the model was built for
         self.train_loss, self.valid_loss, self.train_acc, self.valid_acc = [], [], [], []
         self.data = {}
         self._resident_sets = {}
@@ -281,7 +282,11 @@ class NeuralNet(object):
     def _resident(self, dataset):
         """The graph set of ``dataset`` in HBM (uploaded on first use, every graph read once): mini-batches are
         then assembled on the device from graph numbers (resident.py) instead of re-reading and collating on
-        the host per batch and per epoch as the reference does (DataSet.py:231-366, NeuralNet.py:153-154)."""
+        the host per batch and per epoch as the reference does (DataSet.py:231-366, NeuralNet.py:153-154).  A
+        ``ResidentGraphSet`` (``interface_resident_set``, ``ResidentGraphSet.load_native``) is returned as it is."""
+        if isinstance(dataset, ResidentGraphSet):
+            self._check_width(dataset)
+            return dataset
         rs = self._resident_sets.get(id(dataset), (None, None))[1]
         if rs is None:
             rs = ResidentGraphSet(dataset, self.device, api=self._api)
@@ -293,6 +298,15 @@ class NeuralNet(object):
             for key in [k for k in self._resident_sets if k not in keep][:-2]:
                 del self._resident_sets[key]                       # test sets of earlier test() calls
         return rs
+
+    def _check_width(self, rs):
+        """a resident set handed in ready-made must have the node features the model was built for"""
+        if int(rs.n_feat) != self.n_feat:
+            raise ValueError("the resident set has %d node feature columns, the model was built for %d (node_feature %s)"
+                             % (rs.n_feat, self.n_feat, self.node_feature))
+        if bool(rs.has_attr) != bool(self.edge_feature):
+            raise ValueError("the resident set %s edge_attr, the model was built with edge_feature %s"
+                             % ("carries" if rs.has_attr else "has no", self.edge_feature))
 
     def _use_cache(self, rs):
         """Whether the steps over the resident set ``rs`` read its cached topology (``cached_topology``; logged once per set)."""
@@ -639,6 +653,9 @@ class NeuralNet(object):
                     store['_y'].append(held[2])
                     total = self._sum_of_batch_losses(pred, held[1])
                 return self._stage(store, total)
+        if isinstance(dataset, ResidentGraphSet):
+            raise _lib.DrgnnError("a ResidentGraphSet is scored by the native loop only (native_epoch, graphs within the "
+                                  "fused kernels): the per-batch path collates Data objects, which the set does not hold")
         total = torch.zeros((), dtype=torch.float32, device=self.device)
         need_w = self.trainer.kind == _lib.SGAT
         it = self._batches(dataset, indices, False)
@@ -744,11 +761,18 @@ class NeuralNet(object):
         return self
 
     def test(self, database_test=None, threshold=4, hdf5='test_data.drgs'):
-        # (without database_test the loaded dataset is tested, pretrained or not)
-        ds = self.dataset if database_test is None else GraphDataSet(
-            database_test, node_feature=self.node_feature, edge_feature=self.edge_feature, target=self.target,
-            clustering_method=self.cluster_nodes or 'mcl')
-        if database_test is not None and getattr(ds[0], "cluster0", None) is None:
+        # (without database_test the loaded dataset is tested, pretrained or not; a ResidentGraphSet, e.g. of
+        # interface_resident_set, is scored as it is: no GraphDataSet, no PreCluster, no upload)
+        if isinstance(database_test, ResidentGraphSet):
+            self._check_width(database_test)
+            if not (database_test.has_c0 and database_test.has_c1):
+                raise ValueError("the resident set carries no cluster labels")
+            ds = database_test
+        else:
+            ds = self.dataset if database_test is None else GraphDataSet(
+                database_test, node_feature=self.node_feature, edge_feature=self.edge_feature, target=self.target,
+                clustering_method=self.cluster_nodes or 'mcl')
+        if database_test is not None and ds is not database_test and getattr(ds[0], "cluster0", None) is None:
             from .clustering import PreCluster
             PreCluster(ds, method=self.cluster_nodes or 'mcl', api=self._api, device=self.device)
         loss, store = self.eval(ds, list(range(len(ds))))

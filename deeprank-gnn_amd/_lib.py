@@ -166,6 +166,21 @@ class HseRequest(ctypes.Structure):
                 ("out", _vp), ("status", _vp)]
 
 
+class PackRequest(ctypes.Structure):
+    """drgnn_pack_request (include/drgnn.h): the outputs of drgnn_iface_fill (and bsa / hse rows of exactly its nodes) for
+    drgnn_iface_pack; ``host_cols`` is the address of a host copy of the column descriptor."""
+    _fields_ = [("node_ptr", _vp), ("edge_ptr", _vp), ("iedge_ptr", _vp), ("node_residue", _vp), ("chain", _vp), ("type", _vp),
+                ("pos", _vp), ("edge_index", _vp), ("dist", _vp), ("internal_edge_index", _vp), ("bsa", _vp), ("hse", _vp),
+                ("res_feat", _vp), ("type_table", _vp), ("cols", _vp), ("host_cols", _vp),
+                ("n_complexes", _c_i64), ("n_nodes", _c_i64), ("n_edges", _c_i64), ("n_iedges", _c_i64),
+                ("n_residues", _c_i64), ("n_rows", _c_i64),
+                ("res_width", _c_i32), ("type_width", _c_i32), ("n_cols", _c_i32), ("edge_mode", _c_i32),
+                ("x", _vp), ("edge_index_out", _vp), ("edge_attr", _vp), ("internal_edge_index_out", _vp), ("batch", _vp)]
+
+
+PACK_TYPE, PACK_POS, PACK_CHAIN, PACK_BSA, PACK_HSE, PACK_RES = range(6)      # sources of drgnn_pack_request.cols
+
+
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p)
 
 
@@ -382,6 +397,9 @@ class Api(object):
         lib.drgnn_hse_capacity.argtypes = [_c_i32]
         lib.drgnn_hse_capacity.restype = _c_i32
         lib.drgnn_hse_residues.argtypes = [ctypes.POINTER(HseRequest), _vp]
+        lib.drgnn_pack_capacity.argtypes = [_c_i32]
+        lib.drgnn_pack_capacity.restype = _c_i32
+        lib.drgnn_iface_pack.argtypes = [ctypes.POINTER(PackRequest), _vp]
         if lib.drgnn_abi_version() != 5:
             raise DrgnnError("ABI mismatch in %s" % path)
 
@@ -664,6 +682,12 @@ class Api(object):
 
     def hse_residues(self, request, stream):
         _check(self.lib.drgnn_hse_residues(ctypes.byref(request), stream), "drgnn_hse_residues")
+
+    def pack_capacity(self, what):
+        return int(self.lib.drgnn_pack_capacity(int(what)))
+
+    def iface_pack(self, request, stream):
+        _check(self.lib.drgnn_iface_pack(ctypes.byref(request), stream), "drgnn_iface_pack")
 
     def iface_fill(self, request, n_nodes, n_edges, n_iedges, node_residue, pos, chain, type_, edge_index, dist,
                    internal_edge_index, internal_dist, stream):

@@ -130,10 +130,11 @@ def _labeller(method):
     return labellers[method.lower()]
 
 
-def precluster(batch, method='mcl', api=None):
+def precluster(batch, method='mcl', api=None, with_cluster_ptr=False):
     """(cluster0 [N], cluster1 [sum C0]) of a Batch that carries ``internal_edge_index``: what
     PreCluster would store as clustering/<method>/depth_0 and depth_1 for each of its graphs (per-graph
-    local ids, concatenated in graph order)."""
+    local ids, concatenated in graph order).  ``with_cluster_ptr``: also the int32 [B+1] offsets of the graphs'
+    depth-0 clusters in cluster1 (the builder's CPTR0), on the device."""
     labeller = _labeller(method)
     api = api or _lib.get()
     iei = batch.internal_edge_index.to(torch.int64).contiguous()
@@ -155,7 +156,7 @@ def precluster(batch, method='mcl', api=None):
     node_ptr1 = topo.array("CPTR0")[:B + 1].clone()
     edge_ptr1 = topo.array("E1PTR")[:B + 1].clone()
     d1 = labeller(pooled, node_ptr1, edge_ptr1, api=api)[0]
-    return d0, d1
+    return (d0, d1, node_ptr1) if with_cluster_ptr else (d0, d1)
 
 
 def PreCluster(dataset, method='mcl', batch_size=64, device=None, api=None):

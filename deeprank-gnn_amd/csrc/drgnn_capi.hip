@@ -2369,6 +2369,59 @@ int drgnn_hse_residues(const drgnn_hse_request* q, void* stream) {
     return 0;
 }
 
+// ---- the builder's output packed into a resident set's arrays (drgnn_pack.h) --------------------------
+int32_t drgnn_pack_capacity(int32_t what) { return what == 0 ? PK_FCAP : what == 1 ? PK_TCAP : what == 2 ? PK_MAX_COMPLEXES : -1; }
+
+int drgnn_iface_pack(const drgnn_pack_request* q, void* stream) {
+    if (!q || !q->node_ptr || !q->edge_ptr || !q->iedge_ptr) return DRGNN_E_ARG;
+    const int64_t M = q->n_complexes, N = q->n_nodes, E = q->n_edges, Ei = q->n_iedges, R = q->n_residues, NB = q->n_rows;
+    const int64_t F = q->n_cols, W = q->res_width, Wt = q->type_width;
+    if (M < 0 || N < 0 || E < 0 || Ei < 0 || R < 0 || NB < 0 || F < 0 || W < 0 || Wt < 0) return DRGNN_E_ARG;
+    if (N > INT32_MAX || E > INT32_MAX / 2 || Ei > INT32_MAX / 2) return DRGNN_E_ARG;
+    if (q->edge_mode < 0 || q->edge_mode > 1) return DRGNN_E_ARG;
+    if (M > PK_MAX_COMPLEXES || F > PK_FCAP || Wt > PK_TCAP) return DRGNN_E_CAPACITY;
+    if (q->x) {
+        if (F < 1 || !q->cols || !q->host_cols) return DRGNN_E_ARG;
+        if (N * F > INT32_MAX) return DRGNN_E_CAPACITY;
+        const int64_t width[PK_NSRC] = {Wt, 3, 1, 3, 3, W};
+        for (int64_t f = 0; f < F; ++f) {
+            const int32_t src = q->host_cols[2 * f], c = q->host_cols[2 * f + 1];
+            if (src < 0 || src >= PK_NSRC || c < 0 || c >= width[src]) return DRGNN_E_ARG;
+            if (src == PK_TYPE && !q->type_table) return DRGNN_E_ARG;
+            if (src == PK_RES && (!q->res_feat || NB < 1 || R % NB != 0)) return DRGNN_E_ARG;
+            if (N > 0) {                                               // (an empty batch has no arrays)
+                const void* need = src == PK_TYPE ? (const void*)q->type : src == PK_POS ? (const void*)q->pos :
+                                   src == PK_CHAIN ? (const void*)q->chain : src == PK_BSA ? (const void*)q->bsa :
+                                   src == PK_HSE ? (const void*)q->hse : (const void*)q->node_residue;
+                if (!need) return DRGNN_E_ARG;
+            }
+        }
+    }
+    if (E > 0 && (q->edge_index_out || q->edge_attr) && !q->edge_index) return DRGNN_E_ARG;
+    if (E > 0 && q->edge_attr && !q->dist) return DRGNN_E_ARG;
+    if (Ei > 0 && q->internal_edge_index_out && !q->internal_edge_index) return DRGNN_E_ARG;
+    if (M == 0 || (N == 0 && E == 0 && Ei == 0)) return 0;
+    PackArgs a;
+    memset(&a, 0, sizeof(a));
+    a.node_ptr = q->node_ptr; a.edge_ptr = q->edge_ptr; a.iedge_ptr = q->iedge_ptr;
+    a.node_residue = q->node_residue; a.chain = q->chain; a.type = q->type; a.pos = q->pos;
+    a.edge_index = q->edge_index; a.dist = q->dist; a.iedge_index = q->internal_edge_index;
+    a.bsa = q->bsa; a.hse = q->hse; a.res_feat = q->res_feat; a.type_table = q->type_table; a.cols = q->cols;
+    a.n_rows = (int)std::max<int64_t>(NB, 1); a.W = (int)W; a.Wt = (int)Wt; a.F = (int)F; a.edge_mode = q->edge_mode;
+    a.N = (int)N; a.E = (int)E; a.Ei = (int)Ei;
+    a.x = q->x; a.edge_index_out = q->edge_index_out; a.edge_attr = q->edge_attr;
+    a.iedge_index_out = q->internal_edge_index_out; a.batch = q->batch;
+#ifdef DRGNN_EMU
+    (void)stream;
+    std::unique_ptr<PackShared> lds(new PackShared);
+    for (int64_t k = 0; k < M; ++k) pack_block(a, (int)k, *lds);
+#else
+    hipLaunchKernelGGL(k_iface_pack, dim3((unsigned)M), dim3(PK_NT), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+#endif
+    return 0;
+}
+
 // ---- evaluation scores (drgnn_metrics.h) ---------------------------------------------------------
 int64_t drgnn_metrics_workspace_bytes(int64_t n) {
     if (n < 0 || n > INT32_MAX) return -1;

@@ -15,6 +15,7 @@
 #include "drgnn_score.h"
 #include "drgnn_bsa.h"
 #include "drgnn_hse.h"
+#include "drgnn_pack.h"
 #include "drgnn_metrics.h"
 #include "drgnn_collate.h"
 #include "drgnn_p2p.h"
@@ -1004,6 +1005,11 @@ __global__ void __launch_bounds__(DRGNN_NTHREADS, 8) k_bsa_residues(BsaArgs a) {
 __global__ void __launch_bounds__(DRGNN_NTHREADS) k_hse_residues(HseArgs a) {
     __shared__ HseShared smem_hs;
     hse_tile(a, (int)blockIdx.x, smem_hs);
+}
+// the builder's output packed into a resident set's arrays (drgnn_pack.h): one workgroup per complex
+__global__ void __launch_bounds__(PK_NT) k_iface_pack(PackArgs a) {
+    __shared__ PackShared smem_pk;
+    pack_block(a, (int)blockIdx.x, smem_pk);
 }
 // evaluation scores (drgnn_metrics.h)
 __global__ void __launch_bounds__(MT_NT) k_mt_reduce(MetricsArgs a, int centred) {

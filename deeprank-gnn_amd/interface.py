@@ -35,6 +35,12 @@ which needs the atom names too:
 ``AtomTable`` keeps two chains and merges insertion codes into their residue number, so ``hse`` equals the
 reference's on two-chain complexes without insertion codes.
 
+To score or train on the poses without going through a store, ``interface_resident_set`` packs the same graphs on the
+device (csrc/drgnn_pack.h) into the ``ResidentGraphSet`` that ``NeuralNet.test`` and ``Ensemble.predict`` take:
+
+    rs = interface_resident_set(poses, names, node_feature=["type", "polarity", "bsa", "hse", "pssm"],
+                                residue_features={"pssm": table_R_by_20}, reference=ref, target="irmsd")
+
 Not covered: ``depth`` (Biopython through the MSMS program) and PSSM file parsing (``pssm``, ``cons``, ``ic``).  For those every
 graph carries ``node_data/residue``, each node's index among the residues of its
 ``AtomTable``: a per-residue array the caller holds is attached with ``attach_residue_features``.
@@ -199,10 +205,11 @@ def _ragged(part):
             np.asarray(split).astype(np.int32), res_type.astype(np.int32))
 
 
-def build_ragged(api, xyz, atom_ptr, res_ptr, res_split, res_type, contact_distance=8.5, internal_contact_distance=3.0,
-                 device="cpu", tile_atoms=0, workspace_bytes=None):
-    """One drgnn_iface_count + drgnn_iface_fill over a ragged batch given as numpy arrays (include/drgnn.h).  Returns a
-    dict of numpy arrays: node_ptr / edge_ptr / iedge_ptr int32 [M+1] and the eight outputs of drgnn_iface_fill."""
+def build_ragged_device(api, xyz, atom_ptr, res_ptr, res_split, res_type, contact_distance=8.5, internal_contact_distance=3.0,
+                        device="cpu", tile_atoms=0, workspace_bytes=None):
+    """One drgnn_iface_count + drgnn_iface_fill over a ragged batch given as numpy arrays (include/drgnn.h), the results
+    left on ``device``: (out, ptrs) with ``out`` the dict of the eight outputs of drgnn_iface_fill as tensors and
+    ``ptrs`` int32 [3, M+1] = node_ptr / edge_ptr / iedge_ptr.  Only the three totals come back to the host."""
     dev = torch.device(device)
     M, R = len(res_ptr) - 1, len(atom_ptr) - 1
     host = [np.ascontiguousarray(a, dtype=np.int32) for a in (atom_ptr, res_ptr, res_split)]
@@ -236,6 +243,15 @@ def build_ragged(api, xyz, atom_ptr, res_ptr, res_split, res_type, contact_dista
            "internal_dist": torch.empty(Ei, dtype=torch.float32, device=dev)}
     api.iface_fill(q, N, E, Ei, out["node_residue"], out["pos"], out["chain"], out["type"], out["edge_index"], out["dist"],
                    out["internal_edge_index"], out["internal_dist"], stream)
+    return out, ptrs
+
+
+def build_ragged(api, xyz, atom_ptr, res_ptr, res_split, res_type, contact_distance=8.5, internal_contact_distance=3.0,
+                 device="cpu", tile_atoms=0, workspace_bytes=None):
+    """``build_ragged_device`` copied to the host.  Returns a dict of numpy arrays: node_ptr / edge_ptr / iedge_ptr int32
+    [M+1] and the eight outputs of drgnn_iface_fill."""
+    out, ptrs = build_ragged_device(api, xyz, atom_ptr, res_ptr, res_split, res_type, contact_distance,
+                                    internal_contact_distance, device, tile_atoms, workspace_bytes)
     res = {k: v.cpu().numpy() for k, v in out.items()}
     p = ptrs.cpu().numpy()
     res["node_ptr"], res["edge_ptr"], res["iedge_ptr"] = p[0], p[1], p[2]
@@ -346,8 +362,320 @@ def attach_residue_features(store, name, per_residue_array):
     return store
 
 
+# ---- resident graph sets without host trees (csrc/drgnn_pack.h) --------------------------------------------------------
+FEATURE_WIDTH = {"type": 20, "polarity": 4, "charge": 1, "pos": 3, "chain": 1, "bsa": 1, "hse": 3}
+MCL_WORKSPACE_BUDGET = 256 << 20   # bytes of Markov clustering's dense fp64 workspace (3 n^2 per graph) one precluster call may ask for
+
+
+def pack_type_table():
+    """float32 [20, 25]: row = residue type; columns 0 - 19 the one-hot ``type``, 20 - 23 the one-hot ``polarity``, 24
+    the ``charge``: the rows ``interface_graphs`` writes per node, rounded to float32 as the store path rounds them."""
+    t = np.zeros((20, 25), dtype=np.float32)
+    t[:, :20] = np.eye(20, dtype=np.float32)
+    t[np.arange(20), 20 + RESIDUE_POLARITY] = 1.0
+    t[:, 24] = RESIDUE_CHARGE.astype(np.float32)
+    return t
+
+
+def _pack_columns(node_feature, residue_width):
+    """cols int32 [F,2] of drgnn_iface_pack for the feature names in order; residue_width: {name: (offset, width)}"""
+    P = _lib
+    cols = []
+    for name in node_feature:
+        if name == "type":
+            cols += [(P.PACK_TYPE, j) for j in range(20)]
+        elif name == "polarity":
+            cols += [(P.PACK_TYPE, 20 + j) for j in range(4)]
+        elif name == "charge":
+            cols.append((P.PACK_TYPE, 24))
+        elif name == "pos":
+            cols += [(P.PACK_POS, j) for j in range(3)]
+        elif name == "chain":
+            cols.append((P.PACK_CHAIN, 0))
+        elif name == "bsa":
+            cols.append((P.PACK_BSA, 2))
+        elif name == "hse":
+            cols += [(P.PACK_HSE, j) for j in range(3)]
+        else:
+            off, w = residue_width[name]
+            cols += [(P.PACK_RES, off + j) for j in range(w)]
+    return np.ascontiguousarray(np.array(cols, dtype=np.int32).reshape(-1, 2))
+
+
+def iface_pack_raw(api, built, ptrs, cols, n_residues, type_table=None, bsa=None, hse=None, res_feat=None, edge_mode=1,
+                   want=("x", "edge_index", "edge_attr", "internal_edge_index", "batch")):
+    """One drgnn_iface_pack call (include/drgnn.h) over what ``build_ragged_device`` returned (``built``, ``ptrs``), all
+    on the device: a dict of the outputs named in ``want``.  ``cols`` int32 [F,2] on the host; ``type_table`` /
+    ``bsa`` / ``hse`` / ``res_feat``: device tensors (float32 [20,Wt], float64 [N,3], float64 [N,3], float32 [n_rows,W])."""
+    q, out, _ = pack_request(built, ptrs, cols, n_residues, type_table, bsa, hse, res_feat, edge_mode, want)
+    api.iface_pack(q, _lib.current_stream(ptrs))
+    return out
+
+
+def pack_request(built, ptrs, cols, n_residues, type_table=None, bsa=None, hse=None, res_feat=None, edge_mode=1,
+                 want=("x", "edge_index", "edge_attr", "internal_edge_index", "batch")):
+    """(drgnn_pack_request, its freshly allocated outputs, the arrays the request points into) of ``iface_pack_raw``"""
+    dev = ptrs.device
+    cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1, 2)
+    M = int(ptrs.shape[1]) - 1
+    N, E, Ei = int(built["pos"].shape[0]), int(built["dist"].shape[0]), int(built["internal_edge_index"].shape[0])
+    F = int(cols.shape[0])
+    for name, rows in (("bsa", bsa), ("hse", hse)):                     # (the kernel reads row i of every node i)
+        if rows is not None and (tuple(rows.shape) != (N, 3) or rows.dtype != torch.float64 or not rows.is_contiguous()):
+            raise ValueError("%s must be float64 [%d, 3], one row per node" % (name, N))
+    for name, t, dt in (("type_table", type_table, torch.float32), ("res_feat", res_feat, torch.float32)):
+        if t is not None and (t.dim() != 2 or t.dtype != dt or not t.is_contiguous() or (name == "type_table" and t.shape[0] != 20)):
+            raise ValueError("%s must be a contiguous float32 matrix%s" % (name, " of 20 rows" if name == "type_table" else ""))
+    d_cols = torch.from_numpy(cols).to(dev)
+    out = {}
+    if "x" in want:
+        out["x"] = torch.empty((N, F), dtype=torch.float32, device=dev)
+    if "edge_index" in want:
+        out["edge_index"] = torch.empty((2, 2 * E), dtype=torch.int64, device=dev)
+    if "edge_attr" in want:
+        out["edge_attr"] = torch.empty(2 * E, dtype=torch.float32, device=dev)
+    if "internal_edge_index" in want:
+        out["internal_edge_index"] = torch.empty((2, 2 * Ei), dtype=torch.int64, device=dev)
+    if "batch" in want:
+        out["batch"] = torch.empty(N, dtype=torch.int64, device=dev)
+    p = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+    q = _lib.PackRequest()
+    q.node_ptr, q.edge_ptr, q.iedge_ptr = ptrs[0].data_ptr(), ptrs[1].data_ptr(), ptrs[2].data_ptr()
+    q.node_residue, q.chain, q.type, q.pos = p(built["node_residue"]), p(built["chain"]), p(built["type"]), p(built["pos"])
+    q.edge_index, q.dist, q.internal_edge_index = p(built["edge_index"]), p(built["dist"]), p(built["internal_edge_index"])
+    q.bsa, q.hse, q.res_feat, q.type_table = p(bsa), p(hse), p(res_feat), p(type_table)
+    q.cols, q.host_cols = p(d_cols), (cols.ctypes.data if F else None)
+    q.n_complexes, q.n_nodes, q.n_edges, q.n_iedges, q.n_residues = M, N, E, Ei, int(n_residues)
+    q.n_rows = 0 if res_feat is None else int(res_feat.shape[0])
+    q.res_width = 0 if res_feat is None else int(res_feat.shape[1])
+    q.type_width = 0 if type_table is None else int(type_table.shape[1])
+    q.n_cols, q.edge_mode = F, int(edge_mode)
+    q.x, q.edge_index_out, q.edge_attr = p(out.get("x")), p(out.get("edge_index")), p(out.get("edge_attr"))
+    q.internal_edge_index_out, q.batch = p(out.get("internal_edge_index")), p(out.get("batch"))
+    return q, out, (cols, d_cols)
+
+
+def _residue_tables(residue_features, cx, names):
+    """{feature: (offset, width)}, the total width, and rows(k) -> float32 [R_k, W] of complex k, after checking every
+    table against its AtomTable: a wrongly shaped one raises ValueError"""
+    widths, off = {}, 0
+    per_complex = {}
+    for feat, tab in (residue_features or {}).items():
+        w = None
+        for k, (t, _) in enumerate(cx):
+            if isinstance(tab, dict) and names[k] not in tab:
+                raise ValueError("residue feature %r has no table for %r" % (feat, names[k]))
+            shape = np.shape(tab[names[k]] if isinstance(tab, dict) else tab)
+            if len(shape) not in (1, 2) or shape[0] != t.n_residues or (len(shape) == 2 and shape[1] < 1):
+                raise ValueError("residue feature %r of %r needs one row per residue (%d), got shape %r"
+                                 % (feat, names[k], t.n_residues, shape))
+            wk = 1 if len(shape) == 1 else int(shape[1])
+            if w is not None and wk != w:
+                raise ValueError("residue feature %r: %d columns for %r, %d before" % (feat, wk, names[k], w))
+            w = wk
+        w = w or 1                                                      # (no complex at all: any width does)
+        widths[feat] = (off, w)
+        per_complex[feat] = tab
+        off += w
+    made = {}
+
+    def rows(k):
+        """float32 [R_k, W]; the same object for complexes that share every table"""
+        key = tuple(id(tab[names[k]]) if isinstance(tab, dict) else id(tab) for tab in per_complex.values())
+        if key not in made:
+            parts = [np.asarray(tab[names[k]] if isinstance(tab, dict) else tab, dtype=np.float64).reshape(cx[k][0].n_residues, -1)
+                     for tab in per_complex.values()]
+            made[key] = np.ascontiguousarray(np.hstack(parts).astype(np.float32))
+        return made[key]
+    return widths, off, rows
+
+
+def _mcl_groups(sizes, budget):
+    """consecutive runs [lo, hi) of graphs whose 24 * sum n^2 bytes stay within ``budget`` (a graph beyond it alone)"""
+    groups, lo, used = [], 0, 0
+    for k, n in enumerate(sizes):
+        need = 24 * int(n) * int(n)
+        if k > lo and used + need > budget:
+            groups.append((lo, k))
+            lo, used = k, 0
+        used += need
+    if lo < len(sizes):
+        groups.append((lo, len(sizes)))
+    return groups
+
+
+def interface_resident_set(tables_or_poses, names, node_feature=("type", "polarity", "bsa", "hse"), edge_feature=("dist",),
+                           edge_transform="default", residue_features=None, reference=None, target=None,
+                           clustering_method="mcl", bsa=True, hse=True, contact_distance=8.5, internal_contact_distance=3.0,
+                           chunk=None, device=None, api=None, mcl_budget=MCL_WORKSPACE_BUDGET):
+    """The ``ResidentGraphSet`` of the interface graphs of complexes (as ``interface_graphs`` takes them), assembled on
+    the device: what ``interface_graphs`` -> ``attach_residue_features`` -> ``GraphDataSet(node_feature, edge_feature,
+    target, clustering_method)`` -> ``PreCluster`` -> ``ResidentGraphSet`` gives, bit for bit (``edge_attr`` with the
+    default transform: within 2^-21, see below), without a host tree, a per-graph tensor or a second upload.
+
+    ``node_feature``: names in the order of the columns of ``x``: ``type`` (20 columns), ``polarity`` (4), ``charge``,
+    ``pos`` (3), ``chain``, ``bsa``, ``hse`` (3) and the keys of ``residue_features`` ({name: table with one row per
+    residue of the AtomTable, or {mol: table}}, as ``attach_residue_features`` takes them).  ``"all"``, an unknown
+    name or a wrongly shaped table raises ValueError before any launch.  ``bsa`` / ``hse``: the options of
+    ``interface_graphs``; they are computed only when a feature asks for them.
+    ``edge_feature``: ``("dist",)`` or None (no ``edge_attr``).  ``edge_transform``: "default" (the reference's
+    ``tanh(-d/2 + 2) + 1``, evaluated in fp64 on the float32 distance and rounded once, where the store path evaluates
+    it in float32: the two differ by at most 2^-21), None (the distances as they are) or a callable applied to the
+    device tensor of the distances [2E].
+    ``reference`` and ``target``: ``y`` = ``docking_scores(...)[target]`` as float32, the value the store path reads
+    from ``score/<target>``.  ``clustering_method``: 'mcl' or 'louvain'.
+
+    A complex without a single node gets no graph (a net cannot score one): ``rs.mols`` are the kept names, in order,
+    ``rs.skipped`` the others.
+
+    Per ``chunk`` of complexes (default as for ``interface_graphs``): count and fill (``build_ragged_device``),
+    ``bsa`` / ``hse`` of exactly the nodes, one ``drgnn_iface_pack`` launch, ``precluster`` over runs of graphs whose
+    dense Markov-clustering workspace (24 sum n^2 bytes) stays within ``mcl_budget``; after the last chunk one
+    ``torch.cat`` per array.  What comes back to the host: the three totals of a chunk, its [M+1] offset tables, the
+    offsets of the depth-0 clusters, the status words of the bsa / hse calls and, when ``bsa`` or ``hse`` is asked for,
+    ``node_residue`` (their target lists are made on the host); nothing else.  The result does not depend on ``chunk``,
+    on ``mcl_budget`` or on the run."""
+    from .clustering import _labeller, precluster
+    from .resident import ResidentGraphSet
+    import types
+    api = api or _lib.get()
+    if device is None:
+        device = "cuda" if api is _lib._API else "cpu"
+    cx = _complexes(tables_or_poses)
+    names = [str(n) for n in names]
+    if len(names) != len(cx):
+        raise ValueError("%d names for %d complexes" % (len(names), len(cx)))
+    if len(set(names)) != len(names):
+        raise ValueError("the names must be unique")
+    # ---- everything that can be refused, before any launch
+    if isinstance(node_feature, str) or not len(node_feature):
+        raise ValueError("node_feature must list the features by name (%s and the keys of residue_features), not %r"
+                         % (", ".join(FEATURE_WIDTH), node_feature))
+    node_feature = [str(f) for f in node_feature]
+    residue_features = dict(residue_features or {})
+    for f in node_feature:
+        if f not in FEATURE_WIDTH and f not in residue_features:
+            raise ValueError("unknown node feature %r: %s and the keys of residue_features" % (f, ", ".join(FEATURE_WIDTH)))
+    for f in residue_features:
+        if f in FEATURE_WIDTH:
+            raise ValueError("residue feature %r has the name of a built-in feature" % f)
+    if edge_feature is not None and list(edge_feature) != ["dist"]:
+        raise ValueError("edge_feature must be ('dist',) or None, not %r" % (edge_feature,))
+    if not (edge_transform is None or edge_transform == "default" or callable(edge_transform)):
+        raise ValueError("edge_transform must be 'default', None or a callable, not %r" % (edge_transform,))
+    _labeller(clustering_method)
+    if (reference is None) != (target is None):
+        raise ValueError("`reference` and `target` go together")
+    if reference is not None:
+        if target not in SCORE_KEYS:
+            raise ValueError("target must be one of %s, not %r" % (", ".join(SCORE_KEYS), target))
+        if not all(t is reference.table for t, _ in cx):
+            raise ValueError("with `reference`, every complex must be a pose of the reference's AtomTable")
+    used = {f: residue_features[f] for f in node_feature if f in residue_features}
+    res_cols, res_width, res_rows = _residue_tables(used, cx, names)
+    want_bsa, want_hse = "bsa" in node_feature, "hse" in node_feature
+    if want_bsa:
+        if bsa is False or bsa is None:
+            raise ValueError("the node feature 'bsa' needs bsa=True or a radii option")
+        bsa_radii_of = _radii_lookup([t for t, _ in cx], "reference" if bsa is True else bsa)
+    if want_hse:
+        if hse is False or hse is None:
+            raise ValueError("the node feature 'hse' needs hse=True or a dict of options")
+        hse_opt = _hse_options(**({} if hse is True else dict(hse)))
+        hse_bb_of = _bb_lookup([t for t, _ in cx])
+    cols = _pack_columns(node_feature, res_cols)
+    if cols.shape[0] > api.pack_capacity(0):
+        raise ValueError("%d columns of node features; drgnn_iface_pack takes %d" % (cols.shape[0], api.pack_capacity(0)))
+    if chunk is None:
+        chunk = default_chunk(api, max([t.split for t, _ in cx] + [0]), max([t.n_residues - t.split for t, _ in cx] + [0]),
+                              max([t.n_atoms for t, _ in cx] + [0]))
+    chunk = max(1, min(int(chunk), api.pack_capacity(2)))
+    # ---- the chunks
+    rs = ResidentGraphSet.__new__(ResidentGraphSet)
+    rs._open(device, api)
+    dev = rs.device
+    type_table = torch.from_numpy(pack_type_table()).to(dev)
+    res_dev = {}                                                       # residue tables on the device, by identity
+    edge_mode = 1 if (edge_feature is not None and edge_transform == "default") else 0
+    want = ("x", "edge_index", "internal_edge_index", "batch") + (("edge_attr",) if edge_feature is not None else ())
+    kept, skipped, parts = [], [], []
+    n_nodes, n_edges, n_c1 = [], [], []
+    for lo in range(0, len(cx), chunk):
+        part = cx[lo:lo + chunk]
+        M = len(part)
+        xyz, atom_ptr, res_ptr, split, res_type = _ragged(part)
+        built, ptrs = build_ragged_device(api, xyz, atom_ptr, res_ptr, split, res_type, contact_distance,
+                                          internal_contact_distance, dev)
+        hp = ptrs.cpu().numpy().astype(np.int64)                       # the [M+1] tables
+        nn = np.diff(hp[0])
+        for k in range(M):
+            (kept if nn[k] > 0 else skipped).append(names[lo + k])
+        if hp[0, -1] == 0:
+            continue
+        d_bsa = d_hse = None
+        if want_bsa or want_hse:
+            node_residue = built["node_residue"].cpu().numpy().astype(np.int64)
+            node_res = [node_residue[hp[0, k]:hp[0, k + 1]] - int(res_ptr[k]) for k in range(M)]
+            if want_bsa:
+                d_bsa = _bsa_chunk(api, part, node_res, bsa_radii_of, 1.4, 20, dev, ragged=(xyz, atom_ptr, res_ptr, split),
+                                   keep_device=True)
+            if want_hse:
+                d_hse = _hse_chunk(api, part, node_res, hse_bb_of, hse_opt, dev, ragged=(xyz, atom_ptr, res_ptr),
+                                   keep_device=True)
+        d_res = None
+        if res_width:
+            tabs = [res_rows(lo + k) for k in range(M)]
+            shared = all(t is tabs[0] for t in tabs) and all(t is part[0][0] for t, _ in part)
+            key = id(tabs[0]) if shared else None
+            if key is not None and key in res_dev:
+                d_res = res_dev[key]
+            else:
+                d_res = torch.from_numpy(tabs[0] if shared else np.concatenate(tabs)).to(dev)
+                if key is not None:
+                    res_dev[key] = d_res
+        out = iface_pack_raw(api, built, ptrs, cols, len(atom_ptr) - 1, type_table, d_bsa, d_hse, d_res, edge_mode, want)
+        if edge_feature is not None and callable(edge_transform):
+            out["edge_attr"] = torch.as_tensor(edge_transform(out["edge_attr"]), device=dev).to(torch.float32).reshape(-1)
+        # ---- clusters: the kept graphs of the chunk in runs that fit the budget
+        live = np.flatnonzero(nn > 0)
+        rank = np.full(M, -1, dtype=np.int64)
+        rank[live] = np.arange(live.size)
+        d_rank = torch.from_numpy(rank).to(dev)
+        c0s, c1s = [], []
+        for g0, g1 in _mcl_groups(nn[live], int(mcl_budget)):
+            a, b = int(live[g0]), int(live[g1 - 1]) + 1                # complexes [a, b): the empty ones among them hold nothing
+            na, nb, ia, ib = int(hp[0, a]), int(hp[0, b]), 2 * int(hp[2, a]), 2 * int(hp[2, b])
+            shadow = types.SimpleNamespace(internal_edge_index=out["internal_edge_index"][:, ia:ib] - na,
+                                           batch=d_rank[out["batch"][na:nb]] - g0, num_graphs=g1 - g0)
+            d0, d1, cptr = precluster(shadow, method=clustering_method, api=api, with_cluster_ptr=True)
+            c0s.append(d0)
+            c1s.append(d1)
+            n_c1 += np.diff(cptr.cpu().numpy().astype(np.int64)).tolist()       # the cluster-count table
+        n_nodes += nn[live].tolist()
+        n_edges += (2 * np.diff(hp[1])[live]).tolist()
+        out["cluster0"], out["cluster1"] = torch.cat(c0s), torch.cat(c1s)
+        parts.append(out)
+
+    def cat(key, dim=0, empty=None):
+        return torch.cat([p[key] for p in parts], dim=dim) if parts else empty
+    y = None
+    if reference is not None:
+        scores = docking_scores(np.stack([x for _, x in cx]), reference, device=dev, api=api) if cx else {target: np.zeros(0)}
+        keep = np.array([n not in set(skipped) for n in names], dtype=bool)
+        y = torch.from_numpy(np.asarray(scores[target])[keep].astype(np.float32))       # (host: _adopt keeps it as y_host)
+    F = int(cols.shape[0])
+    rs._adopt(mols=kept, n_nodes=n_nodes, n_edges=n_edges, n_c1=n_c1,
+              x=cat("x", empty=torch.zeros((0, F), dtype=torch.float32, device=dev)),
+              edge_index=cat("edge_index", dim=1, empty=torch.zeros((2, 0), dtype=torch.int64, device=dev)),
+              edge_attr=None if edge_feature is None else cat("edge_attr", empty=torch.zeros(0, dtype=torch.float32, device=dev)),
+              cluster0=cat("cluster0", empty=torch.zeros(0, dtype=torch.int64, device=dev)),
+              cluster1=cat("cluster1", empty=torch.zeros(0, dtype=torch.int64, device=dev)), y=y)
+    rs.skipped = skipped
+    return rs
+
+
 # ---- docking scores (csrc/drgnn_score.h) -------------------------------------------------------------------------------
-BACKBONE = ("CA", "C", "N", "O")
+BACKBONE =("CA", "C", "N", "O")
 SCORE_KEYS = ("irmsd", "lrmsd", "fnat", "dockQ", "binclass", "capri_class")
 SCORE_XYZ_BUDGET = 256 << 20       # bytes of pose coordinates one call uploads (sets the default chunk)
 
@@ -608,9 +936,10 @@ def _radii_lookup(tables, radii):
 
 
 def bsa_raw(api, xyz, atom_ptr, res_ptr, res_split, rad_complex, rad_unbound, target_res, target_complex, probe=1.4,
-            n_slices=20, device="cpu"):
+            n_slices=20, device="cpu", keep_device=False):
     """One drgnn_bsa_residues call (include/drgnn.h) over numpy arrays.  Returns (out float64 [K,3]: sasa_unbound,
-    sasa_complex, bsa; status int): bit 0 of status says a list overflowed (those residues are NaN)."""
+    sasa_complex, bsa; status int): bit 0 of status says a list overflowed (those residues are NaN).  ``keep_device``:
+    ``out`` stays a tensor on ``device``; only the status word comes back."""
     dev = torch.device(device)
     host = [np.ascontiguousarray(a, dtype=np.int32) for a in (atom_ptr, res_ptr, res_split, target_res, target_complex)]
     rad = [np.ascontiguousarray(a, dtype=np.float32) for a in (rad_complex, rad_unbound)]
@@ -635,15 +964,17 @@ def bsa_raw(api, xyz, atom_ptr, res_ptr, res_split, rad_complex, rad_unbound, ta
     q.probe, q.n_slices = float(probe), int(n_slices)
     q.out, q.status = out.data_ptr(), status.data_ptr()
     api.bsa_residues(q, _lib.current_stream(d_xyz))
-    return out.cpu().numpy(), int(status.cpu()[0])
+    return (out if keep_device else out.cpu().numpy()), int(status.cpu()[0])
 
 
-def _bsa_chunk(api, part, residues, radii_of, probe, n_slices, device, ragged=None):
-    """[out float64 [K_c,3]] for the complexes of ``part`` ([(table, xyz)]) and their residue lists (local indices)"""
+def _bsa_chunk(api, part, residues, radii_of, probe, n_slices, device, ragged=None, keep_device=False):
+    """[out float64 [K_c,3]] for the complexes of ``part`` ([(table, xyz)]) and their residue lists (local indices).
+    ``keep_device``: one tensor [sum K_c, 3] on ``device`` instead, the complexes' rows back to back."""
     if len(part) > 1 and sum(len(r) for r in residues) > api.bsa_capacity(3):      # one workgroup per target: the grid's limit
         half = len(part) // 2
-        return (_bsa_chunk(api, part[:half], residues[:half], radii_of, probe, n_slices, device) +
-                _bsa_chunk(api, part[half:], residues[half:], radii_of, probe, n_slices, device))
+        both = (_bsa_chunk(api, part[:half], residues[:half], radii_of, probe, n_slices, device, keep_device=keep_device),
+                _bsa_chunk(api, part[half:], residues[half:], radii_of, probe, n_slices, device, keep_device=keep_device))
+        return torch.cat(both) if keep_device else both[0] + both[1]
     xyz, atom_ptr, res_ptr, split = ragged if ragged is not None else _ragged(part)[:4]
     tables = [t for t, _ in part]
     if all(t is tables[0] for t in tables):                              # poses of one topology: one radius table
@@ -655,9 +986,11 @@ def _bsa_chunk(api, part, residues, radii_of, probe, n_slices, device, ragged=No
     tgt_res = np.concatenate([np.asarray(r, dtype=np.int64) + int(res_ptr[k]) for k, r in enumerate(residues)]
                              + [np.zeros(0, np.int64)])
     tgt_cx = np.repeat(np.arange(len(part)), sizes)
-    out, status = bsa_raw(api, xyz, atom_ptr, res_ptr, split, cr, ur, tgt_res, tgt_cx, probe, n_slices, device)
+    out, status = bsa_raw(api, xyz, atom_ptr, res_ptr, split, cr, ur, tgt_res, tgt_cx, probe, n_slices, device, keep_device)
     if status & 1:
         _lib._check(-2, "drgnn_bsa_residues")
+    if keep_device:
+        return out
     ends = np.cumsum(sizes)
     return [out[e - n:e] for n, e in zip(sizes, ends)]
 
@@ -764,11 +1097,12 @@ def _hse_options(radius=12.0, offset=0, connect="CA", direction="CA"):
 
 
 def hse_raw(api, xyz, atom_ptr, res_ptr, bb, target_res, target_complex, radius=12.0, offset=0, connect="CA",
-            direction="CA", device="cpu", tile=None):
+            direction="CA", device="cpu", tile=None, keep_device=False):
     """One drgnn_hse_residues call (include/drgnn.h) over numpy arrays; the targets in any order (they are grouped by
     complex and cut into tiles of ``tile``, default ``hse_tile``, here, and the rows come back in the order asked for).
     ``connect``: "CA", "CN" or (column, column, cutoff).  Returns (out float64 [K,3]: up, down, angle, NaN rows for no value; status int): bit 0
-    of status says a complex was beyond the capacity (its rows are NaN)."""
+    of status says a complex was beyond the capacity (its rows are NaN).  ``keep_device``: ``out`` stays a tensor on
+    ``device``; only the status word comes back."""
     dev = torch.device(device)
     con = HSE_CONNECT[connect] if isinstance(connect, str) else connect
     tgt_res = np.asarray(target_res, dtype=np.int64).reshape(-1)
@@ -802,17 +1136,25 @@ def hse_raw(api, xyz, atom_ptr, res_ptr, bb, target_res, target_complex, radius=
     q.connect_a, q.connect_b, q.connect_cutoff = int(con[0]), int(con[1]), float(con[2])
     q.out, q.status = out.data_ptr(), status.data_ptr()
     api.hse_residues(q, _lib.current_stream(d_xyz))
+    if keep_device:
+        if not np.array_equal(order, np.arange(K)):                        # (targets listed complex by complex: as they are)
+            rows = torch.empty_like(out)
+            rows[torch.from_numpy(order).to(dev)] = out
+            out = rows
+        return out, int(status.cpu()[0])
     rows = np.empty((K, 3))
     rows[order] = out.cpu().numpy()
     return rows, int(status.cpu()[0])
 
 
-def _hse_chunk(api, part, residues, bb_of, opt, device, ragged=None, tile=None):
-    """[out float64 [K_c,3]] for the complexes of ``part`` ([(table, xyz)]) and their residue lists (local indices)"""
+def _hse_chunk(api, part, residues, bb_of, opt, device, ragged=None, tile=None, keep_device=False):
+    """[out float64 [K_c,3]] for the complexes of ``part`` ([(table, xyz)]) and their residue lists (local indices).
+    ``keep_device``: one tensor [sum K_c, 3] on ``device`` instead, the complexes' rows back to back."""
     if len(part) > 1 and sum(len(r) // (tile or HSE_TILE[0]) + 1 for r in residues) > api.hse_capacity(1):    # one workgroup per tile
         half = len(part) // 2
-        return (_hse_chunk(api, part[:half], residues[:half], bb_of, opt, device, tile=tile) +
-                _hse_chunk(api, part[half:], residues[half:], bb_of, opt, device, tile=tile))
+        both = (_hse_chunk(api, part[:half], residues[:half], bb_of, opt, device, tile=tile, keep_device=keep_device),
+                _hse_chunk(api, part[half:], residues[half:], bb_of, opt, device, tile=tile, keep_device=keep_device))
+        return torch.cat(both) if keep_device else both[0] + both[1]
     xyz, atom_ptr, res_ptr = ragged if ragged is not None else _ragged(part)[:3]
     tables = [t for t, _ in part]
     if all(t is tables[0] for t in tables):                              # poses of one topology: one backbone table
@@ -823,9 +1165,12 @@ def _hse_chunk(api, part, residues, bb_of, opt, device, ragged=None, tile=None):
     tgt_res = np.concatenate([np.asarray(r, dtype=np.int64) + int(res_ptr[k]) for k, r in enumerate(residues)]
                              + [np.zeros(0, np.int64)])
     tgt_cx = np.repeat(np.arange(len(part)), sizes)
-    out, status = hse_raw(api, xyz, atom_ptr, res_ptr, bb, tgt_res, tgt_cx, device=device, tile=tile, **opt)
+    out, status = hse_raw(api, xyz, atom_ptr, res_ptr, bb, tgt_res, tgt_cx, device=device, tile=tile, keep_device=keep_device,
+                          **opt)
     if status & 1:
         _lib._check(-2, "drgnn_hse_residues")
+    if keep_device:
+        return out
     ends = np.cumsum(sizes)
     return [out[e - n:e] for n, e in zip(sizes, ends)]
 

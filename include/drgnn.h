@@ -856,6 +856,62 @@ int32_t drgnn_hse_capacity(int32_t what);
  * No allocation, no workspace, no synchronisation. */
 int drgnn_hse_residues(const drgnn_hse_request* req, void* stream);
 
+/* ---- the builder's output packed into a resident set's arrays (drgnn_pack.h) --------------------------
+ * After drgnn_iface_fill on the same batch (and the optional drgnn_bsa_residues / drgnn_hse_residues over exactly its
+ * nodes, in node order): the arrays a drgnn_graph_set holds, written on the device in one launch, one workgroup per
+ * complex.  What GraphDataSet.load_one_graph and ResidentGraphSet assemble per graph on the host.
+ * Inputs as they lie on the device: node_ptr / edge_ptr / iedge_ptr i32 [M+1]; node_residue, chain, type i32 [N]; pos
+ * f32 [N,3]; edge_index i64 [E,2] and internal_edge_index i64 [Ei,2] with ids local to their complex; dist f32 [E];
+ * optional bsa f64 [N,3] and hse f64 [N,3] (a row whose first entry is NaN reads 0, 0, 0); optional res_feat f32
+ * [n_rows, res_width]: a node reads row node_residue % n_rows (n_rows divides n_residues: poses of one topology share
+ * one table); type_table f32 [20, type_width]: row = the node's type, holding every column that depends on the residue
+ * type alone (the kernel carries no copy of such constants).
+ * cols i32 [n_cols, 2] = (source, column of the source) of every column of x, sources 0 type_table, 1 pos, 2 chain,
+ * 3 bsa, 4 hse, 5 res_feat; also given as the HOST array host_cols: every check comes from it.  f64 sources are rounded
+ * once to f32 (round to nearest even: what torch.tensor(..., dtype=torch.float) does).
+ * Outputs (a null pointer skips one): x f32 [N, n_cols]; edge_index_out i64 [2, 2E], graph k's columns 2 edge_ptr[k]
+ * .. 2 edge_ptr[k+1] holding its pairs and then the same pairs reversed, local ids; edge_attr f32 [2E] in that order,
+ * edge_mode 0 the distance, 1 tanh(-d/2 + 2) + 1 evaluated in fp64 on the f32 distance and rounded once;
+ * internal_edge_index_out i64 [2, 2Ei], the same layout with ids + node_ptr[k] (batch-global); batch i64 [N], the
+ * complex of every node.  Every element has one writer: no atomics, a complex's bits do not depend on the batch, its
+ * place or the run.  The kernel clips the device offset tables to n_nodes / n_edges / n_iedges. */
+typedef struct drgnn_pack_request {
+    const int32_t* node_ptr;
+    const int32_t* edge_ptr;
+    const int32_t* iedge_ptr;
+    const int32_t* node_residue;
+    const int32_t* chain;
+    const int32_t* type;
+    const float* pos;
+    const int64_t* edge_index;
+    const float* dist;
+    const int64_t* internal_edge_index;
+    const double* bsa;
+    const double* hse;
+    const float* res_feat;
+    const float* type_table;
+    const int32_t* cols;
+    const int32_t* host_cols;          /* cols in host memory */
+    int64_t n_complexes, n_nodes, n_edges, n_iedges, n_residues, n_rows;
+    int32_t res_width, type_width, n_cols, edge_mode;
+    float* x;
+    int64_t* edge_index_out;
+    float* edge_attr;
+    int64_t* internal_edge_index_out;
+    int64_t* batch;
+} drgnn_pack_request;
+
+/* the documented capacities: what = 0 columns of x (256), 1 columns of type_table (64), both staged in LDS once per
+ * workgroup, 2 complexes of one call (65 535, one workgroup each); -1 otherwise.  Pure host. */
+int32_t drgnn_pack_capacity(int32_t what);
+
+/* DRGNN_E_ARG, before any launch: a null offset table, with x a null cols / host_cols or n_cols < 1, a descriptor row
+ * with a source outside 0..5, a column outside its source, a source whose array is null, n_rows that does not divide
+ * n_residues, an output whose input is null, a negative count, edge_mode outside 0..1.  DRGNN_E_CAPACITY: n_complexes,
+ * n_cols or type_width beyond drgnn_pack_capacity, n_nodes * n_cols beyond 2^31 - 1 (split the call).  No allocation,
+ * no workspace, no synchronisation. */
+int drgnn_iface_pack(const drgnn_pack_request* req, void* stream);
+
 /* ---- device-resident graph set and mini-batch assembly --------------------
  * Replaces the host collate of every mini-batch: torch_geometric DataLoader -> Batch.from_data_list over
  * HDF5DataSet.load_one_graph's Data objects (NeuralNet.py:153-154, DataSet.py:231-366).  The set is the
