@@ -352,6 +352,38 @@ DEV __amdgpu_buffer_rsrc_t buf_rsrc(const void* p, int bytes) {
 #endif
 
 // ---------------------------------------------------------------------------------
+// Stores of what the NEXT launch reads: the builder's aggregation tiles and the index arrays of its lean chains, the step's
+// gradient slabs, head rows and readout.  A plain store leaves its line dirty in the XCD's L2 until the launch ends, and the
+// write-back then stands between this launch and the one that depends on it; written through (`sc1`: a relaxed agent-scope
+// atomic store for 4 / 8 bytes, a buffer store with aux 16 for 16 bytes) the line leaves for memory while the kernel still
+// runs.  Worth 0.2 - 0.3 us on the rebuilt GINet step (profiles/store_policy_ab.txt).  Measured and left PLAIN: the offsets a
+// builder workgroup publishes in front of its first barrier (written through: + 0.7 us per step), dW1 of step3_dw1_sparse
+// (one wave writes 64 lines: + 0.8 us), the general chains and k_tiles (no launch of the benchmark's main loop runs them).
+// Written through only in the units built with -DDRGNN_WRITE_THROUGH (Makefile: GINet's two-workgroup step kernels, the
+// benchmarked launch); everywhere else, the emulation included, these are plain stores: the sGAT / FoutNet launches measured
+// 0.7 - 1.0 us SLOWER with them written through, the other units were not measured.  out_store16: `base` and `words` (the array's length, the store's bound) are wave-uniform,
+// `word` is per lane and a multiple of 4; `base` is 16-byte aligned.
+// ---------------------------------------------------------------------------------
+template <class T> struct OutValue { typedef T type; };      // (the stored value converts to the array's type as in `*p = v`)
+#if defined(DRGNN_EMU) || !defined(DRGNN_WRITE_THROUGH)
+template <class T> DEV void out_store(T* p, typename OutValue<T>::type v) { *p = v; }
+DEV void out_store16(float* base, int word, int words, float a0, float a1, float a2, float a3) {
+    float* d = base + word;
+    (void)words;
+    d[0] = a0; d[1] = a1; d[2] = a2; d[3] = a3;
+}
+#else
+template <class T> DEV void out_store(T* p, typename OutValue<T>::type v) {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+DEV void out_store16(float* base, int word, int words, float a0, float a1, float a2, float a3) {
+    typedef unsigned int drgnn_u4 __attribute__((ext_vector_type(4)));
+    const drgnn_f4 v = {a0, a1, a2, a3};
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(drgnn_u4, v), buf_rsrc(base, words * 4), word * 4, 0, 16);
+}
+#endif
+
+// ---------------------------------------------------------------------------------
 // Wave-specialised staging of the SMALL arrays (offset tables, index lists, bias vectors): one staging job = one array
 // (or half of one) of at most 1024 32-bit words, handled by ONE wave with up to four 128-bit buffer loads (64 lanes x 4
 // words x 4) that stay in its registers until the LDS store one phase later.  Why: every instruction that all 16 waves of

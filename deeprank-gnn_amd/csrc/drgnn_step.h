@@ -280,7 +280,7 @@ DEV void step_pool_readout(int C1, const int* mp, const int* mem, const float* z
         if (bad) acc = DRGNN_NAN;
         if (kk == 0) {
             if (pub) xchg_publish(pub + c, tag, acc);      // first: the store that has the farthest to go
-            xr[c] = acc; g_readout[c] = acc;
+            xr[c] = acc; out_store(&g_readout[c], acc);
         }
     }
 }
@@ -428,7 +428,7 @@ DEV void step_head_loss_t(const HeadFused& hf, int g, int br, const float* hid, 
                 float acc = b2[o];
                 for (int h = 0; h < H; ++h) acc = fmaf(hid[h], w2[o * H + h], acc);
                 if (hf.sigmoid && hf.task != DRGNN_TASK_CLASS) acc = drgnn_sigmoid(acc);
-                hf.pred[(long)g * O + o] = acc;
+                out_store(&hf.pred[(long)g * O + o], acc);
             }
         }
         return;
@@ -468,13 +468,13 @@ DEV void step_head_loss_t(const HeadFused& hf, int g, int br, const float* hid, 
         const float dh = (hme != 0.0f) ? fmaf(dout, wme, 0.0f) * keep_scale : 0.0f;     // relu' and dropout mask
         dhid[h] = dh;
         if (br == 0) {
-            p_hw2[h] = dout * hme;
-            p_dhid[h] = dh;
+            out_store(&p_hw2[h], dout * hme);
+            out_store(&p_dhid[h], dh);
             if (threadIdx.x == 0) {
-                hf.pred[(long)g] = out;
-                p_hb2[0] = dout;
-                p_loss[0] = ext ? 0.0f : (d * d * inv);
-                p_loss[1] = 1.0f;
+                out_store(&hf.pred[(long)g], out);
+                out_store(&p_hb2[0], dout);
+                out_store(&p_loss[0], ext ? 0.0f : (d * d * inv));
+                out_store(&p_loss[1], 1.0f);
             }
         }
         return;
@@ -506,10 +506,10 @@ DEV void step_head_loss_t(const HeadFused& hf, int g, int br, const float* hid, 
         wsum = wy;
     }
     if (br == 0 && (int)threadIdx.x < O) {
-        hf.pred[(long)g * O + threadIdx.x] = my_out;
-        p_hb2[threadIdx.x] = my_dout;
+        out_store(&hf.pred[(long)g * O + threadIdx.x], my_out);
+        out_store(&p_hb2[threadIdx.x], my_dout);
     }
-    if (br == 0 && threadIdx.x == 0) { p_loss[0] = loss; p_loss[1] = wsum; }
+    if (br == 0 && threadIdx.x == 0) { out_store(&p_loss[0], loss); out_store(&p_loss[1], wsum); }
     for (int h0 = 0; h0 < H; h0 += DRGNN_NTHREADS) {      // uniform trip count: lane_get below is wave-wide
         const int h = h0 + (int)threadIdx.x;
         const bool ok = h < H;
@@ -519,13 +519,13 @@ DEV void step_head_loss_t(const HeadFused& hf, int g, int br, const float* hid, 
             const float dout = lane_get(my_dout, o);
             if (ok) {
                 acc = fmaf(dout, w2[o * H + h], acc);
-                if (br == 0) p_hw2[(long)o * H + h] = dout * hv;
+                if (br == 0) out_store(&p_hw2[(long)o * H + h], dout * hv);
             }
         }
         if (ok) {
             const float dh = (hv != 0.0f) ? acc * keep_scale : 0.0f;     // relu' and dropout mask
             dhid[h] = dh;
-            if (br == 0) p_dhid[h] = dh;
+            if (br == 0) out_store(&p_dhid[h], dh);
         }
     }
 }

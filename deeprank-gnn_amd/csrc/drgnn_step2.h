@@ -393,7 +393,7 @@ DEV void step2_head_fc1(const HeadFused& hf, int g, int half, const float* wb, c
         float r = tot * inv;
         if (bad) r = DRGNN_NAN;
         xr[lane] = r;
-        if (half == 0) g_readout[lane] = r;
+        if (half == 0) out_store(&g_readout[lane], r);
     }
     if (q == 0) {
         float v = fmaf(acc, inv, b1[h]);
@@ -437,7 +437,7 @@ DEV void step2_head_dreadout(const HeadFused& hf, const float* wb, const float* 
         cnt += dpp_take<0xB1>(cnt); cnt += dpp_take<0x4E>(cnt);
         if (sl == 0) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) g_dw2[(4 * f4 + i) * DRGNN_H2 + c] = v * sum[i];
+            for (int i = 0; i < 4; ++i) out_store(&g_dw2[(4 * f4 + i) * DRGNN_H2 + c], v * sum[i]);
             if (f4 == 0) g_db2[c] = v * cnt;
         }
     }

@@ -165,7 +165,7 @@ DEV void step3_dreadout_dw2(const float* wb, const float* dhid, const short* a1,
         for (int i = 0; i < 4; ++i) sum[i] = lanes8_sum(sum[i]);
         if (sl == 0) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) g_dw2[(4 * f4 + i) * DRGNN_H2 + c] = v * sum[i];
+            for (int i = 0; i < 4; ++i) out_store(&g_dw2[(4 * f4 + i) * DRGNN_H2 + c], v * sum[i]);
         }
     }
 }
@@ -661,7 +661,7 @@ DEV void step3d_pool_readout(int tid, int C1, const int* mp, const int* mem, con
     }
     acc = lanes16_sum(acc) * inv;
     if (bad) acc = DRGNN_NAN;
-    if (kk == 0) { xr[c] = acc; g_readout[c] = acc; }
+    if (kk == 0) { xr[c] = acc; out_store(&g_readout[c], acc); }
 }
 // step3_dw1_sparse with the sixteen channels on eight waves (two channels per wave, one after the other)
 template <int XF>

@@ -998,18 +998,16 @@ DEV void topo_tiles_rows(const TopoTile& t, int N, const int* rp, const int* col
                 a0 += xj[0]; a1 += xj[1]; a2 += xj[2]; a3 += xj[3];
             }
         }
-        float* dst = t.ts + (long long)i * F + c;
-        dst[0] = a0; dst[1] = a1; dst[2] = a2; dst[3] = a3;
+        out_store16(t.ts, i * F + c, N * F, a0, a1, a2, a3);
         if (t.tx != nullptr) {
             const float* xi = t.xs + ROW24(i, XLD) + c;
-            float* dx = t.tx + (long long)i * F + c;
-            dx[0] = xi[0]; dx[1] = xi[1]; dx[2] = xi[2]; dx[3] = xi[3];
+            out_store16(t.tx, i * F + c, N * F, xi[0], xi[1], xi[2], xi[3]);
         }
         if (c == 0) {
             float d, sc;
             if (w_s != nullptr) { d = 1.0f / (float)(deg > 0 ? deg : 1); sc = asum * d; }
             else { d = deg > 0 ? 1.0f / (float)deg : 0.0f; sc = 1.0f; }
-            t.td[i] = d; t.tc[i] = sc;
+            out_store(&t.td[i], d); out_store(&t.tc[i], sc);
         }
     }
 }
@@ -1104,7 +1102,7 @@ DEV void topo_lean_rows_claim(const TopoView& tv, int g, int n0, int N, int E, T
     const int* Z = s.rp;
     int32_t* g_rowptr0 = tv.p[DRGNN_TI_ROWPTR0] + (n0 + g);
     FOR_TID(e, E) { const int r = s.er[e]; s.t1[Z[r] + ATOMIC_ADD(&s.cur[r], 1)] = e; }
-    FOR_TID(i, N + 1) { g_rowptr0[i] = Z[i]; }
+    FOR_TID(i, N + 1) { out_store(&g_rowptr0[i], Z[i]); }
 }
 // rank of every edge inside its row by edge id, emitted at once; column / weight by slot stay in LDS for the tiles
 DEV void topo_lean_rows_emit(const TopoView& tv, int e0, int E, bool has_w, TopoScratch& s) {
@@ -1119,10 +1117,10 @@ DEV void topo_lean_rows_emit(const TopoView& tv, int e0, int E, bool has_w, Topo
         int rank = 0;
         for (int q = lo; q < hi; ++q) rank += (s.t1[q] < e) ? 1 : 0;
         const int cc = s.ec[e];
-        g_col0[lo + rank] = cc;
-        g_eid0[lo + rank] = e;
+        out_store(&g_col0[lo + rank], cc);
+        out_store(&g_eid0[lo + rank], e);
         s.col[lo + rank] = cc;
-        if (has_w) { const float w = s.w0[e]; g_w0[lo + rank] = w; s.wr[lo + rank] = w; }
+        if (has_w) { const float w = s.w0[e]; out_store(&g_w0[lo + rank], w); s.wr[lo + rank] = w; }
     }
 }
 // from the claim on (the histogram is scanned); leaves no barrier behind its last phase
@@ -1188,18 +1186,18 @@ DEV int topo_lean_clusters(const TopoView& tv, int g, int n0, int e0, int N, int
         int32_t* g_cl1 = tv.p[DRGNN_TI_CL1] + n0;
         FOR_TID(i, N) {
             const int c = Z[s.pp[i]];
-            s.cl[i] = c; g_cl0[i] = c;
+            s.cl[i] = c; out_store(&g_cl0[i], c);
             ATOMIC_ADD(&csize[c], 1);
         }
         FOR_TID(c, n) {
             const int k = Z[H + s.nb[c]] - C;
             cl1[c] = k;
             key1[c] = (k << 16) | c;                // (k < 2^15, c < 2^15)
-            g_cl1[c] = k;
+            out_store(&g_cl1[c], k);
         }
         if (with_pool) { FOR_TID(q, CB) { bm[q] = 0; bmT[q] = 0; } }
         if (with_pool && has_w) { FOR_TID(q, 2 * E) { s.seg[q] = 0; } }      // 64-bit accumulators of the pooled weights: [seg | col1]
-        FOR_TID(i, 1) { tv.p[DRGNN_TI_NC0][g] = C; tv.p[DRGNN_TI_NC1][g] = C1; }
+        FOR_TID(i, 1) { out_store(&tv.p[DRGNN_TI_NC0][g], C); out_store(&tv.p[DRGNN_TI_NC1][g], C1); }
     }
     if (rows) topo_lean_rows_claim(tv, g, n0, N, E, s);      // (its cursors, s.cur, are this chain's only from the next interval on)
     BARRIER();
@@ -1227,7 +1225,7 @@ DEV int topo_lean_clusters(const TopoView& tv, int g, int n0, int e0, int N, int
         FOR_TID_FROM(item, (C1 + 1) * G, 384) {
             const int k = item / G, sub = item % G;
             const int cnt = topo_count_below<8>(cl1, n, k, sub);
-            if (sub == 0) { mp1[k] = cnt; g_mptr1[k] = cnt; }
+            if (sub == 0) { mp1[k] = cnt; out_store(&g_mptr1[k], cnt); }
         }
         FOR_TID(c, C + 1) { s.cur[c] = 0; }      // cursors of the node claim below
     }
@@ -1237,14 +1235,14 @@ DEV int topo_lean_clusters(const TopoView& tv, int g, int n0, int e0, int N, int
     {
         int32_t* g_mem1 = tv.p[DRGNN_TI_MEM1] + n0;
         int32_t* g_hmp = tv.p[DRGNN_TI_HMP0] + rowbase;
-        FOR_TID(c, n) { g_mem1[qpos[c]] = c; }
+        FOR_TID(c, n) { out_store(&g_mem1[qpos[c]], c); }
         constexpr int G = TOPO_LANES(8);
         FOR_TID(item, (C + 1) * G) {       // first position of the q-th cluster = sizes of the clusters in front of it
             const int q = item / G, sub = item % G;
             int acc = 0;
             for (int c = sub; c < C; c += G) acc += (qpos[c] < q) ? csize[c] : 0;
             acc = topo_group_sum<G>(acc);
-            if (sub == 0) { hmp[q] = acc; g_hmp[q] = acc; }
+            if (sub == 0) { hmp[q] = acc; out_store(&g_hmp[q], acc); }
         }
     }
     if (rows && tile.F > 0) topo_tiles_rows(tile, N, s.rp, s.col, has_w ? (const float*)s.wr : nullptr);
@@ -1263,10 +1261,10 @@ DEV int topo_lean_clusters(const TopoView& tv, int g, int n0, int e0, int N, int
             while (bits) {
                 const int b = __builtin_ctz(bits);
                 bits &= bits - 1;
-                dst[slot] = base + b;
+                out_store(&dst[slot], base + b);
                 if (tr && has_w) {      // CSR1 slot of this CSC1 entry (column r, row base + b): the set bits of row's bitmap in front of it
                     const int row = base + b, w_ = row * BW + (r >> 5);
-                    g_tslot1[slot] = Y[w_] + __builtin_popcount((unsigned)bm[w_] & ((1u << (r & 31)) - 1u));
+                    out_store(&g_tslot1[slot], Y[w_] + __builtin_popcount((unsigned)bm[w_] & ((1u << (r & 31)) - 1u)));
                 }
                 ++slot;
             }
@@ -1289,8 +1287,8 @@ DEV int topo_lean_clusters(const TopoView& tv, int g, int n0, int e0, int N, int
         }
         int32_t* g_rowptr1 = tv.p[DRGNN_TI_ROWPTR1] + rowbase;
         int32_t* g_colptr1 = tv.p[DRGNN_TI_COLPTR1] + rowbase;
-        FOR_TID(r, C + 1) { g_rowptr1[r] = Y[r * BW]; g_colptr1[r] = Y[CB + r * BW] - E1; }
-        FOR_TID(i, 1) { tv.p[DRGNN_TI_NE1][g] = E1; }
+        FOR_TID(r, C + 1) { out_store(&g_rowptr1[r], Y[r * BW]); out_store(&g_colptr1[r], Y[CB + r * BW] - E1); }
+        FOR_TID(i, 1) { out_store(&tv.p[DRGNN_TI_NE1][g], E1); }
     };
     auto node_claim = [&]() {
     FOR_TID_FROM(i, N, 768) {
@@ -1309,8 +1307,8 @@ DEV int topo_lean_clusters(const TopoView& tv, int g, int n0, int e0, int N, int
             const int lo = hmp[b], hi = hmp[b + 1];
             int rank = 0;
             for (int q = lo; q < hi; ++q) rank += (s.t5[q] < me) ? 1 : 0;
-            g_hord[lo + rank] = me;
-            g_ihord[me] = lo + rank;
+            out_store(&g_hord[lo + rank], me);
+            out_store(&g_ihord[me], lo + rank);
         }
     }
     {   // split point: the number k of leading depth-1 clusters whose node total is closest to N / 2 (smallest k on ties)
@@ -1325,7 +1323,7 @@ DEV int topo_lean_clusters(const TopoView& tv, int g, int n0, int e0, int N, int
         }
         const int kb = (int)(best & 0xffffffffLL);
         const int qb = imin(mp1[kb], C);
-        hs[0] = kb; hs[1] = qb; hs[2] = hmp[qb]; hs[3] = C1;
+        out_store(&hs[0], kb); out_store(&hs[1], qb); out_store(&hs[2], hmp[qb]); out_store(&hs[3], C1);
 #else
         if (threadIdx.x < DRGNN_WAVE) {
             long long best = LLONG_MAX, other = LLONG_MIN;
@@ -1339,7 +1337,7 @@ DEV int topo_lean_clusters(const TopoView& tv, int g, int n0, int e0, int N, int
             if (threadIdx.x == 0) {
                 const int kb = (int)(best & 0xffffffffLL);
                 const int qb = imin(mp1[kb], C);
-                hs[0] = kb; hs[1] = qb; hs[2] = hmp[qb]; hs[3] = C1;
+                out_store(&hs[0], kb); out_store(&hs[1], qb); out_store(&hs[2], hmp[qb]); out_store(&hs[3], C1);
             }
         }
 #endif
@@ -1395,7 +1393,7 @@ DEV int topo_lean_clusters(const TopoView& tv, int g, int n0, int e0, int N, int
         const long long* acc = (const long long*)s.seg;
         float* g_w1 = tv.w1 + e0;
         const int E1 = s.t4[CB];      // (= Y[CB]: the pooled edge count)
-        FOR_TID(q, E1) { g_w1[q] = (float)((double)acc[q] * inv); }
+        FOR_TID(q, E1) { out_store(&g_w1[q], (float)((double)acc[q] * inv)); }
     }
     hier_tail();
     return 0;
