@@ -181,6 +181,27 @@ class PackRequest(ctypes.Structure):
 PACK_TYPE, PACK_POS, PACK_CHAIN, PACK_BSA, PACK_HSE, PACK_RES = range(6)      # sources of drgnn_pack_request.cols
 
 
+class PoseContactsRequest(ctypes.Structure):
+    """drgnn_pose_contacts_request (include/drgnn.h): M coordinate sets of the counted atoms of one two-chain topology;
+    ``host_atom_ptr`` is the address of a host copy of the offset table."""
+    _fields_ = [("xyz", _vp), ("atom_ptr", _vp), ("host_atom_ptr", _vp),
+                ("n_poses", _c_i64), ("n_atoms", _c_i64), ("n_residues", _c_i64), ("n_chain_a", _c_i64),
+                ("cutoff", ctypes.c_double), ("bits", _vp), ("n_contacts", _vp)]
+
+
+class PoseCommonRequest(ctypes.Structure):
+    """drgnn_pose_common_request (include/drgnn.h): two sets of contact bit rows of ``n_words`` words each."""
+    _fields_ = [("bits_a", _vp), ("bits_b", _vp), ("n_a", _c_i64), ("n_b", _c_i64), ("n_words", _c_i64), ("common", _vp)]
+
+
+class PoseClusterRequest(ctypes.Structure):
+    """drgnn_pose_cluster_request (include/drgnn.h): the common-contact matrix and the contact counts of M poses."""
+    _fields_ = [("common", _vp), ("n_contacts", _vp), ("n_poses", _c_i64),
+                ("cutoff_fcc", ctypes.c_double), ("cutoff_reverse", ctypes.c_double), ("min_size", _c_i32),
+                ("neighbours", _vp), ("transposed", _vp), ("labels", _vp), ("centres", _vp), ("sizes", _vp),
+                ("n_clusters", _vp)]
+
+
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p)
 
 
@@ -400,6 +421,11 @@ class Api(object):
         lib.drgnn_pack_capacity.argtypes = [_c_i32]
         lib.drgnn_pack_capacity.restype = _c_i32
         lib.drgnn_iface_pack.argtypes = [ctypes.POINTER(PackRequest), _vp]
+        lib.drgnn_fcc_capacity.argtypes = [_c_i32]
+        lib.drgnn_fcc_capacity.restype = _c_i32
+        lib.drgnn_pose_contacts.argtypes = [ctypes.POINTER(PoseContactsRequest), _vp]
+        lib.drgnn_pose_common.argtypes = [ctypes.POINTER(PoseCommonRequest), _vp]
+        lib.drgnn_pose_cluster.argtypes = [ctypes.POINTER(PoseClusterRequest), _vp]
         if lib.drgnn_abi_version() != 5:
             raise DrgnnError("ABI mismatch in %s" % path)
 
@@ -688,6 +714,18 @@ class Api(object):
 
     def iface_pack(self, request, stream):
         _check(self.lib.drgnn_iface_pack(ctypes.byref(request), stream), "drgnn_iface_pack")
+
+    def fcc_capacity(self, what):
+        return int(self.lib.drgnn_fcc_capacity(int(what)))
+
+    def pose_contacts(self, request, stream):
+        _check(self.lib.drgnn_pose_contacts(ctypes.byref(request), stream), "drgnn_pose_contacts")
+
+    def pose_common(self, request, stream):
+        _check(self.lib.drgnn_pose_common(ctypes.byref(request), stream), "drgnn_pose_common")
+
+    def pose_cluster(self, request, stream):
+        _check(self.lib.drgnn_pose_cluster(ctypes.byref(request), stream), "drgnn_pose_cluster")
 
     def iface_fill(self, request, n_nodes, n_edges, n_iedges, node_residue, pos, chain, type_, edge_index, dist,
                    internal_edge_index, internal_dist, stream):

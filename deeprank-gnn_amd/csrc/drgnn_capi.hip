@@ -2422,6 +2422,100 @@ int drgnn_iface_pack(const drgnn_pack_request* q, void* stream) {
     return 0;
 }
 
+// ---- clustering of poses by their fraction of common contacts (drgnn_fcc.h) --------------------------
+int32_t drgnn_fcc_capacity(int32_t what) { return what == 0 ? FC_RCAP : what == 1 ? FC_PCAP : what == 2 ? FC_CCAP : -1; }
+
+int drgnn_pose_contacts(const drgnn_pose_contacts_request* q, void* stream) {
+    if (!q || !q->host_atom_ptr) return DRGNN_E_ARG;
+    const int64_t M = q->n_poses, T = q->n_atoms, R = q->n_residues, A = q->n_chain_a;
+    if (M < 0 || T < 0 || R < 0 || A < 0 || A > R || M > INT32_MAX || T > INT32_MAX / 3) return DRGNN_E_ARG;
+    if (!(q->cutoff > 0.0) || !(q->cutoff < 1.0e18)) return DRGNN_E_ARG;              // (its square is a finite fp32)
+    if (!q->atom_ptr || (M > 0 && !q->n_contacts) || (M > 0 && T > 0 && !q->xyz)) return DRGNN_E_ARG;
+    if (R > FC_RCAP) return DRGNN_E_CAPACITY;
+    const int64_t WB = (R - A + 63) / 64;
+    if (M > 0 && A * WB > 0 && !q->bits) return DRGNN_E_ARG;
+    const int32_t* ap = q->host_atom_ptr;
+    if (ap[0] != 0 || ap[R] != T) return DRGNN_E_ARG;
+    for (int64_t r = 0; r < R; ++r)
+        if (ap[r + 1] < ap[r]) return DRGNN_E_ARG;
+    if (M == 0) return 0;
+    FccContactArgs a;
+    memset(&a, 0, sizeof(a));
+    a.xyz = q->xyz; a.atom_ptr = q->atom_ptr; a.n_atoms = (int)T; a.n_res = (int)R; a.n_a = (int)A;
+    a.cut = (float)q->cutoff; a.cut2 = (float)(q->cutoff * q->cutoff);
+    a.bits = (fc_word*)q->bits; a.n_contacts = q->n_contacts;
+#ifdef DRGNN_EMU
+    (void)stream;
+    std::unique_ptr<FccContactShared> lds(new FccContactShared);
+    for (int64_t m = 0; m < M; ++m) fc_pose(a, m, *lds);
+#else
+    static_assert(sizeof(FccContactShared) <= 64 * 1024, "the spheres fit the static LDS of a workgroup");
+    hipLaunchKernelGGL(k_fcc_contacts, dim3((unsigned)M), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+#endif
+    return 0;
+}
+
+int drgnn_pose_common(const drgnn_pose_common_request* q, void* stream) {
+    if (!q) return DRGNN_E_ARG;
+    const int64_t Ma = q->n_a, Mb = q->n_b, W = q->n_words;
+    if (Ma < 0 || Mb < 0 || W < 0 || W > INT32_MAX) return DRGNN_E_ARG;
+    if (Ma > 0 && Mb > 0 && (!q->common || (W > 0 && (!q->bits_a || !q->bits_b)))) return DRGNN_E_ARG;
+    if (Ma > FC_PCAP || Mb > FC_PCAP) return DRGNN_E_CAPACITY;
+    if (Ma == 0 || Mb == 0) return 0;
+    FccCommonArgs a;
+    memset(&a, 0, sizeof(a));
+    a.a = (const fc_word*)q->bits_a; a.b = (const fc_word*)q->bits_b; a.n_a = (int)Ma; a.n_b = (int)Mb; a.n_words = W;
+    a.common = q->common;
+    const int ti = (int)((Ma + FC_TILE - 1) / FC_TILE), tj = (int)((Mb + FC_TILE - 1) / FC_TILE);
+#ifdef DRGNN_EMU
+    (void)stream;
+    std::unique_ptr<FccCommonShared> lds(new FccCommonShared);
+    for (int i = 0; i < ti; ++i)
+        for (int j = 0; j < tj; ++j) fc_common(a, i, j, *lds);
+#else
+    static_assert(FC_TILE * FC_TILE == DRGNN_NTHREADS, "one lane per pose pair of a tile");
+    static_assert((FC_PCAP + FC_TILE - 1) / FC_TILE <= 65535, "the tiles of a side fit the grid's y");
+    hipLaunchKernelGGL(k_fcc_common, dim3((unsigned)tj, (unsigned)ti), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+#endif
+    return 0;
+}
+
+int drgnn_pose_cluster(const drgnn_pose_cluster_request* q, void* stream) {
+    if (!q) return DRGNN_E_ARG;
+    const int64_t M = q->n_poses;
+    if (M < 0 || q->min_size < 1) return DRGNN_E_ARG;
+    if (!(q->cutoff_fcc > 0.0) || !(q->cutoff_fcc <= 1.0) || !(q->cutoff_reverse > 0.0) || !(q->cutoff_reverse <= 1.0))
+        return DRGNN_E_ARG;
+    if (!q->n_clusters) return DRGNN_E_ARG;
+    if (M > 0 && (!q->common || !q->n_contacts || !q->neighbours || !q->transposed || !q->labels || !q->centres || !q->sizes))
+        return DRGNN_E_ARG;
+    if (M > FC_CCAP) return DRGNN_E_CAPACITY;
+    if (M == 0) return 0;
+    FccClusterArgs a;
+    memset(&a, 0, sizeof(a));
+    a.common = q->common; a.n_contacts = q->n_contacts; a.n = (int)M; a.min_size = q->min_size;
+    a.cut_fwd = q->cutoff_fcc; a.cut_rev = q->cutoff_reverse;
+    a.nb = (fc_word*)q->neighbours; a.nbt = (fc_word*)q->transposed;
+    a.labels = q->labels; a.centres = q->centres; a.sizes = q->sizes; a.n_clusters = q->n_clusters;
+    const int64_t words = M * ((M + 63) / 64), blocks = (words + DRGNN_NWAVES - 1) / DRGNN_NWAVES;
+#ifdef DRGNN_EMU
+    (void)stream;
+    for (int64_t b = 0; b < blocks; ++b) fc_relation(a, b);
+    std::unique_ptr<FccGreedyShared> lds(new FccGreedyShared);
+    fc_greedy(a, *lds);
+#else
+    static_assert(FC_CCAP <= (1 << FC_KEY_SHIFT) && FC_CCAP % 64 == 0, "a pose index fits the low bits of the greedy key");
+    static_assert(sizeof(FccGreedyShared) <= 64 * 1024, "the degrees and the member list fit the static LDS of a workgroup");
+    hipLaunchKernelGGL(k_fcc_relation, dim3((unsigned)blocks), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_fcc_greedy, dim3(1), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+#endif
+    return 0;
+}
+
 // ---- evaluation scores (drgnn_metrics.h) ---------------------------------------------------------
 int64_t drgnn_metrics_workspace_bytes(int64_t n) {
     if (n < 0 || n > INT32_MAX) return -1;

@@ -15,6 +15,7 @@
 #include "drgnn_score.h"
 #include "drgnn_bsa.h"
 #include "drgnn_hse.h"
+#include "drgnn_fcc.h"
 #include "drgnn_pack.h"
 #include "drgnn_metrics.h"
 #include "drgnn_collate.h"
@@ -1005,6 +1006,21 @@ __global__ void __launch_bounds__(DRGNN_NTHREADS, 8) k_bsa_residues(BsaArgs a) {
 __global__ void __launch_bounds__(DRGNN_NTHREADS) k_hse_residues(HseArgs a) {
     __shared__ HseShared smem_hs;
     hse_tile(a, (int)blockIdx.x, smem_hs);
+}
+// fraction of common contacts (drgnn_fcc.h): one workgroup per pose; per tile of pose pairs; a wave per word of the
+// neighbour relation; ONE workgroup for the greedy clustering
+__global__ void __launch_bounds__(DRGNN_NTHREADS) k_fcc_contacts(FccContactArgs a) {
+    __shared__ FccContactShared smem_fc;
+    fc_pose(a, (int64_t)blockIdx.x, smem_fc);
+}
+__global__ void __launch_bounds__(DRGNN_NTHREADS) k_fcc_common(FccCommonArgs a) {
+    __shared__ FccCommonShared smem_fm;
+    fc_common(a, (int)blockIdx.y, (int)blockIdx.x, smem_fm);
+}
+__global__ void __launch_bounds__(DRGNN_NTHREADS) k_fcc_relation(FccClusterArgs a) { fc_relation(a, (int64_t)blockIdx.x); }
+__global__ void __launch_bounds__(DRGNN_NTHREADS) k_fcc_greedy(FccClusterArgs a) {
+    __shared__ FccGreedyShared smem_fg;
+    fc_greedy(a, smem_fg);
 }
 // the builder's output packed into a resident set's arrays (drgnn_pack.h): one workgroup per complex
 __global__ void __launch_bounds__(PK_NT) k_iface_pack(PackArgs a) {

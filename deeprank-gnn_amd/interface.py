@@ -41,6 +41,12 @@ device (csrc/drgnn_pack.h) into the ``ResidentGraphSet`` that ``NeuralNet.test``
     rs = interface_resident_set(poses, names, node_feature=["type", "polarity", "bsa", "hse", "pssm"],
                                 residue_features={"pssm": table_R_by_20}, reference=ref, target="irmsd")
 
+After scoring, the poses are clustered by the fraction of common contacts of their interfaces (FCC, the rule of
+HADDOCK's ``cluster_fcc``; csrc/drgnn_fcc.h) and the clusters ranked by their best members:
+
+    clusters = cluster_poses(poses)                            # labels [M] (-1: in no cluster), centres, sizes
+    order, means = clusters.rank(scores, top=4)                # scores [M]: Ensemble.predict or docking_scores()[key]
+
 Not covered: ``depth`` (Biopython through the MSMS program) and PSSM file parsing (``pssm``, ``cons``, ``ic``).  For those every
 graph carries ``node_data/residue``, each node's index among the residues of its
 ``AtomTable``: a per-residue array the caller holds is attached with ``attach_residue_features``.
@@ -1222,3 +1228,259 @@ def residue_hse(tables_or_poses, residues=None, radius=12.0, offset=0, connect="
     if isinstance(tables_or_poses, Poses):
         return np.stack(full) if full else np.zeros((0, tables_or_poses.table.n_residues, 3))
     return full
+
+
+# ---- clustering of poses by their fraction of common contacts (csrc/drgnn_fcc.h) -----------------------------------
+FCC_XYZ_BUDGET = 256 << 20         # bytes of pose coordinates one drgnn_pose_contacts call uploads (sets the default chunk)
+
+
+def counted_atoms(table, heavy_only=None):
+    """(keep int64 [T'], atom_ptr int32 [R+1]): the atoms of ``table`` (grouped order) that decide contacts and their
+    grouping into residues.  ``heavy_only``: leave out hydrogens, the atoms whose name's first character that is neither a
+    digit nor a blank is ``H``; None: True when the table has atom names."""
+    if heavy_only is None:
+        heavy_only = table.atom_name is not None
+    keep = np.ones(table.n_atoms, dtype=bool)
+    if heavy_only:
+        if table.atom_name is None:
+            raise ValueError("heavy_only=True finds hydrogens by atom name: build the AtomTable with atom_name=")
+        keep = np.array([n.lstrip("0123456789 ")[:1] != "H" for n in table.atom_name], dtype=bool).reshape(-1)
+    res_of_atom = np.repeat(np.arange(table.n_residues), np.diff(table.atom_ptr))
+    counts = np.bincount(res_of_atom[keep], minlength=table.n_residues)
+    return np.flatnonzero(keep), np.concatenate(([0], np.cumsum(counts))).astype(np.int32)
+
+
+def _pose_batch(poses, table):
+    """(table, xyz float32 [M, T, 3] in the table's grouped order) of an ``AtomTable.poses`` batch, a table, or xyz with
+    ``table``"""
+    if isinstance(poses, (Poses, AtomTable)):
+        own = poses.table if isinstance(poses, Poses) else poses
+        if table is not None and own is not table:
+            raise ValueError("the poses must be of the given AtomTable")
+        return own, (poses.xyz if isinstance(poses, Poses) else poses.xyz[None])
+    if table is None:
+        raise ValueError("coordinates need table=, the AtomTable they are poses of")
+    xyz = np.asarray(poses)
+    if xyz.ndim != 3 or xyz.shape[1:] != (table.n_atoms, 3):
+        raise ValueError("poses need xyz [M, %d, 3]" % table.n_atoms)
+    return table, xyz
+
+
+class PoseContacts(object):
+    """``pose_contacts``: ``bits`` int64 [M, nA, WB] on the device (the 64-bit words of drgnn_pose_contacts: bit b % 64
+    of word b / 64 of row a says that residue a of the first chain and residue b of the second are in contact),
+    ``n_contacts`` int64 [M] on the host, ``table``, ``n_a`` / ``n_b`` the residues of the two chains."""
+
+    def __init__(self, table, bits, n_contacts, api, device, cutoff, heavy_only):
+        self.table, self.bits, self.n_contacts, self.api, self.device = table, bits, n_contacts, api, device
+        self.cutoff, self.heavy_only = cutoff, heavy_only
+        self.n_a, self.n_b = table.split, table.n_residues - table.split
+
+    def __len__(self):
+        return int(self.n_contacts.shape[0])
+
+    def words(self, m=None):
+        """the words as numpy uint64 [M, nA, WB], or [nA, WB] of pose m"""
+        w = (self.bits if m is None else self.bits[m]).cpu().numpy().view(np.uint64)
+        return w
+
+    def pairs(self, m):
+        """int32 [n_m, 2]: the contacts of pose m as (residue of the first chain, residue of the second), both indices
+        into the table's residues, sorted"""
+        if self.n_a == 0 or self.n_b == 0:
+            return np.zeros((0, 2), np.int32)
+        w = self.words(m)
+        on = np.unpackbits(w.view(np.uint8).reshape(self.n_a, -1), axis=1, bitorder="little")[:, :self.n_b]
+        a, b = np.nonzero(on)
+        return np.stack((a, b + self.n_a), axis=1).astype(np.int32)
+
+
+def pose_contacts_raw(api, xyz, atom_ptr, n_chain_a, cutoff=5.0, device="cpu"):
+    """One drgnn_pose_contacts call (include/drgnn.h) over numpy arrays: xyz float32 [M, T, 3] of the counted atoms.
+    Returns (bits int64 [M, nA, WB], n_contacts int32 [M]) as tensors on ``device``."""
+    dev = torch.device(device)
+    xyz = np.ascontiguousarray(xyz, dtype=np.float32)
+    host = np.ascontiguousarray(atom_ptr, dtype=np.int32)
+    M, R, nA = int(xyz.shape[0]), len(host) - 1, int(n_chain_a)
+    d_xyz = torch.from_numpy(xyz).to(dev)
+    if api is _lib._API:
+        _lib.require_device(d_xyz)
+    d_ap = torch.from_numpy(host).to(dev)
+    bits = torch.empty((M, max(nA, 0), (max(R - nA, 0) + 63) // 64), dtype=torch.int64, device=dev)
+    count = torch.empty(M, dtype=torch.int32, device=dev)
+    q = _lib.PoseContactsRequest()
+    q.xyz, q.atom_ptr, q.host_atom_ptr = d_xyz.data_ptr(), d_ap.data_ptr(), host.ctypes.data
+    q.n_poses, q.n_atoms, q.n_residues, q.n_chain_a, q.cutoff = M, int(xyz.shape[1]), R, nA, float(cutoff)
+    q.bits, q.n_contacts = bits.data_ptr(), count.data_ptr()
+    api.pose_contacts(q, _lib.current_stream(d_xyz))
+    return bits, count
+
+
+def pose_contacts(poses, cutoff=5.0, heavy_only=None, device=None, api=None, chunk=None, table=None):
+    """The interface contacts of M poses of one topology (an ``AtomTable.poses`` batch, a table, or xyz float32 [M,T,3]
+    in the grouped atom order of ``table``), on the device: residue a of the first chain and residue b of the second are
+    in contact when a counted atom of each lie within ``cutoff`` A (d^2 <= float32(cutoff^2) on the float32 coordinates,
+    the rule of ``fnat``).  ``heavy_only``: hydrogens do not count (the default when the table has atom names).  Returns a
+    ``PoseContacts``; a pose's bits do not depend on M, on ``chunk`` (poses per launch), on its place or on the run."""
+    if not float(cutoff) > 0.0 or not float(cutoff) < 1e18:
+        raise ValueError("cutoff must be > 0")
+    t, xyz = _pose_batch(poses, table)
+    keep, atom_ptr = counted_atoms(t, heavy_only)
+    api = api or _lib.get()
+    if device is None:
+        device = "cuda" if api is _lib._API else "cpu"
+    if t.n_residues > api.fcc_capacity(0):
+        _lib._check(-2, "drgnn_pose_contacts")
+    if chunk is None:
+        chunk = FCC_XYZ_BUDGET // (12 * max(len(keep), 1))
+    chunk = max(1, int(chunk))
+    nA, WB = t.split, (t.n_residues - t.split + 63) // 64
+    parts = [pose_contacts_raw(api, xyz[lo:lo + chunk][:, keep], atom_ptr, nA, cutoff, device)
+             for lo in range(0, xyz.shape[0], chunk)]
+    if parts:
+        bits = torch.cat([p[0] for p in parts]) if len(parts) > 1 else parts[0][0]
+        count = np.concatenate([p[1].cpu().numpy() for p in parts]).astype(np.int64)
+    else:
+        bits, count = torch.empty((0, nA, WB), dtype=torch.int64, device=torch.device(device)), np.zeros(0, np.int64)
+    return PoseContacts(t, bits, count, api, device, float(cutoff), len(keep) != t.n_atoms)
+
+
+def pose_common_raw(api, bits_a, bits_b):
+    """One drgnn_pose_common call over tensors of words [Ma, W] and [Mb, W] (one device): int32 [Ma, Mb] on that device"""
+    Ma, Mb, W = int(bits_a.shape[0]), int(bits_b.shape[0]), int(bits_a.shape[1])
+    out = torch.empty((Ma, Mb), dtype=torch.int32, device=bits_a.device)
+    q = _lib.PoseCommonRequest()
+    q.bits_a, q.bits_b, q.common = bits_a.data_ptr(), bits_b.data_ptr(), out.data_ptr()
+    q.n_a, q.n_b, q.n_words = Ma, Mb, W
+    api.pose_common(q, _lib.current_stream(bits_a))
+    return out
+
+
+def _common_device(a, b=None):
+    """common contacts of two ``PoseContacts`` as an int32 tensor [M, M2] on their device; calls of at most
+    drgnn_fcc_capacity(1) poses a side"""
+    b = a if b is None else b
+    if not isinstance(a, PoseContacts) or not isinstance(b, PoseContacts):
+        raise ValueError("common contacts are taken between PoseContacts (pose_contacts)")
+    if (a.n_a, a.n_b) != (b.n_a, b.n_b) or a.api is not b.api or torch.device(a.device) != torch.device(b.device):
+        raise ValueError("the two sets of contacts must be of one topology, library and device")
+    W = a.n_a * ((a.n_b + 63) // 64)
+    wa, wb = a.bits.reshape(len(a), W), b.bits.reshape(len(b), W)
+    if len(a) == 0 or len(b) == 0:
+        return torch.zeros((len(a), len(b)), dtype=torch.int32, device=wa.device)
+    cap = a.api.fcc_capacity(1)
+    if len(a) <= cap and len(b) <= cap:
+        return pose_common_raw(a.api, wa, wb)
+    out = torch.empty((len(a), len(b)), dtype=torch.int32, device=wa.device)
+    for i in range(0, len(a), cap):
+        for j in range(0, len(b), cap):
+            out[i:i + cap, j:j + cap] = pose_common_raw(a.api, wa[i:i + cap], wb[j:j + cap])
+    return out
+
+
+def common_contacts(a, b=None):
+    """int32 [M, M2]: the number of contacts pose i of ``a`` shares with pose j of ``b`` (``b`` None: of ``a`` itself; the
+    diagonal is then ``n_contacts``).  ``a`` and ``b`` are ``PoseContacts`` of one topology."""
+    return _common_device(a, b).cpu().numpy()
+
+
+def fcc_matrix(a, b=None):
+    """float64 [M, M2]: the fraction of the contacts of pose i of ``a`` that pose j of ``b`` has too, ``common[i, j] /
+    n_contacts[i]`` as one float64 division; a pose without contacts has a row of zeros.  Not symmetric."""
+    common = common_contacts(a, b).astype(np.float64)
+    n = a.n_contacts.astype(np.float64)
+    out = np.zeros_like(common)
+    has = n > 0
+    out[has] = common[has] / n[has, None]
+    return out
+
+
+class PoseClusters(object):
+    """``cluster_poses``: ``labels`` int64 [M] (the cluster of every pose in order of discovery, -1: in none),
+    ``centres`` / ``sizes`` int64 [K] per cluster, ``n_contacts`` int64 [M]."""
+
+    def __init__(self, labels, centres, sizes, n_contacts):
+        self.labels, self.centres, self.sizes, self.n_contacts = labels, centres, sizes, n_contacts
+
+    def __len__(self):
+        return int(self.centres.shape[0])
+
+    def rank(self, scores, top=4, ascending=False):
+        """(order int64 [K], means float64 [K]): the clusters ordered by the mean of their ``top`` best member scores
+        (HADDOCK's convention; all members of a smaller cluster), best first, ties by cluster ordinal; ``means`` per
+        cluster ordinal.  ``scores`` [M]: what ``Ensemble.predict`` or ``docking_scores()[key]`` gives for the same
+        poses; ``ascending``: the smaller score is the better one."""
+        if torch.is_tensor(scores):
+            scores = scores.detach().cpu().numpy()
+        scores = np.asarray(scores, dtype=np.float64).reshape(-1)
+        if scores.shape[0] != self.labels.shape[0]:
+            raise ValueError("%d scores for %d poses" % (scores.shape[0], self.labels.shape[0]))
+        if int(top) < 1:
+            raise ValueError("top must be >= 1")
+        means = np.zeros(len(self))
+        for k in range(len(self)):
+            s = np.sort(scores[self.labels == k])
+            means[k] = (s if ascending else s[::-1])[:int(top)].mean()
+        order = np.lexsort((np.arange(len(self)), means if ascending else -means))
+        return order.astype(np.int64), means
+
+
+def pose_cluster_raw(api, common, n_contacts, cutoff_fcc=0.6, cutoff_reverse=0.45, min_size=4, device="cpu"):
+    """One drgnn_pose_cluster call (include/drgnn.h): ``common`` int32 [M, M] and ``n_contacts`` int32 [M] as numpy arrays
+    or tensors on ``device``.  Returns a dict of numpy arrays: labels int32 [M], centres / sizes int32 [K], neighbours /
+    transposed uint64 [M, ceil(M/64)] (the directed relation and its transpose as bit rows)."""
+    dev = torch.device(device)
+    d_c = common if torch.is_tensor(common) else torch.from_numpy(np.ascontiguousarray(common, dtype=np.int32)).to(dev)
+    d_n = (n_contacts if torch.is_tensor(n_contacts) else
+           torch.from_numpy(np.ascontiguousarray(n_contacts, dtype=np.int32)).to(dev))
+    d_c, d_n = d_c.contiguous(), d_n.contiguous()
+    M = int(d_n.shape[0])
+    if d_c.dtype != torch.int32 or d_n.dtype != torch.int32 or tuple(d_c.shape) != (M, M):
+        raise ValueError("common int32 [M, M] and n_contacts int32 [M]")
+    if api is _lib._API:
+        _lib.require_device(d_c)
+    MW = (M + 63) // 64
+    nb = torch.zeros((2, M, MW), dtype=torch.int64, device=d_c.device)
+    res = torch.zeros((3, M), dtype=torch.int32, device=d_c.device)
+    k = torch.zeros(1, dtype=torch.int32, device=d_c.device)
+    q = _lib.PoseClusterRequest()
+    q.common, q.n_contacts, q.n_poses = d_c.data_ptr(), d_n.data_ptr(), M
+    q.cutoff_fcc, q.cutoff_reverse, q.min_size = float(cutoff_fcc), float(cutoff_reverse), int(min_size)
+    q.neighbours, q.transposed = nb[0].data_ptr(), nb[1].data_ptr()
+    q.labels, q.centres, q.sizes, q.n_clusters = res[0].data_ptr(), res[1].data_ptr(), res[2].data_ptr(), k.data_ptr()
+    api.pose_cluster(q, _lib.current_stream(d_c))
+    K = int(k.cpu()[0])
+    res, nb = res.cpu().numpy(), nb.cpu().numpy().view(np.uint64)
+    return {"labels": res[0].copy(), "centres": res[1, :K].copy(), "sizes": res[2, :K].copy(), "neighbours": nb[0].copy(),
+            "transposed": nb[1].copy()}
+
+
+def cluster_poses(poses_or_contacts, cutoff_fcc=0.6, strictness=0.75, min_size=4, **contact_options):
+    """FCC clustering of docking poses on the device (Rodrigues et al. 2012: the rule of HADDOCK's ``cluster_fcc``, with
+    the tie between equally connected centres broken towards the smaller index; tests/fcc_ref.py states it in numpy).
+    ``fcc[i, j]`` is the fraction of pose i's interface contacts that pose j has too.  Pose j is a neighbour of i when
+    ``fcc[i, j] >= cutoff_fcc`` and ``fcc[j, i] >= cutoff_fcc * strictness``.  The alive pose with the most alive
+    neighbours (the smallest index on a tie) becomes a centre as long as it has ``min_size - 1`` of them; it and they
+    form a cluster and die.  ``poses_or_contacts``: a ``PoseContacts``, or what ``pose_contacts`` takes together with its
+    options (cutoff, heavy_only, table, device, api, chunk).  Returns a ``PoseClusters``.  More poses than
+    drgnn_fcc_capacity(2) (4096) are refused (DrgnnError, capacity)."""
+    for name, v in (("cutoff_fcc", cutoff_fcc), ("strictness", strictness)):
+        if not (float(v) > 0.0 and float(v) <= 1.0):
+            raise ValueError("%s must lie in (0, 1]" % name)
+    if int(min_size) != min_size or int(min_size) < 1:
+        raise ValueError("min_size must be an integer >= 1")
+    c = poses_or_contacts
+    if isinstance(c, PoseContacts):
+        if contact_options:
+            raise ValueError("contact options %s come with poses, not with PoseContacts" % sorted(contact_options))
+    else:
+        c = pose_contacts(c, **contact_options)
+    M = len(c)
+    if M == 0:
+        return PoseClusters(np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int64), c.n_contacts)
+    if M > c.api.fcc_capacity(2):
+        _lib._check(-2, "drgnn_pose_cluster")
+    count = torch.from_numpy(c.n_contacts.astype(np.int32)).to(c.bits.device)
+    r = pose_cluster_raw(c.api, _common_device(c), count, float(cutoff_fcc), float(cutoff_fcc) * float(strictness),
+                         int(min_size), c.device)
+    return PoseClusters(r["labels"].astype(np.int64), r["centres"].astype(np.int64), r["sizes"].astype(np.int64), c.n_contacts)

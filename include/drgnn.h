@@ -856,6 +856,72 @@ int32_t drgnn_hse_capacity(int32_t what);
  * No allocation, no workspace, no synchronisation. */
 int drgnn_hse_residues(const drgnn_hse_request* req, void* stream);
 
+/* ---- clustering of poses by their fraction of common contacts (drgnn_fcc.h) ---------------------------
+ * FCC clustering (Rodrigues et al. 2012; the rule of HADDOCK's cluster_fcc with the tie between equally connected
+ * centres broken towards the smaller index) of M poses of one two-chain topology.  tests/fcc_ref.py states the rule.
+ *
+ * drgnn_pose_contacts: xyz f32 [M, T, 3], the COUNTED atoms of every pose (the caller leaves out hydrogens that do not
+ * count), grouped into residues by atom_ptr i32 [R+1]; residues [0, n_chain_a) are chain 0, the rest chain 1.  Residue
+ * pair (a, b) across the chains is a contact iff an atom pair lies at ((dx dx + dy dy) + dz dz) <= cut2 in fp32
+ * without contraction, cut2 = (float)(cutoff * cutoff) with the product taken in fp64.  Outputs: bits u64 [M, nA, WB],
+ * WB = ceil(nB / 64): bit b % 64 of word b / 64 of row a, the bits past nB zero; n_contacts i32 [M].  One workgroup
+ * per pose, one launch.  atom_ptr is also given as a HOST array: every check comes from it. */
+typedef struct drgnn_pose_contacts_request {
+    const float* xyz;
+    const int32_t* atom_ptr;
+    const int32_t* host_atom_ptr;
+    int64_t n_poses, n_atoms, n_residues, n_chain_a;
+    double cutoff;
+    uint64_t* bits;
+    int32_t* n_contacts;
+} drgnn_pose_contacts_request;
+
+/* drgnn_pose_common: common[i, j] = the number of bits set in both bits_a[i] and bits_b[j] (rows of n_words words;
+ * bits_b may be bits_a), i32 [n_a, n_b].  One launch. */
+typedef struct drgnn_pose_common_request {
+    const uint64_t* bits_a;
+    const uint64_t* bits_b;
+    int64_t n_a, n_b, n_words;
+    int32_t* common;
+} drgnn_pose_common_request;
+
+/* drgnn_pose_cluster: from common i32 [M, M] and n_contacts i32 [M] (device arrays; common need not be symmetric):
+ * fcc(i, j) = n_i == 0 ? 0 : (double)common[i, j] / (double)n_i; j is a neighbour of i iff i != j, fcc(i, j) >= cutoff_fcc
+ * and fcc(j, i) >= cutoff_reverse (the caller's cutoff_fcc * strictness, formed once in fp64).  Outputs: neighbours u64
+ * [M, ceil(M/64)] (bit j of row i) and transposed (bit j of row i: i is a neighbour of j), tail bits zero; then, greedily
+ * over the alive poses: the centre is the alive pose with the most alive neighbours (the smallest index on a tie); with
+ * fewer than min_size - 1 of them the loop stops; else the centre and its alive neighbours form cluster k and die.
+ * labels i32 [M] (-1: in no cluster), centres / sizes i32 [M] of which the first n_clusters[0] are written, n_clusters
+ * i32 [1].  Two launches, no host round trip. */
+typedef struct drgnn_pose_cluster_request {
+    const int32_t* common;
+    const int32_t* n_contacts;
+    int64_t n_poses;
+    double cutoff_fcc, cutoff_reverse;
+    int32_t min_size;
+    uint64_t* neighbours;
+    uint64_t* transposed;
+    int32_t* labels;
+    int32_t* centres;
+    int32_t* sizes;
+    int32_t* n_clusters;
+} drgnn_pose_cluster_request;
+
+/* the documented capacities: what = 0 residues of a complex, both chains (3072: their bounding spheres sit in LDS),
+ * 1 poses on either side of one drgnn_pose_common call (16384: the output stays below 2^28 entries), 2 poses of one
+ * drgnn_pose_cluster call (4096: the degrees and the member list sit in LDS); -1 otherwise.  Pure host. */
+int32_t drgnn_fcc_capacity(int32_t what);
+
+/* All three: DRGNN_E_ARG before any launch for a null request or pointer, a negative count, and
+ *   contacts: n_chain_a outside [0, n_residues], an atom_ptr that does not start at 0, decreases or ends elsewhere than
+ *             n_atoms, a cutoff that is not a positive number whose square fits fp32
+ *   cluster:  cutoff_fcc or cutoff_reverse outside (0, 1], min_size < 1
+ * DRGNN_E_CAPACITY beyond drgnn_fcc_capacity (split the call; clustering cannot be split).  No allocation, no workspace,
+ * no synchronisation; empty inputs return 0 without a launch. */
+int drgnn_pose_contacts(const drgnn_pose_contacts_request* req, void* stream);
+int drgnn_pose_common(const drgnn_pose_common_request* req, void* stream);
+int drgnn_pose_cluster(const drgnn_pose_cluster_request* req, void* stream);
+
 /* ---- the builder's output packed into a resident set's arrays (drgnn_pack.h) --------------------------
  * After drgnn_iface_fill on the same batch (and the optional drgnn_bsa_residues / drgnn_hse_residues over exactly its
  * nodes, in node order): the arrays a drgnn_graph_set holds, written on the device in one launch, one workgroup per

@@ -1,0 +1,85 @@
+"""FCC clustering of docking poses (drgnn_fcc.h; deeprank_gnn_amd.interface.pose_contacts, common_contacts, fcc_matrix,
+cluster_poses) on the host-emulation build: the numpy statement of the rule in tests/fcc_ref.py against the literals of
+the four 1ATN poses, then the kernels against fcc_ref, all by exact equality: 1ATN, hand-made atoms on the 1/8 A grid,
+pose batches across the tile and word edges, hand-written relations, independence of batch / chunk / place / run, rigid
+motions, the capacities, refusals, the empty batch and PoseClusters.rank.  CPU only; tests/test_gpu_fcc.py runs the same
+checks on the device."""
+import pytest
+
+import fcc_cases as C
+
+
+@pytest.fixture(scope="module")
+def api():
+    from emu_api import emu
+    return emu()
+
+
+def test_fcc_ref_reproduces_the_1ATN_literals():
+    C.check_ref_literals()
+
+
+def test_the_family_batch_has_clusters_leftovers_and_a_tie():
+    """on the reference alone: at M = 130 at least 3 clusters, 1 pose in none and a tie on deg at a centre choice"""
+    labels, centres, sizes, ties = C.family_ref()[3]
+    assert len(centres) >= 3 and (labels == -1).sum() >= 1 and ties >= 1
+
+
+def test_1ATN_poses_equal_fcc_ref_and_the_literals(api):
+    C.check_atn(api, "cpu")
+
+
+@pytest.mark.parametrize("name", sorted(C.hand_cases()))
+def test_hand_made_atoms(name, api):
+    C.check_hand_case(name, api, "cpu")
+
+
+@pytest.mark.parametrize("n_b", [64, 65, 128, 129])
+def test_word_boundaries_and_tail_bits(n_b, api):
+    C.check_word_edges(api, "cpu", n_b)
+
+
+def test_a_pose_without_contacts(api):
+    C.check_no_contact_pose(api, "cpu")
+
+
+@pytest.mark.parametrize("M", C.BATCH_SIZES)
+def test_pose_batches_equal_fcc_ref(M, api):
+    C.check_batch(api, "cpu", M)
+
+
+def test_hand_written_relations(api):
+    C.check_hand_relations(api, "cpu")
+
+
+def test_results_do_not_depend_on_batch_chunk_place_or_run(api):
+    C.check_independence(api, "cpu")
+
+
+def test_common_contacts_splits_at_the_capacity(api, monkeypatch):
+    C.check_common_is_split(api, "cpu", monkeypatch)
+
+
+def test_rigid_motions(api):
+    C.check_rigid_motion(api, "cpu")
+
+
+def test_capacity_is_refused_not_wrong(api):
+    C.check_capacity(api, "cpu")
+
+
+def test_empty_batch(api):
+    C.check_empty_batch(api, "cpu")
+
+
+def test_value_errors():
+    C.check_value_errors()
+
+
+@pytest.mark.parametrize("name", C.refusal_names())
+def test_bad_requests_are_refused_before_a_launch(name, api):
+    C.check_refusal(api, "cpu", name)
+
+
+def test_cluster_ranking():
+    C.check_rank()
