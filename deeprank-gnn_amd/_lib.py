@@ -202,6 +202,18 @@ class PoseClusterRequest(ctypes.Structure):
                 ("n_clusters", _vp)]
 
 
+class DepthRequest(ctypes.Structure):
+    """drgnn_depth_request (include/drgnn.h): K target residues of a ragged batch of complexes for drgnn_depth_residues;
+    ``host_*`` are addresses of host copies of the offset and target tables."""
+    _fields_ = [("xyz", _vp), ("atom_ptr", _vp), ("res_ptr", _vp), ("radii", _vp), ("dots", _vp), ("target_res", _vp),
+                ("target_complex", _vp),
+                ("host_atom_ptr", _vp), ("host_res_ptr", _vp), ("host_target_res", _vp), ("host_target_complex", _vp),
+                ("n_atoms", _c_i64), ("n_residues", _c_i64), ("n_complexes", _c_i64), ("n_targets", _c_i64),
+                ("n_radii", _c_i64), ("probe", ctypes.c_double), ("link", ctypes.c_double),
+                ("n_dots", _c_i32), ("components", _c_i32), ("phases", _c_i32), ("reserved", _c_i32), ("workspace", _vp), ("workspace_bytes", _c_i64),
+                ("out", _vp), ("status", _vp)]
+
+
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p)
 
 
@@ -418,6 +430,11 @@ class Api(object):
         lib.drgnn_hse_capacity.argtypes = [_c_i32]
         lib.drgnn_hse_capacity.restype = _c_i32
         lib.drgnn_hse_residues.argtypes = [ctypes.POINTER(HseRequest), _vp]
+        lib.drgnn_depth_capacity.argtypes = [_c_i32]
+        lib.drgnn_depth_capacity.restype = _c_i32
+        lib.drgnn_depth_workspace.argtypes = [_c_i64, _c_i64, _c_i32, ctypes.POINTER(_c_i64)]
+        lib.drgnn_depth_workspace.restype = _c_i64
+        lib.drgnn_depth_residues.argtypes = [ctypes.POINTER(DepthRequest), _vp]
         lib.drgnn_pack_capacity.argtypes = [_c_i32]
         lib.drgnn_pack_capacity.restype = _c_i32
         lib.drgnn_iface_pack.argtypes = [ctypes.POINTER(PackRequest), _vp]
@@ -726,6 +743,20 @@ class Api(object):
 
     def pose_cluster(self, request, stream):
         _check(self.lib.drgnn_pose_cluster(ctypes.byref(request), stream), "drgnn_pose_cluster")
+
+    def depth_capacity(self, what):
+        return int(self.lib.drgnn_depth_capacity(int(what)))
+
+    def depth_workspace(self, n_atoms, n_complexes, n_dots):
+        """(bytes, offsets [10]) of drgnn_depth_workspace; DrgnnError for counts the call refuses"""
+        off = (_c_i64 * 10)()
+        n = int(self.lib.drgnn_depth_workspace(int(n_atoms), int(n_complexes), int(n_dots), off))
+        if n < 0:
+            _check(-2, "drgnn_depth_workspace")
+        return n, [int(v) for v in off]
+
+    def depth_residues(self, request, stream):
+        _check(self.lib.drgnn_depth_residues(ctypes.byref(request), stream), "drgnn_depth_residues")
 
     def iface_fill(self, request, n_nodes, n_edges, n_iedges, node_residue, pos, chain, type_, edge_index, dist,
                    internal_edge_index, internal_dist, stream):

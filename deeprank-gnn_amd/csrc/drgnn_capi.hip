@@ -2422,6 +2422,99 @@ int drgnn_iface_pack(const drgnn_pack_request* q, void* stream) {
     return 0;
 }
 
+// ---- residue depth (drgnn_depth.h) -------------------------------------------------------------------
+int32_t drgnn_depth_capacity(int32_t what) {
+    return what == 0 ? DP_DOTS_CAP : what == 1 ? DP_CX_DOTS_CAP : what == 2 ? DP_MAX_GRID : -1;
+}
+
+// the workspace's arrays, one after the other, each a multiple of 8 bytes: mask, pos, id, label, size, cnt, ptr, cx_nd,
+// cx_outer; offsets[9] is the size
+static int depth_layout(int64_t T, int64_t M, int64_t n_dots, int64_t* off) {
+    if (T < 0 || M < 0 || n_dots < 1 || n_dots > DP_DOTS_CAP || T > INT32_MAX / 3 || M > INT32_MAX) return -1;
+    const int64_t W = (n_dots + 63) / 64, D = T * n_dots;
+    const int64_t i32D = (4 * D + 7) / 8 * 8, i32T = (4 * T + 7) / 8 * 8, i32M = (4 * M + 7) / 8 * 8;
+    const int64_t sizes[9] = {8 * T * W, 24 * D, i32D, i32D, i32D, i32T, i32T, i32M, i32M};
+    off[0] = 0;
+    for (int j = 0; j < 9; ++j) off[j + 1] = off[j] + sizes[j];
+    return 0;
+}
+
+int64_t drgnn_depth_workspace(int64_t n_atoms, int64_t n_complexes, int32_t n_dots, int64_t* offsets) {
+    int64_t off[10];
+    if (depth_layout(n_atoms, n_complexes, n_dots, off) != 0) return -1;
+    if (offsets) memcpy(offsets, off, sizeof(off));
+    return off[9];
+}
+
+int drgnn_depth_residues(const drgnn_depth_request* q, void* stream) {
+    if (!q || !q->host_atom_ptr || !q->host_res_ptr || !q->status) return DRGNN_E_ARG;
+    const int64_t T = q->n_atoms, R = q->n_residues, M = q->n_complexes, K = q->n_targets, NR = q->n_radii;
+    if (T < 0 || R < 0 || M < 0 || K < 0 || NR < 0 || T > INT32_MAX / 3 || R >= INT32_MAX || K > INT32_MAX) return DRGNN_E_ARG;
+    if (M > 0 && !q->res_ptr) return DRGNN_E_ARG;
+    if (R > 0 && !q->atom_ptr) return DRGNN_E_ARG;
+    if (T > 0 && (!q->xyz || !q->radii || NR < 1 || T % NR != 0)) return DRGNN_E_ARG;
+    if (K > 0 && (!q->host_target_res || !q->host_target_complex || !q->target_res || !q->target_complex || !q->out)) return DRGNN_E_ARG;
+    if (q->n_dots < 1 || !q->dots || !(q->probe > 0.0) || !(q->probe < 1.0e150) || !(q->link >= 0.0) || !(q->link < 1.0e150) ||
+        q->components < 0 || q->components > 1 || q->phases < 0 || q->phases > 7)
+        return DRGNN_E_ARG;
+    if (q->n_dots > DP_DOTS_CAP || K > DP_MAX_GRID || M > DP_MAX_GRID || T / DRGNN_NWAVES >= DP_MAX_GRID) return DRGNN_E_CAPACITY;
+    const int32_t *ap = q->host_atom_ptr, *rp = q->host_res_ptr;
+    if (ap[0] != 0 || ap[R] != T || rp[0] != 0 || rp[M] != R) return DRGNN_E_ARG;
+    for (int64_t r = 0; r < R; ++r)
+        if (ap[r + 1] < ap[r]) return DRGNN_E_ARG;
+    for (int64_t c = 0; c < M; ++c)
+        if (rp[c + 1] < rp[c] || rp[c + 1] > R) return DRGNN_E_ARG;
+    for (int64_t k = 0; k < K; ++k) {
+        const int32_t c = q->host_target_complex[k], r = q->host_target_res[k];
+        if (c < 0 || c >= M || r < rp[c] || r >= rp[c + 1]) return DRGNN_E_ARG;
+    }
+    int64_t off[10];
+    if (depth_layout(T, M, q->n_dots, off) != 0) return DRGNN_E_ARG;
+    int ph = q->phases == 0 ? 7 : q->phases;
+    if (K == 0) ph = q->phases == 0 ? 0 : ph & ~4;                      // (the whole call without a target: nothing to do)
+    if (M == 0) ph = 0;
+    if (ph == 0) return 0;
+    if (!q->workspace || ((uintptr_t)q->workspace & 7)) return DRGNN_E_ARG;
+    if (q->workspace_bytes < off[9]) return DRGNN_E_CAPACITY;
+    DepthArgs a;
+    memset(&a, 0, sizeof(a));
+    a.xyz = q->xyz; a.atom_ptr = q->atom_ptr; a.res_ptr = q->res_ptr; a.rad = q->radii; a.dots = q->dots;
+    a.tgt_res = q->target_res; a.tgt_cx = q->target_complex;
+    a.n_atoms = (int)T; a.n_cx = (int)M; a.n_radii = (int)NR; a.n_dots = q->n_dots; a.words = (q->n_dots + 63) / 64;
+    a.all = q->components;
+    a.probe = q->probe; a.link = q->link; a.link2 = q->link * q->link;
+    char* w = (char*)q->workspace;
+    a.mask = (unsigned long long*)(w + off[0]); a.pos = (double*)(w + off[1]); a.id = (int32_t*)(w + off[2]);
+    a.label = (int32_t*)(w + off[3]); a.size = (int32_t*)(w + off[4]); a.cnt = (int32_t*)(w + off[5]);
+    a.ptr = (int32_t*)(w + off[6]); a.cx_nd = (int32_t*)(w + off[7]); a.cx_outer = (int32_t*)(w + off[8]);
+    a.out = q->out; a.status = q->status;
+    const int64_t tiles = (T + DRGNN_NWAVES - 1) / DRGNN_NWAVES;
+#ifdef DRGNN_EMU
+    (void)stream; (void)tiles;
+    std::unique_ptr<DepthShared> lds(new DepthShared);
+    if (ph & 1)
+        for (int64_t t = 0; t < T; ++t) depth_dots_tile(a, t);         // (one "wave" per workgroup: a tile is an atom)
+    if (ph & 2)
+        for (int64_t c = 0; c < M; ++c) depth_components(a, (int)c, *lds);
+    if (ph & 4)
+        for (int64_t k = 0; k < K; ++k) depth_residue(a, k, *lds);
+#else
+    if ((ph & 1) && T > 0) {
+        hipLaunchKernelGGL(k_depth_dots, dim3((unsigned)tiles), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+    if (ph & 2) {
+        hipLaunchKernelGGL(k_depth_components, dim3((unsigned)M), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+    if (ph & 4) {
+        hipLaunchKernelGGL(k_depth_residues, dim3((unsigned)K), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+#endif
+    return 0;
+}
+
 // ---- clustering of poses by their fraction of common contacts (drgnn_fcc.h) --------------------------
 int32_t drgnn_fcc_capacity(int32_t what) { return what == 0 ? FC_RCAP : what == 1 ? FC_PCAP : what == 2 ? FC_CCAP : -1; }
 

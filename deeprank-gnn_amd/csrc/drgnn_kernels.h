@@ -15,6 +15,7 @@
 #include "drgnn_score.h"
 #include "drgnn_bsa.h"
 #include "drgnn_hse.h"
+#include "drgnn_depth.h"
 #include "drgnn_fcc.h"
 #include "drgnn_pack.h"
 #include "drgnn_metrics.h"
@@ -1006,6 +1007,16 @@ __global__ void __launch_bounds__(DRGNN_NTHREADS, 8) k_bsa_residues(BsaArgs a) {
 __global__ void __launch_bounds__(DRGNN_NTHREADS) k_hse_residues(HseArgs a) {
     __shared__ HseShared smem_hs;
     hse_tile(a, (int)blockIdx.x, smem_hs);
+}
+// residue depth (drgnn_depth.h): a wave per atom; one workgroup per complex; one workgroup per target residue
+__global__ void __launch_bounds__(DRGNN_NTHREADS) k_depth_dots(DepthArgs a) { depth_dots_tile(a, (int64_t)blockIdx.x); }
+__global__ void __launch_bounds__(DRGNN_NTHREADS) k_depth_components(DepthArgs a) {
+    __shared__ DepthShared smem_dp;
+    depth_components(a, (int)blockIdx.x, smem_dp);
+}
+__global__ void __launch_bounds__(DRGNN_NTHREADS) k_depth_residues(DepthArgs a) {
+    __shared__ DepthShared smem_dp;
+    depth_residue(a, (int64_t)blockIdx.x, smem_dp);
 }
 // fraction of common contacts (drgnn_fcc.h): one workgroup per pose; per tile of pose pairs; a wave per word of the
 // neighbour relation; ONE workgroup for the greedy clustering

@@ -47,7 +47,13 @@ HADDOCK's ``cluster_fcc``; csrc/drgnn_fcc.h) and the clusters ranked by their be
     clusters = cluster_poses(poses)                            # labels [M] (-1: in no cluster), centres, sizes
     order, means = clusters.rank(scores, top=4)                # scores [M]: Ensemble.predict or docking_scores()[key]
 
-Not covered: ``depth`` (Biopython through the MSMS program) and PSSM file parsing (``pssm``, ``cons``, ``ic``).  For those every
+and the residue depth (``depth``: Biopython's residue depth; the surface is a dot surface of the solvent-accessible
+surface restricted to its outer component instead of MSMS' triangulation, about one vertex spacing away from it):
+
+    depth = residue_depth(poses)                               # float64 [M, R]
+    store = interface_graphs(poses, names, depth=True)         # the graphs with node_data/depth on every molecule
+
+Not covered: PSSM file parsing (``pssm``, ``cons``, ``ic``).  For those every
 graph carries ``node_data/residue``, each node's index among the residues of its
 ``AtomTable``: a per-residue array the caller holds is attached with ``attach_residue_features``.
 
@@ -279,7 +285,7 @@ def default_chunk(api, max_res_a, max_res_b, max_atoms, budget=WORKSPACE_BUDGET)
 
 
 def interface_graphs(tables_or_poses, names, contact_distance=8.5, internal_contact_distance=3.0, device=None, chunk=None,
-                     api=None, reference=None, bsa=False, hse=False):
+                     api=None, reference=None, bsa=False, hse=False, depth=False):
     """Interface graphs of complexes (a sequence of ``AtomTable``, an ``AtomTable.poses`` batch, or a mix) as a
     ``GraphStore`` with one molecule per name, in the reference's tree: ``edge_index``, ``edge_data/dist``,
     ``internal_edge_index``, ``internal_edge_data/dist``, ``nodes`` and, under ``node_data/``, ``pos``, ``chain``,
@@ -292,7 +298,9 @@ def interface_graphs(tables_or_poses, names, contact_distance=8.5, internal_cont
     gets ``node_data/bsa``, float64 [n,1], the buried surface area of exactly its nodes (one more launch per chunk).
     ``hse``: True, or a dict of ``residue_hse`` options (radius, offset, connect, direction): every molecule also gets
     ``node_data/hse``, float64 [n,3], the half-sphere exposure (up, down, angle) of exactly its nodes (one more launch
-    per chunk); a node without a value has the row (0, 0, 0), as in the reference."""
+    per chunk); a node without a value has the row (0, 0, 0), as in the reference.
+    ``depth``: True, or a dict of ``residue_depth`` options (radii, probe, n_dots, link, components): every molecule also
+    gets ``node_data/depth``, float64 [n], the residue depth of exactly its nodes (three more launches per chunk)."""
     from .dataset import GraphStore
     api = api or _lib.get()
     if device is None:
@@ -309,6 +317,10 @@ def interface_graphs(tables_or_poses, names, contact_distance=8.5, internal_cont
     hse_opt = None if hse is False or hse is None else _hse_options(**({} if hse is True else dict(hse)))
     if hse_opt is not None:                                            # a table without atom names refuses before any launch
         hse_bb_of = _bb_lookup([t for t, _ in cx])
+    depth_opt = None if depth is False or depth is None else dict({} if depth is True else depth)
+    if depth_opt is not None:                                          # the radius table refuses before any launch
+        depth_radii_of = _depth_radii_lookup([t for t, _ in cx], depth_opt.pop("radii", "united"))
+        depth_opt = _depth_options(**depth_opt)
     if chunk is None:
         chunk = default_chunk(api, max([t.split for t, _ in cx] + [0]), max([t.n_residues - t.split for t, _ in cx] + [0]),
                               max([t.n_atoms for t, _ in cx] + [0]))
@@ -326,6 +338,10 @@ def interface_graphs(tables_or_poses, names, contact_distance=8.5, internal_cont
             node_res = [r["node_residue"][r["node_ptr"][k]:r["node_ptr"][k + 1]].astype(np.int64) - int(res_ptr[k])
                         for k in range(len(part))]
             exposed = _hse_chunk(api, part, node_res, hse_bb_of, hse_opt, device, ragged=(xyz, atom_ptr, res_ptr))
+        if depth_opt is not None:
+            node_res = [r["node_residue"][r["node_ptr"][k]:r["node_ptr"][k + 1]].astype(np.int64) - int(res_ptr[k])
+                        for k in range(len(part))]
+            deep = _depth_chunk(api, part, node_res, depth_radii_of, depth_opt, device, ragged=(xyz, atom_ptr, res_ptr))
         for k, (t, _) in enumerate(part):
             n0, n1 = r["node_ptr"][k:k + 2]
             e0, e1 = r["edge_ptr"][k:k + 2]
@@ -352,6 +368,8 @@ def interface_graphs(tables_or_poses, names, contact_distance=8.5, internal_cont
                 rows = exposed[k].copy()
                 rows[np.isnan(rows[:, 0])] = 0.0
                 trees[-1]["node_data/hse"] = rows
+            if depth_opt is not None:
+                trees[-1]["node_data/depth"] = deep[k].copy()
     store = GraphStore.from_trees(names, trees)
     if reference is not None and cx:
         attach_scores(store, names, docking_scores(np.stack([x for _, x in cx]), reference, device=device, api=api))
@@ -369,7 +387,7 @@ def attach_residue_features(store, name, per_residue_array):
 
 
 # ---- resident graph sets without host trees (csrc/drgnn_pack.h) --------------------------------------------------------
-FEATURE_WIDTH = {"type": 20, "polarity": 4, "charge": 1, "pos": 3, "chain": 1, "bsa": 1, "hse": 3}
+FEATURE_WIDTH = {"type": 20, "polarity": 4, "charge": 1, "pos": 3, "chain": 1, "bsa": 1, "hse": 3, "depth": 1}
 MCL_WORKSPACE_BUDGET = 256 << 20   # bytes of Markov clustering's dense fp64 workspace (3 n^2 per graph) one precluster call may ask for
 
 
@@ -402,6 +420,8 @@ def _pack_columns(node_feature, residue_width):
             cols.append((P.PACK_BSA, 2))
         elif name == "hse":
             cols += [(P.PACK_HSE, j) for j in range(3)]
+        elif name == "depth":
+            cols.append((P.PACK_POS, 0))                               # a place holder: the caller copies the column in
         else:
             off, w = residue_width[name]
             cols += [(P.PACK_RES, off + j) for j in range(w)]
@@ -512,7 +532,7 @@ def _mcl_groups(sizes, budget):
 
 def interface_resident_set(tables_or_poses, names, node_feature=("type", "polarity", "bsa", "hse"), edge_feature=("dist",),
                            edge_transform="default", residue_features=None, reference=None, target=None,
-                           clustering_method="mcl", bsa=True, hse=True, contact_distance=8.5, internal_contact_distance=3.0,
+                           clustering_method="mcl", bsa=True, hse=True, depth=None, contact_distance=8.5, internal_contact_distance=3.0,
                            chunk=None, device=None, api=None, mcl_budget=MCL_WORKSPACE_BUDGET):
     """The ``ResidentGraphSet`` of the interface graphs of complexes (as ``interface_graphs`` takes them), assembled on
     the device: what ``interface_graphs`` -> ``attach_residue_features`` -> ``GraphDataSet(node_feature, edge_feature,
@@ -520,10 +540,12 @@ def interface_resident_set(tables_or_poses, names, node_feature=("type", "polari
     default transform: within 2^-21, see below), without a host tree, a per-graph tensor or a second upload.
 
     ``node_feature``: names in the order of the columns of ``x``: ``type`` (20 columns), ``polarity`` (4), ``charge``,
-    ``pos`` (3), ``chain``, ``bsa``, ``hse`` (3) and the keys of ``residue_features`` ({name: table with one row per
+    ``pos`` (3), ``chain``, ``bsa``, ``hse`` (3), ``depth`` and the keys of ``residue_features`` ({name: table with one row per
     residue of the AtomTable, or {mol: table}}, as ``attach_residue_features`` takes them).  ``"all"``, an unknown
-    name or a wrongly shaped table raises ValueError before any launch.  ``bsa`` / ``hse``: the options of
-    ``interface_graphs``; they are computed only when a feature asks for them.
+    name or a wrongly shaped table raises ValueError before any launch.  ``bsa`` / ``hse`` / ``depth``: the options
+    of ``interface_graphs``; they are computed only when a feature asks for them, and ``depth`` is a feature only when
+    the argument is given (True or a dict).  The ``depth`` column is copied into
+    ``x`` after the pack launch (one strided copy per chunk, rounded to float32 as the store path rounds it).
     ``edge_feature``: ``("dist",)`` or None (no ``edge_attr``).  ``edge_transform``: "default" (the reference's
     ``tanh(-d/2 + 2) + 1``, evaluated in fp64 on the float32 distance and rounded once, where the store path evaluates
     it in float32: the two differ by at most 2^-21), None (the distances as they are) or a callable applied to the
@@ -535,10 +557,10 @@ def interface_resident_set(tables_or_poses, names, node_feature=("type", "polari
     ``rs.skipped`` the others.
 
     Per ``chunk`` of complexes (default as for ``interface_graphs``): count and fill (``build_ragged_device``),
-    ``bsa`` / ``hse`` of exactly the nodes, one ``drgnn_iface_pack`` launch, ``precluster`` over runs of graphs whose
+    ``bsa`` / ``hse`` / ``depth`` of exactly the nodes, one ``drgnn_iface_pack`` launch, ``precluster`` over runs of graphs whose
     dense Markov-clustering workspace (24 sum n^2 bytes) stays within ``mcl_budget``; after the last chunk one
     ``torch.cat`` per array.  What comes back to the host: the three totals of a chunk, its [M+1] offset tables, the
-    offsets of the depth-0 clusters, the status words of the bsa / hse calls and, when ``bsa`` or ``hse`` is asked for,
+    offsets of the depth-0 clusters, the status words of the bsa / hse / depth calls and, when one of them is asked for,
     ``node_residue`` (their target lists are made on the host); nothing else.  The result does not depend on ``chunk``,
     on ``mcl_budget`` or on the run."""
     from .clustering import _labeller, precluster
@@ -559,12 +581,14 @@ def interface_resident_set(tables_or_poses, names, node_feature=("type", "polari
                          % (", ".join(FEATURE_WIDTH), node_feature))
     node_feature = [str(f) for f in node_feature]
     residue_features = dict(residue_features or {})
-    for f in node_feature:
-        if f not in FEATURE_WIDTH and f not in residue_features:
-            raise ValueError("unknown node feature %r: %s and the keys of residue_features" % (f, ", ".join(FEATURE_WIDTH)))
     for f in residue_features:
         if f in FEATURE_WIDTH:
             raise ValueError("residue feature %r has the name of a built-in feature" % f)
+    for f in node_feature:
+        if f not in FEATURE_WIDTH and f not in residue_features:
+            raise ValueError("unknown node feature %r: %s and the keys of residue_features" % (f, ", ".join(FEATURE_WIDTH)))
+        if f == "depth" and (depth is None or depth is False):         # (built only on request: depth=True or its options)
+            raise ValueError("unknown node feature 'depth' unless depth=True or a dict of residue_depth's options is given")
     if edge_feature is not None and list(edge_feature) != ["dist"]:
         raise ValueError("edge_feature must be ('dist',) or None, not %r" % (edge_feature,))
     if not (edge_transform is None or edge_transform == "default" or callable(edge_transform)):
@@ -589,6 +613,14 @@ def interface_resident_set(tables_or_poses, names, node_feature=("type", "polari
             raise ValueError("the node feature 'hse' needs hse=True or a dict of options")
         hse_opt = _hse_options(**({} if hse is True else dict(hse)))
         hse_bb_of = _bb_lookup([t for t, _ in cx])
+    want_depth = "depth" in node_feature
+    if want_depth:
+        depth_opt = dict({} if depth is True else depth)
+        depth_radii_of = _depth_radii_lookup([t for t, _ in cx], depth_opt.pop("radii", "united"))
+        depth_opt = _depth_options(**depth_opt)
+        if node_feature.count("depth") != 1:
+            raise ValueError("the node feature 'depth' may be listed once")
+        depth_col = sum(FEATURE_WIDTH.get(f, res_cols.get(f, (0, 0))[1]) for f in node_feature[:node_feature.index("depth")])
     cols = _pack_columns(node_feature, res_cols)
     if cols.shape[0] > api.pack_capacity(0):
         raise ValueError("%d columns of node features; drgnn_iface_pack takes %d" % (cols.shape[0], api.pack_capacity(0)))
@@ -618,8 +650,8 @@ def interface_resident_set(tables_or_poses, names, node_feature=("type", "polari
             (kept if nn[k] > 0 else skipped).append(names[lo + k])
         if hp[0, -1] == 0:
             continue
-        d_bsa = d_hse = None
-        if want_bsa or want_hse:
+        d_bsa = d_hse = d_depth = None
+        if want_bsa or want_hse or want_depth:
             node_residue = built["node_residue"].cpu().numpy().astype(np.int64)
             node_res = [node_residue[hp[0, k]:hp[0, k + 1]] - int(res_ptr[k]) for k in range(M)]
             if want_bsa:
@@ -628,6 +660,9 @@ def interface_resident_set(tables_or_poses, names, node_feature=("type", "polari
             if want_hse:
                 d_hse = _hse_chunk(api, part, node_res, hse_bb_of, hse_opt, dev, ragged=(xyz, atom_ptr, res_ptr),
                                    keep_device=True)
+            if want_depth:
+                d_depth = _depth_chunk(api, part, node_res, depth_radii_of, depth_opt, dev, ragged=(xyz, atom_ptr, res_ptr),
+                                       keep_device=True)
         d_res = None
         if res_width:
             tabs = [res_rows(lo + k) for k in range(M)]
@@ -640,6 +675,8 @@ def interface_resident_set(tables_or_poses, names, node_feature=("type", "polari
                 if key is not None:
                     res_dev[key] = d_res
         out = iface_pack_raw(api, built, ptrs, cols, len(atom_ptr) - 1, type_table, d_bsa, d_hse, d_res, edge_mode, want)
+        if want_depth:
+            out["x"][:, depth_col] = d_depth.to(torch.float32)
         if edge_feature is not None and callable(edge_transform):
             out["edge_attr"] = torch.as_tensor(edge_transform(out["edge_attr"]), device=dev).to(torch.float32).reshape(-1)
         # ---- clusters: the kept graphs of the chunk in runs that fit the budget
@@ -1227,6 +1264,213 @@ def residue_hse(tables_or_poses, residues=None, radius=12.0, offset=0, connect="
         return full[0]
     if isinstance(tables_or_poses, Poses):
         return np.stack(full) if full else np.zeros((0, tables_or_poses.table.n_residues, 3))
+    return full
+
+
+# ---- residue depth (csrc/drgnn_depth.h) --------------------------------------------------------------------------------
+DEPTH_UNITED = {"C": 1.9, "N": 1.7, "O": 1.5, "S": 1.85, "H": 0.0}     # MSMS' united-atom radii by the first letter of the name
+DEPTH_OTHER = 1.8                                                      # any other first letter
+DEPTH_COMPONENTS = {"outer": 0, "all": 1}
+# bytes of workspace one drgnn_depth_residues call may ask for (sets the complexes per call): k_depth_components gives a
+# complex one workgroup, so a call on the device should hold about as many complexes as there are compute units (256;
+# 1ATN at 192 dots: 41.7 MB each); the host emulation runs them one after the other
+DEPTH_WORKSPACE_BUDGET = {"cpu": 1 << 30, "cuda": 13 << 30}
+
+
+def depth_radii(table, radii="united"):
+    """float64 [T] in the table's grouped atom order; 0: the atom takes no part in the surface.  "united": MSMS'
+    united-atom radii by the first letter of the atom name (C 1.9, N 1.7, O 1.5, S 1.85, H 0, any other letter 1.8); a
+    name without a letter raises ValueError.  An array [n_input_atoms] in input atom order is taken as
+    it is."""
+    if isinstance(radii, str):
+        if radii != "united":
+            raise ValueError("radii must be 'united' or an array, not %r" % radii)
+        if table.atom_name is None:
+            raise ValueError("the radius table goes by atom name: build the AtomTable with atom_name=")
+        out = np.empty(table.n_atoms)
+        for i, nm in enumerate(table.atom_name):
+            letters = [ch for ch in str(nm) if ch.isalpha()]
+            if not letters:
+                raise ValueError("no radius for the atom name %r: it holds no letter" % str(nm))
+            out[i] = DEPTH_UNITED.get(letters[0], DEPTH_OTHER)
+        return out
+    a = np.asarray(radii, dtype=np.float64)
+    if a.shape != (table.n_input_atoms,):
+        raise ValueError("the radius array needs %d entries, one per input atom" % table.n_input_atoms)
+    if not np.all(a >= 0.0):                                           # (NaN fails too)
+        raise ValueError("radii must be >= 0 (0: the atom takes no part in the surface)")
+    return a[table.order]
+
+
+def depth_dots(n_dots):
+    """float64 [n_dots, 3]: the unit dots S_k = (rho cos phi, rho sin phi, z), z = 1 - (2k + 1) / n, rho = sqrt(1 - z^2),
+    phi = (k + 1/2) pi (3 - sqrt 5), as tests/depth_ref.py writes them"""
+    k = np.arange(int(n_dots), dtype=np.float64)
+    z = 1.0 - (2.0 * k + 1.0) / int(n_dots)
+    rho = np.sqrt(1.0 - z * z)
+    phi = (k + 0.5) * (np.pi * (3.0 - np.sqrt(5.0)))
+    return np.stack((rho * np.cos(phi), rho * np.sin(phi), z), axis=1)
+
+
+def depth_link(n_dots, probe=1.5):
+    """the default link length: one and a half dot spacings on a sphere of radius 1.8 + probe"""
+    return float(1.5 * np.sqrt(4.0 * np.pi * (DEPTH_OTHER + probe) ** 2 / int(n_dots)))
+
+
+def _depth_options(probe=1.5, n_dots=192, link=None, components="outer"):
+    if int(n_dots) != n_dots or int(n_dots) < 1:
+        raise ValueError("n_dots must be an integer >= 1")
+    if not float(probe) > 0.0 or not np.isfinite(float(probe)):
+        raise ValueError("probe must be > 0")
+    if components not in DEPTH_COMPONENTS:
+        raise ValueError("components must be 'outer' or 'all', not %r" % (components,))
+    link = depth_link(n_dots, float(probe)) if link is None else float(link)
+    if not link >= 0.0 or not np.isfinite(link):
+        raise ValueError("link must be >= 0")
+    return {"probe": float(probe), "n_dots": int(n_dots), "link": link, "components": components}
+
+
+def _depth_radii_lookup(tables, radii):
+    """{id(table): radii}: each distinct table's radii, made once"""
+    found = {}
+    for t in tables:
+        if id(t) not in found:
+            found[id(t)] = depth_radii(t, radii)
+    return found
+
+
+def depth_raw(api, xyz, atom_ptr, res_ptr, radii, target_res, target_complex, probe=1.5, n_dots=192, link=None,
+              components="outer", device="cpu", keep_device=False, parts=False):
+    """One drgnn_depth_residues call (include/drgnn.h) over numpy arrays.  Returns (out float64 [K], status int): bit 0 of
+    status says a complex was beyond the capacity (its targets are NaN).  ``keep_device``: ``out`` stays a tensor on
+    ``device``.  ``parts``: a third value, the surface the call left in its workspace, per complex a dict of ``mask`` bool
+    [atoms, n_dots], ``ids`` (dot ids atom n_dots + k of the accessible dots, atoms counted within the complex),
+    ``label`` (the smallest dot id of each dot's component) and ``outer`` (the label kept; -1: all or none)."""
+    dev = torch.device(device)
+    link = depth_link(n_dots, probe) if link is None else float(link)
+    host = [np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (atom_ptr, res_ptr, target_res, target_complex)]
+    if host[2].shape != host[3].shape:
+        raise ValueError("the two target arrays must have one length")
+    rad = np.ascontiguousarray(radii, dtype=np.float64).reshape(-1)
+    d_xyz = torch.from_numpy(np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)).to(dev)
+    if api is _lib._API:
+        _lib.require_device(d_xyz)
+    T, M, K = int(d_xyz.shape[0]), len(host[1]) - 1, int(host[2].shape[0])
+    d_host = [torch.from_numpy(h).to(dev) for h in host]
+    d_rad = torch.from_numpy(rad).to(dev)
+    d_dots = torch.from_numpy(depth_dots(n_dots)).to(dev)
+    n_bytes, off = api.depth_workspace(T, M, n_dots)
+    work = torch.empty(max(1, n_bytes // 8), dtype=torch.int64, device=dev)
+    out = torch.empty(K, dtype=torch.float64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    q = _lib.DepthRequest()
+    q.xyz, q.radii, q.dots = d_xyz.data_ptr(), d_rad.data_ptr(), d_dots.data_ptr()
+    q.atom_ptr, q.res_ptr, q.target_res, q.target_complex = [t.data_ptr() for t in d_host]
+    q.host_atom_ptr, q.host_res_ptr, q.host_target_res, q.host_target_complex = [h.ctypes.data for h in host]
+    q.n_atoms, q.n_residues, q.n_complexes, q.n_targets, q.n_radii = T, len(host[0]) - 1, M, K, int(rad.shape[0])
+    q.probe, q.link, q.n_dots, q.components = float(probe), link, int(n_dots), DEPTH_COMPONENTS.get(components, components)
+    q.workspace, q.workspace_bytes = work.data_ptr(), n_bytes
+    q.out, q.status = out.data_ptr(), status.data_ptr()
+    api.depth_residues(q, _lib.current_stream(d_xyz))
+    result = (out if keep_device else out.cpu().numpy()), int(status.cpu()[0])
+    if not parts:
+        return result
+    w = work.cpu().numpy().view(np.uint8)
+    W, D = (int(n_dots) + 63) // 64, T * int(n_dots)
+    mask = w[off[0]:off[0] + 8 * T * W].view(np.uint64).reshape(T, W)
+    bits = ((mask[:, :, None] >> np.arange(64, dtype=np.uint64)[None, None, :]) & np.uint64(1)).astype(bool)
+    bits = bits.reshape(T, W * 64)[:, :int(n_dots)]
+    ids, label = (w[off[j]:off[j] + 4 * D].view(np.int32) for j in (2, 3))
+    cx_nd, cx_outer = (w[off[j]:off[j] + 4 * M].view(np.int32) for j in (7, 8))
+    first = host[0][host[1]]                                           # the first atom of every complex
+    surf = []
+    for c in range(M):
+        a0, a1, nd = int(first[c]), int(first[c + 1]), int(cx_nd[c])
+        base = a0 * int(n_dots)
+        if K == 0 or cx_outer[c] == -2:
+            surf.append(None)
+            continue
+        cid = ids[base:base + nd].astype(np.int64)
+        surf.append({"mask": bits[a0:a1].copy(), "ids": cid, "label": cid[label[base:base + nd]],
+                     "outer": int(cid[cx_outer[c]]) if cx_outer[c] >= 0 else -1})
+    return result + (surf,)
+
+
+def _depth_chunk(api, part, residues, radii_of, opt, device, ragged=None, keep_device=False):
+    """[out float64 [K_c]] for the complexes of ``part`` ([(table, xyz)]) and their residue lists (local indices).
+    ``keep_device``: one tensor [sum K_c] on ``device`` instead, the complexes' values back to back."""
+    atoms = sum(t.n_atoms for t, _ in part)
+    budget = DEPTH_WORKSPACE_BUDGET["cuda" if torch.device(device).type == "cuda" else "cpu"]
+    if len(part) > 1 and (44 * atoms * opt["n_dots"] > budget or
+                          max(sum(len(r) for r in residues), len(part), atoms // 16 + 1) > api.depth_capacity(2)):
+        half = len(part) // 2
+        both = (_depth_chunk(api, part[:half], residues[:half], radii_of, opt, device, keep_device=keep_device),
+                _depth_chunk(api, part[half:], residues[half:], radii_of, opt, device, keep_device=keep_device))
+        return torch.cat(both) if keep_device else both[0] + both[1]
+    xyz, atom_ptr, res_ptr = ragged if ragged is not None else _ragged(part)[:3]
+    tables = [t for t, _ in part]
+    if all(t is tables[0] for t in tables):                              # poses of one topology: one radius array
+        rad = radii_of[id(tables[0])]
+    else:
+        rad = np.concatenate([radii_of[id(t)] for t in tables])
+    sizes = [len(r) for r in residues]
+    tgt_res = np.concatenate([np.asarray(r, dtype=np.int64) + int(res_ptr[k]) for k, r in enumerate(residues)]
+                             + [np.zeros(0, np.int64)])
+    tgt_cx = np.repeat(np.arange(len(part)), sizes)
+    out, status = depth_raw(api, xyz, atom_ptr, res_ptr, rad, tgt_res, tgt_cx, device=device, keep_device=keep_device, **opt)
+    if status & 1:
+        _lib._check(-2, "drgnn_depth_residues")
+    if keep_device:
+        return out
+    ends = np.cumsum(sizes)
+    return [out[e - n:e] for n, e in zip(sizes, ends)]
+
+
+def residue_depth(tables_or_poses, residues=None, radii="united", probe=1.5, n_dots=192, link=None, components="outer",
+                  device=None, chunk=None, api=None):
+    """Residue depth (A), on the device: the mean, over the atoms of a residue, of the distance to the molecular surface
+    of the complex, as the reference's ``depth`` node feature records it from Biopython's ``residue_depth`` (MSMS).
+    MSMS is not reproduced: the surface is a dot surface of the solvent-accessible surface of all atoms of both chains
+    (``n_dots`` golden-spiral dots on every sphere of radius r + ``probe``; see ``depth_radii`` for ``radii``), restricted
+    to its outer component (dots closer than ``link`` are linked, default one and a half dot spacings; the component with
+    the most dots is kept, so that cavities do not count), and depth(atom) = distance to the nearest kept dot - ``probe``.
+    ``components`` "all" keeps every accessible dot (for comparison).  tests/depth_ref.py states the rule; on the 496
+    recorded 1ATN nodes it lies within 0.15 A rms of the reference's values (r = 0.990), one MSMS vertex spacing.  The
+    dot lattice is fixed in the frame of the input: the value is not invariant under rotation, it varies within the dot
+    spacing.
+
+    An ``AtomTable`` gives float64 [R], an ``AtomTable.poses`` batch [M, R], a sequence of either a list of [R_k], with
+    NaN for the residues not asked for.  ``residues``: None (all), an index array applied to every complex, or one
+    index array per complex.  ``chunk``: complexes per call (the workspace also bounds it); a residue's bits do not
+    depend on it, on the batch or on ``residues``.  The tables must have been made with ``atom_name``.  More than 4096
+    dots per atom, or a complex of more than 4 194 304 atoms x n_dots, is refused (DrgnnError, capacity)."""
+    api = api or _lib.get()
+    if device is None:
+        device = "cuda" if api is _lib._API else "cpu"
+    cx = _complexes(tables_or_poses)
+    opt = _depth_options(probe, n_dots, link, components)
+    radii_of = _depth_radii_lookup([t for t, _ in cx], radii)
+    if residues is None:
+        wanted = [np.arange(t.n_residues) for t, _ in cx]
+    else:
+        per_complex = (isinstance(residues, (list, tuple)) and len(residues) == len(cx) and
+                       all(np.ndim(r) == 1 for r in residues))
+        wanted = [np.asarray(residues[k] if per_complex else residues, dtype=np.int64).reshape(-1) for k in range(len(cx))]
+        for (t, _), w in zip(cx, wanted):
+            if w.size and (w.min() < 0 or w.max() >= t.n_residues):
+                raise ValueError("a residue index outside [0, %d)" % t.n_residues)
+    if chunk is None:
+        chunk = BSA_XYZ_BUDGET // (12 * max([t.n_atoms for t, _ in cx] + [1]))
+    chunk = max(1, int(chunk))
+    full = [np.full(t.n_residues, np.nan) for t, _ in cx]
+    for lo in range(0, len(cx), chunk):
+        part = cx[lo:lo + chunk]
+        for k, o in enumerate(_depth_chunk(api, part, wanted[lo:lo + chunk], radii_of, opt, device)):
+            full[lo + k][wanted[lo + k]] = o
+    if isinstance(tables_or_poses, AtomTable):
+        return full[0]
+    if isinstance(tables_or_poses, Poses):
+        return np.stack(full) if full else np.zeros((0, tables_or_poses.table.n_residues))
     return full
 
 

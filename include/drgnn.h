@@ -856,6 +856,71 @@ int32_t drgnn_hse_capacity(int32_t what);
  * No allocation, no workspace, no synchronisation. */
 int drgnn_hse_residues(const drgnn_hse_request* req, void* stream);
 
+/* ---- residue depth (drgnn_depth.h) --------------------------------------------------------------------
+ * The reference's `depth` node feature (Biopython's residue depth: the mean, over a residue's atoms, of the distance to
+ * the molecular surface) for K chosen residues of a ragged batch of M complexes laid out as for drgnn_bsa_residues: xyz
+ * f32 [T,3], atom_ptr i32 [R+1], res_ptr i32 [M+1].  The surface is a dot surface of the solvent-accessible surface of
+ * ALL atoms of the complex, restricted to its outer component (tests/depth_ref.py states the rule):
+ *   radii f64 [n_radii], atom t reads entry t % n_radii (n_radii divides T: poses of one topology share one array); an
+ *   atom of radius 0 takes no part in the surface, its depth is still measured.  R_i = r_i + probe.
+ *   dots f64 [n_dots,3]: the unit vectors S_k (deeprank_gnn_amd.interface.depth_dots).  p_ik = x_i + R_i S_k is accessible
+ *   when |p_ik - x_j|^2 >= R_j^2 for every other atom j of the complex with a radius.  Two accessible dots are linked when
+ *   |p - q|^2 <= link^2; a component is labelled by its smallest dot id i n_dots + k.  components 0: the component with
+ *   the most dots is kept, ties to the smallest label; 1: every accessible dot is kept.
+ *   depth(atom) = sqrt(min over the kept dots of |x - p|^2) - probe (+inf when no dot is kept); depth(residue) = the mean
+ *   over its atoms, summed in order (NaN for a residue without atoms).
+ * Every product and sum in fp64 on the fp32 coordinates, one by one: the accessible set, the links and the labels are
+ * integers that equal the float64 rule's, the depth has its bits.  No floating-point atomics; a residue's bits do not
+ * depend on the batch, the target list, its place or the run.
+ * Workspace: drgnn_depth_workspace(n_atoms, n_complexes, n_dots, offsets) bytes, 8-byte aligned, allocated by the caller,
+ * contents undefined on entry.  After the call it holds (offsets[0..8], offsets[9] the size; a complex whose first atom
+ * is a0 owns [a0 n_dots, (a0 + atoms) n_dots) of the per-dot arrays and fills the first cx_nd of it, in dot-id order):
+ *   0 mask u64 [T, ceil(n_dots/64)] bit k of atom t: dot (t, k) is accessible    1 pos f64 [T n_dots, 3]
+ *   2 id i32 [T n_dots] (t - a0) n_dots + k    3 label i32 [T n_dots] index within the complex of the component's first dot
+ *   4 size i32 [T n_dots] (at a label: the dots of the component)    5 cnt i32 [T]    6 ptr i32 [T]
+ *   7 cx_nd i32 [M] accessible dots    8 cx_outer i32 [M] the label kept (-1: all are kept, or there is none; -2: refused)
+ * Outputs: out f64 [K]; status i32 [1], to be zeroed by the caller: bit 0 is set when a complex has more than
+ * drgnn_depth_capacity(1) atoms x n_dots; its targets are NaN (DRGNN_E_CAPACITY, reported through status because the call
+ * does not synchronise).  The offset and target tables are also given as HOST arrays: every check comes from them.
+ * phases: a later launch reads what the earlier ones left in the workspace, so a caller may run 1 | 2 once and 4 again for
+ * other targets of the same batch, or time the launches one by one; repeating a launch changes no bit. */
+typedef struct drgnn_depth_request {
+    const float* xyz;
+    const int32_t* atom_ptr;
+    const int32_t* res_ptr;
+    const double* radii;
+    const double* dots;
+    const int32_t* target_res;
+    const int32_t* target_complex;
+    const int32_t* host_atom_ptr;      /* the tables in host memory */
+    const int32_t* host_res_ptr;
+    const int32_t* host_target_res;
+    const int32_t* host_target_complex;
+    int64_t n_atoms, n_residues, n_complexes, n_targets, n_radii;
+    double probe, link;
+    int32_t n_dots, components;
+    int32_t phases;                    /* 0: the whole call; else a set of 1 dots, 2 components, 4 residues: only these launches */
+    int32_t reserved;                  /* 0 */
+    void* workspace;
+    int64_t workspace_bytes;
+    double* out;
+    int32_t* status;
+} drgnn_depth_request;
+
+/* the documented capacities: what = 0 dots per atom (4096), 1 atoms x n_dots of one complex (4 194 304), 2 the most
+ * targets, complexes and atoms / 16 of one call (one workgroup each: the grid's limit); -1 otherwise.  Pure host. */
+int32_t drgnn_depth_capacity(int32_t what);
+
+/* bytes of workspace for a call, -1 for counts the call refuses; offsets (may be null): int64 [10], see above.  Pure host. */
+int64_t drgnn_depth_workspace(int64_t n_atoms, int64_t n_complexes, int32_t n_dots, int64_t* offsets);
+
+/* DRGNN_E_ARG, before any launch: a null pointer, an offset table that does not start at 0, decreases or ends elsewhere
+ * than n_atoms / n_residues, a target outside its complex, n_radii that does not divide n_atoms, n_dots < 1, probe <= 0,
+ * link < 0, components outside 0..1, phases outside 0..7, a workspace that is not 8-byte aligned.  DRGNN_E_CAPACITY: n_dots, n_targets,
+ * n_complexes or n_atoms beyond drgnn_depth_capacity, workspace_bytes too small.  Three launches, no allocation, no
+ * synchronisation. */
+int drgnn_depth_residues(const drgnn_depth_request* req, void* stream);
+
 /* ---- clustering of poses by their fraction of common contacts (drgnn_fcc.h) ---------------------------
  * FCC clustering (Rodrigues et al. 2012; the rule of HADDOCK's cluster_fcc with the tie between equally connected
  * centres broken towards the smaller index) of M poses of one two-chain topology.  tests/fcc_ref.py states the rule.
