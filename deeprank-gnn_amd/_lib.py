@@ -167,7 +167,7 @@ class HseRequest(ctypes.Structure):
 
 
 class PackRequest(ctypes.Structure):
-    """drgnn_pack_request (include/drgnn.h): the outputs of drgnn_iface_fill (and bsa / hse rows of exactly its nodes) for
+    """drgnn_pack_request (include/drgnn.h): the outputs of drgnn_iface_fill (and bsa / hse / depth rows of exactly its nodes) for
     drgnn_iface_pack; ``host_cols`` is the address of a host copy of the column descriptor."""
     _fields_ = [("node_ptr", _vp), ("edge_ptr", _vp), ("iedge_ptr", _vp), ("node_residue", _vp), ("chain", _vp), ("type", _vp),
                 ("pos", _vp), ("edge_index", _vp), ("dist", _vp), ("internal_edge_index", _vp), ("bsa", _vp), ("hse", _vp),
@@ -175,10 +175,11 @@ class PackRequest(ctypes.Structure):
                 ("n_complexes", _c_i64), ("n_nodes", _c_i64), ("n_edges", _c_i64), ("n_iedges", _c_i64),
                 ("n_residues", _c_i64), ("n_rows", _c_i64),
                 ("res_width", _c_i32), ("type_width", _c_i32), ("n_cols", _c_i32), ("edge_mode", _c_i32),
-                ("x", _vp), ("edge_index_out", _vp), ("edge_attr", _vp), ("internal_edge_index_out", _vp), ("batch", _vp)]
+                ("x", _vp), ("edge_index_out", _vp), ("edge_attr", _vp), ("internal_edge_index_out", _vp), ("batch", _vp),
+                ("depth", _vp)]         # (the last field, as in the header: the fields before it keep their offsets)
 
 
-PACK_TYPE, PACK_POS, PACK_CHAIN, PACK_BSA, PACK_HSE, PACK_RES = range(6)      # sources of drgnn_pack_request.cols
+PACK_TYPE, PACK_POS, PACK_CHAIN, PACK_BSA, PACK_HSE, PACK_RES, PACK_DEPTH = range(7)   # sources of drgnn_pack_request.cols
 
 
 class PoseContactsRequest(ctypes.Structure):

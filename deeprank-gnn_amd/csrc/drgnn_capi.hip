@@ -2098,6 +2098,24 @@ int64_t drgnn_iface_workspace_bytes(int64_t n_complexes, int64_t max_res_a, int6
     return off[7];
 }
 
+// the ragged layout on the host, whole, before anything is indexed through it: 0 = ap[0] <= ap[r] <= ap[r + 1], ap[R] = T;
+// with rp, 0 = rp[0] <= rp[c] <= rp[c + 1] <= R = rp[M]; with sp, rp[c] <= sp[c] <= rp[c + 1]
+static bool ragged_check(const int32_t* ap, const int32_t* rp, const int32_t* sp, int64_t T, int64_t R, int64_t M) {
+    if (ap[0] != 0 || ap[R] != T || (rp && (rp[0] != 0 || rp[M] != R))) return false;
+    for (int64_t r = 0; r < R; ++r)
+        if (ap[r + 1] < ap[r]) return false;
+    for (int64_t c = 0; rp && c < M; ++c)
+        if (rp[c + 1] < rp[c] || rp[c + 1] > R || (sp && (sp[c] < rp[c] || sp[c] > rp[c + 1]))) return false;
+    return true;
+}
+
+// every target (complex tc[k], residue tr[k]) lies inside its complex; rp has passed ragged_check
+static bool targets_check(const int32_t* tc, const int32_t* tr, const int32_t* rp, int64_t M, int64_t K) {
+    for (int64_t k = 0; k < K; ++k)
+        if (tc[k] < 0 || tc[k] >= M || tr[k] < rp[tc[k]] || tr[k] >= rp[tc[k] + 1]) return false;
+    return true;
+}
+
 // checks the request on the host and fills the launch record; *max_res: the longest complex
 static int iface_prepare(const drgnn_iface_request* q, IfaceArgs& a, int* max_res) {
     if (!q || !q->host_atom_ptr || !q->host_res_ptr || !q->node_ptr || !q->edge_ptr || !q->iedge_ptr) return DRGNN_E_ARG;
@@ -2108,15 +2126,9 @@ static int iface_prepare(const drgnn_iface_request* q, IfaceArgs& a, int* max_re
     if (T > 0 && !q->xyz) return DRGNN_E_ARG;
     if (!(q->contact_distance >= 0.0) || !(q->internal_contact_distance >= 0.0) || q->tile_atoms < 0) return DRGNN_E_ARG;
     const int32_t *ap = q->host_atom_ptr, *rp = q->host_res_ptr, *sp = q->host_res_split;
-    if (ap[0] != 0 || ap[R] != T || rp[0] != 0 || rp[M] != R) return DRGNN_E_ARG;
+    if (!ragged_check(ap, rp, sp, T, R, M)) return DRGNN_E_ARG;
     int max_atoms = 0, maxA = 0, maxB = 0, maxR = 0, maxB_atoms = 0;
-    for (int64_t r = 0; r < R; ++r) {
-        if (ap[r + 1] < ap[r]) return DRGNN_E_ARG;
-        max_atoms = std::max(max_atoms, ap[r + 1] - ap[r]);
-    }
-    // the residue tables whole, before anything is indexed through them: 0 = rp[0] <= rp[c] <= sp[c] <= rp[c + 1] <= R
-    for (int64_t c = 0; c < M; ++c)
-        if (rp[c + 1] < rp[c] || rp[c + 1] > R || sp[c] < rp[c] || sp[c] > rp[c + 1]) return DRGNN_E_ARG;
+    for (int64_t r = 0; r < R; ++r) max_atoms = std::max(max_atoms, ap[r + 1] - ap[r]);
     for (int64_t c = 0; c < M; ++c) {
         maxA = std::max(maxA, sp[c] - rp[c]);
         maxB = std::max(maxB, rp[c + 1] - sp[c]);
@@ -2238,9 +2250,7 @@ int drgnn_dock_scores(const drgnn_score_request* q, void* stream) {
         if (zp[z + 1] < zp[z] || zp[z + 1] - zp[z] < 3) return DRGNN_E_ARG;
     for (int64_t i = 0; i < zp[3]; ++i)
         if (za[i] < 0 || za[i] >= T) return DRGNN_E_ARG;
-    if (ap[0] != 0 || ap[R] != T) return DRGNN_E_ARG;
-    for (int64_t r = 0; r < R; ++r)
-        if (ap[r + 1] < ap[r]) return DRGNN_E_ARG;
+    if (!ragged_check(ap, nullptr, nullptr, T, R, 0)) return DRGNN_E_ARG;
     int amax = 1;
     for (int64_t p = 0; p < P; ++p) {
         const int32_t ra = pr[2 * p], rb = pr[2 * p + 1];
@@ -2281,15 +2291,8 @@ int drgnn_bsa_residues(const drgnn_bsa_request* q, void* stream) {
     if (!(q->probe >= 0.0) || q->n_slices < 1) return DRGNN_E_ARG;
     if (q->n_slices > BS_MAX_SLICES || K > BS_MAX_TARGETS) return DRGNN_E_CAPACITY;
     const int32_t *ap = q->host_atom_ptr, *rp = q->host_res_ptr, *sp = q->host_res_split;
-    if (ap[0] != 0 || ap[R] != T || rp[0] != 0 || rp[M] != R) return DRGNN_E_ARG;
-    for (int64_t r = 0; r < R; ++r)
-        if (ap[r + 1] < ap[r]) return DRGNN_E_ARG;
-    for (int64_t c = 0; c < M; ++c)
-        if (rp[c + 1] < rp[c] || rp[c + 1] > R || sp[c] < rp[c] || sp[c] > rp[c + 1]) return DRGNN_E_ARG;
-    for (int64_t k = 0; k < K; ++k) {
-        const int32_t c = q->host_target_complex[k], r = q->host_target_res[k];
-        if (c < 0 || c >= M || r < rp[c] || r >= rp[c + 1]) return DRGNN_E_ARG;
-    }
+    if (!ragged_check(ap, rp, sp, T, R, M) || !targets_check(q->host_target_complex, q->host_target_res, rp, M, K))
+        return DRGNN_E_ARG;
     if (K == 0) return 0;
     BsaArgs a;
     memset(&a, 0, sizeof(a));
@@ -2331,19 +2334,13 @@ int drgnn_hse_residues(const drgnn_hse_request* q, void* stream) {
         return DRGNN_E_ARG;
     if (NT > HS_MAX_TILES) return DRGNN_E_CAPACITY;
     const int32_t *ap = q->host_atom_ptr, *rp = q->host_res_ptr, *tp = q->host_tile_ptr, *hb = q->host_bb;
-    if (ap[0] != 0 || ap[R] != T || rp[0] != 0 || rp[M] != R || tp[0] != 0 || tp[NT] != K) return DRGNN_E_ARG;
+    if (!ragged_check(ap, rp, nullptr, T, R, M) || tp[0] != 0 || tp[NT] != K) return DRGNN_E_ARG;
     for (int64_t r = 0; r < R; ++r) {
-        if (ap[r + 1] < ap[r]) return DRGNN_E_ARG;
         const int32_t* row = hb + 5 * (r % NB);                       // every offset the kernel may add lies in its residue
         for (int j = 0; j < 4; ++j)
             if (row[j] < -1 || row[j] >= ap[r + 1] - ap[r]) return DRGNN_E_ARG;
     }
-    for (int64_t c = 0; c < M; ++c)
-        if (rp[c + 1] < rp[c] || rp[c + 1] > R) return DRGNN_E_ARG;
-    for (int64_t k = 0; k < K; ++k) {
-        const int32_t c = q->host_target_complex[k], r = q->host_target_res[k];
-        if (c < 0 || c >= M || r < rp[c] || r >= rp[c + 1]) return DRGNN_E_ARG;
-    }
+    if (!targets_check(q->host_target_complex, q->host_target_res, rp, M, K)) return DRGNN_E_ARG;
     for (int64_t t = 0; t < NT; ++t) {
         if (tp[t + 1] < tp[t] || tp[t + 1] > K) return DRGNN_E_ARG;
         for (int64_t k = tp[t] + 1; k < tp[t + 1]; ++k)               // a tile serves one complex
@@ -2383,7 +2380,7 @@ int drgnn_iface_pack(const drgnn_pack_request* q, void* stream) {
     if (q->x) {
         if (F < 1 || !q->cols || !q->host_cols) return DRGNN_E_ARG;
         if (N * F > INT32_MAX) return DRGNN_E_CAPACITY;
-        const int64_t width[PK_NSRC] = {Wt, 3, 1, 3, 3, W};
+        const int64_t width[PK_NSRC] = {Wt, 3, 1, 3, 3, W, 1};
         for (int64_t f = 0; f < F; ++f) {
             const int32_t src = q->host_cols[2 * f], c = q->host_cols[2 * f + 1];
             if (src < 0 || src >= PK_NSRC || c < 0 || c >= width[src]) return DRGNN_E_ARG;
@@ -2392,7 +2389,8 @@ int drgnn_iface_pack(const drgnn_pack_request* q, void* stream) {
             if (N > 0) {                                               // (an empty batch has no arrays)
                 const void* need = src == PK_TYPE ? (const void*)q->type : src == PK_POS ? (const void*)q->pos :
                                    src == PK_CHAIN ? (const void*)q->chain : src == PK_BSA ? (const void*)q->bsa :
-                                   src == PK_HSE ? (const void*)q->hse : (const void*)q->node_residue;
+                                   src == PK_HSE ? (const void*)q->hse : src == PK_DEPTH ? (const void*)q->depth :
+                                   (const void*)q->node_residue;
                 if (!need) return DRGNN_E_ARG;
             }
         }
@@ -2406,7 +2404,7 @@ int drgnn_iface_pack(const drgnn_pack_request* q, void* stream) {
     a.node_ptr = q->node_ptr; a.edge_ptr = q->edge_ptr; a.iedge_ptr = q->iedge_ptr;
     a.node_residue = q->node_residue; a.chain = q->chain; a.type = q->type; a.pos = q->pos;
     a.edge_index = q->edge_index; a.dist = q->dist; a.iedge_index = q->internal_edge_index;
-    a.bsa = q->bsa; a.hse = q->hse; a.res_feat = q->res_feat; a.type_table = q->type_table; a.cols = q->cols;
+    a.bsa = q->bsa; a.hse = q->hse; a.depth = q->depth; a.res_feat = q->res_feat; a.type_table = q->type_table; a.cols = q->cols;
     a.n_rows = (int)std::max<int64_t>(NB, 1); a.W = (int)W; a.Wt = (int)Wt; a.F = (int)F; a.edge_mode = q->edge_mode;
     a.N = (int)N; a.E = (int)E; a.Ei = (int)Ei;
     a.x = q->x; a.edge_index_out = q->edge_index_out; a.edge_attr = q->edge_attr;
@@ -2459,15 +2457,8 @@ int drgnn_depth_residues(const drgnn_depth_request* q, void* stream) {
         return DRGNN_E_ARG;
     if (q->n_dots > DP_DOTS_CAP || K > DP_MAX_GRID || M > DP_MAX_GRID || T / DRGNN_NWAVES >= DP_MAX_GRID) return DRGNN_E_CAPACITY;
     const int32_t *ap = q->host_atom_ptr, *rp = q->host_res_ptr;
-    if (ap[0] != 0 || ap[R] != T || rp[0] != 0 || rp[M] != R) return DRGNN_E_ARG;
-    for (int64_t r = 0; r < R; ++r)
-        if (ap[r + 1] < ap[r]) return DRGNN_E_ARG;
-    for (int64_t c = 0; c < M; ++c)
-        if (rp[c + 1] < rp[c] || rp[c + 1] > R) return DRGNN_E_ARG;
-    for (int64_t k = 0; k < K; ++k) {
-        const int32_t c = q->host_target_complex[k], r = q->host_target_res[k];
-        if (c < 0 || c >= M || r < rp[c] || r >= rp[c + 1]) return DRGNN_E_ARG;
-    }
+    if (!ragged_check(ap, rp, nullptr, T, R, M) || !targets_check(q->host_target_complex, q->host_target_res, rp, M, K))
+        return DRGNN_E_ARG;
     int64_t off[10];
     if (depth_layout(T, M, q->n_dots, off) != 0) return DRGNN_E_ARG;
     int ph = q->phases == 0 ? 7 : q->phases;
@@ -2528,9 +2519,7 @@ int drgnn_pose_contacts(const drgnn_pose_contacts_request* q, void* stream) {
     const int64_t WB = (R - A + 63) / 64;
     if (M > 0 && A * WB > 0 && !q->bits) return DRGNN_E_ARG;
     const int32_t* ap = q->host_atom_ptr;
-    if (ap[0] != 0 || ap[R] != T) return DRGNN_E_ARG;
-    for (int64_t r = 0; r < R; ++r)
-        if (ap[r + 1] < ap[r]) return DRGNN_E_ARG;
+    if (!ragged_check(ap, nullptr, nullptr, T, R, 0)) return DRGNN_E_ARG;
     if (M == 0) return 0;
     FccContactArgs a;
     memset(&a, 0, sizeof(a));

@@ -1,4 +1,4 @@
-// drgnn_pack.h -- the interface builder's output (drgnn_iface.h, with the optional drgnn_bsa.h / drgnn_hse.h rows) packed
+// drgnn_pack.h -- the interface builder's output (drgnn_iface.h, with the optional drgnn_bsa.h / drgnn_hse.h / drgnn_depth.h rows) packed
 // into the arrays a resident graph set holds (drgnn_collate.h), without leaving the device: what
 // GraphDataSet.load_one_graph + ResidentGraphSet.__init__ assemble per graph on the host.
 //
@@ -9,6 +9,7 @@
 //                PK_BSA    bsa[i]                       f64 [N, 3], rounded once to f32
 //                PK_HSE    hse[i]                       f64 [N, 3], rounded once; a row whose first entry is NaN reads 0, 0, 0
 //                PK_RES    res_feat[node_residue[i] % n_rows]   f32 [n_rows, W]
+//                PK_DEPTH  depth[i]                     f64 [N], rounded once to f32
 //   edge_index_out [2, 2E]  graph k's columns 2 edge_ptr[k] .. 2 edge_ptr[k+1]: its pairs, then the same pairs reversed
 //   edge_attr      [2E]     mode 0 the distance, mode 1 tanh(-d/2 + 2) + 1 in fp64 on the f32 distance, rounded once
 //   iedge_index_out [2, 2Ei] the same layout, node ids + node_ptr[k] (batch-global: what precluster() reads)
@@ -33,7 +34,8 @@
 #define PK_BSA 3
 #define PK_HSE 4
 #define PK_RES 5
-#define PK_NSRC 6
+#define PK_DEPTH 6
+#define PK_NSRC 7
 
 struct PackArgs {
     const int32_t *node_ptr, *edge_ptr, *iedge_ptr;      // [M + 1]
@@ -43,6 +45,7 @@ struct PackArgs {
     const float* dist;                                   // [E]
     const int64_t* iedge_index;                          // [Ei, 2] local ids
     const double *bsa, *hse;                             // [N, 3] or null
+    const double* depth;                                 // [N] or null
     const float* res_feat;                               // [n_rows, W] or null
     const float* type_table;                             // [20, Wt] or null
     const int32_t* cols;                                 // [F, 2]
@@ -81,6 +84,7 @@ DEV float pk_value(const PackArgs& a, const PackShared& s, int src, int c, int64
     case PK_POS: return a.pos[3 * node + c];
     case PK_CHAIN: return (float)a.chain[node];
     case PK_BSA: return (float)a.bsa[3 * node + c];
+    case PK_DEPTH: return (float)a.depth[node];
     case PK_HSE: {
         const double head = a.hse[3 * node];
         return head != head ? 0.0f : (float)a.hse[3 * node + c];

@@ -60,6 +60,7 @@ graph carries ``node_data/residue``, each node's index among the residues of its
 Order (fixed here; the reference's is networkx insertion order): nodes by (chain, position of the residue in the
 input), interface edges (A node, B node) and internal edges (i < j) sorted by their pair.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -311,16 +312,8 @@ def interface_graphs(tables_or_poses, names, contact_distance=8.5, internal_cont
         raise ValueError("%d names for %d complexes" % (len(names), len(cx)))
     if reference is not None and not all(t is reference.table for t, _ in cx):
         raise ValueError("with `reference`, every complex must be a pose of the reference's AtomTable")
-    bsa_mode = None if bsa is False or bsa is None else ("reference" if bsa is True else bsa)
-    if bsa_mode is not None:                                           # the radius tables refuse before any launch
-        bsa_radii_of = _radii_lookup([t for t, _ in cx], bsa_mode)
-    hse_opt = None if hse is False or hse is None else _hse_options(**({} if hse is True else dict(hse)))
-    if hse_opt is not None:                                            # a table without atom names refuses before any launch
-        hse_bb_of = _bb_lookup([t for t, _ in cx])
-    depth_opt = None if depth is False or depth is None else dict({} if depth is True else depth)
-    if depth_opt is not None:                                          # the radius table refuses before any launch
-        depth_radii_of = _depth_radii_lookup([t for t, _ in cx], depth_opt.pop("radii", "united"))
-        depth_opt = _depth_options(**depth_opt)
+    active = [(f,) + f.options(value, [t for t, _ in cx])              # the options and the host tables refuse before any launch
+              for f, value in zip(FEATURES, (bsa, hse, depth)) if value is not None and value is not False]
     if chunk is None:
         chunk = default_chunk(api, max([t.split for t, _ in cx] + [0]), max([t.n_residues - t.split for t, _ in cx] + [0]),
                               max([t.n_atoms for t, _ in cx] + [0]))
@@ -328,25 +321,17 @@ def interface_graphs(tables_or_poses, names, contact_distance=8.5, internal_cont
     trees = []
     for lo in range(0, len(cx), chunk):
         part = cx[lo:lo + chunk]
-        xyz, atom_ptr, res_ptr, split, res_type = _ragged(part)
-        r = build_ragged(api, xyz, atom_ptr, res_ptr, split, res_type, contact_distance, internal_contact_distance, device)
-        if bsa_mode is not None:
-            node_res = [r["node_residue"][r["node_ptr"][k]:r["node_ptr"][k + 1]].astype(np.int64) - int(res_ptr[k])
-                        for k in range(len(part))]
-            buried = _bsa_chunk(api, part, node_res, bsa_radii_of, 1.4, 20, device, ragged=(xyz, atom_ptr, res_ptr, split))
-        if hse_opt is not None:
-            node_res = [r["node_residue"][r["node_ptr"][k]:r["node_ptr"][k + 1]].astype(np.int64) - int(res_ptr[k])
-                        for k in range(len(part))]
-            exposed = _hse_chunk(api, part, node_res, hse_bb_of, hse_opt, device, ragged=(xyz, atom_ptr, res_ptr))
-        if depth_opt is not None:
-            node_res = [r["node_residue"][r["node_ptr"][k]:r["node_ptr"][k + 1]].astype(np.int64) - int(res_ptr[k])
-                        for k in range(len(part))]
-            deep = _depth_chunk(api, part, node_res, depth_radii_of, depth_opt, device, ragged=(xyz, atom_ptr, res_ptr))
+        ragged = _ragged(part)
+        res_ptr = ragged[2]
+        r = build_ragged(api, *ragged, contact_distance, internal_contact_distance, device)
+        node_res = [r["node_residue"][r["node_ptr"][k]:r["node_ptr"][k + 1]].astype(np.int64) - int(res_ptr[k])
+                    for k in range(len(part))]
+        rows = [_feature_chunk(f, api, part, node_res, tabs_of, opt, device, ragged=ragged) for f, opt, tabs_of in active]
         for k, (t, _) in enumerate(part):
             n0, n1 = r["node_ptr"][k:k + 2]
             e0, e1 = r["edge_ptr"][k:k + 2]
             i0, i1 = r["iedge_ptr"][k:k + 2]
-            residue = r["node_residue"][n0:n1].astype(np.int64) - int(res_ptr[k])
+            residue = node_res[k]
             typ = r["type"][n0:n1].astype(np.int64)
             trees.append({
                 "nodes": np.stack((np.asarray(t.chains)[t.res_chain[residue]], t.res_seq[residue].astype("U"),
@@ -362,14 +347,8 @@ def interface_graphs(tables_or_poses, names, contact_distance=8.5, internal_cont
                 "node_data/charge": RESIDUE_CHARGE[typ].astype(np.float64),
                 "node_data/residue": residue,
             })
-            if bsa_mode is not None:
-                trees[-1]["node_data/bsa"] = buried[k][:, 2:3].copy()
-            if hse_opt is not None:
-                rows = exposed[k].copy()
-                rows[np.isnan(rows[:, 0])] = 0.0
-                trees[-1]["node_data/hse"] = rows
-            if depth_opt is not None:
-                trees[-1]["node_data/depth"] = deep[k].copy()
+            for (f, _, _), per_complex in zip(active, rows):
+                trees[-1]["node_data/" + f.name] = f.node_data(per_complex[k])
     store = GraphStore.from_trees(names, trees)
     if reference is not None and cx:
         attach_scores(store, names, docking_scores(np.stack([x for _, x in cx]), reference, device=device, api=api))
@@ -387,7 +366,9 @@ def attach_residue_features(store, name, per_residue_array):
 
 
 # ---- resident graph sets without host trees (csrc/drgnn_pack.h) --------------------------------------------------------
-FEATURE_WIDTH = {"type": 20, "polarity": 4, "charge": 1, "pos": 3, "chain": 1, "bsa": 1, "hse": 3, "depth": 1}
+# the (source, column) pairs of drgnn_iface_pack behind every built-in node feature; FEATURES (below) adds bsa, hse, depth
+PACK_SOURCE = {"type": [(_lib.PACK_TYPE, j) for j in range(20)], "polarity": [(_lib.PACK_TYPE, 20 + j) for j in range(4)],
+               "charge": [(_lib.PACK_TYPE, 24)], "pos": [(_lib.PACK_POS, j) for j in range(3)], "chain": [(_lib.PACK_CHAIN, 0)]}
 MCL_WORKSPACE_BUDGET = 256 << 20   # bytes of Markov clustering's dense fp64 workspace (3 n^2 per graph) one precluster call may ask for
 
 
@@ -403,52 +384,38 @@ def pack_type_table():
 
 def _pack_columns(node_feature, residue_width):
     """cols int32 [F,2] of drgnn_iface_pack for the feature names in order; residue_width: {name: (offset, width)}"""
-    P = _lib
     cols = []
     for name in node_feature:
-        if name == "type":
-            cols += [(P.PACK_TYPE, j) for j in range(20)]
-        elif name == "polarity":
-            cols += [(P.PACK_TYPE, 20 + j) for j in range(4)]
-        elif name == "charge":
-            cols.append((P.PACK_TYPE, 24))
-        elif name == "pos":
-            cols += [(P.PACK_POS, j) for j in range(3)]
-        elif name == "chain":
-            cols.append((P.PACK_CHAIN, 0))
-        elif name == "bsa":
-            cols.append((P.PACK_BSA, 2))
-        elif name == "hse":
-            cols += [(P.PACK_HSE, j) for j in range(3)]
-        elif name == "depth":
-            cols.append((P.PACK_POS, 0))                               # a place holder: the caller copies the column in
+        if name in PACK_SOURCE:
+            cols += PACK_SOURCE[name]
         else:
             off, w = residue_width[name]
-            cols += [(P.PACK_RES, off + j) for j in range(w)]
+            cols += [(_lib.PACK_RES, off + j) for j in range(w)]
     return np.ascontiguousarray(np.array(cols, dtype=np.int32).reshape(-1, 2))
 
 
 def iface_pack_raw(api, built, ptrs, cols, n_residues, type_table=None, bsa=None, hse=None, res_feat=None, edge_mode=1,
-                   want=("x", "edge_index", "edge_attr", "internal_edge_index", "batch")):
+                   want=("x", "edge_index", "edge_attr", "internal_edge_index", "batch"), depth=None):
     """One drgnn_iface_pack call (include/drgnn.h) over what ``build_ragged_device`` returned (``built``, ``ptrs``), all
-    on the device: a dict of the outputs named in ``want``.  ``cols`` int32 [F,2] on the host; ``type_table`` /
-    ``bsa`` / ``hse`` / ``res_feat``: device tensors (float32 [20,Wt], float64 [N,3], float64 [N,3], float32 [n_rows,W])."""
-    q, out, _ = pack_request(built, ptrs, cols, n_residues, type_table, bsa, hse, res_feat, edge_mode, want)
+    on the device: a dict of the outputs named in ``want``.  ``cols`` int32 [F,2] on the host; ``type_table`` / ``bsa`` /
+    ``hse`` / ``res_feat`` / ``depth``: device tensors (float32 [20,Wt], float64 [N,3], float64 [N,3], float32 [n_rows,W],
+    float64 [N])."""
+    q, out, _ = pack_request(built, ptrs, cols, n_residues, type_table, bsa, hse, res_feat, edge_mode, want, depth)
     api.iface_pack(q, _lib.current_stream(ptrs))
     return out
 
 
 def pack_request(built, ptrs, cols, n_residues, type_table=None, bsa=None, hse=None, res_feat=None, edge_mode=1,
-                 want=("x", "edge_index", "edge_attr", "internal_edge_index", "batch")):
+                 want=("x", "edge_index", "edge_attr", "internal_edge_index", "batch"), depth=None):
     """(drgnn_pack_request, its freshly allocated outputs, the arrays the request points into) of ``iface_pack_raw``"""
     dev = ptrs.device
     cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1, 2)
     M = int(ptrs.shape[1]) - 1
     N, E, Ei = int(built["pos"].shape[0]), int(built["dist"].shape[0]), int(built["internal_edge_index"].shape[0])
     F = int(cols.shape[0])
-    for name, rows in (("bsa", bsa), ("hse", hse)):                     # (the kernel reads row i of every node i)
-        if rows is not None and (tuple(rows.shape) != (N, 3) or rows.dtype != torch.float64 or not rows.is_contiguous()):
-            raise ValueError("%s must be float64 [%d, 3], one row per node" % (name, N))
+    for name, rows, shape in (("bsa", bsa, (N, 3)), ("hse", hse, (N, 3)), ("depth", depth, (N,))):    # (the kernel reads row i of node i)
+        if rows is not None and (tuple(rows.shape) != shape or rows.dtype != torch.float64 or not rows.is_contiguous()):
+            raise ValueError("%s must be float64 %s, one row per node" % (name, list(shape)))
     for name, t, dt in (("type_table", type_table, torch.float32), ("res_feat", res_feat, torch.float32)):
         if t is not None and (t.dim() != 2 or t.dtype != dt or not t.is_contiguous() or (name == "type_table" and t.shape[0] != 20)):
             raise ValueError("%s must be a contiguous float32 matrix%s" % (name, " of 20 rows" if name == "type_table" else ""))
@@ -469,7 +436,7 @@ def pack_request(built, ptrs, cols, n_residues, type_table=None, bsa=None, hse=N
     q.node_ptr, q.edge_ptr, q.iedge_ptr = ptrs[0].data_ptr(), ptrs[1].data_ptr(), ptrs[2].data_ptr()
     q.node_residue, q.chain, q.type, q.pos = p(built["node_residue"]), p(built["chain"]), p(built["type"]), p(built["pos"])
     q.edge_index, q.dist, q.internal_edge_index = p(built["edge_index"]), p(built["dist"]), p(built["internal_edge_index"])
-    q.bsa, q.hse, q.res_feat, q.type_table = p(bsa), p(hse), p(res_feat), p(type_table)
+    q.bsa, q.hse, q.depth, q.res_feat, q.type_table = p(bsa), p(hse), p(depth), p(res_feat), p(type_table)
     q.cols, q.host_cols = p(d_cols), (cols.ctypes.data if F else None)
     q.n_complexes, q.n_nodes, q.n_edges, q.n_iedges, q.n_residues = M, N, E, Ei, int(n_residues)
     q.n_rows = 0 if res_feat is None else int(res_feat.shape[0])
@@ -544,8 +511,8 @@ def interface_resident_set(tables_or_poses, names, node_feature=("type", "polari
     residue of the AtomTable, or {mol: table}}, as ``attach_residue_features`` takes them).  ``"all"``, an unknown
     name or a wrongly shaped table raises ValueError before any launch.  ``bsa`` / ``hse`` / ``depth``: the options
     of ``interface_graphs``; they are computed only when a feature asks for them, and ``depth`` is a feature only when
-    the argument is given (True or a dict).  The ``depth`` column is copied into
-    ``x`` after the pack launch (one strided copy per chunk, rounded to float32 as the store path rounds it).
+    the argument is given (True or a dict).  All three reach ``x`` through the pack launch, rounded once to float32 as
+    the store path rounds them; a feature listed twice gives two equal columns.
     ``edge_feature``: ``("dist",)`` or None (no ``edge_attr``).  ``edge_transform``: "default" (the reference's
     ``tanh(-d/2 + 2) + 1``, evaluated in fp64 on the float32 distance and rounded once, where the store path evaluates
     it in float32: the two differ by at most 2^-21), None (the distances as they are) or a callable applied to the
@@ -603,24 +570,12 @@ def interface_resident_set(tables_or_poses, names, node_feature=("type", "polari
             raise ValueError("with `reference`, every complex must be a pose of the reference's AtomTable")
     used = {f: residue_features[f] for f in node_feature if f in residue_features}
     res_cols, res_width, res_rows = _residue_tables(used, cx, names)
-    want_bsa, want_hse = "bsa" in node_feature, "hse" in node_feature
-    if want_bsa:
-        if bsa is False or bsa is None:
-            raise ValueError("the node feature 'bsa' needs bsa=True or a radii option")
-        bsa_radii_of = _radii_lookup([t for t, _ in cx], "reference" if bsa is True else bsa)
-    if want_hse:
-        if hse is False or hse is None:
-            raise ValueError("the node feature 'hse' needs hse=True or a dict of options")
-        hse_opt = _hse_options(**({} if hse is True else dict(hse)))
-        hse_bb_of = _bb_lookup([t for t, _ in cx])
-    want_depth = "depth" in node_feature
-    if want_depth:
-        depth_opt = dict({} if depth is True else depth)
-        depth_radii_of = _depth_radii_lookup([t for t, _ in cx], depth_opt.pop("radii", "united"))
-        depth_opt = _depth_options(**depth_opt)
-        if node_feature.count("depth") != 1:
-            raise ValueError("the node feature 'depth' may be listed once")
-        depth_col = sum(FEATURE_WIDTH.get(f, res_cols.get(f, (0, 0))[1]) for f in node_feature[:node_feature.index("depth")])
+    active = []
+    for f, value in zip(FEATURES, (bsa, hse, depth)):
+        if f.name in node_feature:
+            if value is False or value is None:
+                raise ValueError("the node feature %r needs %s=True or %s" % (f.name, f.name, f.needs))
+            active.append((f,) + f.options(value, [t for t, _ in cx]))
     cols = _pack_columns(node_feature, res_cols)
     if cols.shape[0] > api.pack_capacity(0):
         raise ValueError("%d columns of node features; drgnn_iface_pack takes %d" % (cols.shape[0], api.pack_capacity(0)))
@@ -641,28 +596,21 @@ def interface_resident_set(tables_or_poses, names, node_feature=("type", "polari
     for lo in range(0, len(cx), chunk):
         part = cx[lo:lo + chunk]
         M = len(part)
-        xyz, atom_ptr, res_ptr, split, res_type = _ragged(part)
-        built, ptrs = build_ragged_device(api, xyz, atom_ptr, res_ptr, split, res_type, contact_distance,
-                                          internal_contact_distance, dev)
+        ragged = _ragged(part)
+        atom_ptr, res_ptr = ragged[1:3]
+        built, ptrs = build_ragged_device(api, *ragged, contact_distance, internal_contact_distance, dev)
         hp = ptrs.cpu().numpy().astype(np.int64)                       # the [M+1] tables
         nn = np.diff(hp[0])
         for k in range(M):
             (kept if nn[k] > 0 else skipped).append(names[lo + k])
         if hp[0, -1] == 0:
             continue
-        d_bsa = d_hse = d_depth = None
-        if want_bsa or want_hse or want_depth:
+        rows = {}                                                      # the rows of exactly the nodes, by feature, on the device
+        if active:
             node_residue = built["node_residue"].cpu().numpy().astype(np.int64)
             node_res = [node_residue[hp[0, k]:hp[0, k + 1]] - int(res_ptr[k]) for k in range(M)]
-            if want_bsa:
-                d_bsa = _bsa_chunk(api, part, node_res, bsa_radii_of, 1.4, 20, dev, ragged=(xyz, atom_ptr, res_ptr, split),
-                                   keep_device=True)
-            if want_hse:
-                d_hse = _hse_chunk(api, part, node_res, hse_bb_of, hse_opt, dev, ragged=(xyz, atom_ptr, res_ptr),
-                                   keep_device=True)
-            if want_depth:
-                d_depth = _depth_chunk(api, part, node_res, depth_radii_of, depth_opt, dev, ragged=(xyz, atom_ptr, res_ptr),
-                                       keep_device=True)
+            for f, opt, tabs_of in active:
+                rows[f.name] = _feature_chunk(f, api, part, node_res, tabs_of, opt, dev, ragged=ragged, keep_device=True)
         d_res = None
         if res_width:
             tabs = [res_rows(lo + k) for k in range(M)]
@@ -674,9 +622,8 @@ def interface_resident_set(tables_or_poses, names, node_feature=("type", "polari
                 d_res = torch.from_numpy(tabs[0] if shared else np.concatenate(tabs)).to(dev)
                 if key is not None:
                     res_dev[key] = d_res
-        out = iface_pack_raw(api, built, ptrs, cols, len(atom_ptr) - 1, type_table, d_bsa, d_hse, d_res, edge_mode, want)
-        if want_depth:
-            out["x"][:, depth_col] = d_depth.to(torch.float32)
+        out = iface_pack_raw(api, built, ptrs, cols, len(atom_ptr) - 1, type_table, res_feat=d_res, edge_mode=edge_mode,
+                             want=want, **rows)
         if edge_feature is not None and callable(edge_transform):
             out["edge_attr"] = torch.as_tensor(edge_transform(out["edge_attr"]), device=dev).to(torch.float32).reshape(-1)
         # ---- clusters: the kept graphs of the chunk in runs that fit the budget
@@ -917,7 +864,8 @@ BSA_SIDE_CHAIN = {
 }
 # the unbound chains of the reference: it hands freesasa only the first character of the atom name
 BSA_FIRST_LETTER = {"C": 1.61, "N": 1.64, "O": 1.42, "S": 1.80, "H": 1.10}
-BSA_XYZ_BUDGET = 256 << 20         # bytes of coordinates one call uploads (sets the default chunk)
+RESIDUE_XYZ_BUDGET = 256 << 20     # bytes of coordinates one bsa / hse / depth call uploads (sets their default chunk)
+BSA_XYZ_BUDGET = RESIDUE_XYZ_BUDGET                                    # (its first name)
 
 
 def bsa_radii(table, radii="reference"):
@@ -969,15 +917,6 @@ def bsa_radii(table, radii="reference"):
     return tuple(out)
 
 
-def _radii_lookup(tables, radii):
-    """{id(table): (complex_r, unbound_r)}: each distinct table's radii, made once"""
-    found = {}
-    for t in tables:
-        if id(t) not in found:
-            found[id(t)] = bsa_radii(t, radii)
-    return found
-
-
 def bsa_raw(api, xyz, atom_ptr, res_ptr, res_split, rad_complex, rad_unbound, target_res, target_complex, probe=1.4,
             n_slices=20, device="cpu", keep_device=False):
     """One drgnn_bsa_residues call (include/drgnn.h) over numpy arrays.  Returns (out float64 [K,3]: sasa_unbound,
@@ -1010,32 +949,12 @@ def bsa_raw(api, xyz, atom_ptr, res_ptr, res_split, rad_complex, rad_unbound, ta
     return (out if keep_device else out.cpu().numpy()), int(status.cpu()[0])
 
 
-def _bsa_chunk(api, part, residues, radii_of, probe, n_slices, device, ragged=None, keep_device=False):
-    """[out float64 [K_c,3]] for the complexes of ``part`` ([(table, xyz)]) and their residue lists (local indices).
-    ``keep_device``: one tensor [sum K_c, 3] on ``device`` instead, the complexes' rows back to back."""
-    if len(part) > 1 and sum(len(r) for r in residues) > api.bsa_capacity(3):      # one workgroup per target: the grid's limit
-        half = len(part) // 2
-        both = (_bsa_chunk(api, part[:half], residues[:half], radii_of, probe, n_slices, device, keep_device=keep_device),
-                _bsa_chunk(api, part[half:], residues[half:], radii_of, probe, n_slices, device, keep_device=keep_device))
-        return torch.cat(both) if keep_device else both[0] + both[1]
-    xyz, atom_ptr, res_ptr, split = ragged if ragged is not None else _ragged(part)[:4]
-    tables = [t for t, _ in part]
-    if all(t is tables[0] for t in tables):                              # poses of one topology: one radius table
-        cr, ur = radii_of[id(tables[0])]
-    else:
-        cr = np.concatenate([radii_of[id(t)][0] for t in tables])
-        ur = np.concatenate([radii_of[id(t)][1] for t in tables])
-    sizes = [len(r) for r in residues]
-    tgt_res = np.concatenate([np.asarray(r, dtype=np.int64) + int(res_ptr[k]) for k, r in enumerate(residues)]
-                             + [np.zeros(0, np.int64)])
-    tgt_cx = np.repeat(np.arange(len(part)), sizes)
-    out, status = bsa_raw(api, xyz, atom_ptr, res_ptr, split, cr, ur, tgt_res, tgt_cx, probe, n_slices, device, keep_device)
-    if status & 1:
-        _lib._check(-2, "drgnn_bsa_residues")
-    if keep_device:
-        return out
-    ends = np.cumsum(sizes)
-    return [out[e - n:e] for n, e in zip(sizes, ends)]
+def _bsa_options(probe=1.4, n_slices=20):
+    if int(n_slices) < 1:
+        raise ValueError("n_slices must be at least 1")
+    if not float(probe) >= 0.0:
+        raise ValueError("probe must be >= 0")
+    return {"probe": probe, "n_slices": n_slices}
 
 
 def residue_bsa(tables_or_poses, residues=None, radii="reference", probe=1.4, n_slices=20, device=None, chunk=None, api=None,
@@ -1049,39 +968,12 @@ def residue_bsa(tables_or_poses, residues=None, radii="reference", probe=1.4, n_
     index array per complex.  Only the atoms of the residues asked for are evaluated.  ``chunk``: complexes per
     launch; a residue's bits do not depend on it, on the batch or on ``residues``.  ``parts``: return (bsa,
     sasa_unbound, sasa_complex) instead.  More than 256 neighbours of one atom is refused (DrgnnError, capacity)."""
-    api = api or _lib.get()
-    if device is None:
-        device = "cuda" if api is _lib._API else "cpu"
-    cx = _complexes(tables_or_poses)
-    if int(n_slices) < 1:
-        raise ValueError("n_slices must be at least 1")
-    if not float(probe) >= 0.0:
-        raise ValueError("probe must be >= 0")
-    radii_of = _radii_lookup([t for t, _ in cx], radii)
-    if residues is None:
-        wanted = [np.arange(t.n_residues) for t, _ in cx]
-    else:
-        per_complex = (isinstance(residues, (list, tuple)) and len(residues) == len(cx) and
-                       all(np.ndim(r) == 1 for r in residues))
-        wanted = [np.asarray(residues[k] if per_complex else residues, dtype=np.int64).reshape(-1) for k in range(len(cx))]
-        for (t, _), w in zip(cx, wanted):
-            if w.size and (w.min() < 0 or w.max() >= t.n_residues):
-                raise ValueError("a residue index outside [0, %d)" % t.n_residues)
-    if chunk is None:
-        chunk = BSA_XYZ_BUDGET // (12 * max([t.n_atoms for t, _ in cx] + [1]))
-    chunk = max(1, int(chunk))
-    full = [np.full((3, t.n_residues), np.nan) for t, _ in cx]
-    for lo in range(0, len(cx), chunk):
-        part = cx[lo:lo + chunk]
-        for k, o in enumerate(_bsa_chunk(api, part, wanted[lo:lo + chunk], radii_of, probe, n_slices, device)):
-            full[lo + k][:, wanted[lo + k]] = o.T
-    pick = (lambda f: (f[2], f[0], f[1])) if parts else (lambda f: f[2])
-    if isinstance(tables_or_poses, AtomTable):
-        return pick(full[0])
-    if isinstance(tables_or_poses, Poses):
-        stacked = np.stack(full) if full else np.zeros((0, 3, tables_or_poses.table.n_residues))
-        return pick(stacked.transpose(1, 0, 2))
-    return [pick(f) for f in full]
+    rows = _residue_values(BSA, tables_or_poses, residues, radii, {"probe": probe, "n_slices": n_slices}, device, chunk, api)
+
+    def pick(a):                                                       # the columns of a row: sasa_unbound, sasa_complex, bsa
+        got = tuple(np.ascontiguousarray(a[..., j]) for j in ((2, 0, 1) if parts else (2,)))
+        return got if parts else got[0]
+    return [pick(a) for a in rows] if isinstance(rows, list) else pick(rows)
 
 
 # ---- half-sphere exposure (csrc/drgnn_hse.h) ---------------------------------------------------------------------------
@@ -1116,15 +1008,6 @@ def hse_tile(n_targets):
     residues: 8.0 us at 4 against 32.1 us at 64), large ones stage a complex fewer times (1024 poses: 2.46 ms at 64 against
     3.57 ms at 4); profiles/hse_ab.txt.  It changes no bit of the result."""
     return max(HSE_TILE[0], min(HSE_TILE[1], int(n_targets) // HSE_WORKGROUPS))
-
-
-def _bb_lookup(tables):
-    """{id(table): bb}: each distinct table's backbone table, made once"""
-    found = {}
-    for t in tables:
-        if id(t) not in found:
-            found[id(t)] = hse_table(t)
-    return found
 
 
 def _hse_options(radius=12.0, offset=0, connect="CA", direction="CA"):
@@ -1190,34 +1073,6 @@ def hse_raw(api, xyz, atom_ptr, res_ptr, bb, target_res, target_complex, radius=
     return rows, int(status.cpu()[0])
 
 
-def _hse_chunk(api, part, residues, bb_of, opt, device, ragged=None, tile=None, keep_device=False):
-    """[out float64 [K_c,3]] for the complexes of ``part`` ([(table, xyz)]) and their residue lists (local indices).
-    ``keep_device``: one tensor [sum K_c, 3] on ``device`` instead, the complexes' rows back to back."""
-    if len(part) > 1 and sum(len(r) // (tile or HSE_TILE[0]) + 1 for r in residues) > api.hse_capacity(1):    # one workgroup per tile
-        half = len(part) // 2
-        both = (_hse_chunk(api, part[:half], residues[:half], bb_of, opt, device, tile=tile, keep_device=keep_device),
-                _hse_chunk(api, part[half:], residues[half:], bb_of, opt, device, tile=tile, keep_device=keep_device))
-        return torch.cat(both) if keep_device else both[0] + both[1]
-    xyz, atom_ptr, res_ptr = ragged if ragged is not None else _ragged(part)[:3]
-    tables = [t for t, _ in part]
-    if all(t is tables[0] for t in tables):                              # poses of one topology: one backbone table
-        bb = bb_of[id(tables[0])]
-    else:
-        bb = np.concatenate([bb_of[id(t)] for t in tables])
-    sizes = [len(r) for r in residues]
-    tgt_res = np.concatenate([np.asarray(r, dtype=np.int64) + int(res_ptr[k]) for k, r in enumerate(residues)]
-                             + [np.zeros(0, np.int64)])
-    tgt_cx = np.repeat(np.arange(len(part)), sizes)
-    out, status = hse_raw(api, xyz, atom_ptr, res_ptr, bb, tgt_res, tgt_cx, device=device, tile=tile, keep_device=keep_device,
-                          **opt)
-    if status & 1:
-        _lib._check(-2, "drgnn_hse_residues")
-    if keep_device:
-        return out
-    ends = np.cumsum(sizes)
-    return [out[e - n:e] for n, e in zip(sizes, ends)]
-
-
 def residue_hse(tables_or_poses, residues=None, radius=12.0, offset=0, connect="CA", direction="CA", device=None, chunk=None,
                 api=None):
     """Half-sphere exposure of residues, on the device: (up, down, angle) as the reference's ``hse`` node feature
@@ -1237,34 +1092,8 @@ def residue_hse(tables_or_poses, residues=None, radius=12.0, offset=0, connect="
     applied to every complex, or one index array per complex.  ``chunk``: complexes per launch; a residue's bits do
     not depend on it, on the batch or on ``residues``.  The tables must have been made with ``atom_name``.  A complex of
     more than 4096 residues is refused (DrgnnError, capacity)."""
-    api = api or _lib.get()
-    if device is None:
-        device = "cuda" if api is _lib._API else "cpu"
-    cx = _complexes(tables_or_poses)
-    opt = _hse_options(radius, offset, connect, direction)
-    bb_of = _bb_lookup([t for t, _ in cx])
-    if residues is None:
-        wanted = [np.arange(t.n_residues) for t, _ in cx]
-    else:
-        per_complex = (isinstance(residues, (list, tuple)) and len(residues) == len(cx) and
-                       all(np.ndim(r) == 1 for r in residues))
-        wanted = [np.asarray(residues[k] if per_complex else residues, dtype=np.int64).reshape(-1) for k in range(len(cx))]
-        for (t, _), w in zip(cx, wanted):
-            if w.size and (w.min() < 0 or w.max() >= t.n_residues):
-                raise ValueError("a residue index outside [0, %d)" % t.n_residues)
-    if chunk is None:
-        chunk = BSA_XYZ_BUDGET // (12 * max([t.n_atoms for t, _ in cx] + [1]))
-    chunk = max(1, int(chunk))
-    full = [np.full((t.n_residues, 3), np.nan) for t, _ in cx]
-    for lo in range(0, len(cx), chunk):
-        part = cx[lo:lo + chunk]
-        for k, o in enumerate(_hse_chunk(api, part, wanted[lo:lo + chunk], bb_of, opt, device)):
-            full[lo + k][wanted[lo + k]] = o
-    if isinstance(tables_or_poses, AtomTable):
-        return full[0]
-    if isinstance(tables_or_poses, Poses):
-        return np.stack(full) if full else np.zeros((0, tables_or_poses.table.n_residues, 3))
-    return full
+    return _residue_values(HSE, tables_or_poses, residues, None,
+                           {"radius": radius, "offset": offset, "connect": connect, "direction": direction}, device, chunk, api)
 
 
 # ---- residue depth (csrc/drgnn_depth.h) --------------------------------------------------------------------------------
@@ -1330,15 +1159,6 @@ def _depth_options(probe=1.5, n_dots=192, link=None, components="outer"):
     return {"probe": float(probe), "n_dots": int(n_dots), "link": link, "components": components}
 
 
-def _depth_radii_lookup(tables, radii):
-    """{id(table): radii}: each distinct table's radii, made once"""
-    found = {}
-    for t in tables:
-        if id(t) not in found:
-            found[id(t)] = depth_radii(t, radii)
-    return found
-
-
 def depth_raw(api, xyz, atom_ptr, res_ptr, radii, target_res, target_complex, probe=1.5, n_dots=192, link=None,
               components="outer", device="cpu", keep_device=False, parts=False):
     """One drgnn_depth_residues call (include/drgnn.h) over numpy arrays.  Returns (out float64 [K], status int): bit 0 of
@@ -1396,34 +1216,12 @@ def depth_raw(api, xyz, atom_ptr, res_ptr, radii, target_res, target_complex, pr
     return result + (surf,)
 
 
-def _depth_chunk(api, part, residues, radii_of, opt, device, ragged=None, keep_device=False):
-    """[out float64 [K_c]] for the complexes of ``part`` ([(table, xyz)]) and their residue lists (local indices).
-    ``keep_device``: one tensor [sum K_c] on ``device`` instead, the complexes' values back to back."""
+def _depth_too_large(api, part, residues, opt, device):
+    """a call of these complexes is beyond the workspace budget or the grid"""
     atoms = sum(t.n_atoms for t, _ in part)
     budget = DEPTH_WORKSPACE_BUDGET["cuda" if torch.device(device).type == "cuda" else "cpu"]
-    if len(part) > 1 and (44 * atoms * opt["n_dots"] > budget or
-                          max(sum(len(r) for r in residues), len(part), atoms // 16 + 1) > api.depth_capacity(2)):
-        half = len(part) // 2
-        both = (_depth_chunk(api, part[:half], residues[:half], radii_of, opt, device, keep_device=keep_device),
-                _depth_chunk(api, part[half:], residues[half:], radii_of, opt, device, keep_device=keep_device))
-        return torch.cat(both) if keep_device else both[0] + both[1]
-    xyz, atom_ptr, res_ptr = ragged if ragged is not None else _ragged(part)[:3]
-    tables = [t for t, _ in part]
-    if all(t is tables[0] for t in tables):                              # poses of one topology: one radius array
-        rad = radii_of[id(tables[0])]
-    else:
-        rad = np.concatenate([radii_of[id(t)] for t in tables])
-    sizes = [len(r) for r in residues]
-    tgt_res = np.concatenate([np.asarray(r, dtype=np.int64) + int(res_ptr[k]) for k, r in enumerate(residues)]
-                             + [np.zeros(0, np.int64)])
-    tgt_cx = np.repeat(np.arange(len(part)), sizes)
-    out, status = depth_raw(api, xyz, atom_ptr, res_ptr, rad, tgt_res, tgt_cx, device=device, keep_device=keep_device, **opt)
-    if status & 1:
-        _lib._check(-2, "drgnn_depth_residues")
-    if keep_device:
-        return out
-    ends = np.cumsum(sizes)
-    return [out[e - n:e] for n, e in zip(sizes, ends)]
+    return (44 * atoms * opt["n_dots"] > budget or
+            max(sum(len(r) for r in residues), len(part), atoms // 16 + 1) > api.depth_capacity(2))
 
 
 def residue_depth(tables_or_poses, residues=None, radii="united", probe=1.5, n_dots=192, link=None, components="outer",
@@ -1444,12 +1242,113 @@ def residue_depth(tables_or_poses, residues=None, radii="united", probe=1.5, n_d
     index array per complex.  ``chunk``: complexes per call (the workspace also bounds it); a residue's bits do not
     depend on it, on the batch or on ``residues``.  The tables must have been made with ``atom_name``.  More than 4096
     dots per atom, or a complex of more than 4 194 304 atoms x n_dots, is refused (DrgnnError, capacity)."""
+    return _residue_values(DEPTH, tables_or_poses, residues, radii,
+                           {"probe": probe, "n_dots": n_dots, "link": link, "components": components}, device, chunk, api)
+
+
+# ---- the per-residue features: one record each, one path for all (DESIGN.md, "Per-residue features") --------------------
+# name: of the option, of node_data/<name> and of the node feature;  row: the shape of one row of the raw call's out
+# check(**options): the options of the raw call, validated;  host_table(table, radii): the arrays the raw call takes per
+# table, a tuple;  ragged: how many of (xyz, atom_ptr, res_ptr, res_split) the raw call takes;  raw: one call of the
+# library;  too_large(api, part, residues, opt, device): the call must be halved;  c_name: the entry point, for errors
+# options(value, tables): the graph paths' option (True, a dict, a radii value) as (opt, host tables by id(table))
+# needs: what, besides True, the option may be;  node_data(rows): the rows of a complex as the store keeps them
+# pack: the (source, column) pairs of drgnn_iface_pack, which takes the rows as the argument ``name``
+Feature = collections.namedtuple("Feature", "name row check host_table ragged raw too_large c_name options needs node_data pack")
+
+
+def _per_table(feature, tables, radii):
+    """{id(table): host arrays}: each distinct table's, made once"""
+    found = {}
+    for t in tables:
+        if id(t) not in found:
+            found[id(t)] = feature.host_table(t, radii)
+    return found
+
+
+def _bsa_graph_options(value, tables):
+    return {"probe": 1.4, "n_slices": 20}, _per_table(BSA, tables, "reference" if value is True else value)
+
+
+def _hse_graph_options(value, tables):
+    opt = _hse_options(**({} if value is True else dict(value)))
+    return opt, _per_table(HSE, tables, None)
+
+
+def _depth_graph_options(value, tables):
+    opt = dict({} if value is True else value)
+    tabs_of = _per_table(DEPTH, tables, opt.pop("radii", "united"))
+    return _depth_options(**opt), tabs_of
+
+
+def _hse_node_data(rows):
+    rows = rows.copy()
+    rows[np.isnan(rows[:, 0])] = 0.0
+    return rows
+
+
+BSA = Feature(name="bsa", row=(3,), check=_bsa_options, host_table=bsa_radii, ragged=4, raw=bsa_raw,
+              # one workgroup per target: the grid's limit
+              too_large=lambda api, part, residues, opt, device: sum(len(r) for r in residues) > api.bsa_capacity(3),
+              c_name="drgnn_bsa_residues", options=_bsa_graph_options, needs="a radii option",
+              node_data=lambda rows: rows[:, 2:3].copy(), pack=[(_lib.PACK_BSA, 2)])
+HSE = Feature(name="hse", row=(3,), check=_hse_options, host_table=lambda table, radii: (hse_table(table),), ragged=3, raw=hse_raw,
+              # one workgroup per tile
+              too_large=lambda api, part, residues, opt, device: (sum(len(r) // HSE_TILE[0] + 1 for r in residues) >
+                                                                  api.hse_capacity(1)),
+              c_name="drgnn_hse_residues", options=_hse_graph_options, needs="a dict of options",
+              node_data=_hse_node_data, pack=[(_lib.PACK_HSE, j) for j in range(3)])
+DEPTH = Feature(name="depth", row=(), check=_depth_options, host_table=lambda table, radii: (depth_radii(table, radii),),
+                ragged=3, raw=depth_raw, too_large=_depth_too_large,
+                c_name="drgnn_depth_residues", options=_depth_graph_options, needs="a dict of options",
+                node_data=lambda rows: rows.copy(), pack=[(_lib.PACK_DEPTH, 0)])
+FEATURES = (BSA, HSE, DEPTH)                                           # in the order of the options of the graph paths
+PACK_SOURCE.update({f.name: f.pack for f in FEATURES})
+FEATURE_WIDTH = {name: len(cols) for name, cols in PACK_SOURCE.items()}    # columns of x behind every built-in node feature
+
+
+def _targets(residues, res_ptr):
+    """(target_res, target_complex, sizes) of per-complex lists of local residue indices"""
+    sizes = [len(r) for r in residues]
+    tgt_res = np.concatenate([np.asarray(r, dtype=np.int64) + int(res_ptr[k]) for k, r in enumerate(residues)]
+                             + [np.zeros(0, np.int64)])
+    return tgt_res, np.repeat(np.arange(len(residues)), sizes), sizes
+
+
+def _feature_chunk(feature, api, part, residues, tabs_of, opt, device, ragged=None, keep_device=False):
+    """[rows float64 [K_c] + feature.row] for the complexes of ``part`` ([(table, xyz)]) and their residue lists (local
+    indices); ``ragged``: ``_ragged(part)`` when the caller has it.  ``keep_device``: one tensor [sum K_c] + feature.row
+    on ``device`` instead, the complexes' rows back to back."""
+    if len(part) > 1 and feature.too_large(api, part, residues, opt, device):
+        half = len(part) // 2
+        both = [_feature_chunk(feature, api, part[h], residues[h], tabs_of, opt, device, keep_device=keep_device)
+                for h in (slice(0, half), slice(half, None))]
+        return torch.cat(both) if keep_device else both[0] + both[1]
+    ragged = (ragged if ragged is not None else _ragged(part))[:feature.ragged]
+    tables = [t for t, _ in part]
+    if all(t is tables[0] for t in tables):                              # poses of one topology share one table
+        tabs = tabs_of[id(tables[0])]
+    else:
+        tabs = [np.concatenate(arrays) for arrays in zip(*[tabs_of[id(t)] for t in tables])]
+    tgt_res, tgt_cx, sizes = _targets(residues, ragged[2])
+    out, status = feature.raw(api, *ragged, *tabs, tgt_res, tgt_cx, device=device, keep_device=keep_device, **opt)
+    if status & 1:
+        _lib._check(-2, feature.c_name)
+    if keep_device:
+        return out
+    ends = np.cumsum(sizes)
+    return [out[e - n:e] for n, e in zip(sizes, ends)]
+
+
+def _residue_values(feature, tables_or_poses, residues, radii, options, device, chunk, api):
+    """``residue_bsa`` / ``residue_hse`` / ``residue_depth``: the raw rows of the residues asked for, NaN elsewhere; an
+    ``AtomTable`` gives float64 [R] + feature.row, an ``AtomTable.poses`` batch [M, R] + feature.row, a sequence a list"""
     api = api or _lib.get()
     if device is None:
         device = "cuda" if api is _lib._API else "cpu"
     cx = _complexes(tables_or_poses)
-    opt = _depth_options(probe, n_dots, link, components)
-    radii_of = _depth_radii_lookup([t for t, _ in cx], radii)
+    opt = feature.check(**options)
+    tabs_of = _per_table(feature, [t for t, _ in cx], radii)
     if residues is None:
         wanted = [np.arange(t.n_residues) for t, _ in cx]
     else:
@@ -1460,17 +1359,17 @@ def residue_depth(tables_or_poses, residues=None, radii="united", probe=1.5, n_d
             if w.size and (w.min() < 0 or w.max() >= t.n_residues):
                 raise ValueError("a residue index outside [0, %d)" % t.n_residues)
     if chunk is None:
-        chunk = BSA_XYZ_BUDGET // (12 * max([t.n_atoms for t, _ in cx] + [1]))
+        chunk = RESIDUE_XYZ_BUDGET // (12 * max([t.n_atoms for t, _ in cx] + [1]))
     chunk = max(1, int(chunk))
-    full = [np.full(t.n_residues, np.nan) for t, _ in cx]
+    full = [np.full((t.n_residues,) + feature.row, np.nan) for t, _ in cx]
     for lo in range(0, len(cx), chunk):
         part = cx[lo:lo + chunk]
-        for k, o in enumerate(_depth_chunk(api, part, wanted[lo:lo + chunk], radii_of, opt, device)):
+        for k, o in enumerate(_feature_chunk(feature, api, part, wanted[lo:lo + chunk], tabs_of, opt, device)):
             full[lo + k][wanted[lo + k]] = o
     if isinstance(tables_or_poses, AtomTable):
         return full[0]
     if isinstance(tables_or_poses, Poses):
-        return np.stack(full) if full else np.zeros((0, tables_or_poses.table.n_residues))
+        return np.stack(full) if full else np.zeros((0, tables_or_poses.table.n_residues) + feature.row)
     return full
 
 

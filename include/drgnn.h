@@ -988,18 +988,18 @@ int drgnn_pose_common(const drgnn_pose_common_request* req, void* stream);
 int drgnn_pose_cluster(const drgnn_pose_cluster_request* req, void* stream);
 
 /* ---- the builder's output packed into a resident set's arrays (drgnn_pack.h) --------------------------
- * After drgnn_iface_fill on the same batch (and the optional drgnn_bsa_residues / drgnn_hse_residues over exactly its
- * nodes, in node order): the arrays a drgnn_graph_set holds, written on the device in one launch, one workgroup per
- * complex.  What GraphDataSet.load_one_graph and ResidentGraphSet assemble per graph on the host.
+ * After drgnn_iface_fill on the same batch (and the optional drgnn_bsa_residues / drgnn_hse_residues /
+ * drgnn_depth_residues over exactly its nodes, in node order): the arrays a drgnn_graph_set holds, written on the
+ * device in one launch, one workgroup per complex.  What GraphDataSet.load_one_graph and ResidentGraphSet assemble per graph on the host.
  * Inputs as they lie on the device: node_ptr / edge_ptr / iedge_ptr i32 [M+1]; node_residue, chain, type i32 [N]; pos
  * f32 [N,3]; edge_index i64 [E,2] and internal_edge_index i64 [Ei,2] with ids local to their complex; dist f32 [E];
- * optional bsa f64 [N,3] and hse f64 [N,3] (a row whose first entry is NaN reads 0, 0, 0); optional res_feat f32
- * [n_rows, res_width]: a node reads row node_residue % n_rows (n_rows divides n_residues: poses of one topology share
+ * optional bsa f64 [N,3], hse f64 [N,3] (a row whose first entry is NaN reads 0, 0, 0) and depth f64 [N]; optional
+ * res_feat f32 [n_rows, res_width]: a node reads row node_residue % n_rows (n_rows divides n_residues: poses of one topology share
  * one table); type_table f32 [20, type_width]: row = the node's type, holding every column that depends on the residue
  * type alone (the kernel carries no copy of such constants).
  * cols i32 [n_cols, 2] = (source, column of the source) of every column of x, sources 0 type_table, 1 pos, 2 chain,
- * 3 bsa, 4 hse, 5 res_feat; also given as the HOST array host_cols: every check comes from it.  f64 sources are rounded
- * once to f32 (round to nearest even: what torch.tensor(..., dtype=torch.float) does).
+ * 3 bsa, 4 hse, 5 res_feat, 6 depth (column 0 only); also given as the HOST array host_cols: every check comes from
+ * it.  f64 sources are rounded once to f32 (round to nearest even: what torch.tensor(..., dtype=torch.float) does).
  * Outputs (a null pointer skips one): x f32 [N, n_cols]; edge_index_out i64 [2, 2E], graph k's columns 2 edge_ptr[k]
  * .. 2 edge_ptr[k+1] holding its pairs and then the same pairs reversed, local ids; edge_attr f32 [2E] in that order,
  * edge_mode 0 the distance, 1 tanh(-d/2 + 2) + 1 evaluated in fp64 on the f32 distance and rounded once;
@@ -1030,6 +1030,7 @@ typedef struct drgnn_pack_request {
     float* edge_attr;
     int64_t* internal_edge_index_out;
     int64_t* batch;
+    const double* depth;               /* the last field: every field before it lies where it lay before depth was a source */
 } drgnn_pack_request;
 
 /* the documented capacities: what = 0 columns of x (256), 1 columns of type_table (64), both staged in LDS once per
@@ -1037,7 +1038,7 @@ typedef struct drgnn_pack_request {
 int32_t drgnn_pack_capacity(int32_t what);
 
 /* DRGNN_E_ARG, before any launch: a null offset table, with x a null cols / host_cols or n_cols < 1, a descriptor row
- * with a source outside 0..5, a column outside its source, a source whose array is null, n_rows that does not divide
+ * with a source outside 0..6, a column outside its source, a source whose array is null, n_rows that does not divide
  * n_residues, an output whose input is null, a negative count, edge_mode outside 0..1.  DRGNN_E_CAPACITY: n_complexes,
  * n_cols or type_width beyond drgnn_pack_capacity, n_nodes * n_cols beyond 2^31 - 1 (split the call).  No allocation,
  * no workspace, no synchronisation. */

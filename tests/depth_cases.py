@@ -503,3 +503,10 @@ def check_resident_set(api, device, poses=(0, 1), **opt):
         P.assert_sets_equal(got, want, "1ATN with depth, chunk %s" % chunk, attr="default")
     x = got.x.cpu().numpy()
     assert np.array_equal(x[:got.node_ptr[1], 20], store.get(mols[0], "node_data/depth").astype(np.float32))
+    twice = interface_resident_set(batch, mols, node_feature=["depth", "type", "depth"], depth=depth, api=api, device=device)
+    x = twice.x.cpu().numpy()
+    assert twice.mols == mols and twice.n_feat == 22
+    for g, mol in enumerate(mols):                                     # listed twice: two equal columns, the store's values
+        rows = x[twice.node_ptr[g]:twice.node_ptr[g + 1]]
+        for col in (0, 21):
+            assert same_bits(rows[:, col].copy(), store.get(mol, "node_data/depth").astype(np.float32)), (mol, col)

@@ -155,6 +155,65 @@ def check_raw_outputs(api, device):
     assert all(v.numel() == 0 for v in out1.values())
 
 
+def f64_rows(n):
+    """(depth [n], bsa [n,3], hse [n,3]) float64, one row per node: values exactly halfway between two floats (round to
+    nearest even takes 1 + 2^-24 down to 1 and 1 + 3 * 2^-24 up to 1 + 2^-22), a negative value, a float32 denormal, a
+    float64 denormal (0 as a float) and ordinary values; one hse row whose first entry is NaN"""
+    special = np.array([1 + 2.0 ** -24, 1 + 3 * 2.0 ** -24, -2.5 - 2.0 ** -30, 1e-40, 1e-310, 7.25, -(1 + 2.0 ** -24), 1 / 3])
+    depth = special[np.arange(n) % 8]
+    bsa = special[(np.arange(3 * n).reshape(n, 3) * 5 + 1) % 8]
+    hse = special[(np.arange(3 * n).reshape(n, 3) * 3 + 2) % 8]
+    hse[n // 2, 0] = np.nan
+    return depth, bsa, hse
+
+
+def check_f64_sources(api, device):
+    """depth, bsa and hse columns among chain columns, in scrambled order: every float64 is rounded once, to nearest even"""
+    from deeprank_gnn_amd import _lib
+    from deeprank_gnn_amd import interface as I
+    P = _lib
+    tables, names = hand_batch()                                       # (two of the complexes have no node)
+    xyz, atom_ptr, res_ptr, split, res_type = I._ragged([(t, t.xyz) for t in tables])
+    built, ptrs = I.build_ragged_device(api, xyz, atom_ptr, res_ptr, split, res_type, device=device)
+    n = int(built["pos"].shape[0])
+    assert n > 8 and int(np.diff(ptrs[0].cpu().numpy()).max()) >= 3
+    depth, bsa, hse = f64_rows(n)
+    rows = {k: torch.from_numpy(v).to(ptrs.device) for k, v in (("depth", depth), ("bsa", bsa), ("hse", hse))}
+    zeroed = np.where(np.isnan(hse[:, :1]), 0.0, hse)
+    source = {P.PACK_DEPTH: depth[:, None], P.PACK_BSA: bsa, P.PACK_HSE: zeroed,
+              P.PACK_CHAIN: built["chain"].cpu().numpy().astype(np.float64)[:, None]}
+    seven = [(P.PACK_HSE, 2), (P.PACK_DEPTH, 0), (P.PACK_CHAIN, 0), (P.PACK_BSA, 2), (P.PACK_HSE, 0), (P.PACK_BSA, 0), (P.PACK_HSE, 1)]
+    # 91 columns: 256 = 2 * 91 + 74, so a lane's column wraps as it steps, and a complex of three nodes takes two steps
+    for cols in (seven * 13, [(P.PACK_DEPTH, 0), (P.PACK_CHAIN, 0), (P.PACK_DEPTH, 0)]):
+        assert 256 % len(cols) != 0
+        x = I.iface_pack_raw(api, built, ptrs, cols, len(atom_ptr) - 1, want=("x",), **rows)["x"]
+        want = np.stack([source[s][:, c].astype(np.float32) for s, c in cols], axis=1)
+        assert same(x, want), (len(cols), x, want)
+    x = x.cpu().numpy()                                                # depth listed twice: two equal columns
+    assert same(x[:, 0].copy(), x[:, 2].copy()) and same(x[:, 0].copy(), depth.astype(np.float32))
+    assert np.float32(1 + 2.0 ** -24) == 1 and np.float32(1 + 3 * 2.0 ** -24) == np.float32(1 + 2.0 ** -22)
+    assert 0 < abs(np.float32(1e-40)) < np.finfo(np.float32).tiny and np.float32(1e-310) == 0
+
+
+def check_depth_argument(api, device):
+    """a wrongly shaped ``depth=`` is refused by pack_request before any call"""
+    import pytest
+    from deeprank_gnn_amd import _lib
+    from deeprank_gnn_amd import interface as I
+    cases = dict(IC.hand_cases())
+    t = IC.table_of(cases["chain_of_one"])
+    xyz, atom_ptr, res_ptr, split, res_type = I._ragged([(t, t.xyz)])
+    built, ptrs = I.build_ragged_device(api, xyz, atom_ptr, res_ptr, split, res_type, device=device)
+    n, dev = int(built["pos"].shape[0]), ptrs.device
+    assert n == 3
+    good = torch.zeros(n, dtype=torch.float64, device=dev)
+    I.pack_request(built, ptrs, [(_lib.PACK_DEPTH, 0)], len(atom_ptr) - 1, depth=good)
+    for bad in (torch.zeros(n + 1, dtype=torch.float64, device=dev), torch.zeros((n, 1), dtype=torch.float64, device=dev),
+                good.to(torch.float32), torch.zeros(2 * n, dtype=torch.float64, device=dev)[::2]):
+        with pytest.raises(ValueError, match="depth must be float64"):
+            I.pack_request(built, ptrs, [(_lib.PACK_DEPTH, 0)], len(atom_ptr) - 1, depth=bad)
+
+
 # ---- 2 1ATN ---------------------------------------------------------------------------------------------------------------
 def atn_tables():
     rng = np.random.default_rng(627)
@@ -358,8 +417,14 @@ def refusal_cases():
             for k, v in kw.items():
                 setattr(q, k, v)
         return edit
+    def depth_column_1(q, keep):                                       # the array is there: only the column is wrong
+        keep.append(torch.zeros(int(q.n_nodes), dtype=torch.float64, device=keep[1].device))
+        q.depth = keep[-1].data_ptr()
+        cols_with((_lib.PACK_DEPTH, 1))(q, keep)
     P = _lib
     return {
+        "depth_is_null": (cols_with((P.PACK_DEPTH, 0)), "bad argument"),
+        "column_outside_depth": (depth_column_1, "bad argument"),
         "null_node_ptr": (setter(node_ptr=None), "bad argument"),
         "null_edge_ptr": (setter(edge_ptr=None), "bad argument"),
         "null_iedge_ptr": (setter(iedge_ptr=None), "bad argument"),
@@ -368,7 +433,7 @@ def refusal_cases():
         "null_edge_index": (setter(edge_index=None), "bad argument"),
         "null_dist": (setter(dist=None), "bad argument"),
         "null_internal_edge_index": (setter(internal_edge_index=None), "bad argument"),
-        "unknown_source": (cols_with((6, 0)), "bad argument"),
+        "unknown_source": (cols_with((7, 0)), "bad argument"),
         "negative_source": (cols_with((-1, 0)), "bad argument"),
         "column_outside_pos": (cols_with((P.PACK_POS, 3)), "bad argument"),
         "column_outside_type_table": (cols_with((P.PACK_TYPE, 25)), "bad argument"),

@@ -22,6 +22,14 @@ def test_raw_pack_outputs(api):
     C.check_raw_outputs(api, "cuda")
 
 
+def test_float64_sources_are_rounded_once_and_depth_may_be_listed_twice(api):
+    C.check_f64_sources(api, "cuda")
+
+
+def test_wrongly_shaped_depth_rows_are_refused(api):
+    C.check_depth_argument(api, "cuda")
+
+
 @pytest.mark.parametrize("method", ["mcl", "louvain"])
 def test_1ATN_four_poses_every_source(api, method):
     C.check_atn(api, "cuda", (0, 1, 2, 3), C.ALL_FEATURES, method)

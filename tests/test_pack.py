@@ -20,6 +20,14 @@ def test_raw_pack_outputs(api):
     C.check_raw_outputs(api, "cpu")
 
 
+def test_float64_sources_are_rounded_once_and_depth_may_be_listed_twice(api):
+    C.check_f64_sources(api, "cpu")
+
+
+def test_wrongly_shaped_depth_rows_are_refused(api):
+    C.check_depth_argument(api, "cpu")
+
+
 @pytest.mark.parametrize("method", ["mcl", "louvain"])
 def test_1ATN_every_source_one_pose_with_bsa(api, method):
     C.check_atn(api, "cpu", (0,), C.ALL_FEATURES, method)
