@@ -203,6 +203,21 @@ class PoseClusterRequest(ctypes.Structure):
                 ("n_clusters", _vp)]
 
 
+class PoseRmsdRequest(ctypes.Structure):
+    """drgnn_pose_rmsd_request (include/drgnn.h): two pose batches of one topology and the fit / rms atom lists;
+    ``host_*`` are addresses of host copies of the lists."""
+    _fields_ = [("xyz_a", _vp), ("xyz_b", _vp), ("fit_idx", _vp), ("rms_idx", _vp), ("host_fit_idx", _vp), ("host_rms_idx", _vp),
+                ("n_a", _c_i64), ("n_b", _c_i64), ("n_atoms", _c_i64), ("n_fit", _c_i64), ("n_rms", _c_i64),
+                ("phases", _c_i32), ("reserved", _c_i32), ("workspace", _vp), ("workspace_bytes", _c_i64), ("d", _vp)]
+
+
+class PoseClusterDistRequest(ctypes.Structure):
+    """drgnn_pose_cluster_dist_request (include/drgnn.h): a distance matrix of M poses and the outputs of drgnn_pose_cluster."""
+    _fields_ = [("d", _vp), ("n_poses", _c_i64), ("cutoff", ctypes.c_double), ("min_size", _c_i32), ("reserved", _c_i32),
+                ("neighbours", _vp), ("transposed", _vp), ("labels", _vp), ("centres", _vp), ("sizes", _vp),
+                ("n_clusters", _vp)]
+
+
 class DepthRequest(ctypes.Structure):
     """drgnn_depth_request (include/drgnn.h): K target residues of a ragged batch of complexes for drgnn_depth_residues;
     ``host_*`` are addresses of host copies of the offset and target tables."""
@@ -444,6 +459,12 @@ class Api(object):
         lib.drgnn_pose_contacts.argtypes = [ctypes.POINTER(PoseContactsRequest), _vp]
         lib.drgnn_pose_common.argtypes = [ctypes.POINTER(PoseCommonRequest), _vp]
         lib.drgnn_pose_cluster.argtypes = [ctypes.POINTER(PoseClusterRequest), _vp]
+        lib.drgnn_rmsd_capacity.argtypes = [_c_i32]
+        lib.drgnn_rmsd_capacity.restype = _c_i32
+        lib.drgnn_rmsd_workspace.argtypes = [_c_i64] * 4 + [ctypes.POINTER(_c_i64)]
+        lib.drgnn_rmsd_workspace.restype = _c_i64
+        lib.drgnn_pose_rmsd.argtypes = [ctypes.POINTER(PoseRmsdRequest), _vp]
+        lib.drgnn_pose_cluster_dist.argtypes = [ctypes.POINTER(PoseClusterDistRequest), _vp]
         if lib.drgnn_abi_version() != 5:
             raise DrgnnError("ABI mismatch in %s" % path)
 
@@ -744,6 +765,23 @@ class Api(object):
 
     def pose_cluster(self, request, stream):
         _check(self.lib.drgnn_pose_cluster(ctypes.byref(request), stream), "drgnn_pose_cluster")
+
+    def rmsd_capacity(self, what):
+        return int(self.lib.drgnn_rmsd_capacity(int(what)))
+
+    def rmsd_workspace(self, n_a, n_b, n_fit, n_rms):
+        """(bytes, offsets [3]) of drgnn_rmsd_workspace; DrgnnError for counts the call refuses"""
+        off = (_c_i64 * 3)()
+        n = int(self.lib.drgnn_rmsd_workspace(int(n_a), int(n_b), int(n_fit), int(n_rms), off))
+        if n < 0:
+            _check(-2, "drgnn_rmsd_workspace")
+        return n, list(off)
+
+    def pose_rmsd(self, request, stream):
+        _check(self.lib.drgnn_pose_rmsd(ctypes.byref(request), stream), "drgnn_pose_rmsd")
+
+    def pose_cluster_dist(self, request, stream):
+        _check(self.lib.drgnn_pose_cluster_dist(ctypes.byref(request), stream), "drgnn_pose_cluster_dist")
 
     def depth_capacity(self, what):
         return int(self.lib.drgnn_depth_capacity(int(what)))

@@ -2598,6 +2598,113 @@ int drgnn_pose_cluster(const drgnn_pose_cluster_request* q, void* stream) {
     return 0;
 }
 
+// ---- pairwise pose RMSD and RMSD clustering of poses (drgnn_rmsd.h) ----------------------------------
+int32_t drgnn_rmsd_capacity(int32_t what) { return what == 0 ? RM_PCAP : what == 1 ? FC_CCAP : -1; }
+
+// records of side a, of side b; off[2] is the size
+static int rmsd_layout(int64_t Ma, int64_t Mb, int64_t nF, int64_t nR, int64_t* off) {
+    if (Ma < 0 || Mb < 0 || nF < 0 || nR < 0 || Ma > RM_PCAP || Mb > RM_PCAP || nF > INT32_MAX / 8 || nR > INT32_MAX / 8) return -1;
+    const int64_t L = 3 * (nF + nR) + 2;
+    off[0] = 0; off[1] = 8 * L * Ma; off[2] = 8 * L * (Ma + Mb);
+    return 0;
+}
+
+int64_t drgnn_rmsd_workspace(int64_t n_a, int64_t n_b, int64_t n_fit, int64_t n_rms, int64_t* offsets) {
+    int64_t off[3];
+    if (rmsd_layout(n_a, n_b, n_fit, n_rms, off) != 0) return -1;
+    if (offsets) memcpy(offsets, off, sizeof(off));
+    return off[2];
+}
+
+int drgnn_pose_rmsd(const drgnn_pose_rmsd_request* q, void* stream) {
+    if (!q) return DRGNN_E_ARG;
+    const int64_t Ma = q->n_a, Mb = q->n_b, T = q->n_atoms, nF = q->n_fit, nR = q->n_rms;
+    if (Ma < 0 || Mb < 0 || T < 0 || nF < 0 || nR < 1 || T > INT32_MAX / 3 || nF > INT32_MAX / 8 || nR > INT32_MAX / 8) return DRGNN_E_ARG;
+    if (nF == 1 || nF == 2 || q->phases < 0 || q->phases > 3) return DRGNN_E_ARG;
+    if (!q->rms_idx || !q->host_rms_idx || (nF > 0) != (q->fit_idx != nullptr) || (nF > 0) != (q->host_fit_idx != nullptr)) return DRGNN_E_ARG;
+    for (int64_t k = 0; k < nR; ++k)
+        if (q->host_rms_idx[k] < 0 || q->host_rms_idx[k] >= T) return DRGNN_E_ARG;
+    for (int64_t k = 0; k < nF; ++k)
+        if (q->host_fit_idx[k] < 0 || q->host_fit_idx[k] >= T) return DRGNN_E_ARG;
+    if ((Ma > 0 && !q->xyz_a) || (Mb > 0 && !q->xyz_b) || (Ma > 0 && Mb > 0 && !q->d)) return DRGNN_E_ARG;
+    if (Ma > RM_PCAP || Mb > RM_PCAP) return DRGNN_E_CAPACITY;
+    if (Ma == 0 || Mb == 0) return 0;
+    int64_t off[3];
+    if (rmsd_layout(Ma, Mb, nF, nR, off) != 0) return DRGNN_E_ARG;
+    if (!q->workspace || ((uintptr_t)q->workspace & 7)) return DRGNN_E_ARG;
+    if (q->workspace_bytes < off[2]) return DRGNN_E_CAPACITY;
+    const int ph = q->phases == 0 ? 3 : q->phases;
+    RmsdArgs a;
+    memset(&a, 0, sizeof(a));
+    a.xyz_a = q->xyz_a; a.xyz_b = q->xyz_b; a.fit_idx = q->fit_idx; a.rms_idx = q->rms_idx;
+    a.n_atoms = (int)T; a.n_fit = (int)nF; a.n_rms = (int)nR; a.n_a = (int)Ma; a.n_b = (int)Mb;
+    a.same = q->xyz_a == q->xyz_b && Ma == Mb;
+    a.rec_a = (double*)((char*)q->workspace + off[0]);
+    a.rec_b = a.same ? a.rec_a : (double*)((char*)q->workspace + off[1]);
+    a.d = q->d;
+    const int ti = (int)((Ma + RM_TILE - 1) / RM_TILE), tj = (int)((Mb + RM_TILE - 1) / RM_TILE);
+#ifdef DRGNN_EMU
+    (void)stream;
+    if (ph & 1) {
+        std::unique_ptr<RmsdPrepShared> lds(new RmsdPrepShared);
+        for (int64_t m = 0; m < Ma; ++m) rm_prepare(a, 0, m, *lds);
+        for (int64_t m = 0; m < Mb && !a.same; ++m) rm_prepare(a, 1, m, *lds);
+    }
+    if (ph & 2) {
+        std::unique_ptr<RmsdPairShared> lds(new RmsdPairShared);
+        for (int i = 0; i < ti; ++i)
+            for (int j = 0; j < tj; ++j) rm_pairs(a, i, j, *lds);
+    }
+#else
+    static_assert(RM_TILE * RM_TILE == DRGNN_NTHREADS, "one lane per pose pair of a tile");
+    static_assert(RM_K % 2 == 0 && sizeof(RmsdPairShared) <= 64 * 1024, "odd rows; the staged atoms fit the static LDS of a workgroup");
+    static_assert((RM_PCAP + RM_TILE - 1) / RM_TILE <= 65535, "the tiles of a side fit the grid's y");
+    if (ph & 1) {
+        hipLaunchKernelGGL(k_rmsd_prepare, dim3((unsigned)Ma), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a, 0);
+        HIP_TRY(hipGetLastError());
+        if (!a.same) {
+            hipLaunchKernelGGL(k_rmsd_prepare, dim3((unsigned)Mb), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a, 1);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    if (ph & 2) {
+        hipLaunchKernelGGL(k_rmsd_pairs, dim3((unsigned)tj, (unsigned)ti), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+#endif
+    return 0;
+}
+
+int drgnn_pose_cluster_dist(const drgnn_pose_cluster_dist_request* q, void* stream) {
+    if (!q) return DRGNN_E_ARG;
+    const int64_t M = q->n_poses;
+    if (M < 0 || q->min_size < 1) return DRGNN_E_ARG;
+    if (!(q->cutoff > 0.0) || !(q->cutoff < HUGE_VAL)) return DRGNN_E_ARG;
+    if (!q->n_clusters) return DRGNN_E_ARG;
+    if (M > 0 && (!q->d || !q->neighbours || !q->transposed || !q->labels || !q->centres || !q->sizes)) return DRGNN_E_ARG;
+    if (M > FC_CCAP) return DRGNN_E_CAPACITY;
+    if (M == 0) return 0;
+    RmsdRelationArgs a;
+    memset(&a, 0, sizeof(a));
+    a.d = q->d; a.cutoff = q->cutoff;
+    a.c.n = (int)M; a.c.min_size = q->min_size;
+    a.c.nb = (fc_word*)q->neighbours; a.c.nbt = (fc_word*)q->transposed;
+    a.c.labels = q->labels; a.c.centres = q->centres; a.c.sizes = q->sizes; a.c.n_clusters = q->n_clusters;
+    const int64_t words = M * ((M + 63) / 64), blocks = (words + DRGNN_NWAVES - 1) / DRGNN_NWAVES;
+#ifdef DRGNN_EMU
+    (void)stream;
+    for (int64_t b = 0; b < blocks; ++b) rm_relation(a, b);
+    std::unique_ptr<FccGreedyShared> lds(new FccGreedyShared);
+    fc_greedy(a.c, *lds);
+#else
+    hipLaunchKernelGGL(k_rmsd_relation, dim3((unsigned)blocks), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_fcc_greedy, dim3(1), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a.c);
+    HIP_TRY(hipGetLastError());
+#endif
+    return 0;
+}
+
 // ---- evaluation scores (drgnn_metrics.h) ---------------------------------------------------------
 int64_t drgnn_metrics_workspace_bytes(int64_t n) {
     if (n < 0 || n > INT32_MAX) return -1;

@@ -17,6 +17,7 @@
 #include "drgnn_hse.h"
 #include "drgnn_depth.h"
 #include "drgnn_fcc.h"
+#include "drgnn_rmsd.h"
 #include "drgnn_pack.h"
 #include "drgnn_metrics.h"
 #include "drgnn_collate.h"
@@ -1033,6 +1034,17 @@ __global__ void __launch_bounds__(DRGNN_NTHREADS) k_fcc_greedy(FccClusterArgs a)
     __shared__ FccGreedyShared smem_fg;
     fc_greedy(a, smem_fg);
 }
+// pairwise pose RMSD (drgnn_rmsd.h): one workgroup per pose of one side; per tile of pose pairs; a wave per word of the
+// neighbour relation (the greedy clustering is k_fcc_greedy)
+__global__ void __launch_bounds__(DRGNN_NTHREADS) k_rmsd_prepare(RmsdArgs a, int side) {
+    __shared__ RmsdPrepShared smem_rp;
+    rm_prepare(a, side, (int64_t)blockIdx.x, smem_rp);
+}
+__global__ void __launch_bounds__(DRGNN_NTHREADS) k_rmsd_pairs(RmsdArgs a) {
+    __shared__ RmsdPairShared smem_rq;
+    rm_pairs(a, (int)blockIdx.y, (int)blockIdx.x, smem_rq);
+}
+__global__ void __launch_bounds__(DRGNN_NTHREADS) k_rmsd_relation(RmsdRelationArgs a) { rm_relation(a, (int64_t)blockIdx.x); }
 // the builder's output packed into a resident set's arrays (drgnn_pack.h): one workgroup per complex
 __global__ void __launch_bounds__(PK_NT) k_iface_pack(PackArgs a) {
     __shared__ PackShared smem_pk;

@@ -47,6 +47,11 @@ HADDOCK's ``cluster_fcc``; csrc/drgnn_fcc.h) and the clusters ranked by their be
     clusters = cluster_poses(poses)                            # labels [M] (-1: in no cluster), centres, sizes
     order, means = clusters.rank(scores, top=4)                # scores [M]: Ensemble.predict or docking_scores()[key]
 
+or by their pairwise RMSD (the rule of HADDOCK's ``cluster_struc`` and of ClusPro; csrc/drgnn_rmsd.h):
+
+    D = pose_rmsd(poses, kind="ligand")                        # float64 [M, M] on the device: pairwise l-RMSD
+    clusters = cluster_poses_rmsd(D, cutoff=7.5, min_size=4)   # the same PoseClusters
+
 and the residue depth (``depth``: Biopython's residue depth; the surface is a dot surface of the solvent-accessible
 surface restricted to its outer component instead of MSMS' triangulation, about one vertex spacing away from it):
 
@@ -1540,7 +1545,7 @@ def fcc_matrix(a, b=None):
 
 class PoseClusters(object):
     """``cluster_poses``: ``labels`` int64 [M] (the cluster of every pose in order of discovery, -1: in none),
-    ``centres`` / ``sizes`` int64 [K] per cluster, ``n_contacts`` int64 [M]."""
+    ``centres`` / ``sizes`` int64 [K] per cluster, ``n_contacts`` int64 [M] (None from ``cluster_poses_rmsd``)."""
 
     def __init__(self, labels, centres, sizes, n_contacts):
         self.labels, self.centres, self.sizes, self.n_contacts = labels, centres, sizes, n_contacts
@@ -1627,3 +1632,234 @@ def cluster_poses(poses_or_contacts, cutoff_fcc=0.6, strictness=0.75, min_size=4
     r = pose_cluster_raw(c.api, _common_device(c), count, float(cutoff_fcc), float(cutoff_fcc) * float(strictness),
                          int(min_size), c.device)
     return PoseClusters(r["labels"].astype(np.int64), r["centres"].astype(np.int64), r["sizes"].astype(np.int64), c.n_contacts)
+
+
+# ---- pairwise pose RMSD and RMSD clustering of poses (csrc/drgnn_rmsd.h) --------------------------------------------
+RMSD_KINDS = ("ligand", "interface", "fixed", "all")
+RMSD_WORKSPACE_BUDGET = 1 << 30    # bytes of fp64 pose records one drgnn_pose_rmsd call may ask for (sets the default chunk)
+
+
+def select_atoms(table, names=BACKBONE, chain=None, residues=None):
+    """int32 [n]: the atoms of ``table``, in its grouped atom order, whose name is one of ``names`` (None: every name;
+    names need a table built with ``atom_name=``), that belong to ``chain`` (0 or 1, None: both) and to one of
+    ``residues`` (indices into the table's residues, None: all)."""
+    keep = np.ones(table.n_atoms, dtype=bool)
+    if names is not None:
+        if table.atom_name is None:
+            raise ValueError("atoms are selected by name: build the AtomTable with atom_name=")
+        keep &= np.isin(table.atom_name, list(names))
+    res_of_atom = np.repeat(np.arange(table.n_residues), np.diff(table.atom_ptr))
+    if chain is not None:
+        if chain not in (0, 1):
+            raise ValueError("chain must be 0, 1 or None")
+        keep &= table.res_chain[res_of_atom] == chain
+    if residues is not None:
+        r = np.asarray(residues, dtype=np.int64).reshape(-1)
+        if r.size and (r.min() < 0 or r.max() >= table.n_residues):
+            raise ValueError("residues must be indices into the table's %d residues" % table.n_residues)
+        on = np.zeros(table.n_residues, dtype=bool)
+        on[r] = True
+        keep &= on[res_of_atom]
+    return np.flatnonzero(keep).astype(np.int32)
+
+
+def _atom_list(what, idx, n_atoms, least):
+    a = np.asarray(idx)
+    if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+        raise ValueError("%s must be a list of atom indices" % what)
+    if a.size < least:
+        raise ValueError("%s needs at least %d atom%s" % (what, least, "" if least == 1 else "s"))
+    if a.min() < 0 or a.max() >= n_atoms:
+        raise ValueError("%s must be indices into the table's %d atoms" % (what, n_atoms))
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def rmsd_selection(table, rms=None, fit=None, kind=None, residues=None):
+    """(rms int32 [nR], fit int32 [nF] or None) of ``pose_rmsd``: the two lists as given, or what ``kind`` stands for"""
+    if kind is None:
+        if rms is None:
+            raise ValueError("pose_rmsd needs rms= (atom indices) or kind= (one of %s)" % ", ".join(RMSD_KINDS))
+        if residues is not None:
+            raise ValueError("residues= goes with kind=\"interface\"")
+        return _atom_list("rms", rms, table.n_atoms, 1), None if fit is None else _atom_list("fit", fit, table.n_atoms, 3)
+    if kind not in RMSD_KINDS:
+        raise ValueError("kind must be one of %s" % ", ".join(RMSD_KINDS))
+    if rms is not None or fit is not None:
+        raise ValueError("kind= stands for rms= and fit=: give one or the other")
+    if (kind == "interface") != (residues is not None):
+        raise ValueError("residues= goes with kind=\"interface\", and that kind needs it")
+    long_chain = 0 if table.split >= table.n_residues - table.split else 1
+    if kind == "ligand":
+        rms, fit = select_atoms(table, chain=1 - long_chain), select_atoms(table, chain=long_chain)
+    elif kind == "fixed":
+        rms, fit = select_atoms(table, chain=1 - long_chain), None
+    else:
+        rms = fit = select_atoms(table, residues=residues)
+    return _atom_list("the rms atoms of kind %r" % kind, rms, table.n_atoms, 1), \
+        None if fit is None else _atom_list("the fit atoms of kind %r" % kind, fit, table.n_atoms, 3)
+
+
+def pose_rmsd_raw(api, xyz_a, xyz_b, rms_idx, fit_idx=None, phases=0, workspace=None, out=None):
+    """One drgnn_pose_rmsd call (include/drgnn.h): ``xyz_a`` / ``xyz_b`` float32 tensors [Ma, T, 3] / [Mb, T, 3] on one
+    device (the same tensor: the square matrix of one batch), the lists as numpy int32.  Returns float64 [Ma, Mb] on
+    that device.  ``workspace`` / ``out``: tensors kept between calls that run the launches one by one (``phases``)."""
+    rms_host = np.ascontiguousarray(rms_idx, dtype=np.int32)
+    fit_host = None if fit_idx is None else np.ascontiguousarray(fit_idx, dtype=np.int32)
+    xyz_a, xyz_b = xyz_a.contiguous(), xyz_b.contiguous()
+    if xyz_a.dtype != torch.float32 or xyz_b.dtype != torch.float32 or xyz_a.dim() != 3 or xyz_b.dim() != 3 or \
+            xyz_a.shape[1:] != xyz_b.shape[1:] or xyz_a.shape[2] != 3:
+        raise ValueError("xyz float32 [Ma, T, 3] and [Mb, T, 3]")
+    if api is _lib._API:
+        _lib.require_device(xyz_a)
+    dev = xyz_a.device
+    Ma, Mb, nF = int(xyz_a.shape[0]), int(xyz_b.shape[0]), 0 if fit_host is None else len(fit_host)
+    d_rms = torch.from_numpy(rms_host).to(dev)
+    d_fit = None if fit_host is None else torch.from_numpy(fit_host).to(dev)
+    nbytes = api.rmsd_workspace(Ma, Mb, nF, len(rms_host))[0]
+    if workspace is None:
+        workspace = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
+    d = torch.empty((Ma, Mb), dtype=torch.float64, device=dev) if out is None else out
+    q = _lib.PoseRmsdRequest()
+    q.xyz_a, q.xyz_b = xyz_a.data_ptr() if Ma else None, xyz_b.data_ptr() if Mb else None
+    q.rms_idx, q.host_rms_idx = d_rms.data_ptr() if len(rms_host) else None, rms_host.ctypes.data if len(rms_host) else None
+    if nF:
+        q.fit_idx, q.host_fit_idx = d_fit.data_ptr(), fit_host.ctypes.data
+    q.n_a, q.n_b, q.n_atoms, q.n_fit, q.n_rms, q.phases = Ma, Mb, int(xyz_a.shape[1]), nF, len(rms_host), int(phases)
+    q.workspace, q.workspace_bytes, q.d = workspace.data_ptr(), workspace.numel() * 8, d.data_ptr() if Ma and Mb else None
+    api.pose_rmsd(q, _lib.current_stream(xyz_a))
+    return d
+
+
+def pose_rmsd(poses, rms=None, fit=None, kind=None, other=None, residues=None, device=None, api=None, chunk=None, table=None):
+    """The pose-by-pose RMSD matrix of M poses of one topology (an ``AtomTable.poses`` batch, a table, or xyz float32
+    [M,T,3] in the grouped atom order of ``table``), on the device: a float64 tensor [M, M], or [M, M'] against the poses
+    ``other`` of the same table.  ``rms``: the atoms the RMSD is taken over (indices in the table's grouped order, as
+    ``select_atoms`` returns them); ``fit``: the atoms (at least 3, not collinear) that pose i is superposed on pose j
+    by, with the optimal proper rotation and translation, before the RMSD is taken; None: no superposition.  ``kind``
+    stands for both: ``"ligand"`` fit on the backbone of the chain with more residues (the first on a tie), RMSD of the
+    other chain's backbone (pairwise l-RMSD); ``"interface"`` fit = rms = the backbone of ``residues`` (``interface_residues``;
+    pairwise i-RMSD); ``"fixed"`` no superposition, the shorter chain's backbone (rigid-body runs with a fixed receptor);
+    ``"all"`` fit = rms = every backbone atom.  tests/rmsd_ref.py states the rule.  The matrix is exactly symmetric with
+    a zero diagonal; an entry does not depend on M, on ``chunk`` (poses per side of one launch, at most
+    drgnn_rmsd_capacity(0)), on the side or the place of its poses or on the run."""
+    t, xyz = _pose_batch(poses, table)
+    xyz2 = None
+    if other is not None:
+        t2, xyz2 = _pose_batch(other, t if not isinstance(other, (Poses, AtomTable)) else None)
+        if t2 is not t:
+            raise ValueError("the other poses must be of the same AtomTable")
+    rms_idx, fit_idx = rmsd_selection(t, rms, fit, kind, residues)
+    api = api or _lib.get()
+    if device is None:
+        device = "cuda" if api is _lib._API else "cpu"
+    dev = torch.device(device)
+    # only the selected atoms are uploaded
+    cols = np.unique(np.concatenate((rms_idx, fit_idx if fit_idx is not None else rms_idx[:0])))
+    rms_idx = np.searchsorted(cols, rms_idx).astype(np.int32)
+    fit_idx = None if fit_idx is None else np.searchsorted(cols, fit_idx).astype(np.int32)
+    record = 8 * (3 * (len(rms_idx) + (0 if fit_idx is None else len(fit_idx))) + 2)
+    cap = min(api.rmsd_capacity(0), max(1, RMSD_WORKSPACE_BUDGET // (2 * record)))
+    chunk = cap if chunk is None else max(1, min(int(chunk), cap))
+    M, M2 = int(xyz.shape[0]), int(xyz.shape[0] if xyz2 is None else xyz2.shape[0])
+    if M == 0 or M2 == 0:
+        return torch.zeros((M, M2), dtype=torch.float64, device=dev)
+    up = lambda x: torch.from_numpy(np.ascontiguousarray(x[:, cols], dtype=np.float32)).to(dev)
+    A = up(xyz)
+    B = A if xyz2 is None else up(xyz2)
+    if M <= chunk and M2 <= chunk:
+        return pose_rmsd_raw(api, A, B, rms_idx, fit_idx)
+    out = torch.empty((M, M2), dtype=torch.float64, device=dev)
+    for i in range(0, M, chunk):
+        for j in range(0, M2, chunk):
+            if xyz2 is None and j < i:
+                continue
+            if xyz2 is None and j == i:
+                block = A[i:i + chunk]
+                out[i:i + chunk, i:i + chunk] = pose_rmsd_raw(api, block, block, rms_idx, fit_idx)
+                continue
+            part = pose_rmsd_raw(api, A[i:i + chunk], B[j:j + chunk], rms_idx, fit_idx)
+            out[i:i + chunk, j:j + chunk] = part
+            if xyz2 is None:
+                out[j:j + chunk, i:i + chunk] = part.t()
+    return out
+
+
+def interface_residues(contacts, min_poses=1):
+    """int64 [n], sorted: the residues (indices into the table's residues, both chains) that are in contact in at least
+    ``min_poses`` poses of a ``PoseContacts``: what ``pose_rmsd(kind="interface", residues=...)`` takes"""
+    if not isinstance(contacts, PoseContacts):
+        raise ValueError("interface residues are taken from PoseContacts (pose_contacts)")
+    if int(min_poses) != min_poses or int(min_poses) < 1:
+        raise ValueError("min_poses must be an integer >= 1")
+    w = contacts.words()                                               # uint64 [M, nA, WB]
+    if w.size == 0:
+        return np.zeros(0, np.int64)
+    in_a = (w != 0).any(axis=2).sum(axis=0)                            # poses in which a row has a bit
+    cols = np.bitwise_or.reduce(w, axis=1)                             # [M, WB]: the OR over the rows
+    in_b = np.unpackbits(np.ascontiguousarray(cols).view(np.uint8), axis=1, bitorder="little")[:, :contacts.n_b].sum(axis=0)
+    return np.concatenate((np.flatnonzero(in_a >= int(min_poses)), contacts.n_a + np.flatnonzero(in_b >= int(min_poses)))).astype(np.int64)
+
+
+def pose_cluster_dist_raw(api, d, cutoff=7.5, min_size=4, device="cpu"):
+    """One drgnn_pose_cluster_dist call (include/drgnn.h): ``d`` float64 [M, M] as a numpy array or a tensor on
+    ``device``.  Returns what ``pose_cluster_raw`` returns."""
+    dev = torch.device(device)
+    d_d = (d if torch.is_tensor(d) else torch.from_numpy(np.ascontiguousarray(d, dtype=np.float64)).to(dev)).contiguous()
+    M = int(d_d.shape[0])
+    if d_d.dtype != torch.float64 or tuple(d_d.shape) != (M, M):
+        raise ValueError("d float64 [M, M]")
+    if api is _lib._API:
+        _lib.require_device(d_d)
+    MW = (M + 63) // 64
+    nb = torch.zeros((2, M, MW), dtype=torch.int64, device=d_d.device)
+    res = torch.zeros((3, M), dtype=torch.int32, device=d_d.device)
+    k = torch.zeros(1, dtype=torch.int32, device=d_d.device)
+    q = _lib.PoseClusterDistRequest()
+    q.d, q.n_poses, q.cutoff, q.min_size = d_d.data_ptr(), M, float(cutoff), int(min_size)
+    q.neighbours, q.transposed = nb[0].data_ptr(), nb[1].data_ptr()
+    q.labels, q.centres, q.sizes, q.n_clusters = res[0].data_ptr(), res[1].data_ptr(), res[2].data_ptr(), k.data_ptr()
+    api.pose_cluster_dist(q, _lib.current_stream(d_d))
+    K = int(k.cpu()[0])
+    res, nb = res.cpu().numpy(), nb.cpu().numpy().view(np.uint64)
+    return {"labels": res[0].copy(), "centres": res[1, :K].copy(), "sizes": res[2, :K].copy(), "neighbours": nb[0].copy(),
+            "transposed": nb[1].copy()}
+
+
+def cluster_poses_rmsd(poses_or_matrix, cutoff=7.5, min_size=4, **rmsd_options):
+    """RMSD clustering of docking poses on the device (the rule of HADDOCK's ``cluster_struc`` and of ClusPro, with the
+    tie between equally connected centres broken towards the smaller index; tests/rmsd_ref.py states it in numpy).  Pose
+    j is a neighbour of i when ``D[i, j] <= cutoff`` (A).  The alive pose with the most alive neighbours (the smallest
+    index on a tie) becomes a centre as long as it has ``min_size - 1`` of them; it and they form a cluster and die.
+    ``poses_or_matrix``: a square float64 matrix (a tensor, as ``pose_rmsd`` returns it, or a numpy array; ``api`` and
+    ``device`` are then the only options), or what ``pose_rmsd`` takes together with its options (rms, fit, kind,
+    residues, table, device, api, chunk).  Returns a ``PoseClusters`` with ``n_contacts`` None.  More poses than
+    drgnn_rmsd_capacity(1) (4096) are refused (DrgnnError, capacity)."""
+    if not (float(cutoff) > 0.0 and float(cutoff) < float("inf")):
+        raise ValueError("cutoff must be a positive finite number")
+    if int(min_size) != min_size or int(min_size) < 1:
+        raise ValueError("min_size must be an integer >= 1")
+    if "other" in rmsd_options:
+        raise ValueError("clustering takes the square matrix of one batch: no other=")
+    p = poses_or_matrix
+    is_matrix = (torch.is_tensor(p) or isinstance(p, np.ndarray)) and p.ndim == 2
+    api = rmsd_options.get("api") or _lib.get()
+    device = rmsd_options.get("device") or (str(p.device) if torch.is_tensor(p) and is_matrix else "cuda" if api is _lib._API else "cpu")
+    if is_matrix:
+        if set(rmsd_options) - {"api", "device"}:
+            raise ValueError("rmsd options %s come with poses, not with a matrix" % sorted(set(rmsd_options) - {"api", "device"}))
+        if p.shape[0] != p.shape[1]:
+            raise ValueError("a distance matrix is square")
+        M = int(p.shape[0])
+    else:
+        M = len(p) if isinstance(p, Poses) else 1 if isinstance(p, AtomTable) else int(np.asarray(p).shape[0])
+    if M > api.rmsd_capacity(1):
+        _lib._check(-2, "drgnn_pose_cluster_dist")
+    if M == 0:
+        if not is_matrix:
+            pose_rmsd(p, **dict(rmsd_options, api=api, device=device))             # (the options are checked; nothing is launched)
+        return PoseClusters(np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int64), None)
+    d = p if is_matrix else pose_rmsd(p, **dict(rmsd_options, api=api, device=device))
+    if torch.is_tensor(d):
+        d = d.to(torch.float64)
+    r = pose_cluster_dist_raw(api, d, float(cutoff), int(min_size), device)
+    return PoseClusters(r["labels"].astype(np.int64), r["centres"].astype(np.int64), r["sizes"].astype(np.int64), None)

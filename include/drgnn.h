@@ -987,6 +987,74 @@ int drgnn_pose_contacts(const drgnn_pose_contacts_request* req, void* stream);
 int drgnn_pose_common(const drgnn_pose_common_request* req, void* stream);
 int drgnn_pose_cluster(const drgnn_pose_cluster_request* req, void* stream);
 
+/* ---- pairwise pose RMSD and RMSD clustering of poses (drgnn_rmsd.h) ------------------------------------
+ * The pose-by-pose RMSD matrix of poses of one topology (pairwise l-RMSD / i-RMSD) and the clustering rule of HADDOCK's
+ * cluster_struc and of ClusPro on it.  tests/rmsd_ref.py states both rules.
+ *
+ * drgnn_pose_rmsd: xyz_a f32 [n_a, T, 3], xyz_b f32 [n_b, T, 3] (may be xyz_a; with n_b == n_a the call is then the
+ * square matrix of one batch: pairs i < j are computed and mirrored, the diagonal is written as 0); rms_idx i32 [n_rms]
+ * and fit_idx i32 [n_fit] atoms of a pose (fit_idx null with n_fit 0: no superposition), also given as HOST arrays: every
+ * check comes from them.  Poses go to fp64.  Without fit: d[i, j] = sqrt(sum_a |a_i[a] - b_j[a]|^2 / n_rms) over rms_idx.
+ * With fit: the optimal proper rotation and translation of pose a_i's fit atoms onto pose b_j's (Horn's quaternion, the
+ * Jacobi routine of drgnn_dock_scores), applied to a_i, then the same sum over rms_idx, taken from fp64 moments about the
+ * fit centroids.  Output d f64 [n_a, n_b].  d[i, j] of a pair of poses has the same bits in both directions, on
+ * whichever side of whichever call the two poses are; it does not depend on n_a, n_b, a pose's place or the run.  A
+ * collinear or coincident fit set leaves the rotation undetermined: the result is then undefined.
+ * Workspace: drgnn_rmsd_workspace(n_a, n_b, n_fit, n_rms, offsets) bytes, 8-byte aligned, allocated by the caller, contents
+ * undefined on entry.  After the call it holds a record of 3 n_fit + 3 n_rms + 2 doubles per pose, side a at offsets[0],
+ * side b at offsets[1] (unused when the call is a square matrix), offsets[2] the size: the fit atoms and the rms atoms
+ * about the fit centroid, then sum |x|^2 of either list.
+ * phases: 0 the whole call; else a set of 1 records, 2 pairs: only these launches (the pairs read what an earlier call
+ * left in the workspace; repeating a launch changes no bit). */
+typedef struct drgnn_pose_rmsd_request {
+    const float* xyz_a;
+    const float* xyz_b;
+    const int32_t* fit_idx;
+    const int32_t* rms_idx;
+    const int32_t* host_fit_idx;       /* the lists in host memory */
+    const int32_t* host_rms_idx;
+    int64_t n_a, n_b, n_atoms, n_fit, n_rms;
+    int32_t phases;
+    int32_t reserved;                  /* 0 */
+    void* workspace;
+    int64_t workspace_bytes;
+    double* d;
+} drgnn_pose_rmsd_request;
+
+/* drgnn_pose_cluster_dist: from a distance matrix d f64 [M, M] (a device array; it need not be symmetric): j is a
+ * neighbour of i iff i != j and d[i, j] <= cutoff, decided in fp64 on the stored value (a NaN is no neighbour).  Then the
+ * outputs and the greedy loop of drgnn_pose_cluster.  Two launches, no host round trip. */
+typedef struct drgnn_pose_cluster_dist_request {
+    const double* d;
+    int64_t n_poses;
+    double cutoff;
+    int32_t min_size;
+    int32_t reserved;                  /* 0 */
+    uint64_t* neighbours;
+    uint64_t* transposed;
+    int32_t* labels;
+    int32_t* centres;
+    int32_t* sizes;
+    int32_t* n_clusters;
+} drgnn_pose_cluster_dist_request;
+
+/* the documented capacities: what = 0 poses on either side of one drgnn_pose_rmsd call (4096: split the call), 1 poses
+ * of one drgnn_pose_cluster_dist call (drgnn_fcc_capacity(2), 4096: clustering cannot be split); -1 otherwise.  Pure host. */
+int32_t drgnn_rmsd_capacity(int32_t what);
+
+/* bytes of workspace for a drgnn_pose_rmsd call, -1 for counts the call refuses; offsets (may be null): int64 [3], see
+ * above.  Pure host. */
+int64_t drgnn_rmsd_workspace(int64_t n_a, int64_t n_b, int64_t n_fit, int64_t n_rms, int64_t* offsets);
+
+/* Both: DRGNN_E_ARG before any launch for a null request or pointer, a negative count, and
+ *   rmsd:         an index outside [0, n_atoms), n_fit of 1 or 2, n_rms 0, fit_idx without n_fit or n_fit without fit_idx,
+ *                 phases outside 0..3, a workspace that is not 8-byte aligned
+ *   cluster_dist: a cutoff that is not a positive finite number, min_size < 1
+ * DRGNN_E_CAPACITY beyond drgnn_rmsd_capacity, or workspace_bytes too small.  No allocation, no synchronisation; empty
+ * inputs return 0 without a launch. */
+int drgnn_pose_rmsd(const drgnn_pose_rmsd_request* req, void* stream);
+int drgnn_pose_cluster_dist(const drgnn_pose_cluster_dist_request* req, void* stream);
+
 /* ---- the builder's output packed into a resident set's arrays (drgnn_pack.h) --------------------------
  * After drgnn_iface_fill on the same batch (and the optional drgnn_bsa_residues / drgnn_hse_residues /
  * drgnn_depth_residues over exactly its nodes, in node order): the arrays a drgnn_graph_set holds, written on the
