@@ -1725,6 +1725,42 @@ static int update_run(const UpdateCall& c) {
     return 0;
 }
 
+// ---- clustering of poses (drgnn_posecluster.h) ---------------------------------------------------------
+// The part of drgnn_pose_cluster / drgnn_pose_cluster_dist that does not depend on the rule, after the entry point's own checks:
+// the shared checks, then the relation of `rule` and the greedy loop on it.  `q` is either request: their shared fields
+// have the same names; `relation` is the rule's instantiation of the relation kernel (the emulation calls pc_relation).
+#ifdef DRGNN_EMU
+#define PC_RELATION_KERNEL(k) nullptr
+#else
+#define PC_RELATION_KERNEL(k) k
+#endif
+template <class Rule, class Request, class Kernel>
+static int pose_cluster_run(Rule rule, const Request* q, Kernel relation, void* stream) {
+    const int64_t M = q->n_poses;
+    if (M < 0 || q->min_size < 1 || !q->n_clusters) return DRGNN_E_ARG;
+    if (M > 0 && (!q->neighbours || !q->transposed || !q->labels || !q->centres || !q->sizes)) return DRGNN_E_ARG;
+    if (M > PC_CCAP) return DRGNN_E_CAPACITY;
+    if (M == 0) return 0;
+    PoseClusterArgs a;
+    memset(&a, 0, sizeof(a));
+    rule.n = a.n = (int)M; a.min_size = q->min_size;
+    a.nb = (pc_word*)q->neighbours; a.nbt = (pc_word*)q->transposed;
+    a.labels = q->labels; a.centres = q->centres; a.sizes = q->sizes; a.n_clusters = q->n_clusters;
+    const int64_t words = M * ((M + 63) / 64), blocks = (words + DRGNN_NWAVES - 1) / DRGNN_NWAVES;
+#ifdef DRGNN_EMU
+    (void)stream; (void)relation;
+    for (int64_t b = 0; b < blocks; ++b) pc_relation(rule, a, b);
+    std::unique_ptr<PoseGreedyShared> lds(new PoseGreedyShared);
+    pc_greedy(a, *lds);
+#else
+    hipLaunchKernelGGL(relation, dim3((unsigned)blocks), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, rule, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_fcc_greedy, dim3(1), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+#endif
+    return 0;
+}
+
 extern "C" {
 
 int drgnn_net_reduce_grads(const drgnn_net_desc* net, const float* partials, int64_t n_nodes, int64_t n_graphs,
@@ -2507,7 +2543,7 @@ int drgnn_depth_residues(const drgnn_depth_request* q, void* stream) {
 }
 
 // ---- clustering of poses by their fraction of common contacts (drgnn_fcc.h) --------------------------
-int32_t drgnn_fcc_capacity(int32_t what) { return what == 0 ? FC_RCAP : what == 1 ? FC_PCAP : what == 2 ? FC_CCAP : -1; }
+int32_t drgnn_fcc_capacity(int32_t what) { return what == 0 ? FC_RCAP : what == 1 ? FC_PCAP : what == 2 ? PC_CCAP : -1; }
 
 int drgnn_pose_contacts(const drgnn_pose_contacts_request* q, void* stream) {
     if (!q || !q->host_atom_ptr) return DRGNN_E_ARG;
@@ -2525,7 +2561,7 @@ int drgnn_pose_contacts(const drgnn_pose_contacts_request* q, void* stream) {
     memset(&a, 0, sizeof(a));
     a.xyz = q->xyz; a.atom_ptr = q->atom_ptr; a.n_atoms = (int)T; a.n_res = (int)R; a.n_a = (int)A;
     a.cut = (float)q->cutoff; a.cut2 = (float)(q->cutoff * q->cutoff);
-    a.bits = (fc_word*)q->bits; a.n_contacts = q->n_contacts;
+    a.bits = (pc_word*)q->bits; a.n_contacts = q->n_contacts;
 #ifdef DRGNN_EMU
     (void)stream;
     std::unique_ptr<FccContactShared> lds(new FccContactShared);
@@ -2547,7 +2583,7 @@ int drgnn_pose_common(const drgnn_pose_common_request* q, void* stream) {
     if (Ma == 0 || Mb == 0) return 0;
     FccCommonArgs a;
     memset(&a, 0, sizeof(a));
-    a.a = (const fc_word*)q->bits_a; a.b = (const fc_word*)q->bits_b; a.n_a = (int)Ma; a.n_b = (int)Mb; a.n_words = W;
+    a.a = (const pc_word*)q->bits_a; a.b = (const pc_word*)q->bits_b; a.n_a = (int)Ma; a.n_b = (int)Mb; a.n_words = W;
     a.common = q->common;
     const int ti = (int)((Ma + FC_TILE - 1) / FC_TILE), tj = (int)((Mb + FC_TILE - 1) / FC_TILE);
 #ifdef DRGNN_EMU
@@ -2566,40 +2602,17 @@ int drgnn_pose_common(const drgnn_pose_common_request* q, void* stream) {
 
 int drgnn_pose_cluster(const drgnn_pose_cluster_request* q, void* stream) {
     if (!q) return DRGNN_E_ARG;
-    const int64_t M = q->n_poses;
-    if (M < 0 || q->min_size < 1) return DRGNN_E_ARG;
     if (!(q->cutoff_fcc > 0.0) || !(q->cutoff_fcc <= 1.0) || !(q->cutoff_reverse > 0.0) || !(q->cutoff_reverse <= 1.0))
         return DRGNN_E_ARG;
-    if (!q->n_clusters) return DRGNN_E_ARG;
-    if (M > 0 && (!q->common || !q->n_contacts || !q->neighbours || !q->transposed || !q->labels || !q->centres || !q->sizes))
-        return DRGNN_E_ARG;
-    if (M > FC_CCAP) return DRGNN_E_CAPACITY;
-    if (M == 0) return 0;
-    FccClusterArgs a;
-    memset(&a, 0, sizeof(a));
-    a.common = q->common; a.n_contacts = q->n_contacts; a.n = (int)M; a.min_size = q->min_size;
-    a.cut_fwd = q->cutoff_fcc; a.cut_rev = q->cutoff_reverse;
-    a.nb = (fc_word*)q->neighbours; a.nbt = (fc_word*)q->transposed;
-    a.labels = q->labels; a.centres = q->centres; a.sizes = q->sizes; a.n_clusters = q->n_clusters;
-    const int64_t words = M * ((M + 63) / 64), blocks = (words + DRGNN_NWAVES - 1) / DRGNN_NWAVES;
-#ifdef DRGNN_EMU
-    (void)stream;
-    for (int64_t b = 0; b < blocks; ++b) fc_relation(a, b);
-    std::unique_ptr<FccGreedyShared> lds(new FccGreedyShared);
-    fc_greedy(a, *lds);
-#else
-    static_assert(FC_CCAP <= (1 << FC_KEY_SHIFT) && FC_CCAP % 64 == 0, "a pose index fits the low bits of the greedy key");
-    static_assert(sizeof(FccGreedyShared) <= 64 * 1024, "the degrees and the member list fit the static LDS of a workgroup");
-    hipLaunchKernelGGL(k_fcc_relation, dim3((unsigned)blocks), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_fcc_greedy, dim3(1), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-#endif
-    return 0;
+    if (q->n_poses > 0 && (!q->common || !q->n_contacts)) return DRGNN_E_ARG;
+    FccRule rule;
+    memset(&rule, 0, sizeof(rule));
+    rule.common = q->common; rule.n_contacts = q->n_contacts; rule.cut_fwd = q->cutoff_fcc; rule.cut_rev = q->cutoff_reverse;
+    return pose_cluster_run(rule, q, PC_RELATION_KERNEL(k_fcc_relation), stream);
 }
 
 // ---- pairwise pose RMSD and RMSD clustering of poses (drgnn_rmsd.h) ----------------------------------
-int32_t drgnn_rmsd_capacity(int32_t what) { return what == 0 ? RM_PCAP : what == 1 ? FC_CCAP : -1; }
+int32_t drgnn_rmsd_capacity(int32_t what) { return what == 0 ? RM_PCAP : what == 1 ? PC_CCAP : -1; }
 
 // records of side a, of side b; off[2] is the size
 static int rmsd_layout(int64_t Ma, int64_t Mb, int64_t nF, int64_t nR, int64_t* off) {
@@ -2677,32 +2690,12 @@ int drgnn_pose_rmsd(const drgnn_pose_rmsd_request* q, void* stream) {
 
 int drgnn_pose_cluster_dist(const drgnn_pose_cluster_dist_request* q, void* stream) {
     if (!q) return DRGNN_E_ARG;
-    const int64_t M = q->n_poses;
-    if (M < 0 || q->min_size < 1) return DRGNN_E_ARG;
     if (!(q->cutoff > 0.0) || !(q->cutoff < HUGE_VAL)) return DRGNN_E_ARG;
-    if (!q->n_clusters) return DRGNN_E_ARG;
-    if (M > 0 && (!q->d || !q->neighbours || !q->transposed || !q->labels || !q->centres || !q->sizes)) return DRGNN_E_ARG;
-    if (M > FC_CCAP) return DRGNN_E_CAPACITY;
-    if (M == 0) return 0;
-    RmsdRelationArgs a;
-    memset(&a, 0, sizeof(a));
-    a.d = q->d; a.cutoff = q->cutoff;
-    a.c.n = (int)M; a.c.min_size = q->min_size;
-    a.c.nb = (fc_word*)q->neighbours; a.c.nbt = (fc_word*)q->transposed;
-    a.c.labels = q->labels; a.c.centres = q->centres; a.c.sizes = q->sizes; a.c.n_clusters = q->n_clusters;
-    const int64_t words = M * ((M + 63) / 64), blocks = (words + DRGNN_NWAVES - 1) / DRGNN_NWAVES;
-#ifdef DRGNN_EMU
-    (void)stream;
-    for (int64_t b = 0; b < blocks; ++b) rm_relation(a, b);
-    std::unique_ptr<FccGreedyShared> lds(new FccGreedyShared);
-    fc_greedy(a.c, *lds);
-#else
-    hipLaunchKernelGGL(k_rmsd_relation, dim3((unsigned)blocks), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_fcc_greedy, dim3(1), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a.c);
-    HIP_TRY(hipGetLastError());
-#endif
-    return 0;
+    if (q->n_poses > 0 && !q->d) return DRGNN_E_ARG;
+    DistRule rule;
+    memset(&rule, 0, sizeof(rule));
+    rule.d = q->d; rule.cutoff = q->cutoff;
+    return pose_cluster_run(rule, q, PC_RELATION_KERNEL(k_rmsd_relation), stream);
 }
 
 // ---- evaluation scores (drgnn_metrics.h) ---------------------------------------------------------

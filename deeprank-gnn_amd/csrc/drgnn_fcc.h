@@ -9,10 +9,9 @@
 //             bits u64 [M, nA, WB], WB = ceil(nB / 64): bit b % 64 of word b / 64 of row a; n[m] = the number of set bits
 //   common    common[i, j] = sum over the words of popcount(bits_i & bits_j), int32
 //   relation  fcc(i, j) = n_i == 0 ? 0.0 : (double)common[i, j] / (double)n_i; j is a neighbour of i iff i != j and
-//             fcc(i, j) >= cut_fwd and fcc(j, i) >= cut_rev (directed).  nb u64 [M, MW], MW = ceil(M / 64): bit j of row i;
-//             nbt its transpose (bit j of row i: i is a neighbour of j)
-//   greedy    deg[i] = alive neighbours of i; the centre is the alive pose of largest deg, smallest index on a tie; stop
-//             when deg[centre] < min_size - 1; the cluster is the centre and its alive neighbours, which all die
+//             fcc(i, j) >= cut_fwd and fcc(j, i) >= cut_rev (directed): FccRule and its `related`.  The bit rows of the
+//             relation and the greedy loop on them are rule-independent: pc_relation and pc_greedy of
+//             drgnn_posecluster.h, which the RMSD rule of drgnn_rmsd.h runs too
 //
 // Kernels (one launch each):
 //   fc_pose      one workgroup per pose.  Phase 0: lanes over the residues, a bounding sphere each (its centre is the
@@ -23,10 +22,6 @@
 //                sums through LDS, added by one lane.
 //   fc_common    one workgroup per FC_TILE x FC_TILE tile of pose pairs, one lane per pair; the words of the 2 x FC_TILE
 //                poses go through LDS FC_KW at a time (rows padded by one word: the lanes of a wave read FC_TILE rows).
-//   fc_relation  a wave per (pose i, word of 64 poses j): two ballots give the word of nb and of nbt.
-//   fc_greedy    ONE workgroup: deg from popcounts, then per cluster an integer max over (deg, -index) keys, the members
-//                = nb[centre] & alive, and for every member the alive poses of ITS nbt row lose one (integer atomics on
-//                LDS: order-free).  Per step: M keys + members x MW words, not M x MW.
 // The sphere test is conservative: with the stored centre c and r >= |x - c| up to rounding for every atom x of the
 // residue, two atoms within cut imply |ca - cb| <= cut + ra + rb.  The fp32 rounding of if_d2, sqrt and the sums is below
 // 1e-6 relative plus one step of a coordinate (1e-3 A at |x| < 10^4); the test allows (cut + ra + rb) * 1.0001 + 0.01 A,
@@ -35,21 +30,19 @@
 #pragma once
 #include "drgnn_rt.h"
 #include "drgnn_iface.h"
+#include "drgnn_posecluster.h"
 
 #define FC_RCAP 3072                 // residues of a complex, both chains: 16 B of sphere each in LDS (48 KiB)
 #define FC_PCAP 16384                // poses on either side of one drgnn_pose_common call: the output stays below 2^28 ints
-#define FC_CCAP 4096                 // poses of one drgnn_pose_cluster call: deg + member list 8 B each in LDS (32 KiB)
 #define FC_TILE 32                   // pose pairs per workgroup of fc_common: FC_TILE^2 = the workgroup's lanes
 #define FC_KW 64                     // words staged at a time: 2 * FC_TILE * (FC_KW + 1) * 8 B = 33 KiB
-#define FC_KEY_SHIFT 12              // greedy key = deg << 12 | (FC_CCAP - 1 - index)
-typedef unsigned long long fc_word;
 
 struct FccContactArgs {
     const float* xyz;                // [M, T, 3]
     const int32_t* atom_ptr;         // [R + 1]
     int n_atoms, n_res, n_a;         // T, R, residues of chain 0
     float cut, cut2;
-    fc_word* bits;                   // [M, nA, WB]
+    pc_word* bits;                   // [M, nA, WB]
     int32_t* n_contacts;             // [M]
 };
 struct FccContactShared {
@@ -58,42 +51,22 @@ struct FccContactShared {
 };
 
 struct FccCommonArgs {
-    const fc_word* a;                // [Ma, W]
-    const fc_word* b;                // [Mb, W]
+    const pc_word* a;                // [Ma, W]
+    const pc_word* b;                // [Mb, W]
     int n_a, n_b;
     int64_t n_words;
     int32_t* common;                 // [Ma, Mb]
 };
 struct FccCommonShared {
-    fc_word a[FC_TILE][FC_KW + 1], b[FC_TILE][FC_KW + 1];
+    pc_word a[FC_TILE][FC_KW + 1], b[FC_TILE][FC_KW + 1];
 };
 
-struct FccClusterArgs {
+struct FccRule {                     // the rule of the neighbour relation (pc_relation of drgnn_posecluster.h)
     const int32_t* common;           // [M, M]
     const int32_t* n_contacts;       // [M]
-    int n, min_size;
+    int n;
     double cut_fwd, cut_rev;
-    fc_word* nb;                     // [M, MW]
-    fc_word* nbt;                    // [M, MW]
-    int32_t* labels;                 // [M]
-    int32_t* centres;                // [M], the first n_clusters are set
-    int32_t* sizes;                  // [M]
-    int32_t* n_clusters;             // [1]
 };
-struct FccGreedyShared {
-    int deg[FC_CCAP];
-    int list[FC_CCAP];
-    fc_word alive[FC_CCAP / 64], member[FC_CCAP / 64];
-    int best, n_list;
-};
-
-#ifdef DRGNN_EMU
-DEV int fc_popc(fc_word x) { return __builtin_popcountll(x); }
-DEV int fc_ctz(fc_word x) { return __builtin_ctzll(x); }
-#else
-DEV int fc_popc(fc_word x) { return __popcll(x); }
-DEV int fc_ctz(fc_word x) { return __ffsll((long long)x) - 1; }
-#endif
 
 // ---- contacts -------------------------------------------------------------------------------------------------------
 // the exact rule for residues ra (chain 0) and rb (chain 1, a global residue index) of the pose at X, behind the sphere test
@@ -116,7 +89,7 @@ DEV bool fc_pair(const FccContactArgs& a, const float* X, const FccContactShared
 DEV void fc_pose(const FccContactArgs& a, int64_t m, FccContactShared& s) {
     const float* X = a.xyz + m * (int64_t)a.n_atoms * 3;
     const int nA = a.n_a, nB = a.n_res - a.n_a, WB = (nB + 63) / 64;
-    fc_word* out = a.bits + m * (int64_t)nA * WB;
+    pc_word* out = a.bits + m * (int64_t)nA * WB;
     // ---- 0 spheres
     FOR_TID(r, a.n_res) {
         const int p0 = a.atom_ptr[r], p1 = a.atom_ptr[r + 1];
@@ -138,13 +111,13 @@ DEV void fc_pose(const FccContactArgs& a, int64_t m, FccContactShared& s) {
     int count = 0;
     for (int it = 0; it < nA * WB; ++it) {
         const int ra = it / WB, w = it % WB;
-        fc_word word = 0;
+        pc_word word = 0;
         for (int lane = 0; lane < 64; ++lane) {
             const int b = 64 * w + lane;
-            if (b < nB && fc_pair(a, X, s, ra, nA + b)) word |= (fc_word)1 << lane;
+            if (b < nB && fc_pair(a, X, s, ra, nA + b)) word |= (pc_word)1 << lane;
         }
         out[it] = word;
-        count += fc_popc(word);
+        count += pc_popc(word);
     }
     a.n_contacts[m] = count;
 #else
@@ -154,9 +127,9 @@ DEV void fc_pose(const FccContactArgs& a, int64_t m, FccContactShared& s) {
     for (int it = wave; it < nA * WB; it += DRGNN_NWAVES) {
         const int ra = fastdiv(fd, it), w = fastmod(fd, it, ra);
         const int b = 64 * w + lane;
-        const fc_word word = __ballot(b < nB && fc_pair(a, X, s, ra, nA + b));
+        const pc_word word = __ballot(b < nB && fc_pair(a, X, s, ra, nA + b));
         if (lane == 0) out[it] = word;
-        count += fc_popc(word);
+        count += pc_popc(word);
     }
     if (lane == 0) s.wave_count[wave] = count;
     BARRIER();
@@ -177,7 +150,7 @@ DEV void fc_common(const FccCommonArgs& a, int ti, int tj, FccCommonShared& s) {
     for (int i = i0; i < imin(i0 + FC_TILE, a.n_a); ++i)
         for (int j = j0; j < imin(j0 + FC_TILE, a.n_b); ++j) {
             int acc = 0;
-            for (int64_t k = 0; k < a.n_words; ++k) acc += fc_popc(a.a[i * a.n_words + k] & a.b[j * a.n_words + k]);
+            for (int64_t k = 0; k < a.n_words; ++k) acc += pc_popc(a.a[i * a.n_words + k] & a.b[j * a.n_words + k]);
             a.common[(int64_t)i * a.n_b + j] = acc;
         }
 #else
@@ -188,12 +161,12 @@ DEV void fc_common(const FccCommonArgs& a, int ti, int tj, FccCommonShared& s) {
         FOR_TID(e, 2 * FC_TILE * FC_KW) {                              // consecutive lanes: consecutive words of one pose
             const int side = e / (FC_TILE * FC_KW), row = (e / FC_KW) % FC_TILE, k = e % FC_KW;
             const int pose = (side ? j0 : i0) + row;
-            fc_word v = 0;
+            pc_word v = 0;
             if (k < nk && pose < (side ? a.n_b : a.n_a)) v = (side ? a.b : a.a)[(int64_t)pose * a.n_words + k0 + k];
             if (side) s.b[row][k] = v; else s.a[row][k] = v;
         }
         BARRIER();
-        for (int k = 0; k < nk; ++k) acc += fc_popc(s.a[y][k] & s.b[x][k]);
+        for (int k = 0; k < nk; ++k) acc += pc_popc(s.a[y][k] & s.b[x][k]);
         BARRIER();
     }
     if (i0 + y < a.n_a && j0 + x < a.n_b) a.common[(int64_t)(i0 + y) * a.n_b + j0 + x] = acc;
@@ -202,103 +175,10 @@ DEV void fc_common(const FccCommonArgs& a, int ti, int tj, FccCommonShared& s) {
 
 // ---- neighbour relation ---------------------------------------------------------------------------------------------
 DEV double fc_fraction(int common, int n) { return n == 0 ? 0.0 : (double)common / (double)n; }
-// bits of pose pair (i, j): 1 j is a neighbour of i, 2 i is a neighbour of j
-DEV int fc_related(const FccClusterArgs& a, int i, int j) {
+// bits of pose pair (i, j): 1 j is a neighbour of i, 2 i is a neighbour of j (the rule pc_relation asks)
+DEV int related(const FccRule& a, int i, int j) {
     if (i == j) return 0;
     const double fij = fc_fraction(a.common[(int64_t)i * a.n + j], a.n_contacts[i]);
     const double fji = fc_fraction(a.common[(int64_t)j * a.n + i], a.n_contacts[j]);
     return ((fij >= a.cut_fwd && fji >= a.cut_rev) ? 1 : 0) | ((fji >= a.cut_fwd && fij >= a.cut_rev) ? 2 : 0);
-}
-// One workgroup: words block * DRGNN_NWAVES .. of the M * MW words, a wave each
-DEV void fc_relation(const FccClusterArgs& a, int64_t block) {
-    const int MW = (a.n + 63) / 64;
-#ifdef DRGNN_EMU
-    for (int64_t it = block * DRGNN_NWAVES; it < imin((int)((block + 1) * DRGNN_NWAVES), a.n * MW); ++it) {
-        const int i = (int)(it / MW), w = (int)(it % MW);
-        fc_word fwd = 0, back = 0;
-        for (int lane = 0; lane < 64; ++lane) {
-            const int j = 64 * w + lane;
-            const int rel = j < a.n ? fc_related(a, i, j) : 0;
-            if (rel & 1) fwd |= (fc_word)1 << lane;
-            if (rel & 2) back |= (fc_word)1 << lane;
-        }
-        a.nb[it] = fwd;
-        a.nbt[it] = back;
-    }
-#else
-    const int64_t it = block * DRGNN_NWAVES + (int)threadIdx.x / DRGNN_WAVE;
-    const int lane = (int)threadIdx.x % DRGNN_WAVE;
-    if (it >= (int64_t)a.n * MW) return;                             // (the whole wave)
-    const int i = (int)(it / MW), w = (int)(it % MW), j = 64 * w + lane;
-    const int rel = j < a.n ? fc_related(a, i, j) : 0;
-    const fc_word fwd = __ballot(rel & 1), back = __ballot(rel & 2);
-    if (lane == 0) { a.nb[it] = fwd; a.nbt[it] = back; }
-#endif
-}
-
-// ---- greedy clustering ----------------------------------------------------------------------------------------------
-#ifdef DRGNN_EMU
-#define FC_WAVE_MAX(v) ((void)0)
-#define FC_WAVE_LEADER true
-#else
-#define FC_WAVE_MAX(v) _Pragma("unroll") for (int x_ = 1; x_ < 64; x_ <<= 1) { const int o_ = __shfl_xor((v), x_, 64); (v) = o_ > (v) ? o_ : (v); }
-#define FC_WAVE_LEADER (((int)threadIdx.x & 63) == 0)
-#endif
-// ONE workgroup
-DEV void fc_greedy(const FccClusterArgs& a, FccGreedyShared& s) {
-    const int M = a.n, MW = (M + 63) / 64;
-    FOR_TID(i, M) {
-        int d = 0;
-        for (int w = 0; w < MW; ++w) d += fc_popc(a.nb[(int64_t)i * MW + w]);
-        s.deg[i] = d;
-        a.labels[i] = -1;
-    }
-    FOR_TID(w, MW) s.alive[w] = (w + 1 < MW || M % 64 == 0) ? ~(fc_word)0 : (((fc_word)1 << (M % 64)) - 1);
-    FOR_TID(i, 1) { s.best = -1; s.n_list = 0; }
-    BARRIER();
-    int k = 0;
-    for (; k < M; ++k) {
-        // the centre: the largest (deg, -index) over the alive poses
-        {
-#ifdef DRGNN_EMU
-            for (int i = 0; i < M; ++i)
-                if ((s.alive[i >> 6] >> (i & 63)) & 1) ATOMIC_MAX(&s.best, (s.deg[i] << FC_KEY_SHIFT) | (FC_CCAP - 1 - i));
-#else
-            int key = -1;
-            for (int i = (int)threadIdx.x; i < M; i += DRGNN_NTHREADS)
-                if ((s.alive[i >> 6] >> (i & 63)) & 1) key = imax(key, (s.deg[i] << FC_KEY_SHIFT) | (FC_CCAP - 1 - i));
-            FC_WAVE_MAX(key)
-            if (FC_WAVE_LEADER && key >= 0) ATOMIC_MAX(&s.best, key);
-#endif
-        }
-        BARRIER();
-        const int best = s.best;                                      // (the same on every lane: the loop is uniform)
-        if (best < 0 || (best >> FC_KEY_SHIFT) < a.min_size - 1) break;
-        const int c = FC_CCAP - 1 - (best & (FC_CCAP - 1));
-        FOR_TID(w, MW) s.member[w] = (a.nb[(int64_t)c * MW + w] & s.alive[w]) | (w == (c >> 6) ? (fc_word)1 << (c & 63) : 0);
-        BARRIER();
-        FOR_TID(w, MW) s.alive[w] &= ~s.member[w];
-        FOR_TID(i, M) {
-            if ((s.member[i >> 6] >> (i & 63)) & 1) {
-                a.labels[i] = k;
-                s.list[ATOMIC_ADD(&s.n_list, 1)] = i;
-            }
-        }
-        FOR_TID(i, 1) { a.centres[k] = c; a.sizes[k] = (best >> FC_KEY_SHIFT) + 1; s.best = -1; }
-        BARRIER();
-        // every alive pose that has a member as a neighbour loses one
-        const int nl = s.n_list;
-        FOR_TID(it, nl * MW) {
-            const int j = s.list[it / MW], w = it % MW;
-            fc_word x = a.nbt[(int64_t)j * MW + w] & s.alive[w];
-            while (x) {
-                ATOMIC_ADD(&s.deg[64 * w + fc_ctz(x)], -1);
-                x &= x - 1;
-            }
-        }
-        BARRIER();
-        FOR_TID(i, 1) s.n_list = 0;
-        BARRIER();
-    }
-    FOR_TID(i, 1) a.n_clusters[0] = k;
 }

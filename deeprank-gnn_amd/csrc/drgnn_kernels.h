@@ -16,6 +16,7 @@
 #include "drgnn_bsa.h"
 #include "drgnn_hse.h"
 #include "drgnn_depth.h"
+#include "drgnn_posecluster.h"
 #include "drgnn_fcc.h"
 #include "drgnn_rmsd.h"
 #include "drgnn_pack.h"
@@ -1020,7 +1021,7 @@ __global__ void __launch_bounds__(DRGNN_NTHREADS) k_depth_residues(DepthArgs a) 
     depth_residue(a, (int64_t)blockIdx.x, smem_dp);
 }
 // fraction of common contacts (drgnn_fcc.h): one workgroup per pose; per tile of pose pairs; a wave per word of the
-// neighbour relation; ONE workgroup for the greedy clustering
+// neighbour relation; ONE workgroup for the greedy clustering of either rule (drgnn_posecluster.h)
 __global__ void __launch_bounds__(DRGNN_NTHREADS) k_fcc_contacts(FccContactArgs a) {
     __shared__ FccContactShared smem_fc;
     fc_pose(a, (int64_t)blockIdx.x, smem_fc);
@@ -1029,10 +1030,10 @@ __global__ void __launch_bounds__(DRGNN_NTHREADS) k_fcc_common(FccCommonArgs a) 
     __shared__ FccCommonShared smem_fm;
     fc_common(a, (int)blockIdx.y, (int)blockIdx.x, smem_fm);
 }
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_fcc_relation(FccClusterArgs a) { fc_relation(a, (int64_t)blockIdx.x); }
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_fcc_greedy(FccClusterArgs a) {
-    __shared__ FccGreedyShared smem_fg;
-    fc_greedy(a, smem_fg);
+__global__ void __launch_bounds__(DRGNN_NTHREADS) k_fcc_relation(FccRule r, PoseClusterArgs a) { pc_relation(r, a, (int64_t)blockIdx.x); }
+__global__ void __launch_bounds__(DRGNN_NTHREADS) k_fcc_greedy(PoseClusterArgs a) {
+    __shared__ PoseGreedyShared smem_fg;
+    pc_greedy(a, smem_fg);
 }
 // pairwise pose RMSD (drgnn_rmsd.h): one workgroup per pose of one side; per tile of pose pairs; a wave per word of the
 // neighbour relation (the greedy clustering is k_fcc_greedy)
@@ -1044,7 +1045,7 @@ __global__ void __launch_bounds__(DRGNN_NTHREADS) k_rmsd_pairs(RmsdArgs a) {
     __shared__ RmsdPairShared smem_rq;
     rm_pairs(a, (int)blockIdx.y, (int)blockIdx.x, smem_rq);
 }
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_rmsd_relation(RmsdRelationArgs a) { rm_relation(a, (int64_t)blockIdx.x); }
+__global__ void __launch_bounds__(DRGNN_NTHREADS) k_rmsd_relation(DistRule r, PoseClusterArgs a) { pc_relation(r, a, (int64_t)blockIdx.x); }
 // the builder's output packed into a resident set's arrays (drgnn_pack.h): one workgroup per complex
 __global__ void __launch_bounds__(PK_NT) k_iface_pack(PackArgs a) {
     __shared__ PackShared smem_pk;

@@ -1,6 +1,7 @@
 // drgnn_rmsd.h -- the pose-by-pose RMSD matrix of docking poses of one topology (pairwise l-RMSD / i-RMSD) and the
-// neighbour relation of RMSD clustering (the rule of HADDOCK's cluster_struc and of ClusPro; the greedy loop is fc_greedy
-// of drgnn_fcc.h, unchanged).  tests/rmsd_ref.py states both rules in numpy.
+// neighbour relation of RMSD clustering (the rule of HADDOCK's cluster_struc and of ClusPro: DistRule and its `related`;
+// the bit rows of the relation and the greedy loop are pc_relation and pc_greedy of drgnn_posecluster.h).
+// tests/rmsd_ref.py states both rules in numpy.
 //
 //   distance  poses p_i, p_j (f32 -> f64), an atom list `rms` (nR >= 1) and an atom list `fit` (nF >= 3) or none.
 //             Without fit: D[i, j] = sqrt(sum_a |p_i[a] - p_j[a]|^2 / nR) over rms.  With fit: the optimal proper rotation
@@ -23,7 +24,6 @@
 //                or on M.  Then it fits its pair with the Jacobi routine of drgnn_score.h and writes D.
 //                When both sides are the same batch the tiles below the diagonal do nothing, a lane with i < j writes
 //                D[i, j] and D[j, i], and the diagonal is written as 0.
-//   rm_relation  a wave per (pose i, word of 64 poses j): two ballots give the word of nb and of nbt, as fc_relation.
 // Both directions of a pair have the same bits, whichever side of a call a pose is on: S and C of the reversed pair are
 // the exact transposes (a product and a sum do not depend on the order of their operands), and rm_distance evaluates the
 // pair in ONE of the two directions, chosen by the sign of the first non-zero of Horn's three antisymmetric entries,
@@ -34,7 +34,7 @@
 #pragma once
 #include "drgnn_rt.h"
 #include "drgnn_score.h"
-#include "drgnn_fcc.h"
+#include "drgnn_posecluster.h"
 
 #define RM_PCAP 4096                 // poses on either side of one drgnn_pose_rmsd call: 128 tiles a side
 #define RM_TILE 32                   // pose pairs per workgroup: RM_TILE^2 = the workgroup's lanes
@@ -60,10 +60,10 @@ struct RmsdPrepShared {
 struct RmsdPairShared {
     double a[RM_TILE][RM_LD], b[RM_TILE][RM_LD];
 };
-struct RmsdRelationArgs {
+struct DistRule {                    // the rule of the neighbour relation (pc_relation of drgnn_posecluster.h)
     const double* d;                 // [M, M]
+    int n;
     double cutoff;
-    FccClusterArgs c;                // n, min_size and the outputs; common / n_contacts / cut_* unused
 };
 
 DEV int64_t rm_record(const RmsdArgs& a) { return 3 * ((int64_t)a.n_fit + a.n_rms) + 2; }
@@ -265,34 +265,8 @@ DEV void rm_pairs(const RmsdArgs& a, int ti, int tj, RmsdPairShared& s) {
 }
 
 // ---- neighbour relation ---------------------------------------------------------------------------------------------
-// bits of pose pair (i, j): 1 j is a neighbour of i, 2 i is a neighbour of j
-DEV int rm_related(const RmsdRelationArgs& a, int i, int j) {
+// bits of pose pair (i, j): 1 j is a neighbour of i, 2 i is a neighbour of j (the rule pc_relation asks)
+DEV int related(const DistRule& a, int i, int j) {
     if (i == j) return 0;
-    return (a.d[(int64_t)i * a.c.n + j] <= a.cutoff ? 1 : 0) | (a.d[(int64_t)j * a.c.n + i] <= a.cutoff ? 2 : 0);
-}
-// One workgroup: words block * DRGNN_NWAVES .. of the M * MW words, a wave each
-DEV void rm_relation(const RmsdRelationArgs& a, int64_t block) {
-    const int M = a.c.n, MW = (M + 63) / 64;
-#ifdef DRGNN_EMU
-    for (int64_t it = block * DRGNN_NWAVES; it < imin((int)((block + 1) * DRGNN_NWAVES), M * MW); ++it) {
-        const int i = (int)(it / MW), w = (int)(it % MW);
-        fc_word fwd = 0, back = 0;
-        for (int lane = 0; lane < 64; ++lane) {
-            const int j = 64 * w + lane;
-            const int rel = j < M ? rm_related(a, i, j) : 0;
-            if (rel & 1) fwd |= (fc_word)1 << lane;
-            if (rel & 2) back |= (fc_word)1 << lane;
-        }
-        a.c.nb[it] = fwd;
-        a.c.nbt[it] = back;
-    }
-#else
-    const int64_t it = block * DRGNN_NWAVES + (int)threadIdx.x / DRGNN_WAVE;
-    const int lane = (int)threadIdx.x % DRGNN_WAVE;
-    if (it >= (int64_t)M * MW) return;                                 // (the whole wave)
-    const int i = (int)(it / MW), w = (int)(it % MW), j = 64 * w + lane;
-    const int rel = j < M ? rm_related(a, i, j) : 0;
-    const fc_word fwd = __ballot(rel & 1), back = __ballot(rel & 2);
-    if (lane == 0) { a.c.nb[it] = fwd; a.c.nbt[it] = back; }
-#endif
+    return (a.d[(int64_t)i * a.n + j] <= a.cutoff ? 1 : 0) | (a.d[(int64_t)j * a.n + i] <= a.cutoff ? 2 : 0);
 }

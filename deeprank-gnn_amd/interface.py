@@ -84,6 +84,11 @@ _TYPE_OF = {n: i for i, n in enumerate(RESIDUE_NAMES)}
 WORKSPACE_BUDGET = 256 << 20       # bytes of dense min-d^2 workspace one call may ask for (sets the default chunk)
 
 
+def _default_device(api, device):
+    """``device`` as given; None: where ``api`` computes (the GPU for the product library, the host for any other)"""
+    return device if device is not None else "cuda" if api is _lib._API else "cpu"
+
+
 def read_pdb_atoms(path):
     """(chain str [T], res_seq int32 [T], res_name str [T], xyz float64 [T,3]) of the ``ATOM`` records of a PDB file,
     by the fixed columns of the format, hydrogens included, in file order.  Host-side plumbing."""
@@ -309,8 +314,7 @@ def interface_graphs(tables_or_poses, names, contact_distance=8.5, internal_cont
     gets ``node_data/depth``, float64 [n], the residue depth of exactly its nodes (three more launches per chunk)."""
     from .dataset import GraphStore
     api = api or _lib.get()
-    if device is None:
-        device = "cuda" if api is _lib._API else "cpu"
+    device = _default_device(api, device)
     cx = _complexes(tables_or_poses)
     names = [str(n) for n in names]
     if len(names) != len(cx):
@@ -539,8 +543,7 @@ def interface_resident_set(tables_or_poses, names, node_feature=("type", "polari
     from .resident import ResidentGraphSet
     import types
     api = api or _lib.get()
-    if device is None:
-        device = "cuda" if api is _lib._API else "cpu"
+    device = _default_device(api, device)
     cx = _complexes(tables_or_poses)
     names = [str(n) for n in names]
     if len(names) != len(cx):
@@ -805,17 +808,8 @@ def docking_scores(poses_or_table, reference, device=None, api=None, chunk=None)
     ``chunk`` poses (default: what keeps the uploaded coordinates within SCORE_XYZ_BUDGET bytes); a pose's result does
     not depend on the chunk, on its place in the batch or on the run."""
     api = api or _lib.get()
-    if device is None:
-        device = "cuda" if api is _lib._API else "cpu"
-    t = reference.table
-    if isinstance(poses_or_table, (Poses, AtomTable)):
-        if (poses_or_table.table if isinstance(poses_or_table, Poses) else poses_or_table) is not t:
-            raise ValueError("the poses must be of the reference's AtomTable")
-        xyz = poses_or_table.xyz if isinstance(poses_or_table, Poses) else poses_or_table.xyz[None]
-    else:
-        xyz = np.asarray(poses_or_table)
-    if xyz.ndim != 3 or xyz.shape[1:] != (t.n_atoms, 3):
-        raise ValueError("poses need xyz [M, %d, 3]" % t.n_atoms)
+    device = _default_device(api, device)
+    t, xyz = _pose_batch(poses_or_table, reference.table, "the poses must be of the reference's AtomTable")
     if chunk is None:
         chunk = SCORE_XYZ_BUDGET // (12 * max(t.n_atoms, 1))
     chunk = max(1, int(chunk))
@@ -1349,8 +1343,7 @@ def _residue_values(feature, tables_or_poses, residues, radii, options, device, 
     """``residue_bsa`` / ``residue_hse`` / ``residue_depth``: the raw rows of the residues asked for, NaN elsewhere; an
     ``AtomTable`` gives float64 [R] + feature.row, an ``AtomTable.poses`` batch [M, R] + feature.row, a sequence a list"""
     api = api or _lib.get()
-    if device is None:
-        device = "cuda" if api is _lib._API else "cpu"
+    device = _default_device(api, device)
     cx = _complexes(tables_or_poses)
     opt = feature.check(**options)
     tabs_of = _per_table(feature, [t for t, _ in cx], radii)
@@ -1398,13 +1391,13 @@ def counted_atoms(table, heavy_only=None):
     return np.flatnonzero(keep), np.concatenate(([0], np.cumsum(counts))).astype(np.int32)
 
 
-def _pose_batch(poses, table):
+def _pose_batch(poses, table, mismatch="the poses must be of the given AtomTable"):
     """(table, xyz float32 [M, T, 3] in the table's grouped order) of an ``AtomTable.poses`` batch, a table, or xyz with
-    ``table``"""
+    ``table``; ``mismatch``: what to say of a batch or table that is not ``table``"""
     if isinstance(poses, (Poses, AtomTable)):
         own = poses.table if isinstance(poses, Poses) else poses
         if table is not None and own is not table:
-            raise ValueError("the poses must be of the given AtomTable")
+            raise ValueError(mismatch)
         return own, (poses.xyz if isinstance(poses, Poses) else poses.xyz[None])
     if table is None:
         raise ValueError("coordinates need table=, the AtomTable they are poses of")
@@ -1475,8 +1468,7 @@ def pose_contacts(poses, cutoff=5.0, heavy_only=None, device=None, api=None, chu
     t, xyz = _pose_batch(poses, table)
     keep, atom_ptr = counted_atoms(t, heavy_only)
     api = api or _lib.get()
-    if device is None:
-        device = "cuda" if api is _lib._API else "cpu"
+    device = _default_device(api, device)
     if t.n_residues > api.fcc_capacity(0):
         _lib._check(-2, "drgnn_pose_contacts")
     if chunk is None:
@@ -1504,6 +1496,23 @@ def pose_common_raw(api, bits_a, bits_b):
     return out
 
 
+def _blocked_pairs(raw, A, B, block, dtype, symmetric=False):
+    """``raw(rows of A, rows of B)`` over blocks of at most ``block`` rows a side, as one tensor [len(A), len(B)].
+    ``symmetric`` (B is A): a diagonal block gets one tensor object as both sides, a block above the diagonal is computed
+    once and mirrored by ``.t()``"""
+    if len(A) <= block and len(B) <= block:
+        return raw(A, B)
+    out = torch.empty((len(A), len(B)), dtype=dtype, device=A.device)
+    for i in range(0, len(A), block):
+        for j in range(i if symmetric else 0, len(B), block):
+            rows = A[i:i + block]
+            part = raw(rows, rows if symmetric and j == i else B[j:j + block])
+            out[i:i + block, j:j + block] = part
+            if symmetric and j > i:
+                out[j:j + block, i:i + block] = part.t()
+    return out
+
+
 def _common_device(a, b=None):
     """common contacts of two ``PoseContacts`` as an int32 tensor [M, M2] on their device; calls of at most
     drgnn_fcc_capacity(1) poses a side"""
@@ -1516,14 +1525,7 @@ def _common_device(a, b=None):
     wa, wb = a.bits.reshape(len(a), W), b.bits.reshape(len(b), W)
     if len(a) == 0 or len(b) == 0:
         return torch.zeros((len(a), len(b)), dtype=torch.int32, device=wa.device)
-    cap = a.api.fcc_capacity(1)
-    if len(a) <= cap and len(b) <= cap:
-        return pose_common_raw(a.api, wa, wb)
-    out = torch.empty((len(a), len(b)), dtype=torch.int32, device=wa.device)
-    for i in range(0, len(a), cap):
-        for j in range(0, len(b), cap):
-            out[i:i + cap, j:j + cap] = pose_common_raw(a.api, wa[i:i + cap], wb[j:j + cap])
-    return out
+    return _blocked_pairs(lambda x, y: pose_common_raw(a.api, x, y), wa, wb, a.api.fcc_capacity(1), torch.int32)
 
 
 def common_contacts(a, b=None):
@@ -1573,6 +1575,37 @@ class PoseClusters(object):
         return order.astype(np.int64), means
 
 
+def _cluster_launch(api, call, q, rows, min_size):
+    """One clustering call, whatever the rule (csrc/drgnn_posecluster.h): ``q`` holds the rule's own fields and ``rows``
+    is one of its inputs on the device, a row per pose; this adds the shared fields and the outputs, runs ``call`` (the
+    entry point) and returns the dict ``pose_cluster_raw`` documents"""
+    if api is _lib._API:
+        _lib.require_device(rows)
+    M = int(rows.shape[0])
+    nb = torch.zeros((2, M, (M + 63) // 64), dtype=torch.int64, device=rows.device)
+    res = torch.zeros((3, M), dtype=torch.int32, device=rows.device)
+    k = torch.zeros(1, dtype=torch.int32, device=rows.device)
+    q.n_poses, q.min_size = M, int(min_size)
+    q.neighbours, q.transposed = nb[0].data_ptr(), nb[1].data_ptr()
+    q.labels, q.centres, q.sizes, q.n_clusters = res[0].data_ptr(), res[1].data_ptr(), res[2].data_ptr(), k.data_ptr()
+    call(q, _lib.current_stream(rows))
+    K = int(k.cpu()[0])
+    res, nb = res.cpu().numpy(), nb.cpu().numpy().view(np.uint64)
+    return {"labels": res[0].copy(), "centres": res[1, :K].copy(), "sizes": res[2, :K].copy(), "neighbours": nb[0].copy(),
+            "transposed": nb[1].copy()}
+
+
+def _check_min_size(min_size):
+    if int(min_size) != min_size or int(min_size) < 1:
+        raise ValueError("min_size must be an integer >= 1")
+
+
+def _pose_clusters(r, n_contacts):
+    """the ``PoseClusters`` of a raw result (None: of no poses)"""
+    r = r or dict.fromkeys(("labels", "centres", "sizes"), np.zeros(0, np.int32))
+    return PoseClusters(r["labels"].astype(np.int64), r["centres"].astype(np.int64), r["sizes"].astype(np.int64), n_contacts)
+
+
 def pose_cluster_raw(api, common, n_contacts, cutoff_fcc=0.6, cutoff_reverse=0.45, min_size=4, device="cpu"):
     """One drgnn_pose_cluster call (include/drgnn.h): ``common`` int32 [M, M] and ``n_contacts`` int32 [M] as numpy arrays
     or tensors on ``device``.  Returns a dict of numpy arrays: labels int32 [M], centres / sizes int32 [K], neighbours /
@@ -1585,22 +1618,9 @@ def pose_cluster_raw(api, common, n_contacts, cutoff_fcc=0.6, cutoff_reverse=0.4
     M = int(d_n.shape[0])
     if d_c.dtype != torch.int32 or d_n.dtype != torch.int32 or tuple(d_c.shape) != (M, M):
         raise ValueError("common int32 [M, M] and n_contacts int32 [M]")
-    if api is _lib._API:
-        _lib.require_device(d_c)
-    MW = (M + 63) // 64
-    nb = torch.zeros((2, M, MW), dtype=torch.int64, device=d_c.device)
-    res = torch.zeros((3, M), dtype=torch.int32, device=d_c.device)
-    k = torch.zeros(1, dtype=torch.int32, device=d_c.device)
     q = _lib.PoseClusterRequest()
-    q.common, q.n_contacts, q.n_poses = d_c.data_ptr(), d_n.data_ptr(), M
-    q.cutoff_fcc, q.cutoff_reverse, q.min_size = float(cutoff_fcc), float(cutoff_reverse), int(min_size)
-    q.neighbours, q.transposed = nb[0].data_ptr(), nb[1].data_ptr()
-    q.labels, q.centres, q.sizes, q.n_clusters = res[0].data_ptr(), res[1].data_ptr(), res[2].data_ptr(), k.data_ptr()
-    api.pose_cluster(q, _lib.current_stream(d_c))
-    K = int(k.cpu()[0])
-    res, nb = res.cpu().numpy(), nb.cpu().numpy().view(np.uint64)
-    return {"labels": res[0].copy(), "centres": res[1, :K].copy(), "sizes": res[2, :K].copy(), "neighbours": nb[0].copy(),
-            "transposed": nb[1].copy()}
+    q.common, q.n_contacts, q.cutoff_fcc, q.cutoff_reverse = d_c.data_ptr(), d_n.data_ptr(), float(cutoff_fcc), float(cutoff_reverse)
+    return _cluster_launch(api, api.pose_cluster, q, d_n, min_size)
 
 
 def cluster_poses(poses_or_contacts, cutoff_fcc=0.6, strictness=0.75, min_size=4, **contact_options):
@@ -1615,8 +1635,7 @@ def cluster_poses(poses_or_contacts, cutoff_fcc=0.6, strictness=0.75, min_size=4
     for name, v in (("cutoff_fcc", cutoff_fcc), ("strictness", strictness)):
         if not (float(v) > 0.0 and float(v) <= 1.0):
             raise ValueError("%s must lie in (0, 1]" % name)
-    if int(min_size) != min_size or int(min_size) < 1:
-        raise ValueError("min_size must be an integer >= 1")
+    _check_min_size(min_size)
     c = poses_or_contacts
     if isinstance(c, PoseContacts):
         if contact_options:
@@ -1625,13 +1644,13 @@ def cluster_poses(poses_or_contacts, cutoff_fcc=0.6, strictness=0.75, min_size=4
         c = pose_contacts(c, **contact_options)
     M = len(c)
     if M == 0:
-        return PoseClusters(np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int64), c.n_contacts)
+        return _pose_clusters(None, c.n_contacts)
     if M > c.api.fcc_capacity(2):
         _lib._check(-2, "drgnn_pose_cluster")
     count = torch.from_numpy(c.n_contacts.astype(np.int32)).to(c.bits.device)
     r = pose_cluster_raw(c.api, _common_device(c), count, float(cutoff_fcc), float(cutoff_fcc) * float(strictness),
                          int(min_size), c.device)
-    return PoseClusters(r["labels"].astype(np.int64), r["centres"].astype(np.int64), r["sizes"].astype(np.int64), c.n_contacts)
+    return _pose_clusters(r, c.n_contacts)
 
 
 # ---- pairwise pose RMSD and RMSD clustering of poses (csrc/drgnn_rmsd.h) --------------------------------------------
@@ -1745,13 +1764,10 @@ def pose_rmsd(poses, rms=None, fit=None, kind=None, other=None, residues=None, d
     t, xyz = _pose_batch(poses, table)
     xyz2 = None
     if other is not None:
-        t2, xyz2 = _pose_batch(other, t if not isinstance(other, (Poses, AtomTable)) else None)
-        if t2 is not t:
-            raise ValueError("the other poses must be of the same AtomTable")
+        xyz2 = _pose_batch(other, t, "the other poses must be of the same AtomTable")[1]
     rms_idx, fit_idx = rmsd_selection(t, rms, fit, kind, residues)
     api = api or _lib.get()
-    if device is None:
-        device = "cuda" if api is _lib._API else "cpu"
+    device = _default_device(api, device)
     dev = torch.device(device)
     # only the selected atoms are uploaded
     cols = np.unique(np.concatenate((rms_idx, fit_idx if fit_idx is not None else rms_idx[:0])))
@@ -1766,22 +1782,7 @@ def pose_rmsd(poses, rms=None, fit=None, kind=None, other=None, residues=None, d
     up = lambda x: torch.from_numpy(np.ascontiguousarray(x[:, cols], dtype=np.float32)).to(dev)
     A = up(xyz)
     B = A if xyz2 is None else up(xyz2)
-    if M <= chunk and M2 <= chunk:
-        return pose_rmsd_raw(api, A, B, rms_idx, fit_idx)
-    out = torch.empty((M, M2), dtype=torch.float64, device=dev)
-    for i in range(0, M, chunk):
-        for j in range(0, M2, chunk):
-            if xyz2 is None and j < i:
-                continue
-            if xyz2 is None and j == i:
-                block = A[i:i + chunk]
-                out[i:i + chunk, i:i + chunk] = pose_rmsd_raw(api, block, block, rms_idx, fit_idx)
-                continue
-            part = pose_rmsd_raw(api, A[i:i + chunk], B[j:j + chunk], rms_idx, fit_idx)
-            out[i:i + chunk, j:j + chunk] = part
-            if xyz2 is None:
-                out[j:j + chunk, i:i + chunk] = part.t()
-    return out
+    return _blocked_pairs(lambda x, y: pose_rmsd_raw(api, x, y, rms_idx, fit_idx), A, B, chunk, torch.float64, xyz2 is None)
 
 
 def interface_residues(contacts, min_poses=1):
@@ -1808,21 +1809,9 @@ def pose_cluster_dist_raw(api, d, cutoff=7.5, min_size=4, device="cpu"):
     M = int(d_d.shape[0])
     if d_d.dtype != torch.float64 or tuple(d_d.shape) != (M, M):
         raise ValueError("d float64 [M, M]")
-    if api is _lib._API:
-        _lib.require_device(d_d)
-    MW = (M + 63) // 64
-    nb = torch.zeros((2, M, MW), dtype=torch.int64, device=d_d.device)
-    res = torch.zeros((3, M), dtype=torch.int32, device=d_d.device)
-    k = torch.zeros(1, dtype=torch.int32, device=d_d.device)
     q = _lib.PoseClusterDistRequest()
-    q.d, q.n_poses, q.cutoff, q.min_size = d_d.data_ptr(), M, float(cutoff), int(min_size)
-    q.neighbours, q.transposed = nb[0].data_ptr(), nb[1].data_ptr()
-    q.labels, q.centres, q.sizes, q.n_clusters = res[0].data_ptr(), res[1].data_ptr(), res[2].data_ptr(), k.data_ptr()
-    api.pose_cluster_dist(q, _lib.current_stream(d_d))
-    K = int(k.cpu()[0])
-    res, nb = res.cpu().numpy(), nb.cpu().numpy().view(np.uint64)
-    return {"labels": res[0].copy(), "centres": res[1, :K].copy(), "sizes": res[2, :K].copy(), "neighbours": nb[0].copy(),
-            "transposed": nb[1].copy()}
+    q.d, q.cutoff = d_d.data_ptr(), float(cutoff)
+    return _cluster_launch(api, api.pose_cluster_dist, q, d_d, min_size)
 
 
 def cluster_poses_rmsd(poses_or_matrix, cutoff=7.5, min_size=4, **rmsd_options):
@@ -1836,14 +1825,13 @@ def cluster_poses_rmsd(poses_or_matrix, cutoff=7.5, min_size=4, **rmsd_options):
     drgnn_rmsd_capacity(1) (4096) are refused (DrgnnError, capacity)."""
     if not (float(cutoff) > 0.0 and float(cutoff) < float("inf")):
         raise ValueError("cutoff must be a positive finite number")
-    if int(min_size) != min_size or int(min_size) < 1:
-        raise ValueError("min_size must be an integer >= 1")
+    _check_min_size(min_size)
     if "other" in rmsd_options:
         raise ValueError("clustering takes the square matrix of one batch: no other=")
     p = poses_or_matrix
     is_matrix = (torch.is_tensor(p) or isinstance(p, np.ndarray)) and p.ndim == 2
     api = rmsd_options.get("api") or _lib.get()
-    device = rmsd_options.get("device") or (str(p.device) if torch.is_tensor(p) and is_matrix else "cuda" if api is _lib._API else "cpu")
+    device = _default_device(api, rmsd_options.get("device") or (str(p.device) if torch.is_tensor(p) and is_matrix else None))
     if is_matrix:
         if set(rmsd_options) - {"api", "device"}:
             raise ValueError("rmsd options %s come with poses, not with a matrix" % sorted(set(rmsd_options) - {"api", "device"}))
@@ -1857,9 +1845,9 @@ def cluster_poses_rmsd(poses_or_matrix, cutoff=7.5, min_size=4, **rmsd_options):
     if M == 0:
         if not is_matrix:
             pose_rmsd(p, **dict(rmsd_options, api=api, device=device))             # (the options are checked; nothing is launched)
-        return PoseClusters(np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int64), None)
+        return _pose_clusters(None, None)
     d = p if is_matrix else pose_rmsd(p, **dict(rmsd_options, api=api, device=device))
     if torch.is_tensor(d):
         d = d.to(torch.float64)
     r = pose_cluster_dist_raw(api, d, float(cutoff), int(min_size), device)
-    return PoseClusters(r["labels"].astype(np.int64), r["centres"].astype(np.int64), r["sizes"].astype(np.int64), None)
+    return _pose_clusters(r, None)

@@ -334,6 +334,45 @@ def check_hand_relations(api, device):
     check_raw_cluster(api, device, rng.integers(0, 12, size=(70, 70)), n3, cutoff_fcc=0.5, strictness=0.5, min_size=2)
 
 
+def one_relation_inputs(M):
+    """(common int32 [M, M], n_contacts, d float64 [M, M]): the FCC rule at cutoff_fcc 0.5, strictness 1 on (common, 128)
+    and the distance rule at cutoff 64 on d = 128 - common define one relation.  Every quotient and threshold is a binary
+    fraction, so the two predicates agree exactly, the pairs with common = 64 (on the threshold of both) included"""
+    rng = np.random.default_rng(11)
+    common = rng.integers(0, 64, size=(M, M))
+    high = rng.random((M, M)) < 0.06
+    common[high] = rng.integers(64, 129, size=int(high.sum()))
+    common[rng.integers(0, M, 30), rng.integers(0, M, 30)] = 64
+    common = np.triu(common, 1)
+    common = (common + common.T).astype(np.int32)
+    np.fill_diagonal(common, 128)
+    return common, np.full(M, 128, dtype=np.int32), 128.0 - common.astype(np.float64)
+
+
+def check_one_relation_one_greedy(api, device, M):
+    """the two rules drive one relation kernel and one greedy: on inputs that define the same relation, pose_cluster_raw
+    and pose_cluster_dist_raw give identical outputs, and both equal fcc_ref.cluster on that relation.
+    On the references alone: M = 65: 16 pairs at the threshold, 8 clusters, 14 poses in none, 3 tied centre choices;
+    M = 130: 24, 15, 10, 7"""
+    import rmsd_ref
+    from deeprank_gnn_amd.interface import pose_cluster_dist_raw, pose_cluster_raw
+    common, n, d = one_relation_inputs(M)
+    nb = R.neighbours_of(common, n, 0.5, 1.0)
+    labels, centres, sizes, ties = R.cluster(nb, 3)
+    at_threshold = int((np.triu(common, 1) == 64).sum())
+    print("M = %d: %d pairs at the threshold, %d clusters, %d poses in none, %d tied centre choices"
+          % (M, at_threshold, len(centres), (labels == -1).sum(), ties))
+    assert np.array_equal(rmsd_ref.neighbours_of(d, 64.0), nb)
+    assert len(centres) >= 2 and (labels == -1).sum() >= 1 and ties >= 1 and at_threshold >= 1
+    by_fcc = pose_cluster_raw(api, common, n, 0.5, 0.5, 3, device)
+    by_dist = pose_cluster_dist_raw(api, d, 64.0, 3, device)
+    want = {"neighbours": nb, "transposed": nb.T, "labels": labels, "centres": centres, "sizes": sizes}
+    for key in ("neighbours", "transposed", "labels", "centres", "sizes"):
+        assert by_fcc[key].dtype == by_dist[key].dtype and np.array_equal(by_fcc[key], by_dist[key]), (M, key)
+        got = unpack(by_fcc[key], M) if key in ("neighbours", "transposed") else by_fcc[key]
+        assert np.array_equal(got, want[key]), (M, key)
+
+
 # ---- 4 independence ----------------------------------------------------------------------------------------------------
 def check_independence(api, device, M=17):
     """M, chunk, place and run change no bit; blocks of common; permutations.  Returns the batch's PoseContacts"""
@@ -485,7 +524,7 @@ class NoLaunch(object):
     """an api that answers capacities and fails on every call that would launch"""
 
     def __init__(self, api):
-        self.fcc_capacity = api.fcc_capacity
+        self.fcc_capacity, self.rmsd_capacity = api.fcc_capacity, api.rmsd_capacity
 
 
 def check_value_errors():

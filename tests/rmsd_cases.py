@@ -18,6 +18,7 @@ import numpy as np
 import fcc_cases as F
 import rmsd_ref as R
 from bsa_cases import atn, same_bits
+from fcc_cases import NoLaunch, kw
 from hse_cases import RZ, Chains
 
 K_MEASURED = 8.7           # measured: 8.70 (1ATN, kind "ligand"); the 130-pose family 7.50, 1ATN "interface" 6.55, the hand-made sets <= 2.2
@@ -27,10 +28,6 @@ STAGE = 32                 # RM_K of drgnn_rmsd.h: atoms staged at a time
 BATCH_SIZES = (1, 2, 17, 33, 65)
 CUTOFF, MIN_SIZE = 3.0, 4  # of the end-to-end clustering of the 130-pose family (kind "ligand")
 _CACHE = {}
-
-
-def kw(api, device):
-    return {"api": api, "device": device}
 
 
 def once(key, make):
@@ -393,13 +390,6 @@ def check_interface_residues(api, device):
 
 
 # ---- 4 capacity, empty batch, refusals ---------------------------------------------------------------------------------
-class NoLaunch(object):
-    """an api that answers capacities and fails on every call that would launch"""
-
-    def __init__(self, api):
-        self.rmsd_capacity = api.rmsd_capacity
-
-
 def check_empty_batch(api, device):
     from deeprank_gnn_amd.interface import AtomTable, cluster_poses_rmsd, pose_rmsd
     t, p = family(3)

@@ -52,6 +52,11 @@ def test_hand_written_relations(api):
     C.check_hand_relations(api, "cpu")
 
 
+@pytest.mark.parametrize("M", [65, 130])
+def test_both_rules_run_one_relation_and_one_greedy(M, api):
+    C.check_one_relation_one_greedy(api, "cpu", M)
+
+
 def test_results_do_not_depend_on_batch_chunk_place_or_run(api):
     C.check_independence(api, "cpu")
 
