@@ -1,12 +1,16 @@
 """Metrics (drgnn_metrics) on the MI355X: the golden cases of the reference's own Metrics, 10^6 and 4*10^6 fp32
 predictions with ties and NaN against tests/metrics_ref.py, repeat launches bit for bit, device tensors read in place,
-and the published scripts' flow NeuralNet(pretrained_model=...) -> test() -> get_metrics('test', threshold=...)."""
+and the published scripts' flow NeuralNet(pretrained_model=...) -> test() -> get_metrics('test', threshold=...).
+The low-digit passes of the sort (the large cases' fp32 predictions rounded to 1/64 leave the low five digits of every
+key zero) and the wave, workgroup and tile boundaries are covered by the cases of tests/metrics_cases.py, against the
+reference and bit for bit against the host emulation; `_large` covers scale and the saturation of G."""
 import os
 
 import numpy as np
 import pytest
 import torch
 
+import metrics_cases as MC
 import metrics_ref as R
 from helpers import GOLDEN
 from test_metrics import CASES, NAMES, attrs_of, check_attrs, run_case
@@ -69,6 +73,37 @@ def test_device_tensors_are_read_in_place():
     m32 = Metrics(torch.from_numpy(pred).cuda(), t, "lrmsd", 4.0)      # fp32: converted on the device
     assert m32._pred.is_cuda
     check_attrs(attrs_of(m32), attrs_of(m), exact_floats=True)
+
+
+# ---- tile, wave and digit boundaries with keys of eight varying bytes (tests/metrics_cases.py) ---------------------
+@pytest.fixture(scope="module")
+def api():
+    from deeprank_gnn_amd import _lib
+    return _lib.get()
+
+
+@pytest.mark.parametrize("target", MC.RANK_TARGETS)
+@pytest.mark.parametrize("n", MC.SIZES)
+def test_ranking_of_wide_keys_at_boundaries(n, target, api):
+    from emu_api import emu
+    MC.assert_same_results(MC.check_ranking(n, target, api, "cuda"), MC.check_ranking(n, target, emu(), None))
+
+
+@pytest.mark.parametrize("target", MC.REG_TARGETS)
+@pytest.mark.parametrize("n", MC.SIZES)
+def test_regression_scores_and_median_at_boundaries(n, target, api):
+    from emu_api import emu
+    MC.assert_same_results(MC.check_regression(n, target, api, "cuda"), MC.check_regression(n, target, emu(), None))
+
+
+@pytest.mark.parametrize("n", MC.CLASS_SIZES)
+def test_class_matrix_ignores_outside_labels_across_tiles(n, api):
+    from emu_api import emu
+    MC.assert_same_results(MC.check_classes(n, api, "cuda"), MC.check_classes(n, emu(), None))
+
+
+def test_boundary_ranking_twice_bit_identical(api):
+    MC.check_repeat(api, "cuda")
 
 
 # ---- the published scripts' flow -----------------------------------------------------------------------------------

@@ -3,7 +3,8 @@
 The numpy statement (tests/metrics_ref.py) against the reference's own Metrics (tests/golden/metrics.npz), the emulated
 kernels against both: counts, ranking, hit rate, max_error and the median exactly, the other regression scores to rtol
 1e-9 (sklearn's float64 sums run in another order).  Ties, NaN, the ValueError cases and get_metrics after
-train / eval / test.  CPU only."""
+train / eval / test; the cases of tests/metrics_cases.py (keys of eight varying bytes at the wave, workgroup and tile
+boundaries).  CPU only."""
 import json
 import os
 
@@ -11,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import metrics_cases as MC
 import metrics_ref as R
 from helpers import GOLDEN, NODE_FEATURES
 
@@ -197,6 +199,32 @@ def test_emulated_and_host_restatement_bit_identical_twice(capsys):
     a = attrs_of(Metrics(c["pred"], c["y"], "irmsd", 4, api=emu()))
     b = attrs_of(Metrics(c["pred"], c["y"], "irmsd", 4, api=emu()))
     check_attrs(a, b, exact_floats=True)
+
+
+# ---- tile, wave and digit boundaries with keys of eight varying bytes (tests/metrics_cases.py) ---------------------
+@pytest.mark.parametrize("target", MC.RANK_TARGETS)
+@pytest.mark.parametrize("n", MC.SIZES)
+def test_ranking_of_wide_keys_at_boundaries(n, target, capsys):
+    from emu_api import emu
+    MC.check_ranking(n, target, emu(), None)
+
+
+@pytest.mark.parametrize("target", MC.REG_TARGETS)
+@pytest.mark.parametrize("n", MC.SIZES)
+def test_regression_scores_and_median_at_boundaries(n, target, capsys):
+    from emu_api import emu
+    MC.check_regression(n, target, emu(), None)
+
+
+@pytest.mark.parametrize("n", MC.CLASS_SIZES)
+def test_class_matrix_ignores_outside_labels_across_tiles(n, capsys):
+    from emu_api import emu
+    MC.check_classes(n, emu(), None)
+
+
+def test_boundary_ranking_twice_bit_identical(capsys):
+    from emu_api import emu
+    MC.check_repeat(emu(), None)
 
 
 # ---- NeuralNet.get_metrics -----------------------------------------------------------------------------------------
