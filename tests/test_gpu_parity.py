@@ -354,6 +354,12 @@ def test_lean_topology_on_the_device_equals_the_full_build(weights):
                          "COLPTR1": (n0 + g, C + 1), "ROWIDX1": (e0, E1), "CL1": (n0, C), "MPTR1": (n0 + g, nc1[g] + 1),
                          "MEM1": (n0, C), "HORD": (n0, N), "HMP0": (n0 + g, C + 1), "HSPLIT": (4 * g, 4)}[name]
                 np.testing.assert_array_equal(a[lo:lo + n], b[lo:lo + n], err_msg="%s graph %d" % (name, g))
+        if weights:       # W0 by slot and the fixed-point sums W1: the same bits from both chains
+            for name, count in (("W0", np.diff(eptr)), ("W1", ne1)):
+                a, b = (t.weights(name).cpu().numpy().view(np.int32) for t in (full, lean))
+                for g in range(full.n_graphs):
+                    np.testing.assert_array_equal(a[eptr[g]:eptr[g] + count[g]], b[eptr[g]:eptr[g] + count[g]],
+                                                  err_msg="%s graph %d" % (name, g))
 
 
 @pytest.mark.gpu
