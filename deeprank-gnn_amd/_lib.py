@@ -203,6 +203,28 @@ class PoseClusterRequest(ctypes.Structure):
                 ("n_clusters", _vp)]
 
 
+class ContactCountsRequest(ctypes.Structure):
+    """drgnn_contact_counts_request (include/drgnn.h): contact bit rows of M poses and a grouping of them as lists;
+    ``host_*`` are addresses of host copies of the lists."""
+    _fields_ = [("bits", _vp), ("order", _vp), ("group_ptr", _vp), ("host_order", _vp), ("host_group_ptr", _vp),
+                ("n_poses", _c_i64), ("n_chain_a", _c_i64), ("n_chain_b", _c_i64), ("n_groups", _c_i64), ("n_listed", _c_i64),
+                ("counts", _vp), ("residues", _vp)]
+
+
+class ConsensusNumeratorsRequest(ctypes.Structure):
+    """drgnn_consensus_numerators_request (include/drgnn.h): contact bit rows of poses, the counts of G groups and the
+    row of counts every pose is scored against; ``host_row`` is the address of a host copy of ``row``."""
+    _fields_ = [("bits", _vp), ("counts", _vp), ("row", _vp), ("host_row", _vp),
+                ("n_poses", _c_i64), ("n_chain_a", _c_i64), ("n_chain_b", _c_i64), ("n_groups", _c_i64), ("numerators", _vp)]
+
+
+class ConsensusBitsRequest(ctypes.Structure):
+    """drgnn_consensus_bits_request (include/drgnn.h): the counts of G groups and a threshold each;
+    ``host_min_count`` is the address of a host copy of ``min_count``."""
+    _fields_ = [("counts", _vp), ("min_count", _vp), ("host_min_count", _vp),
+                ("n_chain_a", _c_i64), ("n_chain_b", _c_i64), ("n_groups", _c_i64), ("bits", _vp), ("n_contacts", _vp)]
+
+
 class PoseRmsdRequest(ctypes.Structure):
     """drgnn_pose_rmsd_request (include/drgnn.h): two pose batches of one topology and the fit / rms atom lists;
     ``host_*`` are addresses of host copies of the lists."""
@@ -459,6 +481,11 @@ class Api(object):
         lib.drgnn_pose_contacts.argtypes = [ctypes.POINTER(PoseContactsRequest), _vp]
         lib.drgnn_pose_common.argtypes = [ctypes.POINTER(PoseCommonRequest), _vp]
         lib.drgnn_pose_cluster.argtypes = [ctypes.POINTER(PoseClusterRequest), _vp]
+        lib.drgnn_consensus_capacity.argtypes = [_c_i32]
+        lib.drgnn_consensus_capacity.restype = _c_i32
+        lib.drgnn_pose_contact_counts.argtypes = [ctypes.POINTER(ContactCountsRequest), _vp]
+        lib.drgnn_pose_consensus_numerators.argtypes = [ctypes.POINTER(ConsensusNumeratorsRequest), _vp]
+        lib.drgnn_pose_consensus_bits.argtypes = [ctypes.POINTER(ConsensusBitsRequest), _vp]
         lib.drgnn_rmsd_capacity.argtypes = [_c_i32]
         lib.drgnn_rmsd_capacity.restype = _c_i32
         lib.drgnn_rmsd_workspace.argtypes = [_c_i64] * 4 + [ctypes.POINTER(_c_i64)]
@@ -765,6 +792,18 @@ class Api(object):
 
     def pose_cluster(self, request, stream):
         _check(self.lib.drgnn_pose_cluster(ctypes.byref(request), stream), "drgnn_pose_cluster")
+
+    def consensus_capacity(self, what):
+        return int(self.lib.drgnn_consensus_capacity(int(what)))
+
+    def pose_contact_counts(self, request, stream):
+        _check(self.lib.drgnn_pose_contact_counts(ctypes.byref(request), stream), "drgnn_pose_contact_counts")
+
+    def pose_consensus_numerators(self, request, stream):
+        _check(self.lib.drgnn_pose_consensus_numerators(ctypes.byref(request), stream), "drgnn_pose_consensus_numerators")
+
+    def pose_consensus_bits(self, request, stream):
+        _check(self.lib.drgnn_pose_consensus_bits(ctypes.byref(request), stream), "drgnn_pose_consensus_bits")
 
     def rmsd_capacity(self, what):
         return int(self.lib.drgnn_rmsd_capacity(int(what)))

@@ -2611,6 +2611,109 @@ int drgnn_pose_cluster(const drgnn_pose_cluster_request* q, void* stream) {
     return pose_cluster_run(rule, q, PC_RELATION_KERNEL(k_fcc_relation), stream);
 }
 
+// ---- contact consensus of poses (drgnn_consensus.h) ----------------------------------------------------
+int32_t drgnn_consensus_capacity(int32_t what) { return what == 0 ? FC_RCAP : what == 1 ? CS_GCAP : what == 2 ? CS_ECAP : what == 3 ? CS_NCAP : what == 4 ? CS_PCAP : -1; }
+
+// the counts shared by the three calls: 0, or the error
+static int cons_shape(int64_t nA, int64_t nB, int64_t G) {
+    if (nA < 0 || nB < 0 || G < 0) return DRGNN_E_ARG;
+    if (nA + nB > FC_RCAP || G > CS_GCAP || G * nA * nB > CS_ECAP) return DRGNN_E_CAPACITY;      // (the product is below 2^38)
+    return 0;
+}
+
+int drgnn_pose_contact_counts(const drgnn_contact_counts_request* q, void* stream) {
+    if (!q || !q->host_group_ptr) return DRGNN_E_ARG;
+    const int64_t M = q->n_poses, nA = q->n_chain_a, nB = q->n_chain_b, G = q->n_groups, L = q->n_listed;
+    if (M < 0 || L < 0) return DRGNN_E_ARG;
+    if (int e = cons_shape(nA, nB, G)) return e;
+    if (M > CS_PCAP || L > CS_PCAP) return DRGNN_E_CAPACITY;
+    const int64_t WB = (nB + 63) / 64;
+    if (!q->group_ptr || (L > 0 && (!q->order || !q->host_order))) return DRGNN_E_ARG;
+    if ((L > 0 && nA * WB > 0 && !q->bits) || (G * nA * nB > 0 && !q->counts) || (G * (nA + nB) > 0 && !q->residues)) return DRGNN_E_ARG;
+    const int32_t* gp = q->host_group_ptr;
+    if (gp[0] != 0 || gp[G] != L) return DRGNN_E_ARG;
+    for (int64_t g = 0; g < G; ++g)
+        if (gp[g + 1] < gp[g]) return DRGNN_E_ARG;
+    for (int64_t p = 0; p < L; ++p)
+        if (q->host_order[p] < 0 || q->host_order[p] >= M) return DRGNN_E_ARG;
+    ConsCountArgs a;
+    memset(&a, 0, sizeof(a));
+    a.bits = (const pc_word*)q->bits; a.order = q->order; a.group_ptr = q->group_ptr; a.n_a = (int)nA; a.n_b = (int)nB;
+    a.n_groups = (int)G; a.n_listed = L; a.counts = q->counts; a.residues = q->residues;
+    const size_t count_bytes = (size_t)(G * nA * nB) * sizeof(int32_t), res_bytes = (size_t)(G * (nA + nB)) * sizeof(int32_t);
+    const int blocks = (int)std::min<int64_t>((L + DRGNN_NWAVES - 1) / DRGNN_NWAVES, CS_COUNT_WGS);
+#ifdef DRGNN_EMU
+    (void)stream;
+    if (count_bytes) memset(q->counts, 0, count_bytes);
+    if (res_bytes) memset(q->residues, 0, res_bytes);
+    for (int b = 0; b < blocks; ++b) cs_count(a, b, blocks);
+#else
+    if (count_bytes) HIP_TRY(hipMemsetAsync(q->counts, 0, count_bytes, (hipStream_t)stream));
+    if (res_bytes) HIP_TRY(hipMemsetAsync(q->residues, 0, res_bytes, (hipStream_t)stream));
+    if (blocks > 0 && nA + nB > 0) {
+        hipLaunchKernelGGL(k_cons_count, dim3((unsigned)blocks), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+#endif
+    return 0;
+}
+
+int drgnn_pose_consensus_numerators(const drgnn_consensus_numerators_request* q, void* stream) {
+    if (!q) return DRGNN_E_ARG;
+    const int64_t M = q->n_poses, nA = q->n_chain_a, nB = q->n_chain_b, G = q->n_groups;
+    if (M < 0) return DRGNN_E_ARG;
+    if (int e = cons_shape(nA, nB, G)) return e;
+    if (M > CS_NCAP) return DRGNN_E_CAPACITY;
+    const int64_t WB = (nB + 63) / 64;
+    if (M > 0 && (!q->row || !q->host_row || !q->numerators || (nA * WB > 0 && !q->bits) || (G * nA * nB > 0 && !q->counts))) return DRGNN_E_ARG;
+    for (int64_t m = 0; m < M; ++m)
+        if (q->host_row[m] < -1 || q->host_row[m] >= G) return DRGNN_E_ARG;
+    if (M == 0) return 0;
+    ConsNumerArgs a;
+    memset(&a, 0, sizeof(a));
+    a.bits = (const pc_word*)q->bits; a.counts = q->counts; a.row = q->row; a.n_a = (int)nA; a.n_b = (int)nB;
+    a.numerators = (long long*)q->numerators;
+#ifdef DRGNN_EMU
+    (void)stream;
+    std::unique_ptr<ConsNumerShared> lds(new ConsNumerShared);
+    for (int64_t m = 0; m < M; ++m) cs_numer(a, m, *lds);
+#else
+    hipLaunchKernelGGL(k_cons_numer, dim3((unsigned)M), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+#endif
+    return 0;
+}
+
+int drgnn_pose_consensus_bits(const drgnn_consensus_bits_request* q, void* stream) {
+    if (!q) return DRGNN_E_ARG;
+    const int64_t nA = q->n_chain_a, nB = q->n_chain_b, G = q->n_groups;
+    if (int e = cons_shape(nA, nB, G)) return e;
+    const int64_t WB = (nB + 63) / 64;
+    if (G > 0 && (!q->min_count || !q->host_min_count || !q->n_contacts || (nA * WB > 0 && !q->bits) || (nA * nB > 0 && !q->counts))) return DRGNN_E_ARG;
+    for (int64_t g = 0; g < G; ++g)
+        if (q->host_min_count[g] < 1) return DRGNN_E_ARG;
+    if (G == 0) return 0;
+    ConsBitsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.counts = q->counts; a.min_count = q->min_count; a.n_a = (int)nA; a.n_b = (int)nB;
+    a.bits = (pc_word*)q->bits; a.n_contacts = q->n_contacts;
+    const int blocks = (int)((nA * WB + CS_BW - 1) / CS_BW);
+#ifdef DRGNN_EMU
+    (void)stream;
+    memset(q->n_contacts, 0, (size_t)G * sizeof(int32_t));
+    for (int g = 0; g < (int)G; ++g)
+        for (int b = 0; b < blocks; ++b) cs_bits(a, g, b);
+#else
+    static_assert(CS_GCAP <= 65535, "the groups fit the grid's y");
+    HIP_TRY(hipMemsetAsync(q->n_contacts, 0, (size_t)G * sizeof(int32_t), (hipStream_t)stream));
+    if (blocks > 0) {
+        hipLaunchKernelGGL(k_cons_bits, dim3((unsigned)blocks, (unsigned)G), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+#endif
+    return 0;
+}
+
 // ---- pairwise pose RMSD and RMSD clustering of poses (drgnn_rmsd.h) ----------------------------------
 int32_t drgnn_rmsd_capacity(int32_t what) { return what == 0 ? RM_PCAP : what == 1 ? PC_CCAP : -1; }
 

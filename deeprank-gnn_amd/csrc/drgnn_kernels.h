@@ -18,6 +18,7 @@
 #include "drgnn_depth.h"
 #include "drgnn_posecluster.h"
 #include "drgnn_fcc.h"
+#include "drgnn_consensus.h"
 #include "drgnn_rmsd.h"
 #include "drgnn_pack.h"
 #include "drgnn_metrics.h"
@@ -1035,6 +1036,14 @@ __global__ void __launch_bounds__(DRGNN_NTHREADS) k_fcc_greedy(PoseClusterArgs a
     __shared__ PoseGreedyShared smem_fg;
     pc_greedy(a, smem_fg);
 }
+// contact consensus of poses (drgnn_consensus.h): a wave per list entry; one workgroup per pose; per CS_BW words of a group (the
+// group by y)
+__global__ void __launch_bounds__(DRGNN_NTHREADS) k_cons_count(ConsCountArgs a) { cs_count(a, (int)blockIdx.x, (int)gridDim.x); }
+__global__ void __launch_bounds__(DRGNN_NTHREADS) k_cons_numer(ConsNumerArgs a) {
+    __shared__ ConsNumerShared smem_cn;
+    cs_numer(a, (int64_t)blockIdx.x, smem_cn);
+}
+__global__ void __launch_bounds__(DRGNN_NTHREADS) k_cons_bits(ConsBitsArgs a) { cs_bits(a, (int)blockIdx.y, (int)blockIdx.x); }
 // pairwise pose RMSD (drgnn_rmsd.h): one workgroup per pose of one side; per tile of pose pairs; a wave per word of the
 // neighbour relation (the greedy clustering is k_fcc_greedy)
 __global__ void __launch_bounds__(DRGNN_NTHREADS) k_rmsd_prepare(RmsdArgs a, int side) {

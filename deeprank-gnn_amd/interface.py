@@ -52,6 +52,14 @@ or by their pairwise RMSD (the rule of HADDOCK's ``cluster_struc`` and of ClusPr
     D = pose_rmsd(poses, kind="ligand")                        # float64 [M, M] on the device: pairwise l-RMSD
     clusters = cluster_poses_rmsd(D, cutoff=7.5, min_size=4)   # the same PoseClusters
 
+A set too large for the pairwise stages is first looked at as a whole (CONSRANK: how often the poses have each contact,
+and how well each pose agrees with that; csrc/drgnn_consensus.h), linear in the poses:
+
+    c = pose_contacts(all_decoys)                              # 10^4 - 10^5 poses
+    best = np.argsort(-consensus_scores(c))[:4096]             # the poses that agree best with the set
+    clusters = cluster_poses(c.select(best))
+    maps = consensus_contacts(clusters.consensus(c.select(best)))   # a PoseContacts: the consensus contacts of every cluster
+
 and the residue depth (``depth``: Biopython's residue depth; the surface is a dot surface of the solvent-accessible
 surface restricted to its outer component instead of MSMS' triangulation, about one vertex spacing away from it):
 
@@ -1435,6 +1443,18 @@ class PoseContacts(object):
         a, b = np.nonzero(on)
         return np.stack((a, b + self.n_a), axis=1).astype(np.int32)
 
+    def select(self, index):
+        """the ``PoseContacts`` of the poses ``index`` (int [K], in that order; a pose may repeat), its bits gathered on
+        the device: what carries the best few thousand of a large set into ``cluster_poses``"""
+        idx = np.asarray(index)
+        if idx.dtype == bool or idx.ndim != 1 or (idx.size and not np.issubdtype(idx.dtype, np.integer)):
+            raise ValueError("index must be a list of pose indices")
+        idx = idx.astype(np.int64)
+        if idx.size and (idx.min() < 0 or idx.max() >= len(self)):
+            raise ValueError("index must lie in [0, %d)" % len(self))
+        bits = self.bits.index_select(0, torch.from_numpy(idx).to(self.bits.device))
+        return PoseContacts(self.table, bits, self.n_contacts[idx], self.api, self.device, self.cutoff, self.heavy_only)
+
 
 def pose_contacts_raw(api, xyz, atom_ptr, n_chain_a, cutoff=5.0, device="cpu"):
     """One drgnn_pose_contacts call (include/drgnn.h) over numpy arrays: xyz float32 [M, T, 3] of the counted atoms.
@@ -1574,6 +1594,15 @@ class PoseClusters(object):
         order = np.lexsort((np.arange(len(self)), means if ascending else -means))
         return order.astype(np.int64), means
 
+    def consensus(self, contacts):
+        """the ``ContactFrequency`` of every cluster: ``contact_frequency(contacts, groups=self.labels,
+        n_groups=len(self))`` for the ``PoseContacts`` of the clustered poses"""
+        if not isinstance(contacts, PoseContacts):
+            raise ValueError("a consensus is taken from PoseContacts (pose_contacts)")
+        if len(contacts) != self.labels.shape[0]:
+            raise ValueError("%d poses for %d labels" % (len(contacts), self.labels.shape[0]))
+        return contact_frequency(contacts, groups=self.labels, n_groups=len(self))
+
 
 def _cluster_launch(api, call, q, rows, min_size):
     """One clustering call, whatever the rule (csrc/drgnn_posecluster.h): ``q`` holds the rule's own fields and ``rows``
@@ -1651,6 +1680,235 @@ def cluster_poses(poses_or_contacts, cutoff_fcc=0.6, strictness=0.75, min_size=4
     r = pose_cluster_raw(c.api, _common_device(c), count, float(cutoff_fcc), float(cutoff_fcc) * float(strictness),
                          int(min_size), c.device)
     return _pose_clusters(r, c.n_contacts)
+
+
+# ---- contact consensus of poses (csrc/drgnn_consensus.h) ------------------------------------------------------------
+def _i32(a, dev):
+    """(host int32 array, the same on ``dev``)"""
+    host = np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+    return host, torch.from_numpy(host).to(dev)
+
+
+def _contact_words(bits, n_b):
+    """(the contiguous tensor, M, nA) of contact words int64 [M, nA, ceil(n_b / 64)]"""
+    if bits.dtype != torch.int64 or bits.dim() != 3 or int(bits.shape[2]) != (int(n_b) + 63) // 64:
+        raise ValueError("bits int64 [M, nA, %d]" % ((int(n_b) + 63) // 64))
+    return bits.contiguous(), int(bits.shape[0]), int(bits.shape[1])
+
+
+def contact_counts_raw(api, bits, n_b, order, group_ptr):
+    """One drgnn_pose_contact_counts call (include/drgnn.h): ``bits`` a tensor of words int64 [M, nA, WB], ``order`` int
+    [L] and ``group_ptr`` int [G+1] numpy arrays.  Returns (counts int32 [G, nA, n_b], residues int32 [G, nA + n_b]) as
+    tensors on the device of ``bits``."""
+    bits, M, nA = _contact_words(bits, n_b)
+    if api is _lib._API:
+        _lib.require_device(bits)
+    h_order, d_order = _i32(order, bits.device)
+    h_ptr, d_ptr = _i32(group_ptr, bits.device)
+    G = max(len(h_ptr) - 1, 0)
+    counts = torch.empty((G, nA, int(n_b)), dtype=torch.int32, device=bits.device)
+    residues = torch.empty((G, nA + int(n_b)), dtype=torch.int32, device=bits.device)
+    q = _lib.ContactCountsRequest()
+    q.bits, q.order, q.group_ptr = bits.data_ptr(), d_order.data_ptr(), d_ptr.data_ptr()
+    q.host_order, q.host_group_ptr = h_order.ctypes.data, h_ptr.ctypes.data
+    q.n_poses, q.n_chain_a, q.n_chain_b, q.n_groups, q.n_listed = M, nA, int(n_b), G, len(h_order)
+    q.counts, q.residues = counts.data_ptr(), residues.data_ptr()
+    api.pose_contact_counts(q, _lib.current_stream(bits))
+    return counts, residues
+
+
+def consensus_numerators_raw(api, bits, n_b, counts, row):
+    """One drgnn_pose_consensus_numerators call: ``bits`` words int64 [M, nA, WB] and ``counts`` int32 [G, nA, n_b] as
+    tensors on one device, ``row`` int [M] a numpy array (-1: no row).  Returns int64 [M] on that device."""
+    bits, M, nA = _contact_words(bits, n_b)
+    if counts.dtype != torch.int32 or counts.dim() != 3 or tuple(counts.shape[1:]) != (nA, int(n_b)) or counts.device != bits.device:
+        raise ValueError("counts int32 [G, %d, %d] on the device of bits" % (nA, int(n_b)))
+    if api is _lib._API:
+        _lib.require_device(bits)
+    counts = counts.contiguous()
+    h_row, d_row = _i32(row, bits.device)
+    if len(h_row) != M:
+        raise ValueError("%d rows for %d poses" % (len(h_row), M))
+    out = torch.empty(M, dtype=torch.int64, device=bits.device)
+    q = _lib.ConsensusNumeratorsRequest()
+    q.bits, q.counts, q.row, q.host_row = bits.data_ptr(), counts.data_ptr(), d_row.data_ptr(), h_row.ctypes.data
+    q.n_poses, q.n_chain_a, q.n_chain_b, q.n_groups, q.numerators = M, nA, int(n_b), int(counts.shape[0]), out.data_ptr()
+    api.pose_consensus_numerators(q, _lib.current_stream(bits))
+    return out
+
+
+def consensus_bits_raw(api, counts, min_count):
+    """One drgnn_pose_consensus_bits call: ``counts`` int32 [G, nA, nB] a tensor, ``min_count`` int [G] a numpy array.
+    Returns (bits int64 [G, nA, WB], n_contacts int32 [G]) as tensors on the device of ``counts``."""
+    if counts.dtype != torch.int32 or counts.dim() != 3:
+        raise ValueError("counts int32 [G, nA, nB]")
+    if api is _lib._API:
+        _lib.require_device(counts)
+    counts = counts.contiguous()
+    G, nA, nB = (int(v) for v in counts.shape)
+    h_min, d_min = _i32(min_count, counts.device)
+    if len(h_min) != G:
+        raise ValueError("%d thresholds for %d groups" % (len(h_min), G))
+    bits = torch.empty((G, nA, (nB + 63) // 64), dtype=torch.int64, device=counts.device)
+    n = torch.empty(G, dtype=torch.int32, device=counts.device)
+    q = _lib.ConsensusBitsRequest()
+    q.counts, q.min_count, q.host_min_count = counts.data_ptr(), d_min.data_ptr(), h_min.ctypes.data
+    q.n_chain_a, q.n_chain_b, q.n_groups, q.bits, q.n_contacts = nA, nB, G, bits.data_ptr(), n.data_ptr()
+    api.pose_consensus_bits(q, _lib.current_stream(counts))
+    return bits, n
+
+
+def _group_rows(groups, M, G, what="groups"):
+    """int64 [M] from ``groups`` (None: all 0), checked against [-1, G)"""
+    if groups is None:
+        g = np.zeros(M, dtype=np.int64)
+    else:
+        if torch.is_tensor(groups):
+            groups = groups.detach().cpu().numpy()
+        g = np.asarray(groups)
+        if g.ndim != 1 or g.shape[0] != M:
+            raise ValueError("%d %s for %d poses" % (g.shape[0] if g.ndim == 1 else g.size, what, M))
+        if g.size and not np.issubdtype(g.dtype, np.integer):
+            raise ValueError("%s must be integers" % what)
+        g = g.astype(np.int64)
+    if g.size and (g.min() < -1 or g.max() >= G):
+        raise ValueError("%s must lie in [-1, %d)" % (what, G))
+    return g
+
+
+class ContactFrequency(object):
+    """``contact_frequency``: ``counts`` int32 [G, nA, nB] (the poses of group g that have residue a of the first chain
+    and residue b of the second in contact) and ``residues`` int32 [G, nA + nB] (the poses of g in which a residue has any
+    contact) on the device, ``n_poses`` int64 [G] on the host; ``table``, ``n_a`` / ``n_b``, ``cutoff`` and
+    ``heavy_only`` of the ``PoseContacts`` it was counted from.  The accessors copy to the host once."""
+
+    def __init__(self, contacts, counts, residues, n_poses):
+        self.counts, self.residues, self.n_poses = counts, residues, n_poses
+        self.table, self.api, self.device = contacts.table, contacts.api, contacts.device
+        self.cutoff, self.heavy_only, self.n_a, self.n_b = contacts.cutoff, contacts.heavy_only, contacts.n_a, contacts.n_b
+        self._host = {}
+
+    def __len__(self):
+        return int(self.n_poses.shape[0])
+
+    def _on_host(self, name, g):
+        if not 0 <= int(g) < len(self):
+            raise ValueError("group must lie in [0, %d)" % len(self))
+        if name not in self._host:
+            self._host[name] = getattr(self, name).cpu().numpy()
+        return self._host[name][int(g)]
+
+    def _fraction(self, name, g):
+        c, n = self._on_host(name, g).astype(np.float64), self.n_poses[int(g)]
+        return c / np.float64(n) if n > 0 else np.zeros_like(c)
+
+    def fraction(self, g=0):
+        """float64 [nA, nB]: the fraction of the poses of group g with each contact (zeros for a group without poses)"""
+        return self._fraction("counts", g)
+
+    def residue_fraction(self, g=0):
+        """float64 [R]: the fraction of the poses of group g in which each residue of the table is in contact: a
+        per-residue array for ``attach_residue_features``"""
+        return self._fraction("residues", g)
+
+    def pairs(self, g=0, min_count=1):
+        """int32 [n, 3]: (residue of the first chain, residue of the second, count) of the contacts at least
+        ``min_count`` poses of group g have, both indices into the table's residues, sorted by the pair"""
+        if int(min_count) != min_count or int(min_count) < 1:
+            raise ValueError("min_count must be an integer >= 1")
+        c = self._on_host("counts", g)
+        a, b = np.nonzero(c >= int(min_count))
+        return np.stack((a, b + self.n_a, c[a, b]), axis=1).astype(np.int32)
+
+    def interface_residues(self, g=0, min_poses=1):
+        """int64 [n], sorted: the residues in contact in at least ``min_poses`` poses of group g (for one group of all
+        poses: ``interface_residues(contacts, min_poses)``)"""
+        if int(min_poses) != min_poses or int(min_poses) < 1:
+            raise ValueError("min_poses must be an integer >= 1")
+        return np.flatnonzero(self._on_host("residues", g) >= int(min_poses)).astype(np.int64)
+
+
+def contact_frequency(contacts, groups=None, n_groups=None):
+    """How often the poses of a ``PoseContacts``, or of every group of them, have each residue pair in contact: the
+    consensus map of CONSRANK (Oliva, Vangone and Cavallo 2013; tests/consensus_ref.py states the rule), counted on the
+    device in one launch, linear in the poses.  ``groups`` int [M]: the group of every pose, -1 for none
+    (``PoseClusters.labels`` as it is); None: one group of all poses.  ``n_groups``: G (default: the largest group + 1).
+    A group lists its poses in index order.  Returns a ``ContactFrequency``."""
+    if not isinstance(contacts, PoseContacts):
+        raise ValueError("a contact frequency is taken from PoseContacts (pose_contacts)")
+    M = len(contacts)
+    if n_groups is not None and (int(n_groups) != n_groups or int(n_groups) < 0):
+        raise ValueError("n_groups must be an integer >= 0")
+    if groups is None:
+        G = 1 if n_groups is None else int(n_groups)
+        g = _group_rows(None, M, max(G, 1)) if G > 0 else np.full(M, -1, dtype=np.int64)
+    else:
+        g = _group_rows(groups, M, np.iinfo(np.int32).max if n_groups is None else int(n_groups))
+        G = int(n_groups) if n_groups is not None else int(g.max()) + 1 if g.size else 0
+    order = np.argsort(g, kind="stable")
+    order = order[g[order] >= 0]
+    group_ptr = np.concatenate(([0], np.cumsum(np.bincount(g[order], minlength=G)))).astype(np.int64)
+    counts, residues = contact_counts_raw(contacts.api, contacts.bits, contacts.n_b, order, group_ptr)
+    return ContactFrequency(contacts, counts, residues, np.diff(group_ptr).astype(np.int64))
+
+
+def consensus_scores(contacts, frequency=None, groups=None, leave_one_out=False, return_numerators=False):
+    """float64 [M]: the CONSRANK score of every pose of a ``PoseContacts``, the mean frequency of its contacts:
+    ``num / (n * N)`` with num the sum of ``counts[row]`` over the pose's n contacts and N the poses of its row, one
+    float64 division on the integers; 0.0 for a pose without contacts or in no group.  Without ``frequency`` the one of
+    ``contacts`` and ``groups`` is built and every pose is scored against its own group; ``leave_one_out`` then leaves
+    the pose itself out of its frequency, ``(num - n) / (n * (N - 1))`` (0.0 in a group of one).  With a ``frequency``
+    any ``PoseContacts`` of its topology, library and device is scored, ``groups`` naming the row of every pose (None:
+    row 0).  ``return_numerators``: (scores, num int64 [M])."""
+    if not isinstance(contacts, PoseContacts):
+        raise ValueError("consensus scores are taken of PoseContacts (pose_contacts)")
+    M = len(contacts)
+    if frequency is None:
+        frequency = contact_frequency(contacts, groups)
+        row = _group_rows(groups, M, max(len(frequency), 1))
+    else:
+        if leave_one_out:
+            raise ValueError("leave_one_out needs the frequency built in the same call: a given frequency may not list the pose once")
+        f = frequency
+        if not isinstance(f, ContactFrequency):
+            raise ValueError("frequency is a ContactFrequency (contact_frequency)")
+        if (contacts.n_a, contacts.n_b) != (f.n_a, f.n_b) or contacts.api is not f.api or torch.device(contacts.device) != torch.device(f.device):
+            raise ValueError("the contacts and the frequency must be of one topology, library and device")
+        row = _group_rows(groups, M, len(f))
+    api, step = contacts.api, max(1, contacts.api.consensus_capacity(3))
+    parts = [consensus_numerators_raw(api, contacts.bits[lo:lo + step], contacts.n_b, frequency.counts, row[lo:lo + step])
+             for lo in range(0, M, step)]
+    num = np.concatenate([p.cpu().numpy() for p in parts]).astype(np.int64) if parts else np.zeros(0, np.int64)
+    n = contacts.n_contacts.astype(np.int64)
+    N = np.where(row >= 0, frequency.n_poses[np.maximum(row, 0)] if len(frequency) else 0, 0).astype(np.int64)
+    top, den = (num - n, n * (N - 1)) if leave_one_out else (num, n * N)
+    scores = np.zeros(M, dtype=np.float64)
+    has = den > 0
+    scores[has] = top[has].astype(np.float64) / den[has].astype(np.float64)
+    return (scores, num) if return_numerators else scores
+
+
+def consensus_contacts(frequency, min_fraction=0.5, min_count=None):
+    """The consensus map of every group of a ``ContactFrequency`` as a ``PoseContacts`` of G rows: contact (a, b) of row g
+    is set when at least ``min_count`` poses of g have it; ``min_fraction`` in (0, 1] means ``max(1, ceil(min_fraction *
+    N_g))`` (float64), ``min_count`` an integer >= 1 (or one per group) instead.  ``fcc_matrix(poses, consensus)``,
+    ``common_contacts``, ``interface_residues`` and ``pose_rmsd(kind="interface", residues=...)`` take it like any
+    pose."""
+    if not isinstance(frequency, ContactFrequency):
+        raise ValueError("consensus contacts are taken from a ContactFrequency (contact_frequency)")
+    G = len(frequency)
+    if min_count is None:
+        if not (float(min_fraction) > 0.0 and float(min_fraction) <= 1.0):
+            raise ValueError("min_fraction must lie in (0, 1]")
+        least = np.array([max(1, int(np.ceil(np.float64(min_fraction) * np.float64(n)))) for n in frequency.n_poses], dtype=np.int64)
+    else:
+        least = np.asarray(min_count)
+        if (least.size and not np.issubdtype(least.dtype, np.integer)) or least.shape not in ((), (G,)) or (least < 1).any():
+            raise ValueError("min_count must be an integer >= 1, or one per group")
+        least = np.broadcast_to(least, (G,)).astype(np.int64)
+    bits, n = consensus_bits_raw(frequency.api, frequency.counts, least)
+    return PoseContacts(frequency.table, bits, n.cpu().numpy().astype(np.int64), frequency.api, frequency.device,
+                        frequency.cutoff, frequency.heavy_only)
 
 
 # ---- pairwise pose RMSD and RMSD clustering of poses (csrc/drgnn_rmsd.h) --------------------------------------------

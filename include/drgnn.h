@@ -987,6 +987,75 @@ int drgnn_pose_contacts(const drgnn_pose_contacts_request* req, void* stream);
 int drgnn_pose_common(const drgnn_pose_common_request* req, void* stream);
 int drgnn_pose_cluster(const drgnn_pose_cluster_request* req, void* stream);
 
+/* ---- contact consensus of poses (drgnn_consensus.h) ----------------------------------------------------
+ * The consensus of a set of poses of one two-chain topology, or of every group of it (CONSRANK; Oliva, Vangone and Cavallo
+ * 2013): how many poses have each residue pair in contact, how well a pose agrees with that, and the contacts at least
+ * min_count poses share.  Linear in the poses; integers from end to end.  tests/consensus_ref.py states the rule.
+ *
+ * Shared by the three calls: bits u64 [M, nA, WB] as drgnn_pose_contacts leaves them, nA = n_chain_a, nB = n_chain_b,
+ * WB = ceil(nB / 64).  The bits of a row's last word at or past nB are ignored on input (never counted, never used as an
+ * index) and zero on output.  Index lists are also given as HOST arrays: every check comes from them.
+ *
+ * drgnn_pose_contact_counts: a grouping as lists, order i32 [n_listed] of pose indices and group_ptr i32 [G+1] of offsets
+ * into order; a pose may be listed in no group, in one, in several, or several times in one (it then counts as often).
+ * Outputs: counts i32 [G, nA, nB], counts[g, a, b] = the listed poses of g with bit (a, b) set; residues i32 [G, nA+nB]: for
+ * r < nA the listed poses of g with any bit in row r, for r >= nA those with bit (a, r - nA) set for some a (poses, not
+ * contacts).  A group without listed poses gets rows of zeros.  The call zeroes both outputs on the stream and one launch,
+ * a wave per list entry, adds into them with integer atomics: integer adds commute, so no result depends on an order. */
+typedef struct drgnn_contact_counts_request {
+    const uint64_t* bits;
+    const int32_t* order;
+    const int32_t* group_ptr;
+    const int32_t* host_order;         /* the lists in host memory */
+    const int32_t* host_group_ptr;
+    int64_t n_poses, n_chain_a, n_chain_b, n_groups, n_listed;
+    int32_t* counts;
+    int32_t* residues;
+} drgnn_contact_counts_request;
+
+/* drgnn_pose_consensus_numerators: for the n_poses poses of bits (any poses of the topology of counts i32 [G, nA, nB]) and
+ * row i32 [n_poses]: numerators[m] = 0 when row[m] < 0, else the sum of counts[row[m], a, b] over the set bits (a, b) of
+ * pose m; i64 [n_poses].  Over the set it was counted from this is the row sum of drgnn_pose_common.  One launch. */
+typedef struct drgnn_consensus_numerators_request {
+    const uint64_t* bits;
+    const int32_t* counts;
+    const int32_t* row;
+    const int32_t* host_row;           /* row in host memory */
+    int64_t n_poses, n_chain_a, n_chain_b, n_groups;
+    int64_t* numerators;
+} drgnn_consensus_numerators_request;
+
+/* drgnn_pose_consensus_bits: bits u64 [G, nA, WB] with bit (a, b) set iff counts[g, a, b] >= min_count[g], in the layout of
+ * drgnn_pose_contacts (what drgnn_pose_common and the rest take like any pose), and n_contacts i32 [G], the set bits of
+ * every group.  The call zeroes n_contacts on the stream; one launch writes the words and adds their popcounts to it. */
+typedef struct drgnn_consensus_bits_request {
+    const int32_t* counts;
+    const int32_t* min_count;
+    const int32_t* host_min_count;     /* min_count in host memory */
+    int64_t n_chain_a, n_chain_b, n_groups;
+    uint64_t* bits;
+    int32_t* n_contacts;
+} drgnn_consensus_bits_request;
+
+/* the documented capacities: what = 0 residues of a complex, both chains (drgnn_fcc_capacity(0), 3072: what
+ * drgnn_pose_contacts serves), 1 groups of one call (65535: the launch's second grid dimension), 2 entries of counts,
+ * G nA nB (2^31 - 1: 32-bit indices), 3 poses of one drgnn_pose_consensus_numerators call (4194303: a workgroup each, the
+ * launch stays below 2^32 work-items; split the call), 4 poses and entries of order of one drgnn_pose_contact_counts call
+ * (2^31 - 1: 32-bit indices); -1 otherwise.  Pure host. */
+int32_t drgnn_consensus_capacity(int32_t what);
+
+/* All three: DRGNN_E_ARG before any launch for a null request or pointer, a negative count, and
+ *   counts:      a group_ptr that does not start at 0, decreases or ends elsewhere than n_listed, an order entry outside
+ *                [0, n_poses)
+ *   numerators:  a row entry outside [-1, n_groups)
+ *   bits:        a min_count below 1
+ * DRGNN_E_CAPACITY beyond drgnn_consensus_capacity (split the groups or the poses over several calls).  No allocation, no
+ * workspace, no synchronisation, no floating point; the outputs do not depend on what their buffers held.  Empty inputs
+ * return 0 without a launch. */
+int drgnn_pose_contact_counts(const drgnn_contact_counts_request* req, void* stream);
+int drgnn_pose_consensus_numerators(const drgnn_consensus_numerators_request* req, void* stream);
+int drgnn_pose_consensus_bits(const drgnn_consensus_bits_request* req, void* stream);
+
 /* ---- pairwise pose RMSD and RMSD clustering of poses (drgnn_rmsd.h) ------------------------------------
  * The pose-by-pose RMSD matrix of poses of one topology (pairwise l-RMSD / i-RMSD) and the clustering rule of HADDOCK's
  * cluster_struc and of ClusPro on it.  tests/rmsd_ref.py states both rules.
