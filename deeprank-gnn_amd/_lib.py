@@ -252,6 +252,22 @@ class DepthRequest(ctypes.Structure):
                 ("out", _vp), ("status", _vp)]
 
 
+# the entry points int f(const request*, hipStream_t): (method of Api, C symbol, record).  The table gives each its
+# argtypes and Api a method (self, request, stream) that raises DrgnnError on a non-zero return
+REQUEST_CALLS = (
+    ("iface_count", "drgnn_iface_count", IfaceRequest), ("dock_scores", "drgnn_dock_scores", ScoreRequest),
+    ("bsa_residues", "drgnn_bsa_residues", BsaRequest), ("hse_residues", "drgnn_hse_residues", HseRequest),
+    ("depth_residues", "drgnn_depth_residues", DepthRequest), ("iface_pack", "drgnn_iface_pack", PackRequest),
+    ("pose_contacts", "drgnn_pose_contacts", PoseContactsRequest), ("pose_common", "drgnn_pose_common", PoseCommonRequest),
+    ("pose_cluster", "drgnn_pose_cluster", PoseClusterRequest),
+    ("pose_contact_counts", "drgnn_pose_contact_counts", ContactCountsRequest),
+    ("pose_consensus_numerators", "drgnn_pose_consensus_numerators", ConsensusNumeratorsRequest),
+    ("pose_consensus_bits", "drgnn_pose_consensus_bits", ConsensusBitsRequest),
+    ("pose_rmsd", "drgnn_pose_rmsd", PoseRmsdRequest), ("pose_cluster_dist", "drgnn_pose_cluster_dist", PoseClusterDistRequest))
+# the limit queries int32 drgnn_<name>(int32 what): Api gets a method <name>(self, what) for each
+CAPACITY_CALLS = ("bsa_capacity", "hse_capacity", "depth_capacity", "pack_capacity", "fcc_capacity", "consensus_capacity",
+                  "rmsd_capacity")
+
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p)
 
 
@@ -459,39 +475,15 @@ class Api(object):
         lib.drgnn_train_epoch_opt.argtypes = [ctypes.POINTER(EpochPlan), ctypes.POINTER(Optim), _vp, _c_i64, _vp, _vp, _vp]
         lib.drgnn_iface_workspace_bytes.argtypes = [_c_i64] * 4
         lib.drgnn_iface_workspace_bytes.restype = _c_i64
-        lib.drgnn_iface_count.argtypes = [ctypes.POINTER(IfaceRequest), _vp]
         lib.drgnn_iface_fill.argtypes = [ctypes.POINTER(IfaceRequest)] + [_c_i64] * 3 + [_vp] * 9
-        lib.drgnn_dock_scores.argtypes = [ctypes.POINTER(ScoreRequest), _vp]
-        lib.drgnn_bsa_capacity.argtypes = [_c_i32]
-        lib.drgnn_bsa_capacity.restype = _c_i32
-        lib.drgnn_bsa_residues.argtypes = [ctypes.POINTER(BsaRequest), _vp]
-        lib.drgnn_hse_capacity.argtypes = [_c_i32]
-        lib.drgnn_hse_capacity.restype = _c_i32
-        lib.drgnn_hse_residues.argtypes = [ctypes.POINTER(HseRequest), _vp]
-        lib.drgnn_depth_capacity.argtypes = [_c_i32]
-        lib.drgnn_depth_capacity.restype = _c_i32
         lib.drgnn_depth_workspace.argtypes = [_c_i64, _c_i64, _c_i32, ctypes.POINTER(_c_i64)]
         lib.drgnn_depth_workspace.restype = _c_i64
-        lib.drgnn_depth_residues.argtypes = [ctypes.POINTER(DepthRequest), _vp]
-        lib.drgnn_pack_capacity.argtypes = [_c_i32]
-        lib.drgnn_pack_capacity.restype = _c_i32
-        lib.drgnn_iface_pack.argtypes = [ctypes.POINTER(PackRequest), _vp]
-        lib.drgnn_fcc_capacity.argtypes = [_c_i32]
-        lib.drgnn_fcc_capacity.restype = _c_i32
-        lib.drgnn_pose_contacts.argtypes = [ctypes.POINTER(PoseContactsRequest), _vp]
-        lib.drgnn_pose_common.argtypes = [ctypes.POINTER(PoseCommonRequest), _vp]
-        lib.drgnn_pose_cluster.argtypes = [ctypes.POINTER(PoseClusterRequest), _vp]
-        lib.drgnn_consensus_capacity.argtypes = [_c_i32]
-        lib.drgnn_consensus_capacity.restype = _c_i32
-        lib.drgnn_pose_contact_counts.argtypes = [ctypes.POINTER(ContactCountsRequest), _vp]
-        lib.drgnn_pose_consensus_numerators.argtypes = [ctypes.POINTER(ConsensusNumeratorsRequest), _vp]
-        lib.drgnn_pose_consensus_bits.argtypes = [ctypes.POINTER(ConsensusBitsRequest), _vp]
-        lib.drgnn_rmsd_capacity.argtypes = [_c_i32]
-        lib.drgnn_rmsd_capacity.restype = _c_i32
         lib.drgnn_rmsd_workspace.argtypes = [_c_i64] * 4 + [ctypes.POINTER(_c_i64)]
         lib.drgnn_rmsd_workspace.restype = _c_i64
-        lib.drgnn_pose_rmsd.argtypes = [ctypes.POINTER(PoseRmsdRequest), _vp]
-        lib.drgnn_pose_cluster_dist.argtypes = [ctypes.POINTER(PoseClusterDistRequest), _vp]
+        for _, symbol, record in REQUEST_CALLS:
+            getattr(lib, symbol).argtypes = [ctypes.POINTER(record), _vp]
+        for name in CAPACITY_CALLS:
+            getattr(lib, "drgnn_" + name).argtypes, getattr(lib, "drgnn_" + name).restype = [_c_i32], _c_i32
         if lib.drgnn_abi_version() != 5:
             raise DrgnnError("ABI mismatch in %s" % path)
 
@@ -757,57 +749,6 @@ class Api(object):
     def iface_workspace_bytes(self, n_complexes, max_res_a, max_res_b, n_residues):
         return int(self.lib.drgnn_iface_workspace_bytes(int(n_complexes), int(max_res_a), int(max_res_b), int(n_residues)))
 
-    def iface_count(self, request, stream):
-        _check(self.lib.drgnn_iface_count(ctypes.byref(request), stream), "drgnn_iface_count")
-
-    def dock_scores(self, request, stream):
-        _check(self.lib.drgnn_dock_scores(ctypes.byref(request), stream), "drgnn_dock_scores")
-
-    def bsa_capacity(self, what):
-        return int(self.lib.drgnn_bsa_capacity(int(what)))
-
-    def bsa_residues(self, request, stream):
-        _check(self.lib.drgnn_bsa_residues(ctypes.byref(request), stream), "drgnn_bsa_residues")
-
-    def hse_capacity(self, what):
-        return int(self.lib.drgnn_hse_capacity(int(what)))
-
-    def hse_residues(self, request, stream):
-        _check(self.lib.drgnn_hse_residues(ctypes.byref(request), stream), "drgnn_hse_residues")
-
-    def pack_capacity(self, what):
-        return int(self.lib.drgnn_pack_capacity(int(what)))
-
-    def iface_pack(self, request, stream):
-        _check(self.lib.drgnn_iface_pack(ctypes.byref(request), stream), "drgnn_iface_pack")
-
-    def fcc_capacity(self, what):
-        return int(self.lib.drgnn_fcc_capacity(int(what)))
-
-    def pose_contacts(self, request, stream):
-        _check(self.lib.drgnn_pose_contacts(ctypes.byref(request), stream), "drgnn_pose_contacts")
-
-    def pose_common(self, request, stream):
-        _check(self.lib.drgnn_pose_common(ctypes.byref(request), stream), "drgnn_pose_common")
-
-    def pose_cluster(self, request, stream):
-        _check(self.lib.drgnn_pose_cluster(ctypes.byref(request), stream), "drgnn_pose_cluster")
-
-    def consensus_capacity(self, what):
-        return int(self.lib.drgnn_consensus_capacity(int(what)))
-
-    def pose_contact_counts(self, request, stream):
-        _check(self.lib.drgnn_pose_contact_counts(ctypes.byref(request), stream), "drgnn_pose_contact_counts")
-
-    def pose_consensus_numerators(self, request, stream):
-        _check(self.lib.drgnn_pose_consensus_numerators(ctypes.byref(request), stream), "drgnn_pose_consensus_numerators")
-
-    def pose_consensus_bits(self, request, stream):
-        _check(self.lib.drgnn_pose_consensus_bits(ctypes.byref(request), stream), "drgnn_pose_consensus_bits")
-
-    def rmsd_capacity(self, what):
-        return int(self.lib.drgnn_rmsd_capacity(int(what)))
-
     def rmsd_workspace(self, n_a, n_b, n_fit, n_rms):
         """(bytes, offsets [3]) of drgnn_rmsd_workspace; DrgnnError for counts the call refuses"""
         off = (_c_i64 * 3)()
@@ -816,15 +757,6 @@ class Api(object):
             _check(-2, "drgnn_rmsd_workspace")
         return n, list(off)
 
-    def pose_rmsd(self, request, stream):
-        _check(self.lib.drgnn_pose_rmsd(ctypes.byref(request), stream), "drgnn_pose_rmsd")
-
-    def pose_cluster_dist(self, request, stream):
-        _check(self.lib.drgnn_pose_cluster_dist(ctypes.byref(request), stream), "drgnn_pose_cluster_dist")
-
-    def depth_capacity(self, what):
-        return int(self.lib.drgnn_depth_capacity(int(what)))
-
     def depth_workspace(self, n_atoms, n_complexes, n_dots):
         """(bytes, offsets [10]) of drgnn_depth_workspace; DrgnnError for counts the call refuses"""
         off = (_c_i64 * 10)()
@@ -832,9 +764,6 @@ class Api(object):
         if n < 0:
             _check(-2, "drgnn_depth_workspace")
         return n, [int(v) for v in off]
-
-    def depth_residues(self, request, stream):
-        _check(self.lib.drgnn_depth_residues(ctypes.byref(request), stream), "drgnn_depth_residues")
 
     def iface_fill(self, request, n_nodes, n_edges, n_iedges, node_residue, pos, chain, type_, edge_index, dist,
                    internal_edge_index, internal_dist, stream):
@@ -953,6 +882,25 @@ class Api(object):
         _check(self.lib.drgnn_adam_step_opt(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(step),
                                             param.numel(), ctypes.byref(optim), stream), "drgnn_adam_step_opt")
 
+
+def _request_call(name, symbol):
+    def call(self, request, stream):
+        _check(getattr(self.lib, symbol)(ctypes.byref(request), stream), symbol)
+    call.__name__ = name
+    return call
+
+
+def _capacity_call(name):
+    def call(self, what):
+        return int(getattr(self.lib, "drgnn_" + name)(int(what)))
+    call.__name__ = name
+    return call
+
+
+for _name, _symbol, _ in REQUEST_CALLS:
+    setattr(Api, _name, _request_call(_name, _symbol))
+for _name in CAPACITY_CALLS:
+    setattr(Api, _name, _capacity_call(_name))
 
 _API = None
 
