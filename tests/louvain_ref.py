@@ -15,8 +15,10 @@ def _quality(adj, comm, K, two_m):
     return two_m * inside - sum(k * k for k in K)
 
 
-def _level(adj, two_m):
-    """One level on the weighted graph adj[u] = {v: A[u][v]} (A[u][u] = 2 x self-loop weight)."""
+def _level(adj, two_m, ties=None, log=None):
+    """One level on the weighted graph adj[u] = {v: A[u][v]} (A[u][u] = 2 x self-loop weight).
+    ties: a dict that receives {(pass, node): sorted communities attaining the node's best score} for every
+    visit at which two or more attain it; log: a list that receives (nodes moved, gain of N) of every pass."""
     n = len(adj)
     deg = [sum(row.values()) for row in adj]
     comm = list(range(n))
@@ -40,6 +42,10 @@ def _level(adj, two_m):
                 s = two_m * k - K[c] * ki
                 if best is None or s > best[0] or (s == best[0] and c < best[1]):
                     best = (s, c)
+            if ties is not None and best is not None:
+                top = sorted(c for c, k in kic.items() if c != own and two_m * k - K[c] * ki == best[0])
+                if len(top) > 1:
+                    ties[(passes, i)] = top
             to = best[1] if best is not None and best[0] > s_own else own
             K[to] += ki
             comm[i] = to
@@ -47,15 +53,22 @@ def _level(adj, two_m):
         passes += 1
         new = _quality(adj, comm, K, two_m)
         gain, cur = new - cur, new
+        if log is not None:
+            log.append((moved, gain))
         if moved == 0 or _below(gain, two_m):
             return comm, cur, passes
 
 
-def louvain(pairs, n):
-    """pairs: iterable of (u, v) (one direction or both, repeats allowed, u == v a self-loop), n nodes.
-    Returns (labels list, (recorded levels, total passes), modularity float)."""
+def louvain(pairs, n, trace=None):
+    """pairs: iterable of (u, v) (one direction or both, repeats allowed, u == v a self-loop; an entry with an end
+    outside [0, n) is dropped), n nodes.
+    Returns (labels list, (recorded levels, total passes), modularity float).
+    trace: a list that receives one dict per level that was run, recorded or not: nodes, entries and longest row
+    of the level's graph, (nodes moved, gain of N) of each of its passes, its N, the ties of its visits (_level) and whether it was recorded."""
     adj = [dict() for _ in range(n)]
     for u, v in {(min(int(u), int(v)), max(int(u), int(v))) for u, v in pairs}:
+        if u < 0 or v >= n:
+            continue
         adj[u][v] = 2 if u == v else 1
         adj[v][u] = adj[u][v]
     two_m = sum(sum(row.values()) for row in adj)
@@ -65,9 +78,14 @@ def louvain(pairs, n):
     levels = passes = 0
     rec = None
     while True:
-        comm, q, p = _level(adj, two_m)
+        ties, log = ({}, []) if trace is not None else (None, None)
+        comm, q, p = _level(adj, two_m, ties, log)
         passes += p
-        if levels > 0 and _below(q - rec, two_m):
+        stop = levels > 0 and _below(q - rec, two_m)
+        if trace is not None:
+            trace.append(dict(nodes=len(adj), entries=sum(len(row) for row in adj),
+                              longest_row=max(len(row) for row in adj), passes=log, N=q, ties=ties, recorded=not stop))
+        if stop:
             break
         levels, rec = levels + 1, q
         new_id = {}

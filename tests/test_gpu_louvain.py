@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import louvain_ref as R
+import test_louvain as T
 from helpers import GOLDEN
 from test_louvain import all_cases, check_precluster, _fixture_batch_without_clusters, _names
 
@@ -83,3 +84,51 @@ def test_neuralnet_louvain_trains_on_device(tmp_path):
     np.testing.assert_array_equal(nn.dataset.store.get(mol, "clustering/louvain/depth_0"), d0)
     nn.train(nepoch=2, validate=True, save_model=None, hdf5=None)
     assert len(nn.train_loss) == 2 and all(np.isfinite(nn.train_loss))
+
+
+# ---- beyond the fixture: the checks of tests/test_louvain.py (cases of tests/louvain_cases.py) on the device ---------
+def _device_kw():
+    from deeprank_gnn_amd import _lib
+    return dict(api=_lib.get(), device="cuda")
+
+
+def test_device_raw_edge_lists_one_by_one():
+    T.check_raw_cases_one_by_one(_device_kw())
+
+
+def test_device_raw_ends_outside_the_graph_in_a_batch():
+    T.check_ends_outside_in_a_batch(_device_kw())
+
+
+@pytest.mark.parametrize("with_large", [False, True], ids=["alone", "next_to_600_nodes"])
+def test_device_raw_edge_lists_in_one_batch(with_large):
+    T.check_raw_batch(_device_kw(), with_large)
+
+
+@pytest.mark.parametrize("which", ["capN", "capE"])
+def test_device_graph_beyond_the_caps_is_refused_alone(which):
+    T.check_refusal(_device_kw(), which)
+
+
+def test_device_gain_threshold_decides():
+    T.check_threshold(_device_kw())
+
+
+def test_device_lane_edges_per_graph():
+    T.check_lane_cases(_device_kw())
+
+
+def test_device_lane_edges_in_one_batch_with_the_threshold_graph_twice():
+    T.check_lane_batch(_device_kw(), repeat=True)
+
+
+def test_device_invariants_of_the_existing_cases():
+    T.check_existing_cases_invariants(_device_kw())
+
+
+def test_device_modularity_against_all_set_partitions():
+    T.check_against_enumeration(_device_kw())
+
+
+def test_device_precluster_louvain_on_lane_cases():
+    T.check_precluster_on_lane_cases(_device_kw())
