@@ -4,6 +4,12 @@
 //   hipcc --offload-arch=gfx950 -> csrc/libdrgnn.so        (the product)
 //   g++ -x c++ -DDRGNN_EMU      -> tests/emu/build/libdrgnn_emu.so (CPU test-suite only:
 //        every "launch" becomes a loop over workgroups on host pointers)
+//
+// The feature entry points (pose_cluster_run, then "stand-alone layers / pooling functions" down to drgnn_metrics) write their
+// launch sequence ONCE for both builds, with DRGNN_LAUNCH / DRGNN_EMU_ONLY / drgnn_clear of drgnn_launch.h: the checks, phases,
+// guards and early returns the CPU suite runs are the ones the GPU runs.  A new entry point touches three places: its block
+// function in a drgnn_<subsystem>.h, its __global__ wrapper in drgnn_kernels.h, and its checks and launches here.  A DRGNN_EMU
+// conditional in that range says why the builds differ.  The training path above and below it still spells both builds out.
 #define DRGNN_KERNELS_MAIN
 #include "drgnn_kernels.h"
 
@@ -22,7 +28,7 @@
         if (e_ != hipSuccess) return (int)e_;           \
     } while (0)
 #endif
-
+#include "drgnn_launch.h"
 
 
 // =====================================================================================
@@ -1728,12 +1734,7 @@ static int update_run(const UpdateCall& c) {
 // ---- clustering of poses (drgnn_posecluster.h) ---------------------------------------------------------
 // The part of drgnn_pose_cluster / drgnn_pose_cluster_dist that does not depend on the rule, after the entry point's own checks:
 // the shared checks, then the relation of `rule` and the greedy loop on it.  `q` is either request: their shared fields
-// have the same names; `relation` is the rule's instantiation of the relation kernel (the emulation calls pc_relation).
-#ifdef DRGNN_EMU
-#define PC_RELATION_KERNEL(k) nullptr
-#else
-#define PC_RELATION_KERNEL(k) k
-#endif
+// have the same names; `relation` is the rule's instantiation of the relation kernel, DRGNN_KERNEL(k_..._relation).
 template <class Rule, class Request, class Kernel>
 static int pose_cluster_run(Rule rule, const Request* q, Kernel relation, void* stream) {
     const int64_t M = q->n_poses;
@@ -1747,19 +1748,64 @@ static int pose_cluster_run(Rule rule, const Request* q, Kernel relation, void* 
     a.nb = (pc_word*)q->neighbours; a.nbt = (pc_word*)q->transposed;
     a.labels = q->labels; a.centres = q->centres; a.sizes = q->sizes; a.n_clusters = q->n_clusters;
     const int64_t words = M * ((M + 63) / 64), blocks = (words + DRGNN_NWAVES - 1) / DRGNN_NWAVES;
-#ifdef DRGNN_EMU
-    (void)stream; (void)relation;
-    for (int64_t b = 0; b < blocks; ++b) pc_relation(rule, a, b);
-    std::unique_ptr<PoseGreedyShared> lds(new PoseGreedyShared);
-    pc_greedy(a, *lds);
-#else
-    hipLaunchKernelGGL(relation, dim3((unsigned)blocks), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, rule, a);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_fcc_greedy, dim3(1), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-#endif
+    DRGNN_EMU_ONLY(std::unique_ptr<PoseGreedyShared> lds(new PoseGreedyShared);)
+    DRGNN_LAUNCH(relation, grid1(blocks), stream, pc_relation(rule, a, bx), rule, a);
+    DRGNN_LAUNCH(k_fcc_greedy, grid1(1), stream, pc_greedy(a, *lds), a);
     return 0;
 }
+
+// ---- request checks that several entry points share -----------------------------------------------------
+// the ragged layout on the host, whole, before anything is indexed through it: 0 = ap[0] <= ap[r] <= ap[r + 1], ap[R] = T;
+// with rp, 0 = rp[0] <= rp[c] <= rp[c + 1] <= R = rp[M]; with sp, rp[c] <= sp[c] <= rp[c + 1]
+static bool ragged_check(const int32_t* ap, const int32_t* rp, const int32_t* sp, int64_t T, int64_t R, int64_t M) {
+    if (ap[0] != 0 || ap[R] != T || (rp && (rp[0] != 0 || rp[M] != R))) return false;
+    for (int64_t r = 0; r < R; ++r)
+        if (ap[r + 1] < ap[r]) return false;
+    for (int64_t c = 0; rp && c < M; ++c)
+        if (rp[c + 1] < rp[c] || rp[c + 1] > R || (sp && (sp[c] < rp[c] || sp[c] > rp[c + 1]))) return false;
+    return true;
+}
+
+// every target (complex tc[k], residue tr[k]) lies inside its complex; rp has passed ragged_check
+static bool targets_check(const int32_t* tc, const int32_t* tr, const int32_t* rp, int64_t M, int64_t K) {
+    for (int64_t k = 0; k < K; ++k)
+        if (tc[k] < 0 || tc[k] >= M || tr[k] < rp[tc[k]] || tr[k] >= rp[tc[k] + 1]) return false;
+    return true;
+}
+
+// The checks the residue-feature requests (bsa, hse, depth) share; `q` is any of them: the shared fields have the same names.
+// residue_request_check: the counts and pointers, in front of the entry point's own ARG and CAPACITY checks (k_max: the largest
+// n_targets its indices allow); residue_tables_check: the host tables, behind them (sp: the chain split, or null).
+template <class Request>
+static int residue_request_check(const Request* q, int64_t k_max) {
+    if (!q || !q->host_atom_ptr || !q->host_res_ptr || !q->status) return DRGNN_E_ARG;
+    const int64_t T = q->n_atoms, R = q->n_residues, M = q->n_complexes, K = q->n_targets;
+    if (T < 0 || R < 0 || M < 0 || K < 0 || T > INT32_MAX / 3 || R >= INT32_MAX || K > k_max) return DRGNN_E_ARG;
+    if ((M > 0 && !q->res_ptr) || (R > 0 && !q->atom_ptr) || (T > 0 && !q->xyz)) return DRGNN_E_ARG;
+    if (K > 0 && (!q->host_target_res || !q->host_target_complex || !q->target_res || !q->target_complex || !q->out)) return DRGNN_E_ARG;
+    return 0;
+}
+template <class Request>
+static int residue_tables_check(const Request* q, const int32_t* sp) {
+    const int32_t* rp = q->host_res_ptr;
+    if (!ragged_check(q->host_atom_ptr, rp, sp, q->n_atoms, q->n_residues, q->n_complexes) ||
+        !targets_check(q->host_target_complex, q->host_target_res, rp, q->n_complexes, q->n_targets))
+        return DRGNN_E_ARG;
+    return 0;
+}
+
+// pointer first (alignment: a power of two), then the size: the workspace of depth and RMSD
+static int workspace_check(const void* ptr, int64_t bytes, int64_t need, uintptr_t alignment) {
+    if (!ptr || ((uintptr_t)ptr & (alignment - 1))) return DRGNN_E_ARG;
+    return bytes < need ? DRGNN_E_CAPACITY : 0;
+}
+
+// drgnn_<subsystem>_capacity(what): entry `what` of the subsystem's limits, -1 beyond them
+#define DRGNN_CAPACITY(name, ...)                                                              \
+    int32_t name(int32_t what) {                                                               \
+        static const int32_t cap[] = {__VA_ARGS__};                                            \
+        return what >= 0 && what < (int32_t)(sizeof(cap) / sizeof(cap[0])) ? cap[what] : -1;   \
+    }
 
 extern "C" {
 
@@ -1898,20 +1944,6 @@ int drgnn_step_gradients(const drgnn_net_desc* net, const float* conv_partials, 
 }
 
 // ---- stand-alone layers / pooling functions ---------------------------------------------------
-#ifdef DRGNN_EMU
-#define DRGNN_GRID_ITEMS(kern, item_fn, n_items, stream, ...) \
-    do { for (int64_t it_ = 0; it_ < (int64_t)(n_items); ++it_) item_fn(__VA_ARGS__, it_); (void)stream; } while (0)
-#define DRGNN_GRID_BLOCKS(kern, block_fn, n_blocks, stream, ...) \
-    do { for (int b_ = 0; b_ < (int)(n_blocks); ++b_) block_fn(__VA_ARGS__, b_); (void)stream; } while (0)
-#else
-#define DRGNN_GRID_ITEMS(kern, item_fn, n_items, stream, ...)                                              \
-    do { if ((n_items) > 0) hipLaunchKernelGGL(kern, dim3((unsigned)(((n_items) + 255) / 256)), dim3(256), \
-                                               0, (hipStream_t)(stream), __VA_ARGS__); } while (0)
-#define DRGNN_GRID_BLOCKS(kern, block_fn, n_blocks, stream, ...)                                          \
-    do { if ((n_blocks) > 0) hipLaunchKernelGGL(kern, dim3((unsigned)(n_blocks)), dim3(DRGNN_NTHREADS),   \
-                                                0, (hipStream_t)(stream), __VA_ARGS__); } while (0)
-#endif
-
 static int conv_layer_fill(ConvLayerArgs& a, int32_t kind, const float* x, int64_t n_nodes, int32_t F,
                            int32_t H, const drgnn_conv_params* p, const int32_t* ws_i32,
                            const float* ws_f32, int64_t n_edges) {
@@ -1941,11 +1973,8 @@ int drgnn_conv_layer_forward(int32_t kind, const float* x, int64_t n_nodes, int3
     if (!u || !out) return DRGNN_E_ARG;
     a.u = u; a.out = out;
     const int64_t slabs = drgnn_conv_layer_slabs(n_nodes);
-    DRGNN_GRID_BLOCKS(k_conv_gemm, conv_gemm_block, slabs, stream, a);
-    DRGNN_GRID_ITEMS(k_conv_aggregate, conv_aggregate_item, n_nodes * H, stream, a);
-#ifndef DRGNN_EMU
-    HIP_TRY(hipGetLastError());
-#endif
+    DRGNN_LAUNCH(k_conv_gemm, grid1(slabs), stream, conv_gemm_block(a, (int)bx), a);
+    DRGNN_LAUNCH(k_conv_aggregate, grid_items(n_nodes * H), stream, conv_aggregate_item(a, bx), a);
     return 0;
 }
 
@@ -1959,20 +1988,12 @@ int drgnn_conv_layer_backward(int32_t kind, const float* x, int64_t n_nodes, int
     if (!grad_out || !du || !partials || !g) return DRGNN_E_ARG;
     a.u = du; a.grad_out = grad_out; a.partials = partials; a.grad_x = grad_x;
     const int64_t slabs = drgnn_conv_layer_slabs(n_nodes);
-    DRGNN_GRID_ITEMS(k_conv_bwd_du, conv_bwd_du_item, n_nodes * H, stream, a);
-    DRGNN_GRID_BLOCKS(k_conv_bwd_dw, conv_bwd_dw_block, slabs, stream, a);
+    DRGNN_LAUNCH(k_conv_bwd_du, grid_items(n_nodes * H), stream, conv_bwd_du_item(a, bx), a);
+    DRGNN_LAUNCH(k_conv_bwd_dw, grid1(slabs), stream, conv_bwd_dw_block(a, (int)bx), a);
     ConvReduceArgs r;
     r.partials = partials; r.n_wg = (int)slabs; r.kind = kind; r.F = F; r.H = H; r.lay = *p; r.g = *g;
-    const int64_t P = conv_partial_floats(kind, F, H);
-#ifdef DRGNN_EMU
-    for (int i = 0; i < (int)P; ++i) conv_reduce_item(r, i);
-#else
-    hipLaunchKernelGGL(k_conv_reduce, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, r);
-#endif
-    if (grad_x) DRGNN_GRID_ITEMS(k_conv_bwd_dx, conv_bwd_dx_item, n_nodes * F, stream, a);
-#ifndef DRGNN_EMU
-    HIP_TRY(hipGetLastError());
-#endif
+    DRGNN_LAUNCH(k_conv_reduce, grid_items(conv_partial_floats(kind, F, H)), stream, conv_reduce_item(r, (int)bx), r);
+    if (grad_x) DRGNN_LAUNCH(k_conv_bwd_dx, grid_items(n_nodes * F), stream, conv_bwd_dx_item(a, bx), a);
     return 0;
 }
 
@@ -1985,10 +2006,7 @@ int drgnn_segpool_forward(const int32_t* ws_i32, int64_t n_nodes, int64_t n_edge
     a.tv = topo_view(const_cast<int32_t*>(ws_i32), nullptr, lay);
     a.x = x; a.H = H; a.n_graphs = (int)n_graphs; a.op = op; a.out = out; a.arg = arg;
     a.grad_out = nullptr; a.grad_x = nullptr; a.arg_in = nullptr;
-    DRGNN_GRID_BLOCKS(k_segpool_fwd, segpool_fwd_block, n_graphs, stream, a);
-#ifndef DRGNN_EMU
-    HIP_TRY(hipGetLastError());
-#endif
+    DRGNN_LAUNCH(k_segpool_fwd, grid1(n_graphs), stream, segpool_fwd_block(a, (int)bx), a);
     return 0;
 }
 
@@ -1999,14 +2017,7 @@ int drgnn_segmax_backward(const float* grad_out, const int64_t* arg, int64_t n_c
     a.H = H; a.grad_out = grad_out; a.arg_in = arg; a.grad_x = grad_x;
     a.x = nullptr; a.out = nullptr; a.arg = nullptr; a.n_graphs = 0; a.op = 0;
     const int64_t n_items = n_clusters * H;
-#ifdef DRGNN_EMU
-    for (int64_t i = 0; i < n_items; ++i) segmax_bwd_item(a, i, n_items, n_nodes);
-    (void)stream;
-#else
-    if (n_items > 0)
-        hipLaunchKernelGGL(k_segmax_bwd, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, n_items, n_nodes);
-    HIP_TRY(hipGetLastError());
-#endif
+    DRGNN_LAUNCH(k_segmax_bwd, grid_items(n_items), stream, segmax_bwd_item(a, bx, n_items, n_nodes), a, n_items, n_nodes);
     return 0;
 }
 
@@ -2019,10 +2030,7 @@ int drgnn_pooled_edges_export(const int32_t* ws_i32, const float* ws_f32, int64_
     EdgeExportArgs a;
     a.tv = topo_view(const_cast<int32_t*>(ws_i32), const_cast<float*>(ws_f32), lay);
     a.n_graphs = (int)n_graphs; a.edge_index = edge_index; a.edge_attr = edge_attr; a.e1_total = e1_total;
-    DRGNN_GRID_BLOCKS(k_edge_export, edge_export_block, n_graphs, stream, a);
-#ifndef DRGNN_EMU
-    HIP_TRY(hipGetLastError());
-#endif
+    DRGNN_LAUNCH(k_edge_export, grid1(n_graphs), stream, edge_export_block(a, (int)bx), a);
     return 0;
 }
 
@@ -2032,18 +2040,10 @@ int drgnn_cluster_offset(int64_t* cluster, const int32_t* node_ptr, int64_t n_gr
     if (n_graphs == 0) return 0;
     ClusterOffsetArgs a;
     a.cluster = cluster; a.nptr = node_ptr; a.n_graphs = (int)n_graphs; a.maxes = (long long*)scratch;
-#ifdef DRGNN_EMU
-    long long mm[2];
-    for (int g = 0; g < n_graphs; ++g) cluster_max_block(a, g, mm);
-    cluster_scan_single(a);
-    for (int g = 0; g < n_graphs; ++g) cluster_add_block(a, g);
-    (void)stream;
-#else
-    hipLaunchKernelGGL(k_cluster_max, dim3((unsigned)n_graphs), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
-    hipLaunchKernelGGL(k_cluster_scan, dim3(1), dim3(64), 0, (hipStream_t)stream, a);
-    hipLaunchKernelGGL(k_cluster_add, dim3((unsigned)n_graphs), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-#endif
+    DRGNN_EMU_ONLY(long long mm[2];)
+    DRGNN_LAUNCH(k_cluster_max, grid1(n_graphs), stream, cluster_max_block(a, (int)bx, mm), a);
+    DRGNN_LAUNCH(k_cluster_scan, grid1(1, 64), stream, cluster_scan_single(a), a);
+    DRGNN_LAUNCH(k_cluster_add, grid1(n_graphs), stream, cluster_add_block(a, (int)bx), a);
     return 0;
 }
 
@@ -2061,16 +2061,8 @@ int drgnn_graclus(const int32_t* ws_i32, int64_t n_nodes, int64_t n_edges, int64
     a.capN = max_nodes > 0 ? max_nodes : 1; a.capE = max_edges > 0 ? max_edges : 1;
     const int64_t words = (int64_t)(a.capN + 1) + 2 * (int64_t)a.capE + a.capN;
     if (words * 4 > DRGNN_LDS_LIMIT) return DRGNN_E_CAPACITY;
-#ifdef DRGNN_EMU
-    std::vector<int> buf((size_t)words + 16);
-    for (int g = 0; g < n_graphs; ++g) graclus_block(a, g, buf.data());
-    (void)stream;
-#else
-    if (words * 4 > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void*)k_graclus, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(words * 4)));
-    hipLaunchKernelGGL(k_graclus, dim3((unsigned)n_graphs), dim3(DRGNN_NTHREADS), (size_t)(words * 4), (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-#endif
+    DRGNN_EMU_ONLY(std::vector<int> buf((size_t)words + 16);)
+    DRGNN_LAUNCH(k_graclus, grid1(n_graphs, DRGNN_NTHREADS, words * 4), stream, graclus_block(a, (int)bx, buf.data()), a);
     return 0;
 }
 
@@ -2086,15 +2078,8 @@ int drgnn_mcl(const int64_t* edge_index, int64_t n_edges, const int32_t* node_pt
     a.edge_index = edge_index; a.n_edges = n_edges; a.node_ptr = node_ptr; a.edge_ptr = edge_ptr;
     a.mat_ptr = mat_ptr; a.n_graphs = (int)n_graphs; a.mat = mat_scratch; a.iscr = int_scratch;
     a.labels = labels; a.info = info; a.iterations = 100; a.prune_threshold = 1e-3;
-#ifdef DRGNN_EMU
-    std::vector<double> red(DRGNN_NTHREADS);
-    int flag[2];
-    for (int g = 0; g < n_graphs; ++g) mcl_graph(a, g, flag, red.data());
-    (void)stream;
-#else
-    hipLaunchKernelGGL(k_mcl, dim3((unsigned)n_graphs), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-#endif
+    DRGNN_EMU_ONLY(std::vector<double> red(DRGNN_NTHREADS); int flag[2];)
+    DRGNN_LAUNCH(k_mcl, grid1(n_graphs), stream, mcl_graph(a, (int)bx, flag, red.data()), a);
     return 0;
 }
 
@@ -2113,16 +2098,8 @@ int drgnn_louvain(const int64_t* edge_index, int64_t n_edges, const int32_t* nod
     a.edge_index = edge_index; a.n_edges = n_edges; a.node_ptr = node_ptr; a.edge_ptr = edge_ptr;
     a.n_graphs = (int)n_graphs; a.capN = max_nodes; a.capE = max_edges;
     a.labels = labels; a.info = info; a.modularity = modularity;
-#ifdef DRGNN_EMU
-    std::vector<int> buf((size_t)words + 16);
-    for (int g = 0; g < n_graphs; ++g) louvain_graph(a, g, buf.data());
-    (void)stream;
-#else
-    if (words * 4 > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void*)k_louvain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(words * 4)));
-    hipLaunchKernelGGL(k_louvain, dim3((unsigned)n_graphs), dim3(LV_W), (size_t)(words * 4), (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-#endif
+    DRGNN_EMU_ONLY(std::vector<int> buf((size_t)words + 16);)
+    DRGNN_LAUNCH(k_louvain, grid1(n_graphs, LV_W, words * 4), stream, louvain_graph(a, (int)bx, buf.data()), a);
     return 0;
 }
 
@@ -2132,24 +2109,6 @@ int64_t drgnn_iface_workspace_bytes(int64_t n_complexes, int64_t max_res_a, int6
     int64_t off[8];
     iface_layout(n_complexes, max_res_a, max_res_b, n_residues, off);
     return off[7];
-}
-
-// the ragged layout on the host, whole, before anything is indexed through it: 0 = ap[0] <= ap[r] <= ap[r + 1], ap[R] = T;
-// with rp, 0 = rp[0] <= rp[c] <= rp[c + 1] <= R = rp[M]; with sp, rp[c] <= sp[c] <= rp[c + 1]
-static bool ragged_check(const int32_t* ap, const int32_t* rp, const int32_t* sp, int64_t T, int64_t R, int64_t M) {
-    if (ap[0] != 0 || ap[R] != T || (rp && (rp[0] != 0 || rp[M] != R))) return false;
-    for (int64_t r = 0; r < R; ++r)
-        if (ap[r + 1] < ap[r]) return false;
-    for (int64_t c = 0; rp && c < M; ++c)
-        if (rp[c + 1] < rp[c] || rp[c + 1] > R || (sp && (sp[c] < rp[c] || sp[c] > rp[c + 1]))) return false;
-    return true;
-}
-
-// every target (complex tc[k], residue tr[k]) lies inside its complex; rp has passed ragged_check
-static bool targets_check(const int32_t* tc, const int32_t* tr, const int32_t* rp, int64_t M, int64_t K) {
-    for (int64_t k = 0; k < K; ++k)
-        if (tc[k] < 0 || tc[k] >= M || tr[k] < rp[tc[k]] || tr[k] >= rp[tc[k] + 1]) return false;
-    return true;
 }
 
 // checks the request on the host and fills the launch record; *max_res: the longest complex
@@ -2194,53 +2153,28 @@ static int iface_prepare(const drgnn_iface_request* q, IfaceArgs& a, int* max_re
     return 0;
 }
 
-#ifdef DRGNN_EMU
-static void iface_rows_emu(const IfaceArgs& a, int max_res, bool write) {
-    for (int c = 0; c < a.n_complexes; ++c)
-        for (int blk = 0; blk * IF_AB < max_res; ++blk) iface_rows_block(a, c, blk, write);
+// the rows kernel over (blocks of IF_AB residues, complexes): counting (write 0) or filling (1)
+static int iface_rows(const IfaceArgs& a, int max_res, int write, void* stream) {
+    DRGNN_LAUNCH(k_iface_rows, grid2((max_res + IF_AB - 1) / IF_AB, a.n_complexes, IF_NT), stream,
+                 iface_rows_block(a, (int)by, (int)bx, write != 0), a, write);
+    return 0;
 }
-#endif
 
 int drgnn_iface_count(const drgnn_iface_request* req, void* stream) {
     IfaceArgs a;
     int max_res = 0;
-    const int rc = iface_prepare(req, a, &max_res);
+    int rc = iface_prepare(req, a, &max_res);
     if (rc) return rc;
     const int M = a.n_complexes, R = a.n_residues;
-#ifdef DRGNN_EMU
-    (void)stream;
-    std::vector<float> lds((size_t)(iface_pairs_lds_bytes(a.tile_atoms) / 4) + 4);
-    std::vector<int> part(DRGNN_NTHREADS + 1);
-    for (int r = 0; r < R; ++r) iface_sphere_item(a, r);
-    for (int c = 0; c < M; ++c)
-        for (int blk = 0; blk * IF_AB < a.maxA; ++blk) iface_pairs_block(a, c, blk, lds.data());
-    iface_rows_emu(a, max_res, false);
-    for (int c = 0; c < M; ++c) iface_scan_block(a, c, part.data());
-    iface_offsets_block(a, part.data());
-#else
-    hipStream_t st = (hipStream_t)stream;
-    if (R > 0) {
-        hipLaunchKernelGGL(k_iface_sphere, dim3((unsigned)((R + IF_NT - 1) / IF_NT)), dim3(IF_NT), 0, st, a);
-        HIP_TRY(hipGetLastError());
-    }
-    if (M > 0 && a.maxA > 0) {
-        const int64_t lds = iface_pairs_lds_bytes(a.tile_atoms);
-        if (lds > 64 * 1024)
-            HIP_TRY(hipFuncSetAttribute((const void*)k_iface_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_iface_pairs, dim3((unsigned)((a.maxA + IF_AB - 1) / IF_AB), (unsigned)M), dim3(IF_NT), (size_t)lds, st, a);
-        HIP_TRY(hipGetLastError());
-    }
-    if (M > 0 && max_res > 0) {
-        hipLaunchKernelGGL(k_iface_rows, dim3((unsigned)((max_res + IF_AB - 1) / IF_AB), (unsigned)M), dim3(IF_NT), 0, st, a, 0);
-        HIP_TRY(hipGetLastError());
-    }
-    if (M > 0) {
-        hipLaunchKernelGGL(k_iface_scan, dim3((unsigned)M), dim3(DRGNN_NTHREADS), 0, st, a);
-        HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_iface_offsets, dim3(1), dim3(DRGNN_NTHREADS), 0, st, a);
-    HIP_TRY(hipGetLastError());
-#endif
+    // (without residues, complexes or chain-A residues the grids of the first three launches are empty: skipped)
+    const int64_t lds_bytes = iface_pairs_lds_bytes(a.tile_atoms);
+    DRGNN_EMU_ONLY(std::vector<float> lds((size_t)(lds_bytes / 4) + 4); std::vector<int> part(DRGNN_NTHREADS + 1);)
+    DRGNN_LAUNCH(k_iface_sphere, grid_items(R, IF_NT), stream, iface_sphere_item(a, (int)bx), a);
+    DRGNN_LAUNCH(k_iface_pairs, (Grid{(a.maxA + IF_AB - 1) / IF_AB, M, IF_NT, lds_bytes}), stream,
+                 iface_pairs_block(a, (int)by, (int)bx, lds.data()), a);
+    if ((rc = iface_rows(a, max_res, 0, stream))) return rc;
+    DRGNN_LAUNCH(k_iface_scan, grid1(M), stream, iface_scan_block(a, (int)bx, part.data()), a);
+    DRGNN_LAUNCH(k_iface_offsets, grid1(1), stream, iface_offsets_block(a, part.data()), a);
     return 0;
 }
 
@@ -2259,15 +2193,7 @@ int drgnn_iface_fill(const drgnn_iface_request* req, int64_t n_nodes, int64_t n_
     a.edge_index = edge_index; a.dist = dist; a.iedge_index = internal_edge_index; a.idist = internal_dist;
     a.n_nodes = n_nodes; a.n_edges = n_edges; a.n_iedges = n_iedges;
     if (a.n_complexes == 0 || max_res == 0 || n_nodes == 0) return 0;
-#ifdef DRGNN_EMU
-    (void)stream;
-    iface_rows_emu(a, max_res, true);
-#else
-    hipLaunchKernelGGL(k_iface_rows, dim3((unsigned)((max_res + IF_AB - 1) / IF_AB), (unsigned)a.n_complexes), dim3(IF_NT), 0,
-                       (hipStream_t)stream, a, 1);
-    HIP_TRY(hipGetLastError());
-#endif
-    return 0;
+    return iface_rows(a, max_res, 1, stream);
 }
 
 // ---- docking scores of pose batches (drgnn_score.h) -------------------------------------------------
@@ -2302,33 +2228,22 @@ int drgnn_dock_scores(const drgnn_score_request* q, void* stream) {
     a.n_atoms = (int)T; a.n_pairs = (int)P; a.n_ref_pairs = (int)q->n_ref_pairs; a.amax = amax;
     a.cut2 = (float)(q->fnat_cutoff * q->fnat_cutoff);
     a.scores = q->scores; a.classes = q->classes; a.n_preserved = q->n_preserved;
-#ifdef DRGNN_EMU
-    (void)stream;
-    std::vector<double> lds(SC_LDS_BYTES / 8 + 1);
-    for (int64_t m = 0; m < M; ++m) score_pose(a, m, lds.data());
-#else
-    hipLaunchKernelGGL(k_dock_scores, dim3((unsigned)M), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-#endif
+    DRGNN_EMU_ONLY(std::vector<double> lds(SC_LDS_BYTES / 8 + 1);)
+    DRGNN_LAUNCH(k_dock_scores, grid1(M), stream, score_pose(a, bx, lds.data()), a);
     return 0;
 }
 
 // ---- buried surface area of residues (drgnn_bsa.h) ---------------------------------------------------
-int32_t drgnn_bsa_capacity(int32_t what) { return what == 0 ? BS_NCAP : what == 1 ? BS_CCAP : what == 2 ? BS_MAX_SLICES : what == 3 ? BS_MAX_TARGETS : -1; }
+DRGNN_CAPACITY(drgnn_bsa_capacity, BS_NCAP, BS_CCAP, BS_MAX_SLICES, BS_MAX_TARGETS)
 
 int drgnn_bsa_residues(const drgnn_bsa_request* q, void* stream) {
-    if (!q || !q->host_atom_ptr || !q->host_res_ptr || !q->status) return DRGNN_E_ARG;
-    const int64_t T = q->n_atoms, R = q->n_residues, M = q->n_complexes, K = q->n_targets, NR = q->n_radii;
-    if (T < 0 || R < 0 || M < 0 || K < 0 || NR < 0 || T > INT32_MAX / 3 || R >= INT32_MAX || K > INT32_MAX) return DRGNN_E_ARG;
-    if (M > 0 && (!q->host_res_split || !q->res_ptr || !q->res_split)) return DRGNN_E_ARG;
-    if (R > 0 && !q->atom_ptr) return DRGNN_E_ARG;
-    if (T > 0 && (!q->xyz || !q->rad_complex || !q->rad_unbound || NR < 1 || T % NR != 0)) return DRGNN_E_ARG;
-    if (K > 0 && (!q->host_target_res || !q->host_target_complex || !q->target_res || !q->target_complex || !q->out)) return DRGNN_E_ARG;
+    if (int rc = residue_request_check(q, INT32_MAX)) return rc;
+    const int64_t T = q->n_atoms, M = q->n_complexes, K = q->n_targets, NR = q->n_radii;
+    if (NR < 0 || (M > 0 && (!q->host_res_split || !q->res_split))) return DRGNN_E_ARG;
+    if (T > 0 && (!q->rad_complex || !q->rad_unbound || NR < 1 || T % NR != 0)) return DRGNN_E_ARG;
     if (!(q->probe >= 0.0) || q->n_slices < 1) return DRGNN_E_ARG;
     if (q->n_slices > BS_MAX_SLICES || K > BS_MAX_TARGETS) return DRGNN_E_CAPACITY;
-    const int32_t *ap = q->host_atom_ptr, *rp = q->host_res_ptr, *sp = q->host_res_split;
-    if (!ragged_check(ap, rp, sp, T, R, M) || !targets_check(q->host_target_complex, q->host_target_res, rp, M, K))
-        return DRGNN_E_ARG;
+    if (int rc = residue_tables_check(q, q->host_res_split)) return rc;
     if (K == 0) return 0;
     BsaArgs a;
     memset(&a, 0, sizeof(a));
@@ -2336,47 +2251,35 @@ int drgnn_bsa_residues(const drgnn_bsa_request* q, void* stream) {
     a.rad_c = q->rad_complex; a.rad_u = q->rad_unbound; a.tgt_res = q->target_res; a.tgt_cx = q->target_complex;
     a.n_radii = (int)NR; a.n_slices = q->n_slices; a.probe = (float)q->probe; a.probe_d = q->probe;
     a.out = q->out; a.status = q->status;
-#ifdef DRGNN_EMU
-    (void)stream;
-    std::unique_ptr<BsaShared> lds(new BsaShared);
-    for (int64_t k = 0; k < K; ++k) bsa_residue(a, k, *lds);
-#else
     static_assert(sizeof(BsaShared) <= DRGNN_LDS_LIMIT, "the workgroup's lists fit the LDS");
-    HIP_TRY(hipFuncSetAttribute((const void*)k_bsa_residues, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(BsaShared)));
-    hipLaunchKernelGGL(k_bsa_residues, dim3((unsigned)K), dim3(DRGNN_NTHREADS), sizeof(BsaShared), (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-#endif
+    DRGNN_EMU_ONLY(std::unique_ptr<BsaShared> lds(new BsaShared);)
+    DRGNN_LAUNCH(k_bsa_residues, grid1(K, DRGNN_NTHREADS, sizeof(BsaShared)), stream, bsa_residue(a, bx, *lds), a);
     return 0;
 }
 
 // ---- half-sphere exposure of residues (drgnn_hse.h) --------------------------------------------------
-int32_t drgnn_hse_capacity(int32_t what) { return what == 0 ? HS_RCAP : what == 1 ? HS_MAX_TILES : -1; }
+DRGNN_CAPACITY(drgnn_hse_capacity, HS_RCAP, HS_MAX_TILES)
 
 int drgnn_hse_residues(const drgnn_hse_request* q, void* stream) {
-    if (!q || !q->host_atom_ptr || !q->host_res_ptr || !q->host_tile_ptr || !q->status) return DRGNN_E_ARG;
-    const int64_t T = q->n_atoms, R = q->n_residues, M = q->n_complexes, K = q->n_targets, NT = q->n_tiles, NB = q->n_rows;
-    if (T < 0 || R < 0 || M < 0 || K < 0 || NT < 0 || NB < 0 || T > INT32_MAX / 3 || R >= INT32_MAX || K > INT32_MAX / 3)
-        return DRGNN_E_ARG;
-    if (M > 0 && !q->res_ptr) return DRGNN_E_ARG;
-    if (R > 0 && (!q->atom_ptr || !q->bb || !q->host_bb || NB < 1 || R % NB != 0)) return DRGNN_E_ARG;
-    if (T > 0 && !q->xyz) return DRGNN_E_ARG;
-    if (K > 0 && (!q->host_target_res || !q->host_target_complex || !q->target_res || !q->target_complex || !q->tile_ptr ||
-                  !q->out || NT < 1))
-        return DRGNN_E_ARG;
+    if (int rc = residue_request_check(q, INT32_MAX / 3)) return rc;
+    const int64_t R = q->n_residues, K = q->n_targets, NT = q->n_tiles, NB = q->n_rows;
+    if (!q->host_tile_ptr || NT < 0 || NB < 0) return DRGNN_E_ARG;
+    if (R > 0 && (!q->bb || !q->host_bb || NB < 1 || R % NB != 0)) return DRGNN_E_ARG;
+    if (K > 0 && (!q->tile_ptr || NT < 1)) return DRGNN_E_ARG;
     if (!(q->radius > 0.0) || !(q->radius < 1.0e150) || !(q->connect_cutoff > 0.0) || !(q->connect_cutoff < 1.0e150) ||
         q->offset < 0)
         return DRGNN_E_ARG;
     if (q->connect_a < 0 || q->connect_a > 3 || q->connect_b < 0 || q->connect_b > 3 || q->direction < 0 || q->direction > 1)
         return DRGNN_E_ARG;
     if (NT > HS_MAX_TILES) return DRGNN_E_CAPACITY;
-    const int32_t *ap = q->host_atom_ptr, *rp = q->host_res_ptr, *tp = q->host_tile_ptr, *hb = q->host_bb;
-    if (!ragged_check(ap, rp, nullptr, T, R, M) || tp[0] != 0 || tp[NT] != K) return DRGNN_E_ARG;
+    const int32_t *ap = q->host_atom_ptr, *tp = q->host_tile_ptr, *hb = q->host_bb;
+    if (int rc = residue_tables_check(q, nullptr)) return rc;
+    if (tp[0] != 0 || tp[NT] != K) return DRGNN_E_ARG;
     for (int64_t r = 0; r < R; ++r) {
         const int32_t* row = hb + 5 * (r % NB);                       // every offset the kernel may add lies in its residue
         for (int j = 0; j < 4; ++j)
             if (row[j] < -1 || row[j] >= ap[r + 1] - ap[r]) return DRGNN_E_ARG;
     }
-    if (!targets_check(q->host_target_complex, q->host_target_res, rp, M, K)) return DRGNN_E_ARG;
     for (int64_t t = 0; t < NT; ++t) {
         if (tp[t + 1] < tp[t] || tp[t + 1] > K) return DRGNN_E_ARG;
         for (int64_t k = tp[t] + 1; k < tp[t + 1]; ++k)               // a tile serves one complex
@@ -2390,20 +2293,14 @@ int drgnn_hse_residues(const drgnn_hse_request* q, void* stream) {
     a.n_rows = (int)NB; a.offset = q->offset; a.con_a = q->connect_a; a.con_b = q->connect_b; a.direction = q->direction;
     a.radius2 = q->radius * q->radius; a.cut2 = q->connect_cutoff * q->connect_cutoff;
     a.out = q->out; a.status = q->status;
-#ifdef DRGNN_EMU
-    (void)stream;
-    std::unique_ptr<HseShared> lds(new HseShared);
-    for (int64_t t = 0; t < NT; ++t) hse_tile(a, (int)t, *lds);
-#else
     static_assert(sizeof(HseShared) <= 64 * 1024, "the staged CAs fit the static LDS of a workgroup");
-    hipLaunchKernelGGL(k_hse_residues, dim3((unsigned)NT), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-#endif
+    DRGNN_EMU_ONLY(std::unique_ptr<HseShared> lds(new HseShared);)
+    DRGNN_LAUNCH(k_hse_residues, grid1(NT), stream, hse_tile(a, (int)bx, *lds), a);
     return 0;
 }
 
 // ---- the builder's output packed into a resident set's arrays (drgnn_pack.h) --------------------------
-int32_t drgnn_pack_capacity(int32_t what) { return what == 0 ? PK_FCAP : what == 1 ? PK_TCAP : what == 2 ? PK_MAX_COMPLEXES : -1; }
+DRGNN_CAPACITY(drgnn_pack_capacity, PK_FCAP, PK_TCAP, PK_MAX_COMPLEXES)
 
 int drgnn_iface_pack(const drgnn_pack_request* q, void* stream) {
     if (!q || !q->node_ptr || !q->edge_ptr || !q->iedge_ptr) return DRGNN_E_ARG;
@@ -2445,21 +2342,13 @@ int drgnn_iface_pack(const drgnn_pack_request* q, void* stream) {
     a.N = (int)N; a.E = (int)E; a.Ei = (int)Ei;
     a.x = q->x; a.edge_index_out = q->edge_index_out; a.edge_attr = q->edge_attr;
     a.iedge_index_out = q->internal_edge_index_out; a.batch = q->batch;
-#ifdef DRGNN_EMU
-    (void)stream;
-    std::unique_ptr<PackShared> lds(new PackShared);
-    for (int64_t k = 0; k < M; ++k) pack_block(a, (int)k, *lds);
-#else
-    hipLaunchKernelGGL(k_iface_pack, dim3((unsigned)M), dim3(PK_NT), 0, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-#endif
+    DRGNN_EMU_ONLY(std::unique_ptr<PackShared> lds(new PackShared);)
+    DRGNN_LAUNCH(k_iface_pack, grid1(M, PK_NT), stream, pack_block(a, (int)bx, *lds), a);
     return 0;
 }
 
 // ---- residue depth (drgnn_depth.h) -------------------------------------------------------------------
-int32_t drgnn_depth_capacity(int32_t what) {
-    return what == 0 ? DP_DOTS_CAP : what == 1 ? DP_CX_DOTS_CAP : what == 2 ? DP_MAX_GRID : -1;
-}
+DRGNN_CAPACITY(drgnn_depth_capacity, DP_DOTS_CAP, DP_CX_DOTS_CAP, DP_MAX_GRID)
 
 // the workspace's arrays, one after the other, each a multiple of 8 bytes: mask, pos, id, label, size, cnt, ptr, cx_nd,
 // cx_outer; offsets[9] is the size
@@ -2481,28 +2370,21 @@ int64_t drgnn_depth_workspace(int64_t n_atoms, int64_t n_complexes, int32_t n_do
 }
 
 int drgnn_depth_residues(const drgnn_depth_request* q, void* stream) {
-    if (!q || !q->host_atom_ptr || !q->host_res_ptr || !q->status) return DRGNN_E_ARG;
-    const int64_t T = q->n_atoms, R = q->n_residues, M = q->n_complexes, K = q->n_targets, NR = q->n_radii;
-    if (T < 0 || R < 0 || M < 0 || K < 0 || NR < 0 || T > INT32_MAX / 3 || R >= INT32_MAX || K > INT32_MAX) return DRGNN_E_ARG;
-    if (M > 0 && !q->res_ptr) return DRGNN_E_ARG;
-    if (R > 0 && !q->atom_ptr) return DRGNN_E_ARG;
-    if (T > 0 && (!q->xyz || !q->radii || NR < 1 || T % NR != 0)) return DRGNN_E_ARG;
-    if (K > 0 && (!q->host_target_res || !q->host_target_complex || !q->target_res || !q->target_complex || !q->out)) return DRGNN_E_ARG;
+    if (int rc = residue_request_check(q, INT32_MAX)) return rc;
+    const int64_t T = q->n_atoms, M = q->n_complexes, K = q->n_targets, NR = q->n_radii;
+    if (NR < 0 || (T > 0 && (!q->radii || NR < 1 || T % NR != 0))) return DRGNN_E_ARG;
     if (q->n_dots < 1 || !q->dots || !(q->probe > 0.0) || !(q->probe < 1.0e150) || !(q->link >= 0.0) || !(q->link < 1.0e150) ||
         q->components < 0 || q->components > 1 || q->phases < 0 || q->phases > 7)
         return DRGNN_E_ARG;
     if (q->n_dots > DP_DOTS_CAP || K > DP_MAX_GRID || M > DP_MAX_GRID || T / DRGNN_NWAVES >= DP_MAX_GRID) return DRGNN_E_CAPACITY;
-    const int32_t *ap = q->host_atom_ptr, *rp = q->host_res_ptr;
-    if (!ragged_check(ap, rp, nullptr, T, R, M) || !targets_check(q->host_target_complex, q->host_target_res, rp, M, K))
-        return DRGNN_E_ARG;
+    if (int rc = residue_tables_check(q, nullptr)) return rc;
     int64_t off[10];
     if (depth_layout(T, M, q->n_dots, off) != 0) return DRGNN_E_ARG;
     int ph = q->phases == 0 ? 7 : q->phases;
     if (K == 0) ph = q->phases == 0 ? 0 : ph & ~4;                      // (the whole call without a target: nothing to do)
     if (M == 0) ph = 0;
     if (ph == 0) return 0;
-    if (!q->workspace || ((uintptr_t)q->workspace & 7)) return DRGNN_E_ARG;
-    if (q->workspace_bytes < off[9]) return DRGNN_E_CAPACITY;
+    if (int rc = workspace_check(q->workspace, q->workspace_bytes, off[9], 8)) return rc;
     DepthArgs a;
     memset(&a, 0, sizeof(a));
     a.xyz = q->xyz; a.atom_ptr = q->atom_ptr; a.res_ptr = q->res_ptr; a.rad = q->radii; a.dots = q->dots;
@@ -2515,35 +2397,20 @@ int drgnn_depth_residues(const drgnn_depth_request* q, void* stream) {
     a.label = (int32_t*)(w + off[3]); a.size = (int32_t*)(w + off[4]); a.cnt = (int32_t*)(w + off[5]);
     a.ptr = (int32_t*)(w + off[6]); a.cx_nd = (int32_t*)(w + off[7]); a.cx_outer = (int32_t*)(w + off[8]);
     a.out = q->out; a.status = q->status;
-    const int64_t tiles = (T + DRGNN_NWAVES - 1) / DRGNN_NWAVES;
-#ifdef DRGNN_EMU
-    (void)stream; (void)tiles;
-    std::unique_ptr<DepthShared> lds(new DepthShared);
-    if (ph & 1)
-        for (int64_t t = 0; t < T; ++t) depth_dots_tile(a, t);         // (one "wave" per workgroup: a tile is an atom)
-    if (ph & 2)
-        for (int64_t c = 0; c < M; ++c) depth_components(a, (int)c, *lds);
-    if (ph & 4)
-        for (int64_t k = 0; k < K; ++k) depth_residue(a, k, *lds);
+#ifdef DRGNN_EMU   // the emulation's workgroup is one "wave": its tile is an atom, the device's DRGNN_NWAVES atoms
+    const int64_t tiles = T;
 #else
-    if ((ph & 1) && T > 0) {
-        hipLaunchKernelGGL(k_depth_dots, dim3((unsigned)tiles), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
-        HIP_TRY(hipGetLastError());
-    }
-    if (ph & 2) {
-        hipLaunchKernelGGL(k_depth_components, dim3((unsigned)M), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
-        HIP_TRY(hipGetLastError());
-    }
-    if (ph & 4) {
-        hipLaunchKernelGGL(k_depth_residues, dim3((unsigned)K), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
-        HIP_TRY(hipGetLastError());
-    }
+    const int64_t tiles = (T + DRGNN_NWAVES - 1) / DRGNN_NWAVES;
 #endif
+    DRGNN_EMU_ONLY(std::unique_ptr<DepthShared> lds(new DepthShared);)
+    if (ph & 1) DRGNN_LAUNCH(k_depth_dots, grid1(tiles), stream, depth_dots_tile(a, bx), a);
+    if (ph & 2) DRGNN_LAUNCH(k_depth_components, grid1(M), stream, depth_components(a, (int)bx, *lds), a);
+    if (ph & 4) DRGNN_LAUNCH(k_depth_residues, grid1(K), stream, depth_residue(a, bx, *lds), a);
     return 0;
 }
 
 // ---- clustering of poses by their fraction of common contacts (drgnn_fcc.h) --------------------------
-int32_t drgnn_fcc_capacity(int32_t what) { return what == 0 ? FC_RCAP : what == 1 ? FC_PCAP : what == 2 ? PC_CCAP : -1; }
+DRGNN_CAPACITY(drgnn_fcc_capacity, FC_RCAP, FC_PCAP, PC_CCAP)
 
 int drgnn_pose_contacts(const drgnn_pose_contacts_request* q, void* stream) {
     if (!q || !q->host_atom_ptr) return DRGNN_E_ARG;
@@ -2562,15 +2429,9 @@ int drgnn_pose_contacts(const drgnn_pose_contacts_request* q, void* stream) {
     a.xyz = q->xyz; a.atom_ptr = q->atom_ptr; a.n_atoms = (int)T; a.n_res = (int)R; a.n_a = (int)A;
     a.cut = (float)q->cutoff; a.cut2 = (float)(q->cutoff * q->cutoff);
     a.bits = (pc_word*)q->bits; a.n_contacts = q->n_contacts;
-#ifdef DRGNN_EMU
-    (void)stream;
-    std::unique_ptr<FccContactShared> lds(new FccContactShared);
-    for (int64_t m = 0; m < M; ++m) fc_pose(a, m, *lds);
-#else
     static_assert(sizeof(FccContactShared) <= 64 * 1024, "the spheres fit the static LDS of a workgroup");
-    hipLaunchKernelGGL(k_fcc_contacts, dim3((unsigned)M), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-#endif
+    DRGNN_EMU_ONLY(std::unique_ptr<FccContactShared> lds(new FccContactShared);)
+    DRGNN_LAUNCH(k_fcc_contacts, grid1(M), stream, fc_pose(a, bx, *lds), a);
     return 0;
 }
 
@@ -2586,17 +2447,10 @@ int drgnn_pose_common(const drgnn_pose_common_request* q, void* stream) {
     a.a = (const pc_word*)q->bits_a; a.b = (const pc_word*)q->bits_b; a.n_a = (int)Ma; a.n_b = (int)Mb; a.n_words = W;
     a.common = q->common;
     const int ti = (int)((Ma + FC_TILE - 1) / FC_TILE), tj = (int)((Mb + FC_TILE - 1) / FC_TILE);
-#ifdef DRGNN_EMU
-    (void)stream;
-    std::unique_ptr<FccCommonShared> lds(new FccCommonShared);
-    for (int i = 0; i < ti; ++i)
-        for (int j = 0; j < tj; ++j) fc_common(a, i, j, *lds);
-#else
     static_assert(FC_TILE * FC_TILE == DRGNN_NTHREADS, "one lane per pose pair of a tile");
     static_assert((FC_PCAP + FC_TILE - 1) / FC_TILE <= 65535, "the tiles of a side fit the grid's y");
-    hipLaunchKernelGGL(k_fcc_common, dim3((unsigned)tj, (unsigned)ti), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-#endif
+    DRGNN_EMU_ONLY(std::unique_ptr<FccCommonShared> lds(new FccCommonShared);)
+    DRGNN_LAUNCH(k_fcc_common, grid2(tj, ti), stream, fc_common(a, (int)by, (int)bx, *lds), a);
     return 0;
 }
 
@@ -2608,11 +2462,11 @@ int drgnn_pose_cluster(const drgnn_pose_cluster_request* q, void* stream) {
     FccRule rule;
     memset(&rule, 0, sizeof(rule));
     rule.common = q->common; rule.n_contacts = q->n_contacts; rule.cut_fwd = q->cutoff_fcc; rule.cut_rev = q->cutoff_reverse;
-    return pose_cluster_run(rule, q, PC_RELATION_KERNEL(k_fcc_relation), stream);
+    return pose_cluster_run(rule, q, DRGNN_KERNEL(k_fcc_relation), stream);
 }
 
 // ---- contact consensus of poses (drgnn_consensus.h) ----------------------------------------------------
-int32_t drgnn_consensus_capacity(int32_t what) { return what == 0 ? FC_RCAP : what == 1 ? CS_GCAP : what == 2 ? CS_ECAP : what == 3 ? CS_NCAP : what == 4 ? CS_PCAP : -1; }
+DRGNN_CAPACITY(drgnn_consensus_capacity, FC_RCAP, CS_GCAP, CS_ECAP, CS_NCAP, CS_PCAP)
 
 // the counts shared by the three calls: 0, or the error
 static int cons_shape(int64_t nA, int64_t nB, int64_t G) {
@@ -2642,19 +2496,10 @@ int drgnn_pose_contact_counts(const drgnn_contact_counts_request* q, void* strea
     a.n_groups = (int)G; a.n_listed = L; a.counts = q->counts; a.residues = q->residues;
     const size_t count_bytes = (size_t)(G * nA * nB) * sizeof(int32_t), res_bytes = (size_t)(G * (nA + nB)) * sizeof(int32_t);
     const int blocks = (int)std::min<int64_t>((L + DRGNN_NWAVES - 1) / DRGNN_NWAVES, CS_COUNT_WGS);
-#ifdef DRGNN_EMU
-    (void)stream;
-    if (count_bytes) memset(q->counts, 0, count_bytes);
-    if (res_bytes) memset(q->residues, 0, res_bytes);
-    for (int b = 0; b < blocks; ++b) cs_count(a, b, blocks);
-#else
-    if (count_bytes) HIP_TRY(hipMemsetAsync(q->counts, 0, count_bytes, (hipStream_t)stream));
-    if (res_bytes) HIP_TRY(hipMemsetAsync(q->residues, 0, res_bytes, (hipStream_t)stream));
-    if (blocks > 0 && nA + nB > 0) {
-        hipLaunchKernelGGL(k_cons_count, dim3((unsigned)blocks), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
-        HIP_TRY(hipGetLastError());
-    }
-#endif
+    if (int rc = drgnn_clear(q->counts, count_bytes, stream)) return rc;
+    if (int rc = drgnn_clear(q->residues, res_bytes, stream)) return rc;
+    // (without residues a listed pose has no word to count: cs_count would write nothing)
+    if (nA + nB > 0) DRGNN_LAUNCH(k_cons_count, grid1(blocks), stream, cs_count(a, (int)bx, blocks), a);
     return 0;
 }
 
@@ -2673,14 +2518,8 @@ int drgnn_pose_consensus_numerators(const drgnn_consensus_numerators_request* q,
     memset(&a, 0, sizeof(a));
     a.bits = (const pc_word*)q->bits; a.counts = q->counts; a.row = q->row; a.n_a = (int)nA; a.n_b = (int)nB;
     a.numerators = (long long*)q->numerators;
-#ifdef DRGNN_EMU
-    (void)stream;
-    std::unique_ptr<ConsNumerShared> lds(new ConsNumerShared);
-    for (int64_t m = 0; m < M; ++m) cs_numer(a, m, *lds);
-#else
-    hipLaunchKernelGGL(k_cons_numer, dim3((unsigned)M), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-#endif
+    DRGNN_EMU_ONLY(std::unique_ptr<ConsNumerShared> lds(new ConsNumerShared);)
+    DRGNN_LAUNCH(k_cons_numer, grid1(M), stream, cs_numer(a, bx, *lds), a);
     return 0;
 }
 
@@ -2698,24 +2537,14 @@ int drgnn_pose_consensus_bits(const drgnn_consensus_bits_request* q, void* strea
     a.counts = q->counts; a.min_count = q->min_count; a.n_a = (int)nA; a.n_b = (int)nB;
     a.bits = (pc_word*)q->bits; a.n_contacts = q->n_contacts;
     const int blocks = (int)((nA * WB + CS_BW - 1) / CS_BW);
-#ifdef DRGNN_EMU
-    (void)stream;
-    memset(q->n_contacts, 0, (size_t)G * sizeof(int32_t));
-    for (int g = 0; g < (int)G; ++g)
-        for (int b = 0; b < blocks; ++b) cs_bits(a, g, b);
-#else
     static_assert(CS_GCAP <= 65535, "the groups fit the grid's y");
-    HIP_TRY(hipMemsetAsync(q->n_contacts, 0, (size_t)G * sizeof(int32_t), (hipStream_t)stream));
-    if (blocks > 0) {
-        hipLaunchKernelGGL(k_cons_bits, dim3((unsigned)blocks, (unsigned)G), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
-        HIP_TRY(hipGetLastError());
-    }
-#endif
+    if (int rc = drgnn_clear(q->n_contacts, (size_t)G * sizeof(int32_t), stream)) return rc;
+    DRGNN_LAUNCH(k_cons_bits, grid2(blocks, G), stream, cs_bits(a, (int)by, (int)bx), a);
     return 0;
 }
 
 // ---- pairwise pose RMSD and RMSD clustering of poses (drgnn_rmsd.h) ----------------------------------
-int32_t drgnn_rmsd_capacity(int32_t what) { return what == 0 ? RM_PCAP : what == 1 ? PC_CCAP : -1; }
+DRGNN_CAPACITY(drgnn_rmsd_capacity, RM_PCAP, PC_CCAP)
 
 // records of side a, of side b; off[2] is the size
 static int rmsd_layout(int64_t Ma, int64_t Mb, int64_t nF, int64_t nR, int64_t* off) {
@@ -2747,8 +2576,7 @@ int drgnn_pose_rmsd(const drgnn_pose_rmsd_request* q, void* stream) {
     if (Ma == 0 || Mb == 0) return 0;
     int64_t off[3];
     if (rmsd_layout(Ma, Mb, nF, nR, off) != 0) return DRGNN_E_ARG;
-    if (!q->workspace || ((uintptr_t)q->workspace & 7)) return DRGNN_E_ARG;
-    if (q->workspace_bytes < off[2]) return DRGNN_E_CAPACITY;
+    if (int rc = workspace_check(q->workspace, q->workspace_bytes, off[2], 8)) return rc;
     const int ph = q->phases == 0 ? 3 : q->phases;
     RmsdArgs a;
     memset(&a, 0, sizeof(a));
@@ -2759,35 +2587,18 @@ int drgnn_pose_rmsd(const drgnn_pose_rmsd_request* q, void* stream) {
     a.rec_b = a.same ? a.rec_a : (double*)((char*)q->workspace + off[1]);
     a.d = q->d;
     const int ti = (int)((Ma + RM_TILE - 1) / RM_TILE), tj = (int)((Mb + RM_TILE - 1) / RM_TILE);
-#ifdef DRGNN_EMU
-    (void)stream;
-    if (ph & 1) {
-        std::unique_ptr<RmsdPrepShared> lds(new RmsdPrepShared);
-        for (int64_t m = 0; m < Ma; ++m) rm_prepare(a, 0, m, *lds);
-        for (int64_t m = 0; m < Mb && !a.same; ++m) rm_prepare(a, 1, m, *lds);
-    }
-    if (ph & 2) {
-        std::unique_ptr<RmsdPairShared> lds(new RmsdPairShared);
-        for (int i = 0; i < ti; ++i)
-            for (int j = 0; j < tj; ++j) rm_pairs(a, i, j, *lds);
-    }
-#else
     static_assert(RM_TILE * RM_TILE == DRGNN_NTHREADS, "one lane per pose pair of a tile");
     static_assert(RM_K % 2 == 0 && sizeof(RmsdPairShared) <= 64 * 1024, "odd rows; the staged atoms fit the static LDS of a workgroup");
     static_assert((RM_PCAP + RM_TILE - 1) / RM_TILE <= 65535, "the tiles of a side fit the grid's y");
     if (ph & 1) {
-        hipLaunchKernelGGL(k_rmsd_prepare, dim3((unsigned)Ma), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a, 0);
-        HIP_TRY(hipGetLastError());
-        if (!a.same) {
-            hipLaunchKernelGGL(k_rmsd_prepare, dim3((unsigned)Mb), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a, 1);
-            HIP_TRY(hipGetLastError());
-        }
+        DRGNN_EMU_ONLY(std::unique_ptr<RmsdPrepShared> lds(new RmsdPrepShared);)
+        DRGNN_LAUNCH(k_rmsd_prepare, grid1(Ma), stream, rm_prepare(a, 0, bx, *lds), a, 0);
+        if (!a.same) DRGNN_LAUNCH(k_rmsd_prepare, grid1(Mb), stream, rm_prepare(a, 1, bx, *lds), a, 1);
     }
     if (ph & 2) {
-        hipLaunchKernelGGL(k_rmsd_pairs, dim3((unsigned)tj, (unsigned)ti), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
-        HIP_TRY(hipGetLastError());
+        DRGNN_EMU_ONLY(std::unique_ptr<RmsdPairShared> lds(new RmsdPairShared);)
+        DRGNN_LAUNCH(k_rmsd_pairs, grid2(tj, ti), stream, rm_pairs(a, (int)by, (int)bx, *lds), a);
     }
-#endif
     return 0;
 }
 
@@ -2798,7 +2609,7 @@ int drgnn_pose_cluster_dist(const drgnn_pose_cluster_dist_request* q, void* stre
     DistRule rule;
     memset(&rule, 0, sizeof(rule));
     rule.d = q->d; rule.cutoff = q->cutoff;
-    return pose_cluster_run(rule, q, PC_RELATION_KERNEL(k_rmsd_relation), stream);
+    return pose_cluster_run(rule, q, DRGNN_KERNEL(k_rmsd_relation), stream);
 }
 
 // ---- evaluation scores (drgnn_metrics.h) ---------------------------------------------------------
@@ -2809,37 +2620,16 @@ int64_t drgnn_metrics_workspace_bytes(int64_t n) {
     return off[8];
 }
 
-#ifdef DRGNN_EMU
-// a launch of the emulation: workgroups one after another
-#define MT_GRID(nblocks, body) do { for (int blk = 0; blk < (int)(nblocks); ++blk) { body; } } while (0)
-#else
-#define MT_LAUNCH(kernel, nblocks, nthreads, ...)                                                              \
-    do {                                                                                                       \
-        hipLaunchKernelGGL(kernel, dim3((unsigned)(nblocks)), dim3(nthreads), 0, st, __VA_ARGS__);             \
-        HIP_TRY(hipGetLastError());                                                                            \
-    } while (0)
-#endif
-
 // stable ascending LSD sort of a.keys[0] (payload a.vals[0] when set): MT_PASSES digits, the result back in buffer 0
 static int mt_sort(MetricsArgs& a, void* stream) {
-#ifdef DRGNN_EMU
-    (void)stream;
-    std::unique_ptr<MtHistShared> hs(new MtHistShared);
-    std::unique_ptr<MtScanShared> ss(new MtScanShared);
-    std::unique_ptr<MtScatterShared> xs(new MtScatterShared);
+    DRGNN_EMU_ONLY(std::unique_ptr<MtHistShared> hs(new MtHistShared); std::unique_ptr<MtScanShared> ss(new MtScanShared);
+                   std::unique_ptr<MtScatterShared> xs(new MtScatterShared);)
+    const Grid tiles = grid1(a.n_tiles, MT_NT);
     for (int pass = 0; pass < MT_PASSES; ++pass) {
-        MT_GRID(a.n_tiles, mt_hist_block(a, blk, pass, *hs));
-        mt_exscan_block<int32_t>(a.hist, (int64_t)MT_RADIX * a.n_tiles, *ss);
-        MT_GRID(a.n_tiles, mt_scatter_block(a, blk, pass, *xs));
+        DRGNN_LAUNCH(k_mt_hist, tiles, stream, mt_hist_block(a, (int)bx, pass, *hs), a, pass);
+        DRGNN_LAUNCH(k_mt_scan, grid1(1, MT_SNT), stream, mt_exscan_block<int32_t>(a.hist, (int64_t)MT_RADIX * a.n_tiles, *ss), a);
+        DRGNN_LAUNCH(k_mt_scatter, tiles, stream, mt_scatter_block(a, (int)bx, pass, *xs), a, pass);
     }
-#else
-    hipStream_t st = (hipStream_t)stream;
-    for (int pass = 0; pass < MT_PASSES; ++pass) {
-        MT_LAUNCH(k_mt_hist, a.n_tiles, MT_NT, a, pass);
-        MT_LAUNCH(k_mt_scan, 1, MT_SNT, a);
-        MT_LAUNCH(k_mt_scatter, a.n_tiles, MT_NT, a, pass);
-    }
-#endif
     return 0;
 }
 
@@ -2868,50 +2658,28 @@ int drgnn_metrics(const double* pred, const double* y, int64_t n, int32_t what, 
     a.counts = (long long*)counts; a.scores = scores; a.hits = (long long*)hits;
     MetricsArgs r = a;                  // the |r| sort: keys only
     r.vals[0] = r.vals[1] = nullptr;
-#ifdef DRGNN_EMU
-    std::unique_ptr<MtRedShared> rs(new MtRedShared);
-    std::unique_ptr<MtScanShared> ss(new MtScanShared);
-    std::unique_ptr<MtHitShared> hs(new MtHitShared);
-    if (what & (DRGNN_METRICS_COUNTS | DRGNN_METRICS_REGRESSION)) {
-        MT_GRID(a.G, mt_reduce_block(a, blk, 0, *rs));
-        mt_combine_block(a, 0);
-    }
-    if (what & DRGNN_METRICS_REGRESSION) {
-        MT_GRID(a.G, mt_reduce_block(a, blk, 1, *rs));
-        mt_combine_block(a, 1);
-        MT_GRID(a.n_tiles, mt_keys_block(r, blk, 1));
-        mt_sort(r, stream);
-        mt_median(r);
-    }
-    if (what & DRGNN_METRICS_RANKING) {
-        MT_GRID(a.n_tiles, mt_keys_block(a, blk, 0));
-        mt_sort(a, stream);
-        MT_GRID(a.n_tiles, mt_hit_block(a, blk, 0, *hs));
-        mt_hit_scan_block(a, *ss);
-        MT_GRID(a.n_tiles, mt_hit_block(a, blk, 1, *hs));
-    }
-#else
-    hipStream_t st = (hipStream_t)stream;
+    DRGNN_EMU_ONLY(std::unique_ptr<MtRedShared> rs(new MtRedShared); std::unique_ptr<MtScanShared> ss(new MtScanShared);
+                   std::unique_ptr<MtHitShared> hs(new MtHitShared);)
+    const Grid parts = grid1(a.G, MT_NT), tiles = grid1(a.n_tiles, MT_NT), one = grid1(1, MT_NT);
     int rc;
     if (what & (DRGNN_METRICS_COUNTS | DRGNN_METRICS_REGRESSION)) {
-        MT_LAUNCH(k_mt_reduce, a.G, MT_NT, a, 0);
-        MT_LAUNCH(k_mt_combine, 1, MT_NT, a, 0);
+        DRGNN_LAUNCH(k_mt_reduce, parts, stream, mt_reduce_block(a, (int)bx, 0, *rs), a, 0);
+        DRGNN_LAUNCH(k_mt_combine, one, stream, mt_combine_block(a, 0), a, 0);
     }
     if (what & DRGNN_METRICS_REGRESSION) {
-        MT_LAUNCH(k_mt_reduce, a.G, MT_NT, a, 1);
-        MT_LAUNCH(k_mt_combine, 1, MT_NT, a, 1);
-        MT_LAUNCH(k_mt_keys, a.n_tiles, MT_NT, r, 1);
+        DRGNN_LAUNCH(k_mt_reduce, parts, stream, mt_reduce_block(a, (int)bx, 1, *rs), a, 1);
+        DRGNN_LAUNCH(k_mt_combine, one, stream, mt_combine_block(a, 1), a, 1);
+        DRGNN_LAUNCH(k_mt_keys, tiles, stream, mt_keys_block(r, (int)bx, 1), r, 1);
         if ((rc = mt_sort(r, stream))) return rc;
-        MT_LAUNCH(k_mt_median, 1, 64, r);
+        DRGNN_LAUNCH(k_mt_median, grid1(1, 64), stream, mt_median(r), r);
     }
     if (what & DRGNN_METRICS_RANKING) {
-        MT_LAUNCH(k_mt_keys, a.n_tiles, MT_NT, a, 0);
+        DRGNN_LAUNCH(k_mt_keys, tiles, stream, mt_keys_block(a, (int)bx, 0), a, 0);
         if ((rc = mt_sort(a, stream))) return rc;
-        MT_LAUNCH(k_mt_hit, a.n_tiles, MT_NT, a, 0);
-        MT_LAUNCH(k_mt_hit_scan, 1, MT_SNT, a);
-        MT_LAUNCH(k_mt_hit, a.n_tiles, MT_NT, a, 1);
+        DRGNN_LAUNCH(k_mt_hit, tiles, stream, mt_hit_block(a, (int)bx, 0, *hs), a, 0);
+        DRGNN_LAUNCH(k_mt_hit_scan, grid1(1, MT_SNT), stream, mt_hit_scan_block(a, *ss), a);
+        DRGNN_LAUNCH(k_mt_hit, tiles, stream, mt_hit_block(a, (int)bx, 1, *hs), a, 1);
     }
-#endif
     return 0;
 }
 
