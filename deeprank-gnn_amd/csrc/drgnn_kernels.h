@@ -19,6 +19,7 @@
 #include "drgnn_posecluster.h"
 #include "drgnn_fcc.h"
 #include "drgnn_consensus.h"
+#include "drgnn_lddt.h"
 #include "drgnn_rmsd.h"
 #include "drgnn_pack.h"
 #include "drgnn_metrics.h"
@@ -1044,6 +1045,12 @@ __global__ void __launch_bounds__(DRGNN_NTHREADS) k_cons_numer(ConsNumerArgs a) 
     cs_numer(a, (int64_t)blockIdx.x, smem_cn);
 }
 __global__ void __launch_bounds__(DRGNN_NTHREADS) k_cons_bits(ConsBitsArgs a) { cs_bits(a, (int)blockIdx.y, (int)blockIdx.x); }
+// lDDT of poses (drgnn_lddt.h): one workgroup per LD_RB residues (x) and PP poses (y); an item per word of counts
+template <int PP, int KT> __global__ void __launch_bounds__(DRGNN_NTHREADS) k_pose_lddt(LddtArgs a) {
+    __shared__ LddtShared smem_ld;
+    ld_block<PP, KT>(a, (int)blockIdx.x, a.m0 + (int64_t)blockIdx.y * PP, smem_ld);
+}
+__global__ void __launch_bounds__(256) k_lddt_halve(LddtArgs a) { ld_halve_item(a, a.m0 + (int64_t)blockIdx.x * 256 + threadIdx.x); }
 // pairwise pose RMSD (drgnn_rmsd.h): one workgroup per pose of one side; per tile of pose pairs; a wave per word of the
 // neighbour relation (the greedy clustering is k_fcc_greedy)
 __global__ void __launch_bounds__(DRGNN_NTHREADS) k_rmsd_prepare(RmsdArgs a, int side) {

@@ -1,5 +1,5 @@
 """Docking scores of poses against a reference structure on the device (csrc/drgnn_score.h): irmsd, lrmsd, fnat, dockQ
-and the two classes (Graph.get_score of the reference)."""
+and the two classes (Graph.get_score of the reference); and their lDDT and interface lDDT (csrc/drgnn_lddt.h)."""
 import numpy as np
 import torch
 
@@ -153,11 +153,175 @@ def docking_scores(poses_or_table, reference, device=None, api=None, chunk=None)
 
 
 def attach_scores(store, names, scores):
-    """``score/<key>`` of molecule ``names[i]`` of ``store`` = ``scores[key][i]`` for the keys of SCORE_KEYS that
-    ``scores`` (what ``docking_scores`` returns) holds; ``binclass`` is stored as a bool, as the reference does."""
+    """``score/<key>`` of molecule ``names[i]`` of ``store`` = ``scores[key][i]`` for the keys of SCORE_KEYS and
+    LDDT_KEYS that ``scores`` (what ``docking_scores`` or ``lddt_scores`` returns) holds; ``binclass`` is stored as a
+    bool, as the reference does."""
     for i, mol in enumerate(names):
-        for k in SCORE_KEYS:
+        for k in SCORE_KEYS + LDDT_KEYS:
             if k in scores:
                 v = scores[k][i]
                 store.set(str(mol), "score/" + k, np.asarray(bool(v)) if k == "binclass" else np.asarray(v))
     return store
+
+
+# ---- lDDT and interface lDDT (csrc/drgnn_lddt.h) -----------------------------------------------------------------------
+LDDT_KEYS = ("lddt", "ilddt")
+LDDT_THRESHOLDS = (0.5, 1.0, 2.0, 4.0)
+
+
+def _heavy(names):
+    """bool [N]: not a hydrogen, by the name rule of ``counted_atoms``"""
+    return np.array([str(n).lstrip("0123456789 ")[:1] != "H" for n in names], dtype=bool).reshape(-1)
+
+
+class LddtReference(object):
+    """The once-per-complex half of the lDDT (Mariani et al. 2013), on the host: the reference's heavy-atom pairs of
+    different residues at ``d_ref < inclusion_radius`` on the table's two chains, the matching of the table's heavy
+    atoms to the reference's by (chain, res_seq, atom name) (the first atom of a key on either side), and the tables
+    ``drgnn_pose_lddt`` takes (include/drgnn.h): the matched pairs as entries grouped by owning residue, every pair in
+    both directions.  The pairs are found ``rows`` reference atoms at a time.
+
+    ``n_pairs`` / ``n_inter_pairs``: the reference's pairs and the inter-chain ones, unmatched atoms included (the
+    denominators); ``n_matched_pairs``: those with both atoms in the table; ``n_pairs_of_residue`` /
+    ``n_inter_pairs_of_residue`` int64 [R]: the reference's pairs with an end in each residue of the table;
+    ``n_ref_atoms`` / ``n_matched_atoms``: the reference's heavy atoms on the two chains and those with a partner."""
+
+    def __init__(self, table, ref_chain, ref_res_seq, ref_atom_name, ref_xyz, inclusion_radius=15.0,
+                 thresholds=LDDT_THRESHOLDS, rows=256):
+        if table.atom_name is None:
+            raise ValueError("lDDT matches atoms by name: build the AtomTable with atom_name=")
+        ref_chain = np.asarray(ref_chain).astype("U")
+        seq = np.asarray(ref_res_seq).astype(np.int64)
+        name = np.asarray(ref_atom_name).astype("U")
+        xyz = np.asarray(ref_xyz, dtype=np.float64)
+        if not (ref_chain.shape == seq.shape == name.shape == xyz.shape[:1]) or xyz.shape[1:] != (3,):
+            raise ValueError("ref_chain, ref_res_seq, ref_atom_name [N] and ref_xyz [N,3] must describe the same atoms")
+        thr = np.asarray(thresholds, dtype=np.float64).reshape(-1)
+        if not 1 <= thr.size <= 8 or not np.all(np.isfinite(thr)) or thr[0] < 0.0 or np.any(np.diff(thr) <= 0.0):
+            raise ValueError("1 to 8 thresholds, not negative and increasing")
+        self.table, self.inclusion_radius, self.thresholds = table, float(inclusion_radius), thr
+        side = np.full(ref_chain.shape, -1, dtype=np.int64)
+        side[ref_chain == table.chains[0]] = 0
+        side[ref_chain == table.chains[1]] = 1
+        at = np.flatnonzero((side >= 0) & _heavy(name))                # the reference's heavy atoms on the two chains
+        n, R = int(at.size), table.n_residues
+        side, seq, name, x = side[at], seq[at], name[at], xyz[at]
+        res_id = np.unique(np.stack((side, seq), axis=1), axis=0, return_inverse=True)[1].reshape(-1) if n else np.zeros(0, np.int64)
+        res_of = {(int(c), int(q)): r for r, (c, q) in enumerate(zip(table.res_chain, table.res_seq))}
+        table_res = np.array([res_of.get((int(c), int(q)), -1) for c, q in zip(side, seq)], dtype=np.int64).reshape(-1)
+        # matching: the first heavy atom of every (side, res_seq, name), in the table and in the reference
+        res_of_atom = np.repeat(np.arange(R), np.diff(table.atom_ptr))
+        table_of = {}
+        for i in np.flatnonzero(_heavy(table.atom_name))[::-1]:
+            r = res_of_atom[i]
+            table_of[(int(table.res_chain[r]), int(table.res_seq[r]), str(table.atom_name[i]))] = int(i)
+        partner, seen = np.full(n, -1, dtype=np.int64), set()
+        for k in range(n):
+            key = (int(side[k]), int(seq[k]), str(name[k]))
+            if key not in seen:
+                seen.add(key)
+                partner[k] = table_of.get(key, -1)
+        self.n_ref_atoms, self.n_matched_atoms = n, int((partner >= 0).sum())
+        # the pairs i < j, `rows` atoms i at a time
+        self.n_pairs = self.n_inter_pairs = 0
+        self.n_pairs_of_residue, self.n_inter_pairs_of_residue = np.zeros(R, np.int64), np.zeros(R, np.int64)
+        found, col = [], np.arange(n)
+        for lo in range(0, n, rows):
+            hi = min(lo + rows, n)
+            dx, dy, dz = (x[lo:hi, None, a] - x[None, :, a] for a in range(3))
+            d = np.sqrt((dx * dx + dy * dy) + dz * dz)
+            i, j = np.nonzero((d < self.inclusion_radius) & (res_id[lo:hi, None] != res_id[None, :]) & (col[None, :] > col[lo:hi, None]))
+            d, i = d[i, j], i + lo
+            inter = side[i] != side[j]
+            self.n_pairs += int(i.size)
+            self.n_inter_pairs += int(inter.sum())
+            for end in (i, j):
+                r = table_res[end]
+                self.n_pairs_of_residue += np.bincount(r[r >= 0], minlength=R)
+                self.n_inter_pairs_of_residue += np.bincount(r[(r >= 0) & inter], minlength=R)
+            both = (partner[i] >= 0) & (partner[j] >= 0)
+            found.append((partner[i][both], partner[j][both], d[both]))
+        if self.n_pairs == 0:
+            raise ValueError("the reference has no atom pair within %g" % self.inclusion_radius)
+        if self.n_inter_pairs == 0:
+            raise ValueError("the reference has no inter-chain atom pair within %g" % self.inclusion_radius)
+        ti, tj, d = (np.concatenate([f[a] for f in found]) for a in range(3))
+        self.n_matched_pairs = int(ti.size)
+        if 2 * self.n_matched_pairs > 2 ** 31 - 1:
+            raise ValueError("%d matched pairs are too many for int32 entry offsets" % self.n_matched_pairs)
+        # entries: every pair under both of its atoms, grouped by the residue of the first, sorted by (self, other)
+        own, other, d = np.concatenate((ti, tj)), np.concatenate((tj, ti)), np.concatenate((d, d))
+        order = np.lexsort((other, own))                               # (atoms are grouped by residue: by residue too)
+        self.self_atom = np.ascontiguousarray(own[order], dtype=np.int32)
+        self.other_atom = np.ascontiguousarray(other[order], dtype=np.int32)
+        self.d_ref = np.ascontiguousarray(d[order], dtype=np.float64)
+        self.entry_ptr = np.concatenate(([0], np.cumsum(np.bincount(res_of_atom[own], minlength=R)))).astype(np.int32)
+        self.n_chain_a_atoms = int(table.atom_ptr[table.split])
+        self._device = {}
+
+    def device_tables(self, device):
+        """(entry_ptr, self_atom, other_atom, d_ref) on ``device``, uploaded once"""
+        key = str(torch.device(device))
+        if key not in self._device:
+            self._device[key] = tuple(torch.from_numpy(a).to(device) for a in
+                                      (self.entry_ptr, self.self_atom, self.other_atom, self.d_ref))
+        return self._device[key]
+
+
+def lddt_raw(api, xyz, entry_ptr, self_atom, other_atom, d_ref, n_chain_a_atoms, thresholds=LDDT_THRESHOLDS,
+             residue_counts=False, device="cpu", tables=None, poses_per_pass=0):
+    """One drgnn_pose_lddt call (include/drgnn.h) over numpy arrays: xyz float32 [M,T,3].  Returns (counts int32 [M,2,K],
+    residue_counts int32 [M,R,2,K] or None) as numpy arrays.  ``tables``: the four entry tables already on the device."""
+    xyz = np.ascontiguousarray(xyz, dtype=np.float32)
+    thr = np.asarray(thresholds, dtype=np.float64).reshape(-1)
+    if xyz.ndim != 3 or xyz.shape[2] != 3 or not 1 <= thr.size <= 8:
+        raise ValueError("xyz [M,T,3] and 1 to 8 thresholds")
+    r = Request(_lib.LddtRequest, device)
+    d_ep, d_sa, d_oa, d_dr = tables if tables is not None else (None,) * 4
+    ep = r.table("entry_ptr", entry_ptr, device_copy=d_ep)[0]
+    sa = r.table("self_atom", self_atom, device_copy=d_sa)[0]
+    r.table("other_atom", other_atom, device_copy=d_oa)
+    r.input("d_ref", d_ref if d_dr is None else d_dr, torch.float64, error="d_ref on the device must be float64")
+    r.input("xyz", xyz, torch.float32)
+    M, R, K = int(xyz.shape[0]), len(ep) - 1, int(thr.size)
+    r.set(n_poses=M, n_atoms=int(xyz.shape[1]), n_residues=R, n_entries=int(sa.shape[0]), n_chain_a_atoms=int(n_chain_a_atoms),
+          thresholds=type(r.q.thresholds)(*thr.tolist()), n_thresholds=K, poses_per_pass=int(poses_per_pass))
+    counts = r.output("counts", (M, 2, K), torch.int32)
+    per_res = r.output("residue_counts", (M, R, 2, K), torch.int32) if residue_counts else None
+    r.run(api, "pose_lddt")
+    return counts.cpu().numpy(), per_res.cpu().numpy() if residue_counts else None
+
+
+def lddt_scores(poses_or_table, reference, per_residue=False, device=None, api=None, chunk=None):
+    """The lDDT of M poses of ``reference.table`` (an ``AtomTable.poses`` batch, the table itself, or xyz float32
+    [M,T,3] already in the table's grouped atom order) against ``reference``, an ``LddtReference``: a dict of numpy
+    arrays, ``lddt`` and ``ilddt`` (the inter-chain pairs alone) float64 [M] and ``preserved`` int64 [M,2,K], the
+    preserved pairs (all, inter-chain) at each threshold; with ``per_residue`` also ``residue_lddt`` and
+    ``residue_ilddt`` float64 [M,R] (NaN: a residue without a reference pair) and ``residue_preserved`` int64 [M,R,2,K].
+    A score is the fp64 quotient of the summed counts and K times the reference's pairs.  One call per ``chunk`` poses
+    (default: what keeps the uploaded coordinates, and the per-residue counts, within SCORE_XYZ_BUDGET bytes); a pose's
+    result does not depend on the chunk, on its place in the batch or on the run."""
+    api = api or _lib.get()
+    device = _default_device(api, device)
+    t, xyz = _pose_batch(poses_or_table, reference.table, "the poses must be of the reference's AtomTable")
+    K, R = int(reference.thresholds.size), t.n_residues
+    if chunk is None:
+        chunk = SCORE_XYZ_BUDGET // max(12 * t.n_atoms, 8 * K * R if per_residue else 1, 1)
+    chunk = max(1, int(chunk))
+    tables = reference.device_tables(device)
+    parts = [lddt_raw(api, xyz[lo:lo + chunk], reference.entry_ptr, reference.self_atom, reference.other_atom, reference.d_ref,
+                      reference.n_chain_a_atoms, reference.thresholds, per_residue, device, tables)
+             for lo in range(0, xyz.shape[0], chunk)]
+    counts = np.concatenate([p[0] for p in parts]).astype(np.int64) if parts else np.zeros((0, 2, K), np.int64)
+    total = counts.sum(axis=2).astype(np.float64)
+    out = {"lddt": total[:, 0] / np.float64(K * reference.n_pairs), "ilddt": total[:, 1] / np.float64(K * reference.n_inter_pairs),
+           "preserved": counts}
+    if per_residue:
+        rc = np.concatenate([p[1] for p in parts]).astype(np.int64) if parts else np.zeros((0, R, 2, K), np.int64)
+        total = rc.sum(axis=3).astype(np.float64)
+        for c, (key, pairs) in enumerate((("residue_lddt", reference.n_pairs_of_residue),
+                                          ("residue_ilddt", reference.n_inter_pairs_of_residue))):
+            den = (K * pairs).astype(np.float64)
+            out[key] = total[:, :, c] / np.where(den > 0, den, np.nan)[None, :]
+        out["residue_preserved"] = rc
+    return out

@@ -6,7 +6,7 @@ import torch
 from . import _lib
 from ._request import Request
 from .atoms import RESIDUE_CHARGE, RESIDUE_POLARITY, _complexes, _default_device, _ragged
-from .dock_scores import SCORE_KEYS, attach_scores, docking_scores
+from .dock_scores import SCORE_KEYS, attach_scores, docking_scores, lddt_scores
 from .residue_features import FEATURES, _feature_chunk
 
 WORKSPACE_BUDGET = 256 << 20       # bytes of dense min-d^2 workspace one call may ask for (sets the default chunk)
@@ -71,7 +71,7 @@ def default_chunk(api, max_res_a, max_res_b, max_atoms, budget=WORKSPACE_BUDGET)
 
 
 def interface_graphs(tables_or_poses, names, contact_distance=8.5, internal_contact_distance=3.0, device=None, chunk=None,
-                     api=None, reference=None, bsa=False, hse=False, depth=False):
+                     api=None, reference=None, bsa=False, hse=False, depth=False, lddt=None):
     """Interface graphs of complexes (a sequence of ``AtomTable``, an ``AtomTable.poses`` batch, or a mix) as a
     ``GraphStore`` with one molecule per name, in the reference's tree: ``edge_index``, ``edge_data/dist``,
     ``internal_edge_index``, ``internal_edge_data/dist``, ``nodes`` and, under ``node_data/``, ``pos``, ``chain``,
@@ -86,7 +86,10 @@ def interface_graphs(tables_or_poses, names, contact_distance=8.5, internal_cont
     ``node_data/hse``, float64 [n,3], the half-sphere exposure (up, down, angle) of exactly its nodes (one more launch
     per chunk); a node without a value has the row (0, 0, 0), as in the reference.
     ``depth``: True, or a dict of ``residue_depth`` options (radii, probe, n_dots, link, components): every molecule also
-    gets ``node_data/depth``, float64 [n], the residue depth of exactly its nodes (three more launches per chunk)."""
+    gets ``node_data/depth``, float64 [n], the residue depth of exactly its nodes (three more launches per chunk).
+    ``lddt``: an ``LddtReference``; every complex must then be a pose of its table, and every molecule also gets
+    ``score/lddt``, ``score/ilddt`` and ``node_data/lddt``, float64 [n], the per-residue lDDT of exactly its nodes (0 for
+    a residue without a reference pair)."""
     from .dataset import GraphStore
     api = api or _lib.get()
     device = _default_device(api, device)
@@ -96,6 +99,8 @@ def interface_graphs(tables_or_poses, names, contact_distance=8.5, internal_cont
         raise ValueError("%d names for %d complexes" % (len(names), len(cx)))
     if reference is not None and not all(t is reference.table for t, _ in cx):
         raise ValueError("with `reference`, every complex must be a pose of the reference's AtomTable")
+    if lddt is not None and not all(t is lddt.table for t, _ in cx):
+        raise ValueError("with `lddt`, every complex must be a pose of the reference's AtomTable")
     active = [(f,) + f.options(value, [t for t, _ in cx])              # the options and the host tables refuse before any launch
               for f, value in zip(FEATURES, (bsa, hse, depth)) if value is not None and value is not False]
     if chunk is None:
@@ -136,6 +141,12 @@ def interface_graphs(tables_or_poses, names, contact_distance=8.5, internal_cont
     store = GraphStore.from_trees(names, trees)
     if reference is not None and cx:
         attach_scores(store, names, docking_scores(np.stack([x for _, x in cx]), reference, device=device, api=api))
+    if lddt is not None and cx:
+        scores = lddt_scores(np.stack([x for _, x in cx]), lddt, per_residue=True, device=device, api=api)
+        attach_scores(store, names, scores)
+        for m, mol in enumerate(names):
+            per_residue = scores["residue_lddt"][m]
+            store.set(mol, "node_data/lddt", np.where(np.isnan(per_residue), 0.0, per_residue)[store.get(mol, "node_data/residue")])
     return store
 
 

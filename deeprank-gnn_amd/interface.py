@@ -20,6 +20,13 @@ Graph.py:27-59):
     scores = docking_scores(poses, ref)                        # dict of arrays [M], one launch per chunk of poses
     store = interface_graphs(poses, names, reference=ref)      # the graphs with score/<target> on every molecule
 
+and the superposition-free lDDT of the poses (Mariani et al. 2013; csrc/drgnn_lddt.h), over all atom pairs, over the
+inter-chain ones (the interface lDDT) and per residue:
+
+    lref = LddtReference(table, rc, rs, rn, rx)                # once per complex, on the host
+    q = lddt_scores(poses, lref, per_residue=True)             # lddt, ilddt [M], residue_lddt [M, R]
+    store = interface_graphs(poses, names, lddt=lref)          # score/lddt, score/ilddt and node_data/lddt
+
 and the buried surface area of the interface residues (``bsa``: tools/BSA.py through freesasa's Lee-Richards
 method, with the reference's radii), which needs the atom names:
 
@@ -85,7 +92,8 @@ from .residue_features import (  # noqa: F401
     _hse_options, _per_table, _residue_values, _targets, bsa_radii, bsa_raw, depth_dots, depth_link, depth_radii,
     depth_raw, hse_raw, hse_table, hse_tile, residue_bsa, residue_depth, residue_hse)
 from .dock_scores import (  # noqa: F401
-    SCORE_KEYS, SCORE_XYZ_BUDGET, ScoreReference, _residue_pairs, attach_scores, dock_scores_raw, docking_scores)
+    LDDT_KEYS, LDDT_THRESHOLDS, LddtReference, SCORE_KEYS, SCORE_XYZ_BUDGET, ScoreReference, _heavy, _residue_pairs,
+    attach_scores, dock_scores_raw, docking_scores, lddt_raw, lddt_scores)
 from .iface_graphs import (  # noqa: F401
     FEATURE_WIDTH, MCL_WORKSPACE_BUDGET, PACK_SOURCE, WORKSPACE_BUDGET, _mcl_groups, _pack_columns, _residue_tables,
     attach_residue_features, build_ragged, build_ragged_device, default_chunk, iface_pack_raw, interface_graphs,

@@ -750,6 +750,47 @@ typedef struct drgnn_score_request {
  * DRGNN_E_CAPACITY: M or 3 T beyond 2^31 - 1.  No allocation, no synchronisation. */
 int drgnn_dock_scores(const drgnn_score_request* req, void* stream);
 
+/* ---- lDDT and interface lDDT of pose batches (drgnn_lddt.h) ---------------------------------------------
+ * The local distance difference test (Mariani et al. 2013) of M poses of one topology against one reference structure,
+ * as integers: per pose and threshold the preserved reference pairs over all pairs, over the inter-chain ones and per
+ * residue.  The once-per-complex work and the fp64 quotients are the caller's (deeprank_gnn_amd.interface.LddtReference,
+ * lddt_scores); the rule (tests/lddt_ref.py states it in numpy; conventions at exact ties are this project's own):
+ *   atoms      heavy atoms only, on both sides; a reference atom and a table atom correspond when (chain, res_seq, atom
+ *              name) are equal.  Unmatched table atoms are ignored, unmatched reference atoms stay in the denominators.
+ *   pairs      two reference heavy atoms on the table's two chains, of different residues (chain, res_seq), with
+ *              d_ref < inclusion_radius (strict), d_ref = sqrt((dx dx + dy dy) + dz dz) in fp64 on the host
+ *   preserved  at threshold t: lo = max(d_ref - t, 0), hi = d_ref + t, lo lo <= d2 <= hi hi with d2 = (dx dx + dy dy) +
+ *              dz dz in fp64 from the pose's fp32 coordinates, every product and sum rounded on its own
+ * Inputs (device unless host_*): xyz f32 [M,T,3]; the matched pairs as entries grouped by owning residue, every pair in
+ * both directions: entry_ptr i32 [R+1], self_atom i32 [E] (an atom of the owning residue), other_atom i32 [E], d_ref f64
+ * [E]; n_chain_a_atoms: the first atom of chain B (a pair is inter-chain when exactly one of its atoms lies before it);
+ * thresholds[n_thresholds], increasing.  The index tables are also given as HOST arrays: every check comes from them.
+ * poses_per_pass: 0 the library's choice (4 once such passes make 1 024 workgroups of 64 residues, else 1), 1 or 4 the
+ * poses that share one pass over the entries (the counts do not depend on it).  Outputs: counts i32 [M,2,K] (all, inter-chain), each pair counted once; residue_counts i32 [M,R,2,K]
+ * or NULL, a pair counted for both of its residues.  Everything is an integer: no floating-point atomics; a pose's counts
+ * do not depend on M, on its place in the batch or on the run.  A clear, one launch per 65 535 passes, a halving launch. */
+typedef struct drgnn_lddt_request {
+    const float* xyz;
+    const int32_t* entry_ptr;
+    const int32_t* self_atom;
+    const int32_t* other_atom;
+    const double* d_ref;
+    const int32_t* host_entry_ptr;     /* the index tables in host memory */
+    const int32_t* host_self_atom;
+    const int32_t* host_other_atom;
+    int64_t n_poses, n_atoms, n_residues, n_entries, n_chain_a_atoms;
+    double thresholds[8];
+    int32_t n_thresholds, poses_per_pass;
+    int32_t* counts;
+    int32_t* residue_counts;
+} drgnn_lddt_request;
+
+/* DRGNN_E_ARG, before any launch: a null pointer, an entry_ptr that does not start at 0, decreases or ends elsewhere than
+ * n_entries, an atom index outside [0, T), n_chain_a_atoms outside [0, T], n_thresholds outside 1..8, thresholds that are
+ * negative or not increasing, poses_per_pass other than 0, 1 or 4, a negative count.  DRGNN_E_CAPACITY: M, 3 T or the entry
+ * count beyond 2^31 - 1 (or R beyond 2^28).  No allocation, no synchronisation. */
+int drgnn_pose_lddt(const drgnn_lddt_request* req, void* stream);
+
 /* ---- buried surface area of residues (drgnn_bsa.h) -----------------------------------------------------
  * The reference's `bsa` node feature (tools/BSA.py, through freesasa's Lee-Richards method) for K chosen residues of a
  * ragged batch of M two-chain complexes laid out as for drgnn_iface_count: xyz f32 [T,3], atom_ptr i32 [R+1], res_ptr
