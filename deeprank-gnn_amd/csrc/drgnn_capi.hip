@@ -5,24 +5,28 @@
 //   g++ -x c++ -DDRGNN_EMU      -> tests/emu/build/libdrgnn_emu.so (CPU test-suite only:
 //        every "launch" becomes a loop over workgroups on host pointers)
 //
-// The feature entry points (pose_cluster_run, then "stand-alone layers / pooling functions" down to drgnn_metrics) write their
-// launch sequence ONCE for both builds, with DRGNN_LAUNCH / DRGNN_EMU_ONLY / drgnn_clear of drgnn_launch.h: the checks, phases,
-// guards and early returns the CPU suite runs are the ones the GPU runs.  A new entry point touches three places: its block
-// function in a drgnn_<subsystem>.h, its __global__ wrapper in drgnn_kernels.h, and its checks and launches here.  A DRGNN_EMU
-// conditional in that range says why the builds differ.  The training path above and below it still spells both builds out.
+// The entry points write their launch sequence ONCE for both builds, with DRGNN_LAUNCH / DRGNN_EMU_ONLY / drgnn_clear of
+// drgnn_launch.h: the checks, phases, guards and early returns the CPU suite runs are the ones the GPU runs.  That holds for the
+// feature entry points (pose_cluster_run, then "stand-alone layers / pooling functions" down to drgnn_metrics) and for the
+// launches of the training path: the topology builder (topo_launch) and its prologue, the launch pair (net_launch, its co-built
+// builder included), the head, the flat Adam, the all-reduce, collation and the epoch loop's clear.  A new entry point touches
+// three places: its block function in a drgnn_<subsystem>.h, its __global__ wrapper in drgnn_kernels.h, and its checks and
+// launches here.  A DRGNN_EMU conditional says on its line why the builds differ in what they DO: the fused step (emu_step
+// stands in for the aggregation-first kernels, so its pick, checks, plans and launch differ), the device queries,
+// drgnn_topology_status, the update / gradient / reduce launches and adam_opt_impl (item-wise sums against the kernels' blocks),
+// the drgnn_p2p_* allocation functions and the profiling hook.
 #define DRGNN_KERNELS_MAIN
 #include "drgnn_kernels.h"
 
 #include <vector>
 #include <algorithm>
 #include <memory>
+#include <type_traits>
 #include <string.h>
 #include <stdlib.h>
-#ifdef DRGNN_EMU
 #define DRGNN_LDS_LIMIT (160 * 1024)
-#else
-#define DRGNN_LDS_LIMIT (160 * 1024)
-#define HIP_TRY(expr)                                   \
+#ifndef DRGNN_EMU      // (the emulation makes no runtime call)
+#define HIP_TRY(expr)                                 \
     do {                                                \
         hipError_t e_ = (expr);                         \
         if (e_ != hipSuccess) return (int)e_;           \
@@ -180,14 +184,24 @@ static int topo_prepare_req(TopoLaunch& T, int64_t* tlds, const drgnn_topology_r
     return 0;
 }
 
+// One launch of a prepared builder: out of `lds` bytes of LDS at L.roles workgroups per graph, or out of the global scratch.
+static int topo_launch(const TopoLaunch& L, int64_t lds, void* stream) {
+    DRGNN_EMU_ONLY(std::vector<int> buf((size_t)(lds / 4) + 16);)
+    if (L.capN > 0)
+        DRGNN_LAUNCH(k_topo<true>, grid1((int64_t)L.args.n_graphs * L.roles, DRGNN_NTHREADS, lds), stream,
+                     topo_block<true>(L, (int)bx, buf.data()), L);
+    else
+        DRGNN_LAUNCH(k_topo<false>, grid1(L.args.n_graphs), stream, topo_block<false>(L, (int)bx, buf.data()), L);
+    return 0;
+}
+
 static int topology_build_impl(const int64_t* edge_index, const float* edge_attr, const int64_t* batch,
                          const int64_t* cluster0, const int64_t* cluster1, const int32_t* node_ptr,
                          const int32_t* edge_ptr, const int32_t* c1_ptr, int64_t n_nodes,
                          int64_t n_edges, int64_t len_cluster1, int64_t n_graphs, int32_t max_nodes,
                          int32_t max_edges, int32_t* ws_i32, float* ws_f32, int32_t* scratch_i32,
-                         int32_t flags, void* stream_, const float* x_in = nullptr, float* tiles = nullptr,
+                         int32_t flags, void* stream, const float* x_in = nullptr, float* tiles = nullptr,
                          int32_t tile_f = 0) {
-    drgnn_stream_t stream = (drgnn_stream_t)stream_;
     TopoLaunch L;
     int64_t lds = 0;
     int rc0 = topo_prepare(L, &lds, edge_index, edge_attr, batch, cluster0, cluster1, node_ptr, edge_ptr, c1_ptr,
@@ -200,39 +214,20 @@ static int topology_build_impl(const int64_t* edge_index, const float* edge_attr
     pa.batch = batch; pa.edge_row = edge_index; pa.n_nodes = n_nodes; pa.n_edges = n_edges;
     pa.n_graphs = (int)n_graphs; pa.nptr = L.tv.p[DRGNN_TI_NPTR]; pa.eptr = L.tv.p[DRGNN_TI_EPTR];
     pa.err = L.tv.p[DRGNN_TI_ERR];
-    const bool need_ptrs = !(node_ptr && edge_ptr);
-    const int64_t span = n_nodes > n_edges ? n_nodes : n_edges;
-#ifdef DRGNN_EMU
-    if (need_ptrs) {
-        for (int k = 0; k < 4; ++k) pa.err[k] = 0;
-        for (int64_t i = 0; i < (span > 0 ? span : 1); ++i) ptr_item(pa, i);
-    }
-    std::vector<int> lds_buf((size_t)(lds / 4) + 16);
-    for (int pass = 0; pass < 2; ++pass) {
-        if (pass == 1) { if (!(cluster1 && !c1_ptr)) break; L.level1_only = 1; L.roles = 1; }
-        for (int gph = 0; gph < n_graphs * (pass == 0 ? L.roles : 1); ++gph) {
-            if (L.capN > 0) topo_block<true>(L, gph, lds_buf.data());
-            else topo_block<false>(L, gph, lds_buf.data());
-        }
-    }
-    (void)stream;
-#else
-    if (need_ptrs) {
+    if (!(node_ptr && edge_ptr)) {
+        // the offsets prologue.  k_topo_begin has no tables to copy here: what is left of it is the clear of the four status
+        // words, which the emulation spells out (the kernel has no item function to name)
         const int n = (int)n_graphs + 1;
-        hipLaunchKernelGGL(k_topo_begin, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
-                           (const int32_t*)nullptr, (const int32_t*)nullptr, pa.nptr, pa.eptr, pa.err, n);
-        const int64_t items = span > 0 ? span : 1;
-        hipLaunchKernelGGL(k_ptrs, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, stream, pa);
+        const int64_t span = n_nodes > n_edges ? n_nodes : n_edges;
+        DRGNN_LAUNCH(k_topo_begin, grid_items(n), stream, if (bx == 0) memset(pa.err, 0, 4 * sizeof(int32_t)),
+                     (const int32_t*)nullptr, (const int32_t*)nullptr, pa.nptr, pa.eptr, pa.err, n);
+        DRGNN_LAUNCH(k_ptrs, grid_items(span > 0 ? span : 1), stream, ptr_item(pa, bx), pa);
     }
-    if (lds > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void*)k_topo<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    // a second pass for the depth-1 clusters when their offsets were not supplied (they follow from the first pass)
     for (int pass = 0; pass < 2; ++pass) {
         if (pass == 1) { if (!(cluster1 && !c1_ptr)) break; L.level1_only = 1; L.roles = 1; }
-        if (L.capN > 0) hipLaunchKernelGGL(k_topo<true>, dim3((unsigned)(n_graphs * L.roles)), dim3(DRGNN_NTHREADS), (size_t)lds, stream, L);
-        else hipLaunchKernelGGL(k_topo<false>, dim3((unsigned)n_graphs), dim3(DRGNN_NTHREADS), 0, stream, L);
+        if ((rc0 = topo_launch(L, lds, stream))) return rc0;
     }
-    HIP_TRY(hipGetLastError());
-#endif
     return 0;
 }
 
@@ -261,27 +256,11 @@ int drgnn_topology_build_request(const drgnn_topology_request* r, void* stream_)
     const int rc = topo_prepare_req(L, &lds, r);
     if (rc) return rc;
     if (L.capN == 0 && !r->scratch_i32) return DRGNN_E_CAPACITY;
-    if (r->n_graphs == 0) return 0;
-#ifdef DRGNN_EMU
-    std::vector<int> lds_buf((size_t)(lds / 4) + 16);
-    for (int gph = 0; gph < r->n_graphs * L.roles; ++gph) {
-        if (L.capN > 0) topo_block<true>(L, gph, lds_buf.data());
-        else topo_block<false>(L, gph, lds_buf.data());
-    }
-    (void)stream_;
-#else
-    hipStream_t stream = (hipStream_t)stream_;
-    if (lds > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void*)k_topo<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (L.capN > 0) hipLaunchKernelGGL(k_topo<true>, dim3((unsigned)(r->n_graphs * L.roles)), dim3(DRGNN_NTHREADS), (size_t)lds, stream, L);
-    else hipLaunchKernelGGL(k_topo<false>, dim3((unsigned)r->n_graphs), dim3(DRGNN_NTHREADS), 0, stream, L);
-    HIP_TRY(hipGetLastError());
-#endif
-    return 0;
+    return topo_launch(L, lds, stream_);      // (a request without graphs: an empty grid)
 }
 
 int drgnn_topology_tiles(const int32_t* ws_i32, const float* ws_f32, int64_t n_nodes, int64_t n_edges, int64_t n_graphs,
-                         const float* x, int32_t n_feat, int32_t use_weights, float* tiles, void* stream_) {
+                         const float* x, int32_t n_feat, int32_t use_weights, float* tiles, void* stream) {
     if (!ws_i32 || !x || !tiles || n_nodes < 0 || n_edges < 0 || n_graphs < 0 || n_feat <= 0) return DRGNN_E_ARG;
     if (use_weights && !ws_f32) return DRGNN_E_ARG;
     if (n_graphs == 0) return 0;
@@ -290,52 +269,36 @@ int drgnn_topology_tiles(const int32_t* ws_i32, const float* ws_f32, int64_t n_n
     TilesArgs a;
     a.tv = topo_view(const_cast<int32_t*>(ws_i32), const_cast<float*>(ws_f32), lay);
     a.x = x; a.tiles = tiles; a.n_nodes = n_nodes; a.n_feat = n_feat; a.use_weights = use_weights ? 1 : 0;
-#ifdef DRGNN_EMU
-    for (int64_t g = 0; g < n_graphs; ++g) tiles_block(a, (int)g);
-    (void)stream_;
-#else
-    hipLaunchKernelGGL(k_tiles, dim3((unsigned)n_graphs), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream_, a);
-    HIP_TRY(hipGetLastError());
-#endif
+    DRGNN_LAUNCH(k_tiles, grid1(n_graphs), stream, tiles_block(a, (int)bx), a);
     return 0;
 }
 
 int drgnn_batch_offsets(const drgnn_graph_set* set, const int32_t* ids, int64_t n_ids, int32_t batch_size,
-                        int32_t* ptrs, void* stream_) {
+                        int32_t* ptrs, void* stream) {
     if (!set || !ids || !ptrs || n_ids < 0 || batch_size < 1 || !set->node_ptr || !set->edge_ptr) return DRGNN_E_ARG;
     if (batch_size > 4096) return DRGNN_E_CAPACITY;
     if (n_ids == 0) return 0;
     OffsetsArgs a;
     a.set = *set; a.ids = ids; a.n_ids = n_ids; a.batch_size = batch_size; a.ptrs = ptrs;
     const int64_t nb = (n_ids + batch_size - 1) / batch_size;
-    const size_t words = (size_t)DRGNN_NTHREADS + 4 + 3 * ((size_t)batch_size + 1);
-#ifdef DRGNN_EMU
-    std::vector<int> buf(words);
-    for (int64_t k = 0; k < nb; ++k) batch_offsets_block(a, (int)k, buf.data() + DRGNN_NTHREADS + 4, buf.data());
-    (void)stream_;
-#else
-    hipLaunchKernelGGL(k_batch_offsets, dim3((unsigned)nb), dim3(DRGNN_NTHREADS), words * 4, (hipStream_t)stream_, a);
-    HIP_TRY(hipGetLastError());
-#endif
+    // (batch_size <= 4096: at most 53 276 bytes of dynamic LDS, never beyond 64 KiB)
+    const int64_t words = (int64_t)DRGNN_NTHREADS + 4 + 3 * ((int64_t)batch_size + 1);
+    DRGNN_EMU_ONLY(std::vector<int> buf((size_t)words);)
+    DRGNN_LAUNCH(k_batch_offsets, grid1(nb, DRGNN_NTHREADS, words * 4), stream,
+                 batch_offsets_block(a, (int)bx, buf.data() + DRGNN_NTHREADS + 4, buf.data()), a);
     return 0;
 }
 
 int drgnn_topology_finalize(int32_t* ws_i32, int64_t n_nodes, int64_t n_edges, int64_t n_graphs,
-                            void* stream_) {
+                            void* stream) {
     if (!ws_i32 || n_graphs < 0) return DRGNN_E_ARG;
     TopoLayout lay;
     topo_layout(n_nodes, n_edges, n_graphs, &lay);
     ScanArgs a;
     a.tv = topo_view(ws_i32, nullptr, lay);
     a.n_graphs = (int)n_graphs;
-#ifdef DRGNN_EMU
-    int part[DRGNN_NTHREADS + 4];
-    finalize_block(a, part);
-    (void)stream_;
-#else
-    hipLaunchKernelGGL(k_finalize, dim3(1), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream_, a);
-    HIP_TRY(hipGetLastError());
-#endif
+    DRGNN_EMU_ONLY(int part[DRGNN_NTHREADS + 4];)
+    DRGNN_LAUNCH(k_finalize, grid1(1), stream, finalize_block(a, part), a);
     return 0;
 }
 
@@ -347,7 +310,7 @@ int drgnn_topology_status(const int32_t* ws_i32, int64_t n_nodes, int64_t n_edge
     const int32_t* err = ws_i32 + lay.i32[DRGNN_TI_ERR];
     const int32_t* gst = ws_i32 + lay.i32[DRGNN_TI_GSTAT];
     std::vector<int32_t> host((size_t)(2 * n_graphs) + 4);
-#ifdef DRGNN_EMU
+#ifdef DRGNN_EMU      // no launch: the device copies the words to the host and waits, the emulation reads them where they are
     for (int k = 0; k < 4; ++k) host[k] = err[k];
     for (int64_t g = 0; g < 2 * n_graphs; ++g) host[4 + g] = gst[g];
     (void)stream_;
@@ -409,9 +372,20 @@ static int net_check(const drgnn_net_desc* net) {
     return 0;
 }
 
+// the one dispatch over a net's kind: launch(kind as a compile-time constant)
+template <class Launch>
+static int net_by_kind(int kind, Launch launch) {
+    switch (kind) {
+    case DRGNN_GINET: return launch(std::integral_constant<int, DRGNN_GINET>());
+    case DRGNN_SGAT: return launch(std::integral_constant<int, DRGNN_SGAT>());
+    default: return launch(std::integral_constant<int, DRGNN_FOUT>());
+    }
+}
+
+// *co_built (when given): the topology of `co` has been built by this launch as well
 template <bool BWD>
 static int net_launch(NetLaunch& L, int32_t max_nodes, int32_t max_edges, int32_t max_c0, float* scratch,
-                      void* stream_, const TopoLaunch* co = nullptr, int64_t co_lds = 0) {
+                      void* stream, const TopoLaunch* co = nullptr, int64_t co_lds = 0, bool* co_built = nullptr) {
     const int kind = L.a.net.kind;
     const int64_t lds = drgnn_net_lds_bytes(kind, L.a.net.n_feat, max_nodes, max_edges, max_c0, BWD ? 1 : 0);
     L.capN = 0; L.capE = 0; L.capC = 0; L.gscratch = scratch;
@@ -434,65 +408,49 @@ static int net_launch(NetLaunch& L, int32_t max_nodes, int32_t max_edges, int32_
     const bool co_ok = co != nullptr && use_lds > 0 && co->capN > 0 && co->user_nptr != nullptr &&
                        !(co->args.cluster1 != nullptr && co->args.c1_ptr == nullptr) && co->args.n_graphs > 0 &&
                        blocks > 0;
-    if (blocks == 0 && !co) return 0;
-#ifdef DRGNN_EMU
-    std::vector<float> buf((size_t)((use_lds > co_lds ? use_lds : co_lds) / 4) + 16);
-    for (int b = 0; b < blocks; ++b) {
-        if (use_lds) {
-            if (kind == DRGNN_GINET) net_block<DRGNN_GINET, BWD, true>(L, b, buf.data());
-            else if (kind == DRGNN_SGAT) net_block<DRGNN_SGAT, BWD, true>(L, b, buf.data());
-            else net_block<DRGNN_FOUT, BWD, true>(L, b, buf.data());
-        } else {
-            if (kind == DRGNN_GINET) net_block<DRGNN_GINET, BWD, false>(L, b, buf.data());
-            else if (kind == DRGNN_SGAT) net_block<DRGNN_SGAT, BWD, false>(L, b, buf.data());
-            else net_block<DRGNN_FOUT, BWD, false>(L, b, buf.data());
-        }
-    }
-    if (co_ok)
-        for (int g = 0; g < co->args.n_graphs * co->roles; ++g) topo_block<true>(*co, g, (int*)buf.data());
-    (void)stream_;
-    return co_ok ? 1 : 0;       // 1: the co-launched topology has been built as well
-#else
-    hipStream_t stream = (hipStream_t)stream_;
-    if (co_ok) {
+    const int64_t all_lds = (co_ok && co_lds > use_lds) ? co_lds : use_lds;
+    DRGNN_EMU_ONLY(std::vector<float> buf((size_t)(all_lds / 4) + 16);)
+    if (co_ok) {      // the builder's workgroups behind the net's, in the same grid
         CoLaunch C;
         C.net = L; C.topo = *co; C.n_net = blocks;
-        const int64_t both = use_lds > co_lds ? use_lds : co_lds;
-#define DRGNN_CO_LAUNCH(K)                                                                               \
-    do {                                                                                                 \
-        if (both > 64 * 1024)                                                                            \
-            HIP_TRY(hipFuncSetAttribute((const void*)k_net_co_topo<K, BWD>,                              \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)both));         \
-        hipLaunchKernelGGL((k_net_co_topo<K, BWD>), dim3((unsigned)(blocks + co->args.n_graphs * co->roles)), \
-                           dim3(DRGNN_NTHREADS), (size_t)both, stream, C);                               \
-    } while (0)
-        if (kind == DRGNN_GINET) DRGNN_CO_LAUNCH(DRGNN_GINET);
-        else if (kind == DRGNN_SGAT) DRGNN_CO_LAUNCH(DRGNN_SGAT);
-        else DRGNN_CO_LAUNCH(DRGNN_FOUT);
-#undef DRGNN_CO_LAUNCH
-        HIP_TRY(hipGetLastError());
-        return 1;
+        const int rc = net_by_kind(kind, [&](auto K) {
+            constexpr int KIND = decltype(K)::value;
+            DRGNN_LAUNCH((k_net_co_topo<KIND, BWD>), grid1(blocks + (int64_t)co->args.n_graphs * co->roles, DRGNN_NTHREADS, all_lds),
+                         stream, (bx < blocks ? net_block<KIND, BWD, true>(C.net, (int)bx, buf.data())
+                                              : topo_block<true>(C.topo, (int)bx - blocks, (int*)buf.data())), C);
+            return 0;
+        });
+        if (co_built) *co_built = rc == 0;
+        return rc;
     }
-    if (blocks == 0) return 0;
-#define DRGNN_NET_LAUNCH(K)                                                                         \
-    do {                                                                                            \
-        if (use_lds > 64 * 1024)                                                                    \
-            HIP_TRY(hipFuncSetAttribute((const void*)k_net<K, BWD, true>,                           \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)use_lds)); \
-        if (use_lds)                                                                                \
-            hipLaunchKernelGGL((k_net<K, BWD, true>), dim3((unsigned)blocks), dim3(DRGNN_NTHREADS), \
-                               (size_t)use_lds, stream, L);                                         \
-        else                                                                                        \
-            hipLaunchKernelGGL((k_net<K, BWD, false>), dim3((unsigned)blocks), dim3(DRGNN_NTHREADS),\
-                               0, stream, L);                                                       \
-    } while (0)
-    if (kind == DRGNN_GINET) DRGNN_NET_LAUNCH(DRGNN_GINET);
-    else if (kind == DRGNN_SGAT) DRGNN_NET_LAUNCH(DRGNN_SGAT);
-    else DRGNN_NET_LAUNCH(DRGNN_FOUT);
-#undef DRGNN_NET_LAUNCH
-    HIP_TRY(hipGetLastError());
-    return 0;
-#endif
+    // (a launch without graphs: an empty grid)
+    return net_by_kind(kind, [&](auto K) {
+        constexpr int KIND = decltype(K)::value;
+        if (use_lds)
+            DRGNN_LAUNCH((k_net<KIND, BWD, true>), grid1(blocks, DRGNN_NTHREADS, use_lds), stream,
+                         (net_block<KIND, BWD, true>(L, (int)bx, buf.data())), L);
+        else
+            DRGNN_LAUNCH((k_net<KIND, BWD, false>), grid1(blocks), stream,
+                         (net_block<KIND, BWD, false>(L, (int)bx, buf.data())), L);
+        return 0;
+    });
+}
+
+// what a forward and a backward launch share; the rest as for a launch that writes no readout, reads no gradient and has no head
+static void net_fill(NetLaunch& L, const drgnn_net_desc* net, const float* x, const int32_t* ws_i32, const float* ws_f32,
+                     int64_t n_nodes, int64_t n_edges, int64_t n_graphs, float* xp, int32_t* arg0, int32_t* arg1, int32_t* step_inc) {
+    TopoLayout lay;
+    topo_layout(n_nodes, n_edges, n_graphs, &lay);
+    L.a.net = *net;
+    L.a.x = x;
+    L.a.tv = topo_view(const_cast<int32_t*>(ws_i32), const_cast<float*>(ws_f32), lay);
+    L.a.n_nodes = n_nodes;
+    L.a.n_graphs = (int)n_graphs;
+    L.a.xp = xp; L.a.arg0 = arg0; L.a.arg1 = arg1; L.a.readout = nullptr;
+    L.a.grad_readout = nullptr; L.a.partials = nullptr; L.a.grad_x = nullptr; L.a.n_partial = 0;
+    L.a.step_inc = step_inc;
+    L.a.hf.enabled = 0;
+    L.n_edges = n_edges;
 }
 
 extern "C" {
@@ -505,21 +463,10 @@ int drgnn_net_forward(const drgnn_net_desc* net, const float* x, const int32_t* 
     if (rc) return rc;
     if (!x || !ws_i32 || !xp || !arg0 || !arg1 || !readout) return DRGNN_E_ARG;
     if (net->kind == DRGNN_SGAT && !ws_f32) return DRGNN_E_ARG;
-    TopoLayout lay;
-    topo_layout(n_nodes, n_edges, n_graphs, &lay);
     NetLaunch L;
-    L.a.net = *net;
-    L.a.x = x;
-    L.a.tv = topo_view(const_cast<int32_t*>(ws_i32), const_cast<float*>(ws_f32), lay);
-    L.a.n_nodes = n_nodes;
-    L.a.n_graphs = (int)n_graphs;
-    L.a.xp = xp; L.a.arg0 = arg0; L.a.arg1 = arg1; L.a.readout = readout;
-    L.a.grad_readout = nullptr; L.a.partials = nullptr; L.a.grad_x = nullptr; L.a.n_partial = 0;
-    L.a.step_inc = step_inc;
-    L.a.hf.enabled = 0;
-    L.n_edges = n_edges;
-    const int rc2 = net_launch<false>(L, max_nodes, max_edges, max_c0, scratch_f32, stream_);
-    return rc2 < 0 ? rc2 : (rc2 > 1 ? rc2 : 0);
+    net_fill(L, net, x, ws_i32, ws_f32, n_nodes, n_edges, n_graphs, xp, arg0, arg1, step_inc);
+    L.a.readout = readout;
+    return net_launch<false>(L, max_nodes, max_edges, max_c0, scratch_f32, stream_);
 }
 
 static int net_backward_impl(const drgnn_net_desc* net, const float* x, const float* grad_readout,
@@ -531,39 +478,27 @@ static int net_backward_impl(const drgnn_net_desc* net, const float* x, const fl
     int rc = net_check(net);
     if (rc) return rc;
     if (!x || (!grad_readout && !hf) || !ws_i32 || !xp || !arg0 || !arg1 || !partials) return DRGNN_E_ARG;
-    TopoLayout lay;
-    topo_layout(n_nodes, n_edges, n_graphs, &lay);
     NetLaunch L;
-    L.a.net = *net;
-    L.a.x = x;
-    L.a.tv = topo_view(const_cast<int32_t*>(ws_i32), const_cast<float*>(ws_f32), lay);
-    L.a.n_nodes = n_nodes;
-    L.a.n_graphs = (int)n_graphs;
-    L.a.xp = const_cast<float*>(xp); L.a.arg0 = const_cast<int32_t*>(arg0);
-    L.a.arg1 = const_cast<int32_t*>(arg1); L.a.readout = nullptr;
+    net_fill(L, net, x, ws_i32, ws_f32, n_nodes, n_edges, n_graphs, const_cast<float*>(xp), const_cast<int32_t*>(arg0),
+             const_cast<int32_t*>(arg1), step_inc);
     L.a.grad_readout = grad_readout; L.a.partials = partials; L.a.grad_x = grad_x;
     L.a.n_partial = (int)net_partial_floats(net->n_feat);
-    L.a.step_inc = step_inc;
-    if (hf) L.a.hf = *hf; else L.a.hf.enabled = 0;
-    L.n_edges = n_edges;
-    if (!next) {
-        const int rc2 = net_launch<true>(L, max_nodes, max_edges, max_c0, scratch_f32, stream_);
-        return rc2 < 0 ? rc2 : (rc2 > 1 ? rc2 : 0);
-    }
+    if (hf) L.a.hf = *hf;
+    if (!next) return net_launch<true>(L, max_nodes, max_edges, max_c0, scratch_f32, stream_);
     TopoLaunch T;
     int64_t tlds = 0;
     rc = topo_prepare_req(T, &tlds, next);
     if (rc) return rc;
-    const int rc2 = net_launch<true>(L, max_nodes, max_edges, max_c0, scratch_f32, stream_, &T, tlds);
-    if (rc2 < 0 || rc2 > 1) return rc2;
-    if (rc2 == 1) return 0;
+    bool co_built = false;
+    rc = net_launch<true>(L, max_nodes, max_edges, max_c0, scratch_f32, stream_, &T, tlds, &co_built);
+    if (rc || co_built) return rc;
     // could not share the launch: build the next topology with its own launches
     return drgnn_topology_build_request(next, stream_);
 }
 
 }  // extern "C"
 
-#ifdef DRGNN_EMU
+#ifdef DRGNN_EMU      // (emu_step: what the emulation runs in place of the aggregation-first kernels)
 // The host emulation's fused step.  The aggregation-first kernels are SIMT code (MFMA fragments, DPP, lane reads) the
 // emulation cannot execute; it steps the launch with the launch pair's per-graph routines instead -- net_forward_graph for
 // both branches, then net_backward_graph with head_graph inside (inference: head_graph alone) -- and writes what the fused
@@ -612,6 +547,19 @@ static void emu_step(const StepArgs& a, bool train, int capN, int capE, int capC
 }
 #endif
 
+// The head of a fused launch from its descriptor.  upstream: a TASK_GRAD target is the upstream gradient, read where a regression
+// target is (the fused step; the launch pair has no such task); step_bias, train: drgnn_net.h, HeadFused.
+static void head_fused_fill(HeadFused& hf, const drgnn_head_desc* hd, int64_t n_graphs, const void* target, bool upstream, int step_bias,
+                            int train, const float* readout, const int32_t* step, float* pred, float* partials) {
+    hf.enabled = 1; hf.B = (int)n_graphs; hf.R = hd->R; hf.H = hd->H; hf.O = hd->O; hf.task = hd->task;
+    hf.p_drop = hd->train ? hd->p_drop : 0.0f; hf.seed = hd->seed; hf.step_bias = step_bias; hf.train = train; hf.sigmoid = hd->transform_sigmoid;
+    hf.drop_mask = hd->train ? hd->drop_mask : nullptr;
+    hf.w1 = hd->w1; hf.b1 = hd->b1; hf.w2 = hd->w2; hf.b2 = hd->b2; hf.class_w = hd->class_w;
+    hf.y_reg = (upstream ? hd->task != DRGNN_TASK_CLASS : hd->task == DRGNN_TASK_REG) ? (const float*)target : nullptr;
+    hf.y_cls = (hd->task == DRGNN_TASK_CLASS) ? (const int64_t*)target : nullptr;
+    hf.readout = readout; hf.step = step; hf.pred = pred; hf.partials = partials; hf.stage = 0;
+}
+
 extern "C" {
 
 int drgnn_net_backward(const drgnn_net_desc* net, const float* x, const float* grad_readout,
@@ -637,13 +585,7 @@ int drgnn_net_backward_fused_head(const drgnn_net_desc* net, const drgnn_head_de
     if (!net || hd->R != DRGNN_H2 * net->n_branch || hd->H < 1 || hd->H > 512 || hd->O < 1 || hd->O > DRGNN_MAX_OUT)
         return DRGNN_E_WIDTH;
     HeadFused hf;
-    hf.enabled = 1; hf.B = (int)n_graphs; hf.R = hd->R; hf.H = hd->H; hf.O = hd->O; hf.task = hd->task;
-    hf.p_drop = hd->train ? hd->p_drop : 0.0f; hf.seed = hd->seed; hf.step_bias = -1; hf.train = 1; hf.sigmoid = hd->transform_sigmoid;
-    hf.drop_mask = hd->train ? hd->drop_mask : nullptr;
-    hf.w1 = hd->w1; hf.b1 = hd->b1; hf.w2 = hd->w2; hf.b2 = hd->b2; hf.class_w = hd->class_w;
-    hf.y_reg = (hd->task == DRGNN_TASK_REG) ? (const float*)target : nullptr;
-    hf.y_cls = (hd->task == DRGNN_TASK_CLASS) ? (const int64_t*)target : nullptr;
-    hf.readout = readout; hf.step = step; hf.pred = pred; hf.partials = head_partials;
+    head_fused_fill(hf, hd, n_graphs, target, false, -1, 1, readout, step, pred, head_partials);
     return net_backward_impl(net, x, nullptr, &hf, ws_i32, ws_f32, n_nodes, n_edges, n_graphs, max_nodes,
                              max_edges, max_c0, xp, arg0, arg1, grad_x, partials, scratch_f32, nullptr, stream_,
                              next_topology);
@@ -669,7 +611,7 @@ int64_t drgnn_head_compact_elems(int32_t R, int32_t H, int32_t O) { return head_
 // ROC_GLOBAL_CU_MASK -- or a share of the GPU leaves fewer CUs than the attribute says); DRGNN_SHARED_GPU=1 means "assume
 // nothing": every layout that waits for a partner workgroup is off (one workgroup per graph).
 static int device_cu_count() {
-#ifdef DRGNN_EMU
+#ifdef DRGNN_EMU      // (no device to ask)
     return 256;
 #else
     static int cus[64];
@@ -689,7 +631,7 @@ static int device_cu_count() {
     return cus[dev];
 #endif
 }
-#ifndef DRGNN_EMU
+#ifndef DRGNN_EMU      // (the emulation has no device)
 static int step_current_device() { int dev = 0; return hipGetDevice(&dev) == hipSuccess ? dev : 0; }
 #endif
 
@@ -785,7 +727,7 @@ static StepPick step_pick(const StepAsk& q) {
     };
     const int emu_width = q.x_ok ? step_variant(q.kind, nullptr, q.F, q.capN, q.capE, q.capC, q.H, q.O) : 0;
     // the aggregation-first family: a workspace with the hierarchical order and usable tiles, a width class, the reference head
-#ifdef DRGNN_EMU
+#ifdef DRGNN_EMU      // (the emulation has no aggregation-first kernel: no shape qualifies)
     const bool af_shape = false;
     const int af_w = 0;
 #else
@@ -802,7 +744,7 @@ static StepPick step_pick(const StepAsk& q) {
     // workspace without the hierarchical order or usable tiles, the no_aggregate override -- is family NONE on the device: the
     // launch pair (drgnn_net_forward + drgnn_net_backward_fused_head) steps it.  The host emulation has none of those kernels:
     // it reports family PRODUCT for its stand-in (SK_EMU), bounded by the LDS of the retired product-first kernel.
-#ifdef DRGNN_EMU
+#ifdef DRGNN_EMU      // (the LDS bound of the emulation's stand-in; the device never picks SK_EMU)
     const int64_t lemu = step_lds_bytes(q.kind, q.F, q.capN, q.capE, q.capC, q.R, q.H, q.O);
 #else
     const int64_t lemu = STEP_LDS_NEVER;
@@ -811,7 +753,7 @@ static StepPick step_pick(const StepAsk& q) {
         const bool narrow = q.H < DRGNN_H2;      // (the exchange words of a graph are 2 x 32 of its 2 x H: a narrower head runs one workgroup per graph)
         const int64_t l2af = af_shape ? 4 * step3_scratch_words(q.F, q.capN, q.capE, q.capC, q.H, q.O) : STEP_LDS_NEVER;
         int64_t l1af = af_shape ? 4 * step3b_scratch_words(q.F, q.capN, q.capE, q.capC, q.H, q.O) : STEP_LDS_NEVER;
-#ifndef DRGNN_EMU
+#ifndef DRGNN_EMU      // (a from-memory form of the aggregation-first kernels)
         if (l1af > DRGNN_LDS_LIMIT && sg_w != 0) {
             const int64_t l1sg = 4 * step3b_scratch_words(q.F, q.capN, q.capE, q.capC, q.H, q.O, 1);
             if (l1sg <= DRGNN_LDS_LIMIT) { l1af = l1sg; k.sg = 1; af_w = sg_w; }
@@ -841,7 +783,7 @@ static StepPick step_pick(const StepAsk& q) {
             const int64_t lxg = 4 * step2_scratch_words(q.kind, q.F, q.capN, q.capE, q.capC, q.H, q.O, 1);
             if (lxg <= DRGNN_LDS_LIMIT) { laf = lxg; k.xg = 1; }
         }
-#ifndef DRGNN_EMU
+#ifndef DRGNN_EMU      // (a from-memory form of the aggregation-first kernels)
         if (laf > DRGNN_LDS_LIMIT && sg_w >= 32 && ((q.F & 3) != 0 || q.x_ok)) {
             // ... and where the S tile alone is too much (the 32-, 48- and 64-wide kernels beyond 250 - 360 nodes): the S rows too
             const int64_t lxg = 4 * step2_scratch_words(q.kind, q.F, q.capN, q.capE, q.capC, q.H, q.O, 2);
@@ -887,7 +829,7 @@ static StepPick step_pick(const StepAsk& q) {
     // Capacity class (drgnn_step.h: STEP_CLS_*): a batch whose maxima lie inside the class is stepped by the 32- or 48-wide
     // kernels whose LDS layout is a compile-time constant (the training and the inference instances; 48 features: the feature
     // count of the reference's shipped regression models)
-#ifndef DRGNN_EMU
+#ifndef DRGNN_EMU      // (the capacity classes are instances of the aggregation-first kernels)
     if (!q.ov.no_class && !k.sg && !k.xg && (k.width == 32 || k.width == 48) && q.capN <= STEP_CLS_N && q.capE <= STEP_CLS_E &&
         q.capC <= STEP_CLS_C && step_af_width(q.kind, q.F, STEP_CLS_N, STEP_CLS_E, STEP_CLS_C, q.H, q.O) == k.width) {
         // (the 32-wide class instance of the one-workgroup kernel keeps Z1 / XP / dS per branch: STEP3B_DUAL)
@@ -954,7 +896,7 @@ int32_t drgnn_net_step_variant(int32_t kind, const float* x, int32_t n_feat, int
     return step_variant(kind, x, n_feat, c.N, c.E, c.C, H, O);
 }
 
-#ifndef DRGNN_EMU
+#ifndef DRGNN_EMU      // (a runtime launch of the aggregation-first kernels)
 // One launch of a step kernel instance (+ the co-launched builder's workgroups) with the argument array its caller built.  These
 // kernels use up to the whole 160 KiB of LDS: the attribute is raised once per kernel instance and device (the call costs host
 // time on every launch otherwise).
@@ -1023,7 +965,7 @@ static int step_check(const StepOperands& s) {
     const drgnn_head_desc* hd = s.hd;
     const int rc = net_check(net);
     if (rc) return rc;
-#ifdef DRGNN_EMU
+#ifdef DRGNN_EMU      // (what a member axis asks for: the emulation has neither launch)
     if (s.ens || s.coh) return DRGNN_E_CAPACITY;      // (the host emulation has no ensemble / cohort launch: their plans answer NONE)
 #else
     // a cohort launch (drgnn_cohort_train_step_cached): the members' parameters, outputs, slabs and step words come from the
@@ -1141,7 +1083,6 @@ static int step_host_dims(const StepOperands& s, const StepAsk& q, StepDims& D) 
 }
 
 static void step_args(const StepOperands& s, const StepAsk& q, StepArgs& a) {
-    const drgnn_head_desc* hd = s.hd;
     TopoLayout lay;
     topo_layout(s.n_nodes, s.n_edges, s.ws_graphs, &lay);
     a.gather_ids = s.gather_ids; a.ws_graphs = (int)s.ws_graphs;
@@ -1152,17 +1093,10 @@ static void step_args(const StepOperands& s, const StepAsk& q, StepArgs& a) {
     a.partials = s.partials; a.n_partial = (int)net_partial_floats(q.F);
     a.xchg = (unsigned long long*)s.xchg; a.step2 = s.step2;
     a.xchg_stride = (int)step2_xchg_words(q.capC > 0 ? q.capC : 1);
-    HeadFused& hf = a.hf;
-    hf.enabled = 1; hf.B = (int)s.n_graphs; hf.R = hd->R; hf.H = hd->H; hf.O = hd->O; hf.task = hd->task;
-    hf.p_drop = hd->train ? hd->p_drop : 0.0f; hf.seed = hd->seed; hf.step_bias = 0; hf.train = q.train ? 1 : 0; hf.sigmoid = hd->transform_sigmoid;
-    hf.drop_mask = hd->train ? hd->drop_mask : nullptr;
-    hf.w1 = hd->w1; hf.b1 = hd->b1; hf.w2 = hd->w2; hf.b2 = hd->b2; hf.class_w = hd->class_w;
-    hf.y_reg = (hd->task != DRGNN_TASK_CLASS) ? (const float*)s.target : nullptr;
-    hf.y_cls = (hd->task == DRGNN_TASK_CLASS) ? (const int64_t*)s.target : nullptr;
-    hf.readout = s.readout; hf.step = s.step2; hf.pred = s.pred; hf.partials = s.head_partials; hf.stage = 0;
+    head_fused_fill(a.hf, s.hd, s.n_graphs, s.target, true, 0, q.train ? 1 : 0, s.readout, s.step2, s.pred, s.head_partials);
 }
 
-#ifndef DRGNN_EMU
+#ifndef DRGNN_EMU      // (the launch of the aggregation-first kernels: emu_step stands in for it)
 // What shares the grid with the step's workgroups: the builder's, or the next mini-batch's prefetchers.  Returns their number;
 // *lds: the launch's dynamic LDS.
 static int step_co_setup(const StepOperands& s, const StepBuilder& b, const StepPick& k, int blocks, StepCoLaunch& C, int64_t* lds) {
@@ -1226,7 +1160,7 @@ static int train_step_impl(const StepOperands& s) {
     StepAsk q;
     StepPick k;
     if ((rc = step_layout(s, b, q, k))) return rc;
-#ifdef DRGNN_EMU
+#ifdef DRGNN_EMU      // (the emulation's stand-in steps the graphs itself: no co-launch record)
     StepLaunch L;
 #else
     StepCoLaunch C;
@@ -1242,14 +1176,11 @@ static int train_step_impl(const StepOperands& s) {
     const int multi_K = s.ens ? s.ens_K : s.coh ? s.coh->K : 0;
     const int blocks = multi_K ? (int)((n_graphs + 7) / 8) * 8 * multi_K : (k.wgs == 2) ? (int)((n_graphs + 7) / 8) * 16 : (int)n_graphs;
     if (blocks > 0) {
-#ifdef DRGNN_EMU
+#ifdef DRGNN_EMU      // emu_step (above) in place of the aggregation-first kernels, then the co-built topology as a launch of its own
         if (q.kind == DRGNN_GINET) emu_step<DRGNN_GINET>(L.a, q.train, k.capN, k.capE, k.capC);
         else if (q.kind == DRGNN_SGAT) emu_step<DRGNN_SGAT>(L.a, q.train, k.capN, k.capE, k.capC);
         else emu_step<DRGNN_FOUT>(L.a, q.train, k.capN, k.capE, k.capC);
-        if (b.ok) {
-            std::vector<int> tbuf((size_t)(b.lds / 4) + 16);
-            for (int g = 0; g < b.T.args.n_graphs * b.T.roles; ++g) topo_block<true>(b.T, g, tbuf.data());
-        }
+        if (b.ok && (rc = topo_launch(b.T, b.lds, s.stream))) return rc;
 #else
         C.n_net = blocks;
         int64_t lds = 0;
@@ -1299,7 +1230,7 @@ static int32_t member_step_plan(drgnn_step_plan* p, int32_t K, int32_t max_K, in
     p->force_wgs = 1;
     p->co_built_graphs = 0;
     const int32_t wgs = drgnn_net_step_plan(p);
-#ifdef DRGNN_EMU
+#ifdef DRGNN_EMU      // (the emulation has no launch with a member axis)
     (void)K; (void)max_K; (void)wgs;
     p->family = DRGNN_STEP_FAMILY_NONE;
     return 0;
@@ -1335,7 +1266,7 @@ int drgnn_cohort_train_step_cached(const drgnn_net_desc* net, const drgnn_head_d
     if (!members || K < 1 || K > 65535 || !hd || hd->train != 1 || !ids || !counts || ids_stride < n_graphs) return DRGNN_E_ARG;
     if (!cache || !cache->ws_i32 || !cache->x || n_graphs < 0 || n_graphs > cache->n_graphs) return DRGNN_E_ARG;
     if (!cache->y || cache->y_bytes != (hd->task == DRGNN_TASK_REG ? 4 : 8)) return DRGNN_E_ARG;
-#ifdef DRGNN_EMU
+#ifdef DRGNN_EMU      // (no cohort launch in the emulation)
     (void)net; (void)max_nodes; (void)max_edges; (void)max_c0; (void)hints; (void)stream_;
     return DRGNN_E_CAPACITY;      // (the host emulation has no cohort launch: drgnn_cohort_step_plan answers NONE)
 #else
@@ -1381,7 +1312,7 @@ static int head_check(const drgnn_head_desc* hd) {
 
 int drgnn_head_step(const drgnn_head_desc* hd, const float* readout, const void* target,
                     int64_t n_graphs, const int32_t* step, float* pred, float* grad_readout,
-                    float* partials, void* stream_) {
+                    float* partials, void* stream) {
     int rc = head_check(hd);
     if (rc) return rc;
     if (!readout || !pred || n_graphs < 0) return DRGNN_E_ARG;
@@ -1401,52 +1332,32 @@ int drgnn_head_step(const drgnn_head_desc* hd, const float* readout, const void*
     a.HC = head_chunk(hd, a.T);
     const int blocks = (int)((n_graphs + a.T - 1) / a.T);
     const int64_t lds = 4 * head_lds_words(hd->R, a.HC, hd->O, a.T);
-#ifdef DRGNN_EMU
-    std::vector<float> buf((size_t)(lds / 4) + 16);
-    for (int b = 0; b < blocks; ++b) head_block(a, b, buf.data());
-    (void)stream_;
-#else
-    if (lds > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void*)k_head, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_head, dim3((unsigned)blocks), dim3(DRGNN_NTHREADS), (size_t)lds, (hipStream_t)stream_, a);
-    HIP_TRY(hipGetLastError());
-#endif
+    DRGNN_EMU_ONLY(std::vector<float> buf((size_t)(lds / 4) + 16);)
+    DRGNN_LAUNCH(k_head, grid1(blocks, DRGNN_NTHREADS, lds), stream, head_block(a, (int)bx, buf.data()), a);
     return 0;
 }
 
 int drgnn_head_reduce(const float* partials, int64_t n_graphs, int32_t R, int32_t H, int32_t O,
-                      float* grad_block, float* loss, int32_t* step, void* stream_) {
+                      float* grad_block, float* loss, int32_t* step, void* stream) {
     if (!partials || !grad_block) return DRGNN_E_ARG;
     HeadReduceArgs a;
     a.partials = partials;
     a.n_wg = (int)((n_graphs + head_tile(n_graphs) - 1) / head_tile(n_graphs));
     a.P = (int)head_partial_floats(R, H, O);
     a.grad = grad_block; a.loss = loss; a.step = step;
-#ifdef DRGNN_EMU
-    for (int i = 0; i < a.P - 1; ++i) head_reduce_item(a, i);
-    (void)stream_;
-#else
-    hipLaunchKernelGGL(k_head_reduce, dim3((unsigned)((a.P - 1 + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, a);
-    HIP_TRY(hipGetLastError());
-#endif
+    DRGNN_LAUNCH(k_head_reduce, grid_items(a.P - 1), stream, head_reduce_item(a, (int)bx), a);
     return 0;
 }
 
 int drgnn_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                     const int32_t* step, int64_t n, double lr, double beta1, double beta2, double eps,
-                    double weight_decay, void* stream_) {
+                    double weight_decay, void* stream) {
     if (!param || !grad || !exp_avg || !exp_avg_sq || !step || n < 0) return DRGNN_E_ARG;
     if (n == 0) return 0;
     AdamArgs a;
     a.param = param; a.grad = grad; a.exp_avg = exp_avg; a.exp_avg_sq = exp_avg_sq; a.step = step; a.n = n;
     adam_set_hyper(a, lr, beta1, beta2, eps, weight_decay);
-#ifdef DRGNN_EMU
-    for (int64_t i = 0; i < n; ++i) adam_item(a, i);
-    (void)stream_;
-#else
-    hipLaunchKernelGGL(k_adam, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, a);
-    HIP_TRY(hipGetLastError());
-#endif
+    DRGNN_LAUNCH(k_adam, grid_items(n), stream, adam_item(a, bx), a);
     return 0;
 }
 
@@ -1471,7 +1382,7 @@ static int adam_opt_impl(AdamArgs a, float* grad, const drgnn_optim* o, int n_wo
     if (a.n == 0) return 0;
     const int64_t flat_words = (a.n + 255) / 256;
     if (o->clip && n_words == 0 && flat_words > o->norm_cap) return DRGNN_E_CAPACITY;
-#ifdef DRGNN_EMU
+#ifdef DRGNN_EMU      // (another algorithm: the emulation forms Adam's scalars and the norm once and loops over the items)
     AdamOptScalars sc;
     adam_bias_scalars<true>(a, sc.step_size, sc.sqrt_bc2, o, &sc.decay);
     sc.clip = 1.0f;
@@ -1525,7 +1436,7 @@ int64_t drgnn_p2p_bytes(int64_t n_floats) { return n_floats < 0 ? (int64_t)DRGNN
 
 int drgnn_p2p_alloc(int64_t bytes, void** dev_ptr, void* handle) {
     if (bytes <= 0 || !dev_ptr) return DRGNN_E_ARG;
-#ifdef DRGNN_EMU
+#ifdef DRGNN_EMU      // (device memory and its IPC handle; the emulation: host memory, the pointer as the handle)
     *dev_ptr = calloc(1, (size_t)bytes);
     if (handle) { memset(handle, 0, 64); memcpy(handle, dev_ptr, sizeof(void*)); }     // same-process "handle"
     return *dev_ptr ? 0 : DRGNN_E_CAPACITY;
@@ -1544,7 +1455,7 @@ int drgnn_p2p_alloc(int64_t bytes, void** dev_ptr, void* handle) {
 
 int drgnn_p2p_open(const void* handle, void** dev_ptr) {
     if (!handle || !dev_ptr) return DRGNN_E_ARG;
-#ifdef DRGNN_EMU
+#ifdef DRGNN_EMU      // (as drgnn_p2p_alloc)
     memcpy(dev_ptr, handle, sizeof(void*));
     return 0;
 #else
@@ -1555,7 +1466,7 @@ int drgnn_p2p_open(const void* handle, void** dev_ptr) {
 }
 
 int drgnn_p2p_close(void* dev_ptr) {
-#ifdef DRGNN_EMU
+#ifdef DRGNN_EMU      // (as drgnn_p2p_alloc)
     (void)dev_ptr;
     return 0;
 #else
@@ -1566,7 +1477,7 @@ int drgnn_p2p_close(void* dev_ptr) {
 }
 
 int drgnn_p2p_free(void* dev_ptr) {
-#ifdef DRGNN_EMU
+#ifdef DRGNN_EMU      // (as drgnn_p2p_alloc)
     free(dev_ptr);
     return 0;
 #else
@@ -1577,7 +1488,7 @@ int drgnn_p2p_free(void* dev_ptr) {
 }
 
 int drgnn_allreduce_oneshot(float* grad, int64_t n, void* const* peer_bufs, int32_t world, int32_t rank, float weight,
-                            uint32_t* seq, int32_t* status, int32_t part, void* stream_) {
+                            uint32_t* seq, int32_t* status, int32_t part, void* stream) {
     if (!grad || n < 0 || !peer_bufs || world < 1 || world > DRGNN_P2P_MAX || rank < 0 || rank >= world || !seq || !status ||
         part < 0 || part > 2)
         return DRGNN_E_ARG;
@@ -1586,13 +1497,7 @@ int drgnn_allreduce_oneshot(float* grad, int64_t n, void* const* peer_bufs, int3
     a.grad = grad; a.n = n; a.world = world; a.rank = rank; a.weight = weight; a.seq = seq; a.status = status; a.part = part;
     for (int r = 0; r < DRGNN_P2P_MAX; ++r) a.peer[r] = (r < world) ? (float*)peer_bufs[r] : nullptr;
     for (int r = 0; r < world; ++r) if (!a.peer[r]) return DRGNN_E_ARG;
-#ifdef DRGNN_EMU
-    for (int j = 0; j < DRGNN_P2P_WGS; ++j) p2p_block(a, j);
-    (void)stream_;
-#else
-    hipLaunchKernelGGL(k_allreduce_oneshot, dim3(DRGNN_P2P_WGS), dim3(DRGNN_P2P_THREADS), 0, (hipStream_t)stream_, a);
-    HIP_TRY(hipGetLastError());
-#endif
+    DRGNN_LAUNCH(k_allreduce_oneshot, grid1(DRGNN_P2P_WGS, DRGNN_P2P_THREADS), stream, p2p_block(a, (int)bx), a);
     return 0;
 }
 
@@ -1689,7 +1594,7 @@ static int update_run(const UpdateCall& c) {
     if (c.optim) optim_adam_args(u.ad, c.optim);
     else adam_set_hyper(u.ad, c.lr, c.beta1, c.beta2, c.eps, 0.0);
     u.apply_adam = (c.apply_adam && !opt_flat) ? 1 : 0;
-#ifdef DRGNN_EMU
+#ifdef DRGNN_EMU      // (another algorithm: item by item, sums in slab order, against the kernels' 64-element blocks of four quarter sums)
     if (c.cohort) return DRGNN_E_CAPACITY;
     if (opt) u.apply_adam = 0;           // (host loop: the sums here, then the flat loop with the options)
     const ReduceArgs& r = u.r;
@@ -1832,7 +1737,7 @@ int drgnn_net_reduce_grads(const drgnn_net_desc* net, const float* partials, int
     r.grad_x = grad_x; r.n_nodes = n_nodes;
     int64_t items = (int64_t)net->n_branch * r.n_partial;
     if (grad_x && net->n_branch > 1 && n_nodes * net->n_feat > items) items = n_nodes * net->n_feat;
-#ifdef DRGNN_EMU
+#ifdef DRGNN_EMU      // (another algorithm: item by item against k_reduce's blocks of four quarter sums)
     for (int64_t i = 0; i < (int64_t)net->n_branch * r.n_partial; ++i) {
         const int br = (int)(i / r.n_partial), p = (int)(i % r.n_partial);
         if (reduce_live(r, p)) reduce_write(r, br, p, reduce_sum(r, br, p, 0, 1));
@@ -1937,7 +1842,7 @@ int drgnn_step_gradients(const drgnn_net_desc* net, const float* conv_partials, 
         if (!zero_ptr[i] || zero_len[i] < 0) return DRGNN_E_ARG;
         ga.zero_ptr[i] = zero_ptr[i]; ga.zero_len[i] = zero_len[i];
     }
-#ifdef DRGNN_EMU
+#ifdef DRGNN_EMU      // (another algorithm: item by item against k_gradients' blocks of four quarter sums)
     const ReduceArgs& r = u.r;
     for (int64_t i = 0; i < (int64_t)net->n_branch * r.n_partial; ++i) {
         const int br = (int)(i / r.n_partial), p = (int)(i % r.n_partial);
@@ -2756,14 +2661,8 @@ int drgnn_collate(const drgnn_graph_set* set, const int32_t* ids, int64_t n_grap
     a.x = x; a.edge_index = edge_index; a.edge_attr = edge_attr; a.batch = batch;
     a.cluster0 = cluster0; a.cluster1 = cluster1; a.y = y;
     a.node_ptr = node_ptr; a.edge_ptr = edge_ptr; a.c1_ptr = set->c1_ptr ? c1_ptr : nullptr;
-#ifdef DRGNN_EMU
-    int sh[4];
-    for (int g = 0; g < n_graphs; ++g) collate_block(a, g, sh);
-    (void)stream;
-#else
-    hipLaunchKernelGGL(k_collate, dim3((unsigned)n_graphs), dim3(DRGNN_NTHREADS), 0, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-#endif
+    DRGNN_EMU_ONLY(int sh[4];)
+    DRGNN_LAUNCH(k_collate, grid1(n_graphs), stream, collate_block(a, (int)bx, sh), a);
     return 0;
 }
 
@@ -2964,11 +2863,7 @@ static int train_epoch_impl(const drgnn_epoch_plan* p, const drgnn_optim* optim,
     drgnn_head_desc head = *hd;
     head.train = train ? 1 : 0;
     // the exchange words carry the step index as a tag: they only have to start from a value no step uses
-#ifdef DRGNN_EMU
-    memset(c.xchg, 0, (size_t)c.xchg_bytes);
-#else
-    HIP_TRY(hipMemsetAsync(c.xchg, 0, (size_t)c.xchg_bytes, (hipStream_t)stream));
-#endif
+    if ((rc = drgnn_clear(c.xchg, (size_t)c.xchg_bytes, stream))) return rc;
     if (p->cache) {
         // cached topology: a mini-batch is its list of graph numbers -- step launch (+ update launch), nothing else
         for (int64_t k = 0; k < nb; ++k) {

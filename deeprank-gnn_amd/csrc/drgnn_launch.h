@@ -1,4 +1,4 @@
-// drgnn_launch.h -- the one launch form of drgnn_capi.hip's feature entry points (included by that file alone).
+// drgnn_launch.h -- the one launch form of drgnn_capi.hip's entry points, features and training path (included by that file alone).
 //
 //     DRGNN_EMU_ONLY(std::unique_ptr<XShared> lds(new XShared);)
 //     DRGNN_LAUNCH(k_x, grid1(n_blocks), stream, x_block(a, bx, *lds), a);

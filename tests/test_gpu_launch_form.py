@@ -1,4 +1,4 @@
-"""The launch form of the feature entry points (csrc/drgnn_launch.h) on the device: the checks of
+"""The launch form of the feature entry points and the training path (csrc/drgnn_launch.h) on the device: the checks of
 tests/test_launch_form.py on the MI355X, where a grid without blocks is skipped (launching it is an error) and a kernel
 that asks for more than 64 KiB of dynamic LDS has its limit raised, and the builder's large tile against the emulation."""
 import pytest
