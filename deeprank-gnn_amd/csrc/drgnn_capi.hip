@@ -1,38 +1,29 @@
-// drgnn_capi.hip -- kernels + the extern "C" surface declared in include/drgnn.h.
+// drgnn_capi.hip -- the training path of the extern "C" surface declared in include/drgnn.h: layout queries, topology builder,
+// launch pair, fused step, head, Adam, p2p, the update launches, collation and the epoch loop, with its kernels
+// (drgnn_kernels.h).  The feature entry points live next to it, one unit per subsystem, named after the Python modules that
+// call them: drgnn_capi_layers.hip, _iface.hip, _residues.hip, _poses.hip, _metrics.hip.  What several units use is in
+// drgnn_capi_common.h.
 //
-// Built twice from this one source:
-//   hipcc --offload-arch=gfx950 -> csrc/libdrgnn.so        (the product)
+// Built twice from these sources, every drgnn_capi*.hip:
+//   hipcc --offload-arch=gfx950 -> csrc/libdrgnn.so        (the product: an object per unit, Makefile)
 //   g++ -x c++ -DDRGNN_EMU      -> tests/emu/build/libdrgnn_emu.so (CPU test-suite only:
-//        every "launch" becomes a loop over workgroups on host pointers)
+//        every "launch" becomes a loop over workgroups on host pointers; ONE unit: tests/emu/build_emu.sh compiles this
+//        file, which includes the feature units at its end)
 //
 // The entry points write their launch sequence ONCE for both builds, with DRGNN_LAUNCH / DRGNN_EMU_ONLY / drgnn_clear of
-// drgnn_launch.h: the checks, phases, guards and early returns the CPU suite runs are the ones the GPU runs.  That holds for the
-// feature entry points (pose_cluster_run, then "stand-alone layers / pooling functions" down to drgnn_metrics) and for the
-// launches of the training path: the topology builder (topo_launch) and its prologue, the launch pair (net_launch, its co-built
-// builder included), the head, the flat Adam, the all-reduce, collation and the epoch loop's clear.  A new entry point touches
-// three places: its block function in a drgnn_<subsystem>.h, its __global__ wrapper in drgnn_kernels.h, and its checks and
-// launches here.  A DRGNN_EMU conditional says on its line why the builds differ in what they DO: the fused step (emu_step
-// stands in for the aggregation-first kernels, so its pick, checks, plans and launch differ), the device queries,
-// drgnn_topology_status, the update / gradient / reduce launches and adam_opt_impl (item-wise sums against the kernels' blocks),
-// the drgnn_p2p_* allocation functions and the profiling hook.
+// drgnn_launch.h: the checks, phases, guards and early returns the CPU suite runs are the ones the GPU runs.  That holds for
+// the feature entry points (the drgnn_capi_<subsystem>.hip units) and for the launches of the training path: the topology
+// builder (topo_launch) and its prologue, the launch pair (net_launch, its co-built builder included), the head, the flat Adam,
+// the all-reduce, collation and the epoch loop's clear.  A new feature entry point touches two places, both its subsystem's
+// own: its block function in drgnn_<subsystem>.h, and its __global__ wrapper, checks and launches in
+// drgnn_capi_<subsystem>.hip; a new UNIT also gets its include line at the end of this file.  A DRGNN_EMU conditional says on
+// its line why the builds differ in what they DO: the fused step (emu_step stands in for the aggregation-first kernels, so its
+// pick, checks, plans and launch differ), the device queries, drgnn_topology_status, the update / gradient / reduce launches
+// and adam_opt_impl (item-wise sums against the kernels' blocks), the drgnn_p2p_* allocation functions and the profiling hook.
 #define DRGNN_KERNELS_MAIN
 #include "drgnn_kernels.h"
 
-#include <vector>
-#include <algorithm>
-#include <memory>
-#include <type_traits>
-#include <string.h>
-#include <stdlib.h>
-#define DRGNN_LDS_LIMIT (160 * 1024)
-#ifndef DRGNN_EMU      // (the emulation makes no runtime call)
-#define HIP_TRY(expr)                                 \
-    do {                                                \
-        hipError_t e_ = (expr);                         \
-        if (e_ != hipSuccess) return (int)e_;           \
-    } while (0)
-#endif
-#include "drgnn_launch.h"
+#include "drgnn_capi_common.h"
 
 
 // =====================================================================================
@@ -1636,96 +1627,6 @@ static int update_run(const UpdateCall& c) {
     return 0;
 }
 
-// ---- clustering of poses (drgnn_posecluster.h) ---------------------------------------------------------
-// The part of drgnn_pose_cluster / drgnn_pose_cluster_dist that does not depend on the rule, after the entry point's own checks:
-// the shared checks, then the relation of `rule` and the greedy loop on it.  `q` is either request: their shared fields
-// have the same names; `relation` is the rule's instantiation of the relation kernel, DRGNN_KERNEL(k_..._relation).
-template <class Rule, class Request, class Kernel>
-static int pose_cluster_run(Rule rule, const Request* q, Kernel relation, void* stream) {
-    const int64_t M = q->n_poses;
-    if (M < 0 || q->min_size < 1 || !q->n_clusters) return DRGNN_E_ARG;
-    if (M > 0 && (!q->neighbours || !q->transposed || !q->labels || !q->centres || !q->sizes)) return DRGNN_E_ARG;
-    if (M > PC_CCAP) return DRGNN_E_CAPACITY;
-    if (M == 0) return 0;
-    PoseClusterArgs a;
-    memset(&a, 0, sizeof(a));
-    rule.n = a.n = (int)M; a.min_size = q->min_size;
-    a.nb = (pc_word*)q->neighbours; a.nbt = (pc_word*)q->transposed;
-    a.labels = q->labels; a.centres = q->centres; a.sizes = q->sizes; a.n_clusters = q->n_clusters;
-    const int64_t words = M * ((M + 63) / 64), blocks = (words + DRGNN_NWAVES - 1) / DRGNN_NWAVES;
-    DRGNN_EMU_ONLY(std::unique_ptr<PoseGreedyShared> lds(new PoseGreedyShared);)
-    DRGNN_LAUNCH(relation, grid1(blocks), stream, pc_relation(rule, a, bx), rule, a);
-    DRGNN_LAUNCH(k_fcc_greedy, grid1(1), stream, pc_greedy(a, *lds), a);
-    return 0;
-}
-
-// ---- request checks that several entry points share -----------------------------------------------------
-// the ragged layout on the host, whole, before anything is indexed through it: 0 = ap[0] <= ap[r] <= ap[r + 1], ap[R] = T;
-// with rp, 0 = rp[0] <= rp[c] <= rp[c + 1] <= R = rp[M]; with sp, rp[c] <= sp[c] <= rp[c + 1]
-static bool ragged_check(const int32_t* ap, const int32_t* rp, const int32_t* sp, int64_t T, int64_t R, int64_t M) {
-    if (ap[0] != 0 || ap[R] != T || (rp && (rp[0] != 0 || rp[M] != R))) return false;
-    for (int64_t r = 0; r < R; ++r)
-        if (ap[r + 1] < ap[r]) return false;
-    for (int64_t c = 0; rp && c < M; ++c)
-        if (rp[c + 1] < rp[c] || rp[c + 1] > R || (sp && (sp[c] < rp[c] || sp[c] > rp[c + 1]))) return false;
-    return true;
-}
-
-// every target (complex tc[k], residue tr[k]) lies inside its complex; rp has passed ragged_check
-static bool targets_check(const int32_t* tc, const int32_t* tr, const int32_t* rp, int64_t M, int64_t K) {
-    for (int64_t k = 0; k < K; ++k)
-        if (tc[k] < 0 || tc[k] >= M || tr[k] < rp[tc[k]] || tr[k] >= rp[tc[k] + 1]) return false;
-    return true;
-}
-
-// The checks the residue-feature requests (bsa, hse, depth) share; `q` is any of them: the shared fields have the same names.
-// residue_request_check: the counts and pointers, in front of the entry point's own ARG and CAPACITY checks (k_max: the largest
-// n_targets its indices allow); residue_tables_check: the host tables, behind them (sp: the chain split, or null).
-template <class Request>
-static int residue_request_check(const Request* q, int64_t k_max) {
-    if (!q || !q->host_atom_ptr || !q->host_res_ptr || !q->status) return DRGNN_E_ARG;
-    const int64_t T = q->n_atoms, R = q->n_residues, M = q->n_complexes, K = q->n_targets;
-    if (T < 0 || R < 0 || M < 0 || K < 0 || T > INT32_MAX / 3 || R >= INT32_MAX || K > k_max) return DRGNN_E_ARG;
-    if ((M > 0 && !q->res_ptr) || (R > 0 && !q->atom_ptr) || (T > 0 && !q->xyz)) return DRGNN_E_ARG;
-    if (K > 0 && (!q->host_target_res || !q->host_target_complex || !q->target_res || !q->target_complex || !q->out)) return DRGNN_E_ARG;
-    return 0;
-}
-template <class Request>
-static int residue_tables_check(const Request* q, const int32_t* sp) {
-    const int32_t* rp = q->host_res_ptr;
-    if (!ragged_check(q->host_atom_ptr, rp, sp, q->n_atoms, q->n_residues, q->n_complexes) ||
-        !targets_check(q->host_target_complex, q->host_target_res, rp, q->n_complexes, q->n_targets))
-        return DRGNN_E_ARG;
-    return 0;
-}
-
-// pointer first (alignment: a power of two), then the size: the workspace of depth and RMSD
-static int workspace_check(const void* ptr, int64_t bytes, int64_t need, uintptr_t alignment) {
-    if (!ptr || ((uintptr_t)ptr & (alignment - 1))) return DRGNN_E_ARG;
-    return bytes < need ? DRGNN_E_CAPACITY : 0;
-}
-
-// drgnn_<subsystem>_capacity(what): entry `what` of the subsystem's limits, -1 beyond them
-#define DRGNN_CAPACITY(name, ...)                                                              \
-    int32_t name(int32_t what) {                                                               \
-        static const int32_t cap[] = {__VA_ARGS__};                                            \
-        return what >= 0 && what < (int32_t)(sizeof(cap) / sizeof(cap[0])) ? cap[what] : -1;   \
-    }
-
-// the launches of drgnn_pose_lddt for PP poses per pass and KT thresholds at most: at most LD_MAX_Y passes and LD_MAX_WGS
-// workgroups each (a template cannot stand inside extern "C")
-template <int PP, int KT>
-static int lddt_launches(LddtArgs a, int64_t n_blocks, void* stream) {
-    DRGNN_EMU_ONLY(std::unique_ptr<LddtShared> lds(new LddtShared);)
-    const int64_t passes = (a.n_poses + PP - 1) / PP, step = std::max<int64_t>(1, std::min<int64_t>(LD_MAX_Y, LD_MAX_WGS / n_blocks));
-    for (int64_t p0 = 0; p0 < passes; p0 += step) {
-        a.m0 = p0 * PP;
-        DRGNN_LAUNCH((k_pose_lddt<PP, KT>), grid2(n_blocks, std::min(step, passes - p0)), stream,
-                     (ld_block<PP, KT>(a, (int)bx, a.m0 + by * PP, *lds)), a);
-    }
-    return 0;
-}
-
 extern "C" {
 
 int drgnn_net_reduce_grads(const drgnn_net_desc* net, const float* partials, int64_t n_nodes, int64_t n_graphs,
@@ -1859,786 +1760,6 @@ int drgnn_step_gradients(const drgnn_net_desc* net, const float* conv_partials, 
     hipLaunchKernelGGL(k_gradients, dim3((unsigned)(u.conv_blocks + head_blocks + 1)), dim3(256), 0, (hipStream_t)stream_, ga);
     HIP_TRY(hipGetLastError());
 #endif
-    return 0;
-}
-
-// ---- stand-alone layers / pooling functions ---------------------------------------------------
-static int conv_layer_fill(ConvLayerArgs& a, int32_t kind, const float* x, int64_t n_nodes, int32_t F,
-                           int32_t H, const drgnn_conv_params* p, const int32_t* ws_i32,
-                           const float* ws_f32, int64_t n_edges) {
-    if (kind < DRGNN_GINET || kind > DRGNN_FOUT || !x || !p || !p->w_nbr || !ws_i32) return DRGNN_E_ARG;
-    if (kind != DRGNN_GINET && (!p->w_self || !p->bias)) return DRGNN_E_ARG;
-    if (kind == DRGNN_SGAT && !ws_f32) return DRGNN_E_ARG;
-    if (F < 1 || H < 1 || H > DRGNN_LAYER_MAXH || n_nodes >= INT32_MAX) return DRGNN_E_WIDTH;
-    TopoLayout lay;
-    topo_layout(n_nodes, n_edges, 1, &lay);
-    TopoView tv = topo_view(const_cast<int32_t*>(ws_i32), const_cast<float*>(ws_f32), lay);
-    a.kind = kind; a.x = x; a.F = F; a.H = H; a.p = *p; a.N = (int)n_nodes;
-    a.rowptr = tv.p[DRGNN_TI_ROWPTR0]; a.col = tv.p[DRGNN_TI_COL0]; a.w = tv.w0;
-    a.colptr = tv.p[DRGNN_TI_COLPTR0]; a.ridx = tv.p[DRGNN_TI_ROWIDX0]; a.tslot = tv.p[DRGNN_TI_TSLOT0];
-    a.u = nullptr; a.out = nullptr; a.grad_out = nullptr; a.partials = nullptr; a.grad_x = nullptr;
-    return 0;
-}
-
-int64_t drgnn_conv_layer_slabs(int64_t n_nodes) { return (n_nodes + DRGNN_LAYER_ROWS - 1) / DRGNN_LAYER_ROWS; }
-int64_t drgnn_conv_layer_partial_elems(int32_t kind, int32_t F, int32_t H) { return conv_partial_floats(kind, F, H); }
-
-int drgnn_conv_layer_forward(int32_t kind, const float* x, int64_t n_nodes, int32_t F, int32_t H,
-                             const drgnn_conv_params* p, const int32_t* ws_i32, const float* ws_f32,
-                             int64_t n_edges, float* u, float* out, void* stream) {
-    ConvLayerArgs a;
-    int rc = conv_layer_fill(a, kind, x, n_nodes, F, H, p, ws_i32, ws_f32, n_edges);
-    if (rc) return rc;
-    if (!u || !out) return DRGNN_E_ARG;
-    a.u = u; a.out = out;
-    const int64_t slabs = drgnn_conv_layer_slabs(n_nodes);
-    DRGNN_LAUNCH(k_conv_gemm, grid1(slabs), stream, conv_gemm_block(a, (int)bx), a);
-    DRGNN_LAUNCH(k_conv_aggregate, grid_items(n_nodes * H), stream, conv_aggregate_item(a, bx), a);
-    return 0;
-}
-
-int drgnn_conv_layer_backward(int32_t kind, const float* x, int64_t n_nodes, int32_t F, int32_t H,
-                              const drgnn_conv_params* p, const int32_t* ws_i32, const float* ws_f32,
-                              int64_t n_edges, const float* grad_out, float* du, float* partials,
-                              const drgnn_conv_grads* g, float* grad_x, void* stream) {
-    ConvLayerArgs a;
-    int rc = conv_layer_fill(a, kind, x, n_nodes, F, H, p, ws_i32, ws_f32, n_edges);
-    if (rc) return rc;
-    if (!grad_out || !du || !partials || !g) return DRGNN_E_ARG;
-    a.u = du; a.grad_out = grad_out; a.partials = partials; a.grad_x = grad_x;
-    const int64_t slabs = drgnn_conv_layer_slabs(n_nodes);
-    DRGNN_LAUNCH(k_conv_bwd_du, grid_items(n_nodes * H), stream, conv_bwd_du_item(a, bx), a);
-    DRGNN_LAUNCH(k_conv_bwd_dw, grid1(slabs), stream, conv_bwd_dw_block(a, (int)bx), a);
-    ConvReduceArgs r;
-    r.partials = partials; r.n_wg = (int)slabs; r.kind = kind; r.F = F; r.H = H; r.lay = *p; r.g = *g;
-    DRGNN_LAUNCH(k_conv_reduce, grid_items(conv_partial_floats(kind, F, H)), stream, conv_reduce_item(r, (int)bx), r);
-    if (grad_x) DRGNN_LAUNCH(k_conv_bwd_dx, grid_items(n_nodes * F), stream, conv_bwd_dx_item(a, bx), a);
-    return 0;
-}
-
-int drgnn_segpool_forward(const int32_t* ws_i32, int64_t n_nodes, int64_t n_edges, int64_t n_graphs,
-                          const float* x, int32_t H, int32_t op, float* out, int64_t* arg, void* stream) {
-    if (!ws_i32 || !x || !out || H < 1 || (op != 0 && op != 1)) return DRGNN_E_ARG;
-    TopoLayout lay;
-    topo_layout(n_nodes, n_edges, n_graphs, &lay);
-    SegPoolArgs a;
-    a.tv = topo_view(const_cast<int32_t*>(ws_i32), nullptr, lay);
-    a.x = x; a.H = H; a.n_graphs = (int)n_graphs; a.op = op; a.out = out; a.arg = arg;
-    a.grad_out = nullptr; a.grad_x = nullptr; a.arg_in = nullptr;
-    DRGNN_LAUNCH(k_segpool_fwd, grid1(n_graphs), stream, segpool_fwd_block(a, (int)bx), a);
-    return 0;
-}
-
-int drgnn_segmax_backward(const float* grad_out, const int64_t* arg, int64_t n_clusters, int32_t H,
-                          int64_t n_nodes, float* grad_x, void* stream) {
-    if (!grad_out || !arg || !grad_x) return DRGNN_E_ARG;
-    SegPoolArgs a;
-    a.H = H; a.grad_out = grad_out; a.arg_in = arg; a.grad_x = grad_x;
-    a.x = nullptr; a.out = nullptr; a.arg = nullptr; a.n_graphs = 0; a.op = 0;
-    const int64_t n_items = n_clusters * H;
-    DRGNN_LAUNCH(k_segmax_bwd, grid_items(n_items), stream, segmax_bwd_item(a, bx, n_items, n_nodes), a, n_items, n_nodes);
-    return 0;
-}
-
-int drgnn_pooled_edges_export(const int32_t* ws_i32, const float* ws_f32, int64_t n_nodes, int64_t n_edges,
-                              int64_t n_graphs, int64_t e1_total, int64_t* edge_index, float* edge_attr,
-                              void* stream) {
-    if (!ws_i32 || (e1_total > 0 && !edge_index)) return DRGNN_E_ARG;
-    TopoLayout lay;
-    topo_layout(n_nodes, n_edges, n_graphs, &lay);
-    EdgeExportArgs a;
-    a.tv = topo_view(const_cast<int32_t*>(ws_i32), const_cast<float*>(ws_f32), lay);
-    a.n_graphs = (int)n_graphs; a.edge_index = edge_index; a.edge_attr = edge_attr; a.e1_total = e1_total;
-    DRGNN_LAUNCH(k_edge_export, grid1(n_graphs), stream, edge_export_block(a, (int)bx), a);
-    return 0;
-}
-
-int drgnn_cluster_offset(int64_t* cluster, const int32_t* node_ptr, int64_t n_graphs, int64_t* scratch,
-                         void* stream) {
-    if (!cluster || !node_ptr || !scratch || n_graphs < 0) return DRGNN_E_ARG;
-    if (n_graphs == 0) return 0;
-    ClusterOffsetArgs a;
-    a.cluster = cluster; a.nptr = node_ptr; a.n_graphs = (int)n_graphs; a.maxes = (long long*)scratch;
-    DRGNN_EMU_ONLY(long long mm[2];)
-    DRGNN_LAUNCH(k_cluster_max, grid1(n_graphs), stream, cluster_max_block(a, (int)bx, mm), a);
-    DRGNN_LAUNCH(k_cluster_scan, grid1(1, 64), stream, cluster_scan_single(a), a);
-    DRGNN_LAUNCH(k_cluster_add, grid1(n_graphs), stream, cluster_add_block(a, (int)bx), a);
-    return 0;
-}
-
-// ---- graclus ----------------------------------------------------------------------------------------
-int drgnn_graclus(const int32_t* ws_i32, int64_t n_nodes, int64_t n_edges, int64_t n_graphs, int32_t max_nodes,
-                  int32_t max_edges, const float* weight, const int64_t* perm, int64_t* cluster, void* stream) {
-    if (!ws_i32 || n_nodes < 0 || n_edges < 0 || n_graphs < 0 || max_nodes < 0 || max_edges < 0) return DRGNN_E_ARG;
-    if (n_nodes > 0 && !cluster) return DRGNN_E_ARG;
-    if (n_graphs == 0) return 0;
-    TopoLayout lay;
-    topo_layout(n_nodes, n_edges, n_graphs, &lay);
-    GraclusArgs a;
-    a.tv = topo_view(const_cast<int32_t*>(ws_i32), nullptr, lay);
-    a.n_graphs = (int)n_graphs; a.weight = weight; a.perm = perm; a.cluster = cluster;
-    a.capN = max_nodes > 0 ? max_nodes : 1; a.capE = max_edges > 0 ? max_edges : 1;
-    const int64_t words = (int64_t)(a.capN + 1) + 2 * (int64_t)a.capE + a.capN;
-    if (words * 4 > DRGNN_LDS_LIMIT) return DRGNN_E_CAPACITY;
-    DRGNN_EMU_ONLY(std::vector<int> buf((size_t)words + 16);)
-    DRGNN_LAUNCH(k_graclus, grid1(n_graphs, DRGNN_NTHREADS, words * 4), stream, graclus_block(a, (int)bx, buf.data()), a);
-    return 0;
-}
-
-// ---- offline clustering ---------------------------------------------------------------------------
-int drgnn_mcl(const int64_t* edge_index, int64_t n_edges, const int32_t* node_ptr, const int32_t* edge_ptr,
-              const int64_t* mat_ptr, int64_t n_graphs, double* mat_scratch, int32_t* int_scratch,
-              int64_t* labels, int32_t* info, void* stream) {
-    if (!node_ptr || !edge_ptr || !mat_ptr || !mat_scratch || !int_scratch || !labels || !info || n_graphs < 0)
-        return DRGNN_E_ARG;
-    if (n_edges > 0 && !edge_index) return DRGNN_E_ARG;
-    if (n_graphs == 0) return 0;
-    MclArgs a;
-    a.edge_index = edge_index; a.n_edges = n_edges; a.node_ptr = node_ptr; a.edge_ptr = edge_ptr;
-    a.mat_ptr = mat_ptr; a.n_graphs = (int)n_graphs; a.mat = mat_scratch; a.iscr = int_scratch;
-    a.labels = labels; a.info = info; a.iterations = 100; a.prune_threshold = 1e-3;
-    DRGNN_EMU_ONLY(std::vector<double> red(DRGNN_NTHREADS); int flag[2];)
-    DRGNN_LAUNCH(k_mcl, grid1(n_graphs), stream, mcl_graph(a, (int)bx, flag, red.data()), a);
-    return 0;
-}
-
-int drgnn_louvain(const int64_t* edge_index, int64_t n_edges, const int32_t* node_ptr, const int32_t* edge_ptr,
-                  int64_t n_graphs, int32_t max_nodes, int32_t max_edges, int64_t* labels, int32_t* info,
-                  double* modularity, void* stream) {
-    if (!node_ptr || !edge_ptr || !info || !modularity || n_graphs < 0 || n_edges < 0 || max_nodes < 0 ||
-        max_edges < 0)
-        return DRGNN_E_ARG;
-    if (n_edges > 0 && !edge_index) return DRGNN_E_ARG;
-    if (max_nodes > 0 && !labels) return DRGNN_E_ARG;
-    if (n_graphs == 0) return 0;
-    const int64_t words = louvain_lds_words(max_nodes, max_edges);
-    if (words * 4 > DRGNN_LDS_LIMIT) return DRGNN_E_CAPACITY;
-    LouvainArgs a;
-    a.edge_index = edge_index; a.n_edges = n_edges; a.node_ptr = node_ptr; a.edge_ptr = edge_ptr;
-    a.n_graphs = (int)n_graphs; a.capN = max_nodes; a.capE = max_edges;
-    a.labels = labels; a.info = info; a.modularity = modularity;
-    DRGNN_EMU_ONLY(std::vector<int> buf((size_t)words + 16);)
-    DRGNN_LAUNCH(k_louvain, grid1(n_graphs, LV_W, words * 4), stream, louvain_graph(a, (int)bx, buf.data()), a);
-    return 0;
-}
-
-// ---- interface graphs from atom coordinates (drgnn_iface.h) ------------------------------------------
-int64_t drgnn_iface_workspace_bytes(int64_t n_complexes, int64_t max_res_a, int64_t max_res_b, int64_t n_residues) {
-    if (n_complexes < 0 || max_res_a < 0 || max_res_b < 0 || n_residues < 0) return -1;
-    int64_t off[8];
-    iface_layout(n_complexes, max_res_a, max_res_b, n_residues, off);
-    return off[7];
-}
-
-// checks the request on the host and fills the launch record; *max_res: the longest complex
-static int iface_prepare(const drgnn_iface_request* q, IfaceArgs& a, int* max_res) {
-    if (!q || !q->host_atom_ptr || !q->host_res_ptr || !q->node_ptr || !q->edge_ptr || !q->iedge_ptr) return DRGNN_E_ARG;
-    const int64_t T = q->n_atoms, R = q->n_residues, M = q->n_complexes;
-    if (T < 0 || R < 0 || M < 0 || T > INT32_MAX / 3 || R >= INT32_MAX) return DRGNN_E_ARG;
-    if (M > 0 && (!q->host_res_split || !q->res_ptr || !q->res_split)) return DRGNN_E_ARG;
-    if (R > 0 && (!q->atom_ptr || !q->res_type || !q->workspace)) return DRGNN_E_ARG;
-    if (T > 0 && !q->xyz) return DRGNN_E_ARG;
-    if (!(q->contact_distance >= 0.0) || !(q->internal_contact_distance >= 0.0) || q->tile_atoms < 0) return DRGNN_E_ARG;
-    const int32_t *ap = q->host_atom_ptr, *rp = q->host_res_ptr, *sp = q->host_res_split;
-    if (!ragged_check(ap, rp, sp, T, R, M)) return DRGNN_E_ARG;
-    int max_atoms = 0, maxA = 0, maxB = 0, maxR = 0, maxB_atoms = 0;
-    for (int64_t r = 0; r < R; ++r) max_atoms = std::max(max_atoms, ap[r + 1] - ap[r]);
-    for (int64_t c = 0; c < M; ++c) {
-        maxA = std::max(maxA, sp[c] - rp[c]);
-        maxB = std::max(maxB, rp[c + 1] - sp[c]);
-        maxR = std::max(maxR, rp[c + 1] - rp[c]);
-        maxB_atoms = std::max(maxB_atoms, ap[rp[c + 1]] - ap[sp[c]]);
-    }
-    if (M > 65535) return DRGNN_E_CAPACITY;
-    if (M * (int64_t)maxA * maxB > INT32_MAX) return DRGNN_E_CAPACITY;      // (the edge counts and their prefix sums are int32)
-    int tile = q->tile_atoms > 0 ? q->tile_atoms : IF_TILE_DEFAULT;
-    tile = std::max(std::max(std::min(tile, maxB_atoms), max_atoms), 1);
-    if (iface_pairs_lds_bytes(tile) > DRGNN_LDS_LIMIT) return DRGNN_E_CAPACITY;
-    int64_t off[8];
-    iface_layout(M, maxA, maxB, R, off);
-    if (q->workspace_bytes < off[7]) return DRGNN_E_CAPACITY;
-    if (off[7] > 0 && ((uintptr_t)q->workspace & 15) != 0) return DRGNN_E_ARG;
-    char* ws = (char*)q->workspace;
-    memset(&a, 0, sizeof(a));
-    a.xyz = q->xyz; a.atom_ptr = q->atom_ptr; a.res_ptr = q->res_ptr; a.res_split = q->res_split; a.res_type = q->res_type;
-    a.n_complexes = (int)M; a.n_residues = (int)R; a.maxA = maxA; a.maxB = maxB; a.tile_atoms = tile;
-    a.cut = (float)q->contact_distance; a.cut2 = (float)(q->contact_distance * q->contact_distance);
-    a.icut = (float)q->internal_contact_distance;
-    a.icut2 = (float)(q->internal_contact_distance * q->internal_contact_distance);
-    a.D = (float*)(ws + off[0]); a.sphere = (float*)(ws + off[1]); a.flag = (int*)(ws + off[2]); a.nloc = (int*)(ws + off[3]);
-    a.eoff = (int*)(ws + off[4]); a.ioff = (int*)(ws + off[5]); a.cnt = (int*)(ws + off[6]);
-    a.node_ptr = q->node_ptr; a.edge_ptr = q->edge_ptr; a.iedge_ptr = q->iedge_ptr;
-    *max_res = maxR;
-    return 0;
-}
-
-// the rows kernel over (blocks of IF_AB residues, complexes): counting (write 0) or filling (1)
-static int iface_rows(const IfaceArgs& a, int max_res, int write, void* stream) {
-    DRGNN_LAUNCH(k_iface_rows, grid2((max_res + IF_AB - 1) / IF_AB, a.n_complexes, IF_NT), stream,
-                 iface_rows_block(a, (int)by, (int)bx, write != 0), a, write);
-    return 0;
-}
-
-int drgnn_iface_count(const drgnn_iface_request* req, void* stream) {
-    IfaceArgs a;
-    int max_res = 0;
-    int rc = iface_prepare(req, a, &max_res);
-    if (rc) return rc;
-    const int M = a.n_complexes, R = a.n_residues;
-    // (without residues, complexes or chain-A residues the grids of the first three launches are empty: skipped)
-    const int64_t lds_bytes = iface_pairs_lds_bytes(a.tile_atoms);
-    DRGNN_EMU_ONLY(std::vector<float> lds((size_t)(lds_bytes / 4) + 4); std::vector<int> part(DRGNN_NTHREADS + 1);)
-    DRGNN_LAUNCH(k_iface_sphere, grid_items(R, IF_NT), stream, iface_sphere_item(a, (int)bx), a);
-    DRGNN_LAUNCH(k_iface_pairs, (Grid{(a.maxA + IF_AB - 1) / IF_AB, M, IF_NT, lds_bytes}), stream,
-                 iface_pairs_block(a, (int)by, (int)bx, lds.data()), a);
-    if ((rc = iface_rows(a, max_res, 0, stream))) return rc;
-    DRGNN_LAUNCH(k_iface_scan, grid1(M), stream, iface_scan_block(a, (int)bx, part.data()), a);
-    DRGNN_LAUNCH(k_iface_offsets, grid1(1), stream, iface_offsets_block(a, part.data()), a);
-    return 0;
-}
-
-int drgnn_iface_fill(const drgnn_iface_request* req, int64_t n_nodes, int64_t n_edges, int64_t n_iedges,
-                     int32_t* node_residue, float* pos, int32_t* chain, int32_t* type, int64_t* edge_index, float* dist,
-                     int64_t* internal_edge_index, float* internal_dist, void* stream) {
-    IfaceArgs a;
-    int max_res = 0;
-    const int rc = iface_prepare(req, a, &max_res);
-    if (rc) return rc;
-    if (n_nodes < 0 || n_edges < 0 || n_iedges < 0) return DRGNN_E_ARG;
-    if (n_nodes > 0 && (!node_residue || !pos || !chain || !type)) return DRGNN_E_ARG;
-    if (n_edges > 0 && (!edge_index || !dist)) return DRGNN_E_ARG;
-    if (n_iedges > 0 && (!internal_edge_index || !internal_dist)) return DRGNN_E_ARG;
-    a.node_residue = node_residue; a.pos = pos; a.chain = chain; a.type = type;
-    a.edge_index = edge_index; a.dist = dist; a.iedge_index = internal_edge_index; a.idist = internal_dist;
-    a.n_nodes = n_nodes; a.n_edges = n_edges; a.n_iedges = n_iedges;
-    if (a.n_complexes == 0 || max_res == 0 || n_nodes == 0) return 0;
-    return iface_rows(a, max_res, 1, stream);
-}
-
-// ---- docking scores of pose batches (drgnn_score.h) -------------------------------------------------
-int drgnn_dock_scores(const drgnn_score_request* q, void* stream) {
-    if (!q || !q->host_zone_ptr || !q->host_zone_atom || !q->host_atom_ptr || !q->zone_atom || !q->zone_ref ||
-        !q->atom_ptr || !q->xyz || !q->scores || !q->classes || !q->n_preserved)
-        return DRGNN_E_ARG;
-    const int64_t M = q->n_poses, T = q->n_atoms, R = q->n_residues, P = q->n_pairs;
-    if (M < 0 || T < 1 || R < 1 || P < 0 || q->n_ref_pairs < 1 || P > q->n_ref_pairs || !(q->fnat_cutoff >= 0.0))
-        return DRGNN_E_ARG;
-    if (P > 0 && (!q->pair_res || !q->host_pair_res)) return DRGNN_E_ARG;
-    if (M > INT32_MAX || T > INT32_MAX / 3 || R >= INT32_MAX || q->n_ref_pairs > INT32_MAX) return DRGNN_E_CAPACITY;
-    const int32_t *zp = q->host_zone_ptr, *za = q->host_zone_atom, *ap = q->host_atom_ptr, *pr = q->host_pair_res;
-    if (zp[0] != 0) return DRGNN_E_ARG;
-    for (int z = 0; z < 3; ++z)
-        if (zp[z + 1] < zp[z] || zp[z + 1] - zp[z] < 3) return DRGNN_E_ARG;
-    for (int64_t i = 0; i < zp[3]; ++i)
-        if (za[i] < 0 || za[i] >= T) return DRGNN_E_ARG;
-    if (!ragged_check(ap, nullptr, nullptr, T, R, 0)) return DRGNN_E_ARG;
-    int amax = 1;
-    for (int64_t p = 0; p < P; ++p) {
-        const int32_t ra = pr[2 * p], rb = pr[2 * p + 1];
-        if (ra < 0 || ra >= R || rb < 0 || rb >= R) return DRGNN_E_ARG;
-        amax = std::max(amax, ap[ra + 1] - ap[ra]);
-    }
-    if ((int64_t)amax * SC_PCHUNK > INT32_MAX) return DRGNN_E_CAPACITY;
-    if (M == 0) return 0;
-    ScoreArgs a;
-    memset(&a, 0, sizeof(a));
-    a.xyz = q->xyz; a.zone_atom = q->zone_atom; a.zone_ref = q->zone_ref; a.pair_res = q->pair_res; a.atom_ptr = q->atom_ptr;
-    for (int z = 0; z < 4; ++z) a.zp[z] = zp[z];
-    a.n_atoms = (int)T; a.n_pairs = (int)P; a.n_ref_pairs = (int)q->n_ref_pairs; a.amax = amax;
-    a.cut2 = (float)(q->fnat_cutoff * q->fnat_cutoff);
-    a.scores = q->scores; a.classes = q->classes; a.n_preserved = q->n_preserved;
-    DRGNN_EMU_ONLY(std::vector<double> lds(SC_LDS_BYTES / 8 + 1);)
-    DRGNN_LAUNCH(k_dock_scores, grid1(M), stream, score_pose(a, bx, lds.data()), a);
-    return 0;
-}
-
-// ---- lDDT and interface lDDT of pose batches (drgnn_lddt.h) -------------------------------------------
-int drgnn_pose_lddt(const drgnn_lddt_request* q, void* stream) {
-    if (!q || !q->host_entry_ptr || !q->entry_ptr || !q->xyz || !q->counts) return DRGNN_E_ARG;
-    const int64_t M = q->n_poses, T = q->n_atoms, R = q->n_residues, E = q->n_entries, K = q->n_thresholds;
-    if (M < 0 || T < 1 || R < 1 || E < 0 || q->n_chain_a_atoms < 0 || q->n_chain_a_atoms > T) return DRGNN_E_ARG;
-    if (K < 1 || K > LD_KMAX || (q->poses_per_pass != 0 && q->poses_per_pass != 1 && q->poses_per_pass != LD_PPMAX)) return DRGNN_E_ARG;
-    for (int64_t k = 0; k < K; ++k)                                    // (a NaN fails both)
-        if (!(q->thresholds[k] >= 0.0) || !(q->thresholds[k] < 1.0e150) || (k > 0 && !(q->thresholds[k] > q->thresholds[k - 1])))
-            return DRGNN_E_ARG;
-    if (E > 0 && (!q->self_atom || !q->other_atom || !q->d_ref || !q->host_self_atom || !q->host_other_atom)) return DRGNN_E_ARG;
-    const int64_t n_blocks = (R + LD_RB - 1) / LD_RB;
-    if (M > INT32_MAX || T > INT32_MAX / 3 || E > INT32_MAX || R >= INT32_MAX || n_blocks > LD_MAX_WGS) return DRGNN_E_CAPACITY;
-    const int32_t *ep = q->host_entry_ptr, *sa = q->host_self_atom, *oa = q->host_other_atom;
-    if (ep[0] != 0 || ep[R] != E) return DRGNN_E_ARG;
-    for (int64_t r = 0; r < R; ++r)
-        if (ep[r + 1] < ep[r]) return DRGNN_E_ARG;
-    for (int64_t e = 0; e < E; ++e)
-        if (sa[e] < 0 || sa[e] >= T || oa[e] < 0 || oa[e] >= T) return DRGNN_E_ARG;
-    if (M == 0) return 0;
-    LddtArgs a;
-    memset(&a, 0, sizeof(a));
-    a.xyz = q->xyz; a.entry_ptr = q->entry_ptr; a.self_atom = q->self_atom; a.other_atom = q->other_atom; a.d_ref = q->d_ref;
-    for (int64_t k = 0; k < K; ++k) a.t[k] = q->thresholds[k];
-    a.n_thresholds = (int)K; a.n_atoms = (int)T; a.n_residues = (int)R; a.first_b = (int)q->n_chain_a_atoms; a.n_poses = M;
-    a.counts = q->counts; a.residue_counts = q->residue_counts;
-    if (int rc = drgnn_clear(q->counts, (size_t)(M * 2 * K) * sizeof(int32_t), stream)) return rc;
-    // four poses to a pass share an entry's loads and bounds: taken once such passes still give every compute unit several
-    // workgroups (profiles/lddt_ab.txt: 1 024 poses of 1ATN 6.1 against 6.9 ms; at 64 poses, 160 such workgroups, the two are
-    // within their spread, 0.88 - 0.91 ms, of which the checks above are 0.76)
-    const int pp = q->poses_per_pass ? q->poses_per_pass : (n_blocks * ((M + LD_PPMAX - 1) / LD_PPMAX) >= LD_FILL ? LD_PPMAX : 1);
-    int rc;
-    if (pp == 1) rc = K <= 4 ? lddt_launches<1, 4>(a, n_blocks, stream) : lddt_launches<1, LD_KMAX>(a, n_blocks, stream);
-    else rc = K <= 4 ? lddt_launches<LD_PPMAX, 4>(a, n_blocks, stream) : lddt_launches<LD_PPMAX, LD_KMAX>(a, n_blocks, stream);
-    if (rc) return rc;
-    const int64_t words = M * 2 * K, span = (int64_t)LD_MAX_WGS * 256;
-    for (a.m0 = 0; a.m0 < words; a.m0 += span)                         // (m0: here the first word of the launch)
-        DRGNN_LAUNCH(k_lddt_halve, grid_items(std::min(span, words - a.m0)), stream, ld_halve_item(a, a.m0 + bx), a);
-    return 0;
-}
-
-// ---- buried surface area of residues (drgnn_bsa.h) ---------------------------------------------------
-DRGNN_CAPACITY(drgnn_bsa_capacity, BS_NCAP, BS_CCAP, BS_MAX_SLICES, BS_MAX_TARGETS)
-
-int drgnn_bsa_residues(const drgnn_bsa_request* q, void* stream) {
-    if (int rc = residue_request_check(q, INT32_MAX)) return rc;
-    const int64_t T = q->n_atoms, M = q->n_complexes, K = q->n_targets, NR = q->n_radii;
-    if (NR < 0 || (M > 0 && (!q->host_res_split || !q->res_split))) return DRGNN_E_ARG;
-    if (T > 0 && (!q->rad_complex || !q->rad_unbound || NR < 1 || T % NR != 0)) return DRGNN_E_ARG;
-    if (!(q->probe >= 0.0) || q->n_slices < 1) return DRGNN_E_ARG;
-    if (q->n_slices > BS_MAX_SLICES || K > BS_MAX_TARGETS) return DRGNN_E_CAPACITY;
-    if (int rc = residue_tables_check(q, q->host_res_split)) return rc;
-    if (K == 0) return 0;
-    BsaArgs a;
-    memset(&a, 0, sizeof(a));
-    a.xyz = q->xyz; a.atom_ptr = q->atom_ptr; a.res_ptr = q->res_ptr; a.res_split = q->res_split;
-    a.rad_c = q->rad_complex; a.rad_u = q->rad_unbound; a.tgt_res = q->target_res; a.tgt_cx = q->target_complex;
-    a.n_radii = (int)NR; a.n_slices = q->n_slices; a.probe = (float)q->probe; a.probe_d = q->probe;
-    a.out = q->out; a.status = q->status;
-    static_assert(sizeof(BsaShared) <= DRGNN_LDS_LIMIT, "the workgroup's lists fit the LDS");
-    DRGNN_EMU_ONLY(std::unique_ptr<BsaShared> lds(new BsaShared);)
-    DRGNN_LAUNCH(k_bsa_residues, grid1(K, DRGNN_NTHREADS, sizeof(BsaShared)), stream, bsa_residue(a, bx, *lds), a);
-    return 0;
-}
-
-// ---- half-sphere exposure of residues (drgnn_hse.h) --------------------------------------------------
-DRGNN_CAPACITY(drgnn_hse_capacity, HS_RCAP, HS_MAX_TILES)
-
-int drgnn_hse_residues(const drgnn_hse_request* q, void* stream) {
-    if (int rc = residue_request_check(q, INT32_MAX / 3)) return rc;
-    const int64_t R = q->n_residues, K = q->n_targets, NT = q->n_tiles, NB = q->n_rows;
-    if (!q->host_tile_ptr || NT < 0 || NB < 0) return DRGNN_E_ARG;
-    if (R > 0 && (!q->bb || !q->host_bb || NB < 1 || R % NB != 0)) return DRGNN_E_ARG;
-    if (K > 0 && (!q->tile_ptr || NT < 1)) return DRGNN_E_ARG;
-    if (!(q->radius > 0.0) || !(q->radius < 1.0e150) || !(q->connect_cutoff > 0.0) || !(q->connect_cutoff < 1.0e150) ||
-        q->offset < 0)
-        return DRGNN_E_ARG;
-    if (q->connect_a < 0 || q->connect_a > 3 || q->connect_b < 0 || q->connect_b > 3 || q->direction < 0 || q->direction > 1)
-        return DRGNN_E_ARG;
-    if (NT > HS_MAX_TILES) return DRGNN_E_CAPACITY;
-    const int32_t *ap = q->host_atom_ptr, *tp = q->host_tile_ptr, *hb = q->host_bb;
-    if (int rc = residue_tables_check(q, nullptr)) return rc;
-    if (tp[0] != 0 || tp[NT] != K) return DRGNN_E_ARG;
-    for (int64_t r = 0; r < R; ++r) {
-        const int32_t* row = hb + 5 * (r % NB);                       // every offset the kernel may add lies in its residue
-        for (int j = 0; j < 4; ++j)
-            if (row[j] < -1 || row[j] >= ap[r + 1] - ap[r]) return DRGNN_E_ARG;
-    }
-    for (int64_t t = 0; t < NT; ++t) {
-        if (tp[t + 1] < tp[t] || tp[t + 1] > K) return DRGNN_E_ARG;
-        for (int64_t k = tp[t] + 1; k < tp[t + 1]; ++k)               // a tile serves one complex
-            if (q->host_target_complex[k] != q->host_target_complex[tp[t]]) return DRGNN_E_ARG;
-    }
-    if (K == 0) return 0;
-    HseArgs a;
-    memset(&a, 0, sizeof(a));
-    a.xyz = q->xyz; a.atom_ptr = q->atom_ptr; a.res_ptr = q->res_ptr; a.bb = q->bb;
-    a.tgt_res = q->target_res; a.tgt_cx = q->target_complex; a.tile_ptr = q->tile_ptr;
-    a.n_rows = (int)NB; a.offset = q->offset; a.con_a = q->connect_a; a.con_b = q->connect_b; a.direction = q->direction;
-    a.radius2 = q->radius * q->radius; a.cut2 = q->connect_cutoff * q->connect_cutoff;
-    a.out = q->out; a.status = q->status;
-    static_assert(sizeof(HseShared) <= 64 * 1024, "the staged CAs fit the static LDS of a workgroup");
-    DRGNN_EMU_ONLY(std::unique_ptr<HseShared> lds(new HseShared);)
-    DRGNN_LAUNCH(k_hse_residues, grid1(NT), stream, hse_tile(a, (int)bx, *lds), a);
-    return 0;
-}
-
-// ---- the builder's output packed into a resident set's arrays (drgnn_pack.h) --------------------------
-DRGNN_CAPACITY(drgnn_pack_capacity, PK_FCAP, PK_TCAP, PK_MAX_COMPLEXES)
-
-int drgnn_iface_pack(const drgnn_pack_request* q, void* stream) {
-    if (!q || !q->node_ptr || !q->edge_ptr || !q->iedge_ptr) return DRGNN_E_ARG;
-    const int64_t M = q->n_complexes, N = q->n_nodes, E = q->n_edges, Ei = q->n_iedges, R = q->n_residues, NB = q->n_rows;
-    const int64_t F = q->n_cols, W = q->res_width, Wt = q->type_width;
-    if (M < 0 || N < 0 || E < 0 || Ei < 0 || R < 0 || NB < 0 || F < 0 || W < 0 || Wt < 0) return DRGNN_E_ARG;
-    if (N > INT32_MAX || E > INT32_MAX / 2 || Ei > INT32_MAX / 2) return DRGNN_E_ARG;
-    if (q->edge_mode < 0 || q->edge_mode > 1) return DRGNN_E_ARG;
-    if (M > PK_MAX_COMPLEXES || F > PK_FCAP || Wt > PK_TCAP) return DRGNN_E_CAPACITY;
-    if (q->x) {
-        if (F < 1 || !q->cols || !q->host_cols) return DRGNN_E_ARG;
-        if (N * F > INT32_MAX) return DRGNN_E_CAPACITY;
-        const int64_t width[PK_NSRC] = {Wt, 3, 1, 3, 3, W, 1};
-        for (int64_t f = 0; f < F; ++f) {
-            const int32_t src = q->host_cols[2 * f], c = q->host_cols[2 * f + 1];
-            if (src < 0 || src >= PK_NSRC || c < 0 || c >= width[src]) return DRGNN_E_ARG;
-            if (src == PK_TYPE && !q->type_table) return DRGNN_E_ARG;
-            if (src == PK_RES && (!q->res_feat || NB < 1 || R % NB != 0)) return DRGNN_E_ARG;
-            if (N > 0) {                                               // (an empty batch has no arrays)
-                const void* need = src == PK_TYPE ? (const void*)q->type : src == PK_POS ? (const void*)q->pos :
-                                   src == PK_CHAIN ? (const void*)q->chain : src == PK_BSA ? (const void*)q->bsa :
-                                   src == PK_HSE ? (const void*)q->hse : src == PK_DEPTH ? (const void*)q->depth :
-                                   (const void*)q->node_residue;
-                if (!need) return DRGNN_E_ARG;
-            }
-        }
-    }
-    if (E > 0 && (q->edge_index_out || q->edge_attr) && !q->edge_index) return DRGNN_E_ARG;
-    if (E > 0 && q->edge_attr && !q->dist) return DRGNN_E_ARG;
-    if (Ei > 0 && q->internal_edge_index_out && !q->internal_edge_index) return DRGNN_E_ARG;
-    if (M == 0 || (N == 0 && E == 0 && Ei == 0)) return 0;
-    PackArgs a;
-    memset(&a, 0, sizeof(a));
-    a.node_ptr = q->node_ptr; a.edge_ptr = q->edge_ptr; a.iedge_ptr = q->iedge_ptr;
-    a.node_residue = q->node_residue; a.chain = q->chain; a.type = q->type; a.pos = q->pos;
-    a.edge_index = q->edge_index; a.dist = q->dist; a.iedge_index = q->internal_edge_index;
-    a.bsa = q->bsa; a.hse = q->hse; a.depth = q->depth; a.res_feat = q->res_feat; a.type_table = q->type_table; a.cols = q->cols;
-    a.n_rows = (int)std::max<int64_t>(NB, 1); a.W = (int)W; a.Wt = (int)Wt; a.F = (int)F; a.edge_mode = q->edge_mode;
-    a.N = (int)N; a.E = (int)E; a.Ei = (int)Ei;
-    a.x = q->x; a.edge_index_out = q->edge_index_out; a.edge_attr = q->edge_attr;
-    a.iedge_index_out = q->internal_edge_index_out; a.batch = q->batch;
-    DRGNN_EMU_ONLY(std::unique_ptr<PackShared> lds(new PackShared);)
-    DRGNN_LAUNCH(k_iface_pack, grid1(M, PK_NT), stream, pack_block(a, (int)bx, *lds), a);
-    return 0;
-}
-
-// ---- residue depth (drgnn_depth.h) -------------------------------------------------------------------
-DRGNN_CAPACITY(drgnn_depth_capacity, DP_DOTS_CAP, DP_CX_DOTS_CAP, DP_MAX_GRID)
-
-// the workspace's arrays, one after the other, each a multiple of 8 bytes: mask, pos, id, label, size, cnt, ptr, cx_nd,
-// cx_outer; offsets[9] is the size
-static int depth_layout(int64_t T, int64_t M, int64_t n_dots, int64_t* off) {
-    if (T < 0 || M < 0 || n_dots < 1 || n_dots > DP_DOTS_CAP || T > INT32_MAX / 3 || M > INT32_MAX) return -1;
-    const int64_t W = (n_dots + 63) / 64, D = T * n_dots;
-    const int64_t i32D = (4 * D + 7) / 8 * 8, i32T = (4 * T + 7) / 8 * 8, i32M = (4 * M + 7) / 8 * 8;
-    const int64_t sizes[9] = {8 * T * W, 24 * D, i32D, i32D, i32D, i32T, i32T, i32M, i32M};
-    off[0] = 0;
-    for (int j = 0; j < 9; ++j) off[j + 1] = off[j] + sizes[j];
-    return 0;
-}
-
-int64_t drgnn_depth_workspace(int64_t n_atoms, int64_t n_complexes, int32_t n_dots, int64_t* offsets) {
-    int64_t off[10];
-    if (depth_layout(n_atoms, n_complexes, n_dots, off) != 0) return -1;
-    if (offsets) memcpy(offsets, off, sizeof(off));
-    return off[9];
-}
-
-int drgnn_depth_residues(const drgnn_depth_request* q, void* stream) {
-    if (int rc = residue_request_check(q, INT32_MAX)) return rc;
-    const int64_t T = q->n_atoms, M = q->n_complexes, K = q->n_targets, NR = q->n_radii;
-    if (NR < 0 || (T > 0 && (!q->radii || NR < 1 || T % NR != 0))) return DRGNN_E_ARG;
-    if (q->n_dots < 1 || !q->dots || !(q->probe > 0.0) || !(q->probe < 1.0e150) || !(q->link >= 0.0) || !(q->link < 1.0e150) ||
-        q->components < 0 || q->components > 1 || q->phases < 0 || q->phases > 7)
-        return DRGNN_E_ARG;
-    if (q->n_dots > DP_DOTS_CAP || K > DP_MAX_GRID || M > DP_MAX_GRID || T / DRGNN_NWAVES >= DP_MAX_GRID) return DRGNN_E_CAPACITY;
-    if (int rc = residue_tables_check(q, nullptr)) return rc;
-    int64_t off[10];
-    if (depth_layout(T, M, q->n_dots, off) != 0) return DRGNN_E_ARG;
-    int ph = q->phases == 0 ? 7 : q->phases;
-    if (K == 0) ph = q->phases == 0 ? 0 : ph & ~4;                      // (the whole call without a target: nothing to do)
-    if (M == 0) ph = 0;
-    if (ph == 0) return 0;
-    if (int rc = workspace_check(q->workspace, q->workspace_bytes, off[9], 8)) return rc;
-    DepthArgs a;
-    memset(&a, 0, sizeof(a));
-    a.xyz = q->xyz; a.atom_ptr = q->atom_ptr; a.res_ptr = q->res_ptr; a.rad = q->radii; a.dots = q->dots;
-    a.tgt_res = q->target_res; a.tgt_cx = q->target_complex;
-    a.n_atoms = (int)T; a.n_cx = (int)M; a.n_radii = (int)NR; a.n_dots = q->n_dots; a.words = (q->n_dots + 63) / 64;
-    a.all = q->components;
-    a.probe = q->probe; a.link = q->link; a.link2 = q->link * q->link;
-    char* w = (char*)q->workspace;
-    a.mask = (unsigned long long*)(w + off[0]); a.pos = (double*)(w + off[1]); a.id = (int32_t*)(w + off[2]);
-    a.label = (int32_t*)(w + off[3]); a.size = (int32_t*)(w + off[4]); a.cnt = (int32_t*)(w + off[5]);
-    a.ptr = (int32_t*)(w + off[6]); a.cx_nd = (int32_t*)(w + off[7]); a.cx_outer = (int32_t*)(w + off[8]);
-    a.out = q->out; a.status = q->status;
-#ifdef DRGNN_EMU   // the emulation's workgroup is one "wave": its tile is an atom, the device's DRGNN_NWAVES atoms
-    const int64_t tiles = T;
-#else
-    const int64_t tiles = (T + DRGNN_NWAVES - 1) / DRGNN_NWAVES;
-#endif
-    DRGNN_EMU_ONLY(std::unique_ptr<DepthShared> lds(new DepthShared);)
-    if (ph & 1) DRGNN_LAUNCH(k_depth_dots, grid1(tiles), stream, depth_dots_tile(a, bx), a);
-    if (ph & 2) DRGNN_LAUNCH(k_depth_components, grid1(M), stream, depth_components(a, (int)bx, *lds), a);
-    if (ph & 4) DRGNN_LAUNCH(k_depth_residues, grid1(K), stream, depth_residue(a, bx, *lds), a);
-    return 0;
-}
-
-// ---- clustering of poses by their fraction of common contacts (drgnn_fcc.h) --------------------------
-DRGNN_CAPACITY(drgnn_fcc_capacity, FC_RCAP, FC_PCAP, PC_CCAP)
-
-int drgnn_pose_contacts(const drgnn_pose_contacts_request* q, void* stream) {
-    if (!q || !q->host_atom_ptr) return DRGNN_E_ARG;
-    const int64_t M = q->n_poses, T = q->n_atoms, R = q->n_residues, A = q->n_chain_a;
-    if (M < 0 || T < 0 || R < 0 || A < 0 || A > R || M > INT32_MAX || T > INT32_MAX / 3) return DRGNN_E_ARG;
-    if (!(q->cutoff > 0.0) || !(q->cutoff < 1.0e18)) return DRGNN_E_ARG;              // (its square is a finite fp32)
-    if (!q->atom_ptr || (M > 0 && !q->n_contacts) || (M > 0 && T > 0 && !q->xyz)) return DRGNN_E_ARG;
-    if (R > FC_RCAP) return DRGNN_E_CAPACITY;
-    const int64_t WB = (R - A + 63) / 64;
-    if (M > 0 && A * WB > 0 && !q->bits) return DRGNN_E_ARG;
-    const int32_t* ap = q->host_atom_ptr;
-    if (!ragged_check(ap, nullptr, nullptr, T, R, 0)) return DRGNN_E_ARG;
-    if (M == 0) return 0;
-    FccContactArgs a;
-    memset(&a, 0, sizeof(a));
-    a.xyz = q->xyz; a.atom_ptr = q->atom_ptr; a.n_atoms = (int)T; a.n_res = (int)R; a.n_a = (int)A;
-    a.cut = (float)q->cutoff; a.cut2 = (float)(q->cutoff * q->cutoff);
-    a.bits = (pc_word*)q->bits; a.n_contacts = q->n_contacts;
-    static_assert(sizeof(FccContactShared) <= 64 * 1024, "the spheres fit the static LDS of a workgroup");
-    DRGNN_EMU_ONLY(std::unique_ptr<FccContactShared> lds(new FccContactShared);)
-    DRGNN_LAUNCH(k_fcc_contacts, grid1(M), stream, fc_pose(a, bx, *lds), a);
-    return 0;
-}
-
-int drgnn_pose_common(const drgnn_pose_common_request* q, void* stream) {
-    if (!q) return DRGNN_E_ARG;
-    const int64_t Ma = q->n_a, Mb = q->n_b, W = q->n_words;
-    if (Ma < 0 || Mb < 0 || W < 0 || W > INT32_MAX) return DRGNN_E_ARG;
-    if (Ma > 0 && Mb > 0 && (!q->common || (W > 0 && (!q->bits_a || !q->bits_b)))) return DRGNN_E_ARG;
-    if (Ma > FC_PCAP || Mb > FC_PCAP) return DRGNN_E_CAPACITY;
-    if (Ma == 0 || Mb == 0) return 0;
-    FccCommonArgs a;
-    memset(&a, 0, sizeof(a));
-    a.a = (const pc_word*)q->bits_a; a.b = (const pc_word*)q->bits_b; a.n_a = (int)Ma; a.n_b = (int)Mb; a.n_words = W;
-    a.common = q->common;
-    const int ti = (int)((Ma + FC_TILE - 1) / FC_TILE), tj = (int)((Mb + FC_TILE - 1) / FC_TILE);
-    static_assert(FC_TILE * FC_TILE == DRGNN_NTHREADS, "one lane per pose pair of a tile");
-    static_assert((FC_PCAP + FC_TILE - 1) / FC_TILE <= 65535, "the tiles of a side fit the grid's y");
-    DRGNN_EMU_ONLY(std::unique_ptr<FccCommonShared> lds(new FccCommonShared);)
-    DRGNN_LAUNCH(k_fcc_common, grid2(tj, ti), stream, fc_common(a, (int)by, (int)bx, *lds), a);
-    return 0;
-}
-
-int drgnn_pose_cluster(const drgnn_pose_cluster_request* q, void* stream) {
-    if (!q) return DRGNN_E_ARG;
-    if (!(q->cutoff_fcc > 0.0) || !(q->cutoff_fcc <= 1.0) || !(q->cutoff_reverse > 0.0) || !(q->cutoff_reverse <= 1.0))
-        return DRGNN_E_ARG;
-    if (q->n_poses > 0 && (!q->common || !q->n_contacts)) return DRGNN_E_ARG;
-    FccRule rule;
-    memset(&rule, 0, sizeof(rule));
-    rule.common = q->common; rule.n_contacts = q->n_contacts; rule.cut_fwd = q->cutoff_fcc; rule.cut_rev = q->cutoff_reverse;
-    return pose_cluster_run(rule, q, DRGNN_KERNEL(k_fcc_relation), stream);
-}
-
-// ---- contact consensus of poses (drgnn_consensus.h) ----------------------------------------------------
-DRGNN_CAPACITY(drgnn_consensus_capacity, FC_RCAP, CS_GCAP, CS_ECAP, CS_NCAP, CS_PCAP)
-
-// the counts shared by the three calls: 0, or the error
-static int cons_shape(int64_t nA, int64_t nB, int64_t G) {
-    if (nA < 0 || nB < 0 || G < 0) return DRGNN_E_ARG;
-    if (nA + nB > FC_RCAP || G > CS_GCAP || G * nA * nB > CS_ECAP) return DRGNN_E_CAPACITY;      // (the product is below 2^38)
-    return 0;
-}
-
-int drgnn_pose_contact_counts(const drgnn_contact_counts_request* q, void* stream) {
-    if (!q || !q->host_group_ptr) return DRGNN_E_ARG;
-    const int64_t M = q->n_poses, nA = q->n_chain_a, nB = q->n_chain_b, G = q->n_groups, L = q->n_listed;
-    if (M < 0 || L < 0) return DRGNN_E_ARG;
-    if (int e = cons_shape(nA, nB, G)) return e;
-    if (M > CS_PCAP || L > CS_PCAP) return DRGNN_E_CAPACITY;
-    const int64_t WB = (nB + 63) / 64;
-    if (!q->group_ptr || (L > 0 && (!q->order || !q->host_order))) return DRGNN_E_ARG;
-    if ((L > 0 && nA * WB > 0 && !q->bits) || (G * nA * nB > 0 && !q->counts) || (G * (nA + nB) > 0 && !q->residues)) return DRGNN_E_ARG;
-    const int32_t* gp = q->host_group_ptr;
-    if (gp[0] != 0 || gp[G] != L) return DRGNN_E_ARG;
-    for (int64_t g = 0; g < G; ++g)
-        if (gp[g + 1] < gp[g]) return DRGNN_E_ARG;
-    for (int64_t p = 0; p < L; ++p)
-        if (q->host_order[p] < 0 || q->host_order[p] >= M) return DRGNN_E_ARG;
-    ConsCountArgs a;
-    memset(&a, 0, sizeof(a));
-    a.bits = (const pc_word*)q->bits; a.order = q->order; a.group_ptr = q->group_ptr; a.n_a = (int)nA; a.n_b = (int)nB;
-    a.n_groups = (int)G; a.n_listed = L; a.counts = q->counts; a.residues = q->residues;
-    const size_t count_bytes = (size_t)(G * nA * nB) * sizeof(int32_t), res_bytes = (size_t)(G * (nA + nB)) * sizeof(int32_t);
-    const int blocks = (int)std::min<int64_t>((L + DRGNN_NWAVES - 1) / DRGNN_NWAVES, CS_COUNT_WGS);
-    if (int rc = drgnn_clear(q->counts, count_bytes, stream)) return rc;
-    if (int rc = drgnn_clear(q->residues, res_bytes, stream)) return rc;
-    // (without residues a listed pose has no word to count: cs_count would write nothing)
-    if (nA + nB > 0) DRGNN_LAUNCH(k_cons_count, grid1(blocks), stream, cs_count(a, (int)bx, blocks), a);
-    return 0;
-}
-
-int drgnn_pose_consensus_numerators(const drgnn_consensus_numerators_request* q, void* stream) {
-    if (!q) return DRGNN_E_ARG;
-    const int64_t M = q->n_poses, nA = q->n_chain_a, nB = q->n_chain_b, G = q->n_groups;
-    if (M < 0) return DRGNN_E_ARG;
-    if (int e = cons_shape(nA, nB, G)) return e;
-    if (M > CS_NCAP) return DRGNN_E_CAPACITY;
-    const int64_t WB = (nB + 63) / 64;
-    if (M > 0 && (!q->row || !q->host_row || !q->numerators || (nA * WB > 0 && !q->bits) || (G * nA * nB > 0 && !q->counts))) return DRGNN_E_ARG;
-    for (int64_t m = 0; m < M; ++m)
-        if (q->host_row[m] < -1 || q->host_row[m] >= G) return DRGNN_E_ARG;
-    if (M == 0) return 0;
-    ConsNumerArgs a;
-    memset(&a, 0, sizeof(a));
-    a.bits = (const pc_word*)q->bits; a.counts = q->counts; a.row = q->row; a.n_a = (int)nA; a.n_b = (int)nB;
-    a.numerators = (long long*)q->numerators;
-    DRGNN_EMU_ONLY(std::unique_ptr<ConsNumerShared> lds(new ConsNumerShared);)
-    DRGNN_LAUNCH(k_cons_numer, grid1(M), stream, cs_numer(a, bx, *lds), a);
-    return 0;
-}
-
-int drgnn_pose_consensus_bits(const drgnn_consensus_bits_request* q, void* stream) {
-    if (!q) return DRGNN_E_ARG;
-    const int64_t nA = q->n_chain_a, nB = q->n_chain_b, G = q->n_groups;
-    if (int e = cons_shape(nA, nB, G)) return e;
-    const int64_t WB = (nB + 63) / 64;
-    if (G > 0 && (!q->min_count || !q->host_min_count || !q->n_contacts || (nA * WB > 0 && !q->bits) || (nA * nB > 0 && !q->counts))) return DRGNN_E_ARG;
-    for (int64_t g = 0; g < G; ++g)
-        if (q->host_min_count[g] < 1) return DRGNN_E_ARG;
-    if (G == 0) return 0;
-    ConsBitsArgs a;
-    memset(&a, 0, sizeof(a));
-    a.counts = q->counts; a.min_count = q->min_count; a.n_a = (int)nA; a.n_b = (int)nB;
-    a.bits = (pc_word*)q->bits; a.n_contacts = q->n_contacts;
-    const int blocks = (int)((nA * WB + CS_BW - 1) / CS_BW);
-    static_assert(CS_GCAP <= 65535, "the groups fit the grid's y");
-    if (int rc = drgnn_clear(q->n_contacts, (size_t)G * sizeof(int32_t), stream)) return rc;
-    DRGNN_LAUNCH(k_cons_bits, grid2(blocks, G), stream, cs_bits(a, (int)by, (int)bx), a);
-    return 0;
-}
-
-// ---- pairwise pose RMSD and RMSD clustering of poses (drgnn_rmsd.h) ----------------------------------
-DRGNN_CAPACITY(drgnn_rmsd_capacity, RM_PCAP, PC_CCAP)
-
-// records of side a, of side b; off[2] is the size
-static int rmsd_layout(int64_t Ma, int64_t Mb, int64_t nF, int64_t nR, int64_t* off) {
-    if (Ma < 0 || Mb < 0 || nF < 0 || nR < 0 || Ma > RM_PCAP || Mb > RM_PCAP || nF > INT32_MAX / 8 || nR > INT32_MAX / 8) return -1;
-    const int64_t L = 3 * (nF + nR) + 2;
-    off[0] = 0; off[1] = 8 * L * Ma; off[2] = 8 * L * (Ma + Mb);
-    return 0;
-}
-
-int64_t drgnn_rmsd_workspace(int64_t n_a, int64_t n_b, int64_t n_fit, int64_t n_rms, int64_t* offsets) {
-    int64_t off[3];
-    if (rmsd_layout(n_a, n_b, n_fit, n_rms, off) != 0) return -1;
-    if (offsets) memcpy(offsets, off, sizeof(off));
-    return off[2];
-}
-
-int drgnn_pose_rmsd(const drgnn_pose_rmsd_request* q, void* stream) {
-    if (!q) return DRGNN_E_ARG;
-    const int64_t Ma = q->n_a, Mb = q->n_b, T = q->n_atoms, nF = q->n_fit, nR = q->n_rms;
-    if (Ma < 0 || Mb < 0 || T < 0 || nF < 0 || nR < 1 || T > INT32_MAX / 3 || nF > INT32_MAX / 8 || nR > INT32_MAX / 8) return DRGNN_E_ARG;
-    if (nF == 1 || nF == 2 || q->phases < 0 || q->phases > 3) return DRGNN_E_ARG;
-    if (!q->rms_idx || !q->host_rms_idx || (nF > 0) != (q->fit_idx != nullptr) || (nF > 0) != (q->host_fit_idx != nullptr)) return DRGNN_E_ARG;
-    for (int64_t k = 0; k < nR; ++k)
-        if (q->host_rms_idx[k] < 0 || q->host_rms_idx[k] >= T) return DRGNN_E_ARG;
-    for (int64_t k = 0; k < nF; ++k)
-        if (q->host_fit_idx[k] < 0 || q->host_fit_idx[k] >= T) return DRGNN_E_ARG;
-    if ((Ma > 0 && !q->xyz_a) || (Mb > 0 && !q->xyz_b) || (Ma > 0 && Mb > 0 && !q->d)) return DRGNN_E_ARG;
-    if (Ma > RM_PCAP || Mb > RM_PCAP) return DRGNN_E_CAPACITY;
-    if (Ma == 0 || Mb == 0) return 0;
-    int64_t off[3];
-    if (rmsd_layout(Ma, Mb, nF, nR, off) != 0) return DRGNN_E_ARG;
-    if (int rc = workspace_check(q->workspace, q->workspace_bytes, off[2], 8)) return rc;
-    const int ph = q->phases == 0 ? 3 : q->phases;
-    RmsdArgs a;
-    memset(&a, 0, sizeof(a));
-    a.xyz_a = q->xyz_a; a.xyz_b = q->xyz_b; a.fit_idx = q->fit_idx; a.rms_idx = q->rms_idx;
-    a.n_atoms = (int)T; a.n_fit = (int)nF; a.n_rms = (int)nR; a.n_a = (int)Ma; a.n_b = (int)Mb;
-    a.same = q->xyz_a == q->xyz_b && Ma == Mb;
-    a.rec_a = (double*)((char*)q->workspace + off[0]);
-    a.rec_b = a.same ? a.rec_a : (double*)((char*)q->workspace + off[1]);
-    a.d = q->d;
-    const int ti = (int)((Ma + RM_TILE - 1) / RM_TILE), tj = (int)((Mb + RM_TILE - 1) / RM_TILE);
-    static_assert(RM_TILE * RM_TILE == DRGNN_NTHREADS, "one lane per pose pair of a tile");
-    static_assert(RM_K % 2 == 0 && sizeof(RmsdPairShared) <= 64 * 1024, "odd rows; the staged atoms fit the static LDS of a workgroup");
-    static_assert((RM_PCAP + RM_TILE - 1) / RM_TILE <= 65535, "the tiles of a side fit the grid's y");
-    if (ph & 1) {
-        DRGNN_EMU_ONLY(std::unique_ptr<RmsdPrepShared> lds(new RmsdPrepShared);)
-        DRGNN_LAUNCH(k_rmsd_prepare, grid1(Ma), stream, rm_prepare(a, 0, bx, *lds), a, 0);
-        if (!a.same) DRGNN_LAUNCH(k_rmsd_prepare, grid1(Mb), stream, rm_prepare(a, 1, bx, *lds), a, 1);
-    }
-    if (ph & 2) {
-        DRGNN_EMU_ONLY(std::unique_ptr<RmsdPairShared> lds(new RmsdPairShared);)
-        DRGNN_LAUNCH(k_rmsd_pairs, grid2(tj, ti), stream, rm_pairs(a, (int)by, (int)bx, *lds), a);
-    }
-    return 0;
-}
-
-int drgnn_pose_cluster_dist(const drgnn_pose_cluster_dist_request* q, void* stream) {
-    if (!q) return DRGNN_E_ARG;
-    if (!(q->cutoff > 0.0) || !(q->cutoff < HUGE_VAL)) return DRGNN_E_ARG;
-    if (q->n_poses > 0 && !q->d) return DRGNN_E_ARG;
-    DistRule rule;
-    memset(&rule, 0, sizeof(rule));
-    rule.d = q->d; rule.cutoff = q->cutoff;
-    return pose_cluster_run(rule, q, DRGNN_KERNEL(k_rmsd_relation), stream);
-}
-
-// ---- evaluation scores (drgnn_metrics.h) ---------------------------------------------------------
-int64_t drgnn_metrics_workspace_bytes(int64_t n) {
-    if (n < 0 || n > INT32_MAX) return -1;
-    int64_t off[9];
-    mt_layout(n, off);
-    return off[8];
-}
-
-// stable ascending LSD sort of a.keys[0] (payload a.vals[0] when set): MT_PASSES digits, the result back in buffer 0
-static int mt_sort(MetricsArgs& a, void* stream) {
-    DRGNN_EMU_ONLY(std::unique_ptr<MtHistShared> hs(new MtHistShared); std::unique_ptr<MtScanShared> ss(new MtScanShared);
-                   std::unique_ptr<MtScatterShared> xs(new MtScatterShared);)
-    const Grid tiles = grid1(a.n_tiles, MT_NT);
-    for (int pass = 0; pass < MT_PASSES; ++pass) {
-        DRGNN_LAUNCH(k_mt_hist, tiles, stream, mt_hist_block(a, (int)bx, pass, *hs), a, pass);
-        DRGNN_LAUNCH(k_mt_scan, grid1(1, MT_SNT), stream, mt_exscan_block<int32_t>(a.hist, (int64_t)MT_RADIX * a.n_tiles, *ss), a);
-        DRGNN_LAUNCH(k_mt_scatter, tiles, stream, mt_scatter_block(a, (int)bx, pass, *xs), a, pass);
-    }
-    return 0;
-}
-
-int drgnn_metrics(const double* pred, const double* y, int64_t n, int32_t what, int32_t direction, double threshold,
-                  int32_t label_lo, int32_t n_labels, void* workspace, int64_t workspace_bytes, int64_t* counts,
-                  double* scores, int32_t* order, int64_t* hits, void* stream) {
-    if (n < 1 || n > INT32_MAX || !pred || !y || !workspace || !counts || !scores) return DRGNN_E_ARG;
-    if ((what & ~(DRGNN_METRICS_COUNTS | DRGNN_METRICS_REGRESSION | DRGNN_METRICS_RANKING)) != 0) return DRGNN_E_ARG;
-    if ((direction != 1 && direction != -1) || n_labels < 0 || n_labels > MT_KMAX) return DRGNN_E_ARG;
-    if ((what & DRGNN_METRICS_RANKING) && (!order || !hits)) return DRGNN_E_ARG;
-    if (workspace_bytes < drgnn_metrics_workspace_bytes(n)) return DRGNN_E_CAPACITY;
-    if (n_labels > 0 && (label_lo < -(1 << 20) || label_lo > (1 << 20))) return DRGNN_E_ARG;
-    int64_t off[9];
-    mt_layout(n, off);
-    char* ws = (char*)workspace;
-    MetricsArgs a;
-    a.pred = pred; a.y = y; a.n = n; a.thr = threshold; a.dir = direction; a.lo = label_lo; a.K = n_labels;
-    a.G = (int)((n + 8 * MT_NT - 1) / (8 * MT_NT));
-    if (a.G > MT_RED_WGS) a.G = MT_RED_WGS;
-    a.n_tiles = (int)mt_tiles(n);
-    a.keys[0] = (unsigned long long*)(ws + off[0]); a.keys[1] = (unsigned long long*)(ws + off[1]);
-    a.vals[0] = order; a.vals[1] = (int32_t*)(ws + off[2]);
-    a.hist = (int32_t*)(ws + off[3]);
-    a.fpart = (double*)(ws + off[4]); a.ipart = (long long*)(ws + off[5]);
-    a.tsum = (long long*)(ws + off[6]); a.ssum = (long long*)(ws + off[7]);
-    a.counts = (long long*)counts; a.scores = scores; a.hits = (long long*)hits;
-    MetricsArgs r = a;                  // the |r| sort: keys only
-    r.vals[0] = r.vals[1] = nullptr;
-    DRGNN_EMU_ONLY(std::unique_ptr<MtRedShared> rs(new MtRedShared); std::unique_ptr<MtScanShared> ss(new MtScanShared);
-                   std::unique_ptr<MtHitShared> hs(new MtHitShared);)
-    const Grid parts = grid1(a.G, MT_NT), tiles = grid1(a.n_tiles, MT_NT), one = grid1(1, MT_NT);
-    int rc;
-    if (what & (DRGNN_METRICS_COUNTS | DRGNN_METRICS_REGRESSION)) {
-        DRGNN_LAUNCH(k_mt_reduce, parts, stream, mt_reduce_block(a, (int)bx, 0, *rs), a, 0);
-        DRGNN_LAUNCH(k_mt_combine, one, stream, mt_combine_block(a, 0), a, 0);
-    }
-    if (what & DRGNN_METRICS_REGRESSION) {
-        DRGNN_LAUNCH(k_mt_reduce, parts, stream, mt_reduce_block(a, (int)bx, 1, *rs), a, 1);
-        DRGNN_LAUNCH(k_mt_combine, one, stream, mt_combine_block(a, 1), a, 1);
-        DRGNN_LAUNCH(k_mt_keys, tiles, stream, mt_keys_block(r, (int)bx, 1), r, 1);
-        if ((rc = mt_sort(r, stream))) return rc;
-        DRGNN_LAUNCH(k_mt_median, grid1(1, 64), stream, mt_median(r), r);
-    }
-    if (what & DRGNN_METRICS_RANKING) {
-        DRGNN_LAUNCH(k_mt_keys, tiles, stream, mt_keys_block(a, (int)bx, 0), a, 0);
-        if ((rc = mt_sort(a, stream))) return rc;
-        DRGNN_LAUNCH(k_mt_hit, tiles, stream, mt_hit_block(a, (int)bx, 0, *hs), a, 0);
-        DRGNN_LAUNCH(k_mt_hit_scan, grid1(1, MT_SNT), stream, mt_hit_scan_block(a, *ss), a);
-        DRGNN_LAUNCH(k_mt_hit, tiles, stream, mt_hit_block(a, (int)bx, 1, *hs), a, 1);
-    }
     return 0;
 }
 
@@ -2953,3 +2074,11 @@ static int train_epoch_impl(const drgnn_epoch_plan* p, const drgnn_optim* optim,
 }
 
 }  // extern "C"
+
+#ifdef DRGNN_EMU      // (the emulation is built from this file alone, in one g++ call: the feature units are part of it)
+#include "drgnn_capi_layers.hip"
+#include "drgnn_capi_iface.hip"
+#include "drgnn_capi_residues.hip"
+#include "drgnn_capi_poses.hip"
+#include "drgnn_capi_metrics.hip"
+#endif

@@ -1,28 +1,16 @@
-// drgnn_kernels.h -- launch descriptions, per-workgroup drivers and the __global__ kernels of the library.
+// drgnn_kernels.h -- launch descriptions, per-workgroup drivers and the __global__ kernels of the training path: topology
+// builder, launch pair, fused step (single model, ensemble, cohort), head, collation and the update kernels.
 //
-// Included by drgnn_capi.hip (which defines DRGNN_KERNELS_MAIN: it owns the plain kernels and the host side) and by
-// drgnn_step_tu.hip, compiled once per kind of net: the instantiations of the fused step kernel are by far the largest
-// part of the build, so three more translation units compile them in parallel (make -j).
+// Included by drgnn_capi.hip (which defines DRGNN_KERNELS_MAIN: it owns the training path's plain kernels and its host side) and
+// by drgnn_step_tu.hip, compiled once per (family, padded feature width) of the fused step kernel: those instantiations are by far
+// the largest part of the build, so a translation unit each compiles them in parallel (make -j; drgnn_step_af.h).  The kernels
+// of a feature subsystem are not here: drgnn_capi_<subsystem>.hip defines the wrappers it launches, over the block functions of
+// the drgnn_<subsystem>.h it includes.
 #pragma once
 #include "drgnn_head.h"
 #include "drgnn_step.h"
 #include "drgnn_step2.h"
 #include "drgnn_step3.h"
-#include "drgnn_layers.h"
-#include "drgnn_mcl.h"
-#include "drgnn_louvain.h"
-#include "drgnn_iface.h"
-#include "drgnn_score.h"
-#include "drgnn_bsa.h"
-#include "drgnn_hse.h"
-#include "drgnn_depth.h"
-#include "drgnn_posecluster.h"
-#include "drgnn_fcc.h"
-#include "drgnn_consensus.h"
-#include "drgnn_lddt.h"
-#include "drgnn_rmsd.h"
-#include "drgnn_pack.h"
-#include "drgnn_metrics.h"
 #include "drgnn_collate.h"
 #include "drgnn_p2p.h"
 
@@ -669,6 +657,7 @@ struct CohortStep {
     int64_t stride;
 };
 #ifndef DRGNN_EMU
+// DRGNN_KERNELS_MAIN (drgnn_capi.hip alone): the training path's kernels that are no templates, defined in that one unit
 #ifdef DRGNN_KERNELS_MAIN
 __global__ void __launch_bounds__(256) k_ptrs(PtrArgs a) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -944,163 +933,6 @@ __global__ void __launch_bounds__(DRGNN_NTHREADS) k_step2_cohort(StepCoLaunch C_
     step2_block<KIND, XF, true, CLS, 1, true, XG>(C.step, a, g, smem_c2);
 }
 #ifdef DRGNN_KERNELS_MAIN
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_conv_gemm(ConvLayerArgs a) { conv_gemm_block(a, blockIdx.x); }
-__global__ void __launch_bounds__(256) k_conv_aggregate(ConvLayerArgs a) {
-    conv_aggregate_item(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
-}
-__global__ void __launch_bounds__(256) k_conv_bwd_du(ConvLayerArgs a) {
-    conv_bwd_du_item(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
-}
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_conv_bwd_dw(ConvLayerArgs a) { conv_bwd_dw_block(a, blockIdx.x); }
-__global__ void __launch_bounds__(256) k_conv_reduce(ConvReduceArgs a) {
-    conv_reduce_item(a, blockIdx.x * blockDim.x + threadIdx.x);
-}
-__global__ void __launch_bounds__(256) k_conv_bwd_dx(ConvLayerArgs a) {
-    conv_bwd_dx_item(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
-}
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_segpool_fwd(SegPoolArgs a) { segpool_fwd_block(a, blockIdx.x); }
-__global__ void __launch_bounds__(256) k_segmax_bwd(SegPoolArgs a, int64_t n_items, int64_t n_nodes) {
-    segmax_bwd_item(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, n_items, n_nodes);
-}
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_edge_export(EdgeExportArgs a) { edge_export_block(a, blockIdx.x); }
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_cluster_max(ClusterOffsetArgs a) {
-    __shared__ long long mm[2];
-    cluster_max_block(a, blockIdx.x, mm);
-}
-__global__ void k_cluster_scan(ClusterOffsetArgs a) { cluster_scan_single(a); }
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_cluster_add(ClusterOffsetArgs a) { cluster_add_block(a, blockIdx.x); }
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_mcl(MclArgs a) {
-    __shared__ double red[DRGNN_NTHREADS];
-    __shared__ int flag[2];
-    mcl_graph(a, blockIdx.x, flag, red);
-}
-__global__ void __launch_bounds__(LV_W) k_louvain(LouvainArgs a) {
-    extern __shared__ __attribute__((aligned(16))) int smem_lv[];
-    louvain_graph(a, blockIdx.x, smem_lv);
-}
-// interface graphs from atom coordinates (drgnn_iface.h)
-__global__ void __launch_bounds__(IF_NT) k_iface_sphere(IfaceArgs a) {
-    const int r = blockIdx.x * IF_NT + threadIdx.x;
-    if (r < a.n_residues) iface_sphere_item(a, r);
-}
-__global__ void __launch_bounds__(IF_NT) k_iface_pairs(IfaceArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float smem_if[];
-    iface_pairs_block(a, blockIdx.y, blockIdx.x, smem_if);
-}
-__global__ void __launch_bounds__(IF_NT) k_iface_rows(IfaceArgs a, int write) { iface_rows_block(a, blockIdx.y, blockIdx.x, write != 0); }
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_iface_scan(IfaceArgs a) {
-    __shared__ int part[DRGNN_NTHREADS + 1];
-    iface_scan_block(a, blockIdx.x, part);
-}
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_iface_offsets(IfaceArgs a) {
-    __shared__ int part[DRGNN_NTHREADS + 1];
-    iface_offsets_block(a, part);
-}
-// docking scores (drgnn_score.h): one workgroup per pose
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_dock_scores(ScoreArgs a) {
-    __shared__ double smem_sc[SC_LDS_BYTES / 8];
-    score_pose(a, (int64_t)blockIdx.x, smem_sc);
-}
-// buried surface area (drgnn_bsa.h): one workgroup per target residue
-// (8 waves per SIMD: two workgroups per CU; the fp64 path of nearly tangent circles must not cost the others their registers)
-__global__ void __launch_bounds__(DRGNN_NTHREADS, 8) k_bsa_residues(BsaArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem_bs[];
-    bsa_residue(a, (int64_t)blockIdx.x, *(BsaShared*)smem_bs);
-}
-// half-sphere exposure (drgnn_hse.h): one workgroup per tile of targets of one complex
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_hse_residues(HseArgs a) {
-    __shared__ HseShared smem_hs;
-    hse_tile(a, (int)blockIdx.x, smem_hs);
-}
-// residue depth (drgnn_depth.h): a wave per atom; one workgroup per complex; one workgroup per target residue
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_depth_dots(DepthArgs a) { depth_dots_tile(a, (int64_t)blockIdx.x); }
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_depth_components(DepthArgs a) {
-    __shared__ DepthShared smem_dp;
-    depth_components(a, (int)blockIdx.x, smem_dp);
-}
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_depth_residues(DepthArgs a) {
-    __shared__ DepthShared smem_dp;
-    depth_residue(a, (int64_t)blockIdx.x, smem_dp);
-}
-// fraction of common contacts (drgnn_fcc.h): one workgroup per pose; per tile of pose pairs; a wave per word of the
-// neighbour relation; ONE workgroup for the greedy clustering of either rule (drgnn_posecluster.h)
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_fcc_contacts(FccContactArgs a) {
-    __shared__ FccContactShared smem_fc;
-    fc_pose(a, (int64_t)blockIdx.x, smem_fc);
-}
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_fcc_common(FccCommonArgs a) {
-    __shared__ FccCommonShared smem_fm;
-    fc_common(a, (int)blockIdx.y, (int)blockIdx.x, smem_fm);
-}
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_fcc_relation(FccRule r, PoseClusterArgs a) { pc_relation(r, a, (int64_t)blockIdx.x); }
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_fcc_greedy(PoseClusterArgs a) {
-    __shared__ PoseGreedyShared smem_fg;
-    pc_greedy(a, smem_fg);
-}
-// contact consensus of poses (drgnn_consensus.h): a wave per list entry; one workgroup per pose; per CS_BW words of a group (the
-// group by y)
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_cons_count(ConsCountArgs a) { cs_count(a, (int)blockIdx.x, (int)gridDim.x); }
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_cons_numer(ConsNumerArgs a) {
-    __shared__ ConsNumerShared smem_cn;
-    cs_numer(a, (int64_t)blockIdx.x, smem_cn);
-}
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_cons_bits(ConsBitsArgs a) { cs_bits(a, (int)blockIdx.y, (int)blockIdx.x); }
-// lDDT of poses (drgnn_lddt.h): one workgroup per LD_RB residues (x) and PP poses (y); an item per word of counts
-template <int PP, int KT> __global__ void __launch_bounds__(DRGNN_NTHREADS) k_pose_lddt(LddtArgs a) {
-    __shared__ LddtShared smem_ld;
-    ld_block<PP, KT>(a, (int)blockIdx.x, a.m0 + (int64_t)blockIdx.y * PP, smem_ld);
-}
-__global__ void __launch_bounds__(256) k_lddt_halve(LddtArgs a) { ld_halve_item(a, a.m0 + (int64_t)blockIdx.x * 256 + threadIdx.x); }
-// pairwise pose RMSD (drgnn_rmsd.h): one workgroup per pose of one side; per tile of pose pairs; a wave per word of the
-// neighbour relation (the greedy clustering is k_fcc_greedy)
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_rmsd_prepare(RmsdArgs a, int side) {
-    __shared__ RmsdPrepShared smem_rp;
-    rm_prepare(a, side, (int64_t)blockIdx.x, smem_rp);
-}
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_rmsd_pairs(RmsdArgs a) {
-    __shared__ RmsdPairShared smem_rq;
-    rm_pairs(a, (int)blockIdx.y, (int)blockIdx.x, smem_rq);
-}
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_rmsd_relation(DistRule r, PoseClusterArgs a) { pc_relation(r, a, (int64_t)blockIdx.x); }
-// the builder's output packed into a resident set's arrays (drgnn_pack.h): one workgroup per complex
-__global__ void __launch_bounds__(PK_NT) k_iface_pack(PackArgs a) {
-    __shared__ PackShared smem_pk;
-    pack_block(a, (int)blockIdx.x, smem_pk);
-}
-// evaluation scores (drgnn_metrics.h)
-__global__ void __launch_bounds__(MT_NT) k_mt_reduce(MetricsArgs a, int centred) {
-    __shared__ MtRedShared s;
-    mt_reduce_block(a, blockIdx.x, centred, s);
-}
-__global__ void __launch_bounds__(MT_NT) k_mt_combine(MetricsArgs a, int centred) { mt_combine_block(a, centred); }
-__global__ void __launch_bounds__(MT_NT) k_mt_keys(MetricsArgs a, int absres) { mt_keys_block(a, blockIdx.x, absres); }
-__global__ void __launch_bounds__(MT_NT) k_mt_hist(MetricsArgs a, int pass) {
-    __shared__ MtHistShared s;
-    mt_hist_block(a, blockIdx.x, pass, s);
-}
-__global__ void __launch_bounds__(MT_SNT) k_mt_scan(MetricsArgs a) {
-    __shared__ MtScanShared s;
-    mt_exscan_block<int32_t>(a.hist, (int64_t)MT_RADIX * a.n_tiles, s);
-}
-__global__ void __launch_bounds__(MT_NT) k_mt_scatter(MetricsArgs a, int pass) {
-    __shared__ MtScatterShared s;
-    mt_scatter_block(a, blockIdx.x, pass, s);
-}
-__global__ void __launch_bounds__(64) k_mt_median(MetricsArgs a) {
-    if (threadIdx.x == 0) mt_median(a);
-}
-__global__ void __launch_bounds__(MT_NT) k_mt_hit(MetricsArgs a, int write) {
-    __shared__ MtHitShared s;
-    mt_hit_block(a, blockIdx.x, write, s);
-}
-__global__ void __launch_bounds__(MT_SNT) k_mt_hit_scan(MetricsArgs a) {
-    __shared__ MtScanShared s;
-    mt_hit_scan_block(a, s);
-}
-__global__ void __launch_bounds__(DRGNN_NTHREADS) k_graclus(GraclusArgs a) {
-    extern __shared__ __attribute__((aligned(16))) int smem_g[];
-    graclus_block(a, blockIdx.x, smem_g);
-}
 __global__ void __launch_bounds__(DRGNN_NTHREADS) k_batch_offsets(OffsetsArgs a) {
     extern __shared__ __attribute__((aligned(16))) int smem_o[];
     batch_offsets_block(a, blockIdx.x, smem_o + DRGNN_NTHREADS + 4, smem_o);

@@ -1,4 +1,5 @@
-// drgnn_launch.h -- the one launch form of drgnn_capi.hip's entry points, features and training path (included by that file alone).
+// drgnn_launch.h -- the one launch form of the entry points of the drgnn_capi*.hip units, features and training path (included
+// through drgnn_capi_common.h, by those units alone).
 //
 //     DRGNN_EMU_ONLY(std::unique_ptr<XShared> lds(new XShared);)
 //     DRGNN_LAUNCH(k_x, grid1(n_blocks), stream, x_block(a, bx, *lds), a);

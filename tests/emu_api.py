@@ -1,9 +1,10 @@
 """Loads the HOST-EMULATION build of the kernels (tests only).
 
-The emulation library is the product source (deeprank-gnn_amd/csrc/drgnn_capi.hip)
-compiled by g++ with -DDRGNN_EMU: every kernel launch becomes a loop over workgroups and
-work items on host memory (see csrc/drgnn_rt.h).  It lets the CPU suite check the kernels'
-index logic and arithmetic against the oracle without a GPU.  The package never loads it.
+The emulation library is the product source (deeprank-gnn_amd/csrc/drgnn_capi.hip, which
+in this build includes the drgnn_capi_<subsystem>.hip units next to it) compiled by g++
+with -DDRGNN_EMU: every kernel launch becomes a loop over workgroups and work items on
+host memory (see csrc/drgnn_rt.h).  It lets the CPU suite check the kernels' index logic
+and arithmetic against the oracle without a GPU.  The package never loads it.
 """
 import os
 import subprocess

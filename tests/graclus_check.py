@@ -86,7 +86,7 @@ def _properties(edge_index, labels, n):
         assert not (a in single and b in single)
 
 
-LDS_LIMIT = 160 * 1024          # DRGNN_LDS_LIMIT of csrc/drgnn_capi.hip: the largest carve drgnn_graclus accepts
+LDS_LIMIT = 160 * 1024          # DRGNN_LDS_LIMIT of csrc/drgnn_capi_common.h: the largest carve drgnn_graclus accepts
 
 
 def carve_bytes(n, e):
