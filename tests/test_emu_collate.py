@@ -82,3 +82,74 @@ def test_topology_from_the_resident_set_global_scratch_path():
     graphs.insert(1, big)
     assert emu().topology_lds_bytes(2500, int(big.edge_index.size(1))) > 160 * 1024
     check_set_topology(graphs, "cpu", api=emu(), need_weights=True, batch_size=4)
+
+
+# ---- beyond nine graphs: the cases of collate_cases.py, shared with tests/test_gpu_collate.py ---------------------------
+import collate_cases as CC
+
+
+@pytest.mark.parametrize("B", CC.SLOT_COUNTS)
+def test_collate_at_slot_count_edges(B):
+    CC.check_slot_counts(B, emu(), "cpu")
+
+
+@pytest.mark.parametrize("n_feat", CC.ROW_FEATS)
+def test_collate_row_copy_paths(n_feat):
+    CC.check_row_copies(n_feat, emu(), "cpu")
+
+
+@pytest.mark.parametrize("field", ["edge_attr", "y", "cluster1", "cluster0"])
+def test_collate_without_one_field(field):
+    CC.check_without(field, emu(), "cpu")
+
+
+def test_collate_int64_targets_and_replaced_targets():
+    CC.check_int64_targets(emu(), "cpu")
+
+
+@pytest.mark.parametrize("batch_size", CC.OFFSET_BATCH_SIZES)
+def test_batch_offsets(batch_size):
+    CC.check_batch_offsets(batch_size, emu(), "cpu")
+
+
+def test_batch_offsets_without_ids():
+    CC.check_batch_offsets_no_ids(emu(), "cpu")
+
+
+def test_batch_offsets_capacity():
+    CC.check_batch_offsets_capacity(emu(), "cpu")
+
+
+@pytest.mark.parametrize("need_weights", [False, True])
+@pytest.mark.parametrize("which,batch_size", [("tiny", 65), ("tiny", 1025), ("mixed", 65)])
+def test_topology_from_the_resident_set_at_slot_count_edges(which, batch_size, need_weights):
+    CC.check_topology(which, batch_size, need_weights, emu(), "cpu")
+
+
+@pytest.mark.parametrize("which", range(CC.N_OUTSIDE_LISTS))
+def test_collate_ids_outside_the_set(which):
+    CC.check_collate_outside_ids(which, emu(), "cpu")
+
+
+def test_batch_offsets_ids_outside_the_set():
+    CC.check_offsets_outside_ids(emu(), "cpu")
+
+
+def test_batch_offsets_ids_outside_the_declared_set():
+    CC.check_offsets_outside_declared_set(emu(), "cpu")
+
+
+def test_collate_refusals():
+    CC.check_collate_refusals(emu(), "cpu")
+
+
+def test_batch_offsets_refusals():
+    CC.check_offsets_refusals(emu(), "cpu")
+
+
+def test_upload_ids_out_of_range():
+    CC.check_upload_ids_range(emu(), "cpu")
+
+
+def test_resident_set_image_round_trip_mixed_set(tmp_path):
+    CC.check_image_round_trip(str(tmp_path / "set.npz"), emu(), "cpu")

@@ -54,3 +54,78 @@ def test_topology_from_the_resident_set(need_weights):
     check_set_topology(ragged_graphs(4, 6), "cuda", need_weights=need_weights, batch_size=4)
     check_set_topology(fixture_graphs(), "cuda", need_weights=need_weights, batch_size=3)
     check_set_topology([synth.make_graph(i) for i in range(96)], "cuda", need_weights=need_weights, batch_size=64)
+
+
+# ---- beyond nine graphs: the cases of collate_cases.py, shared with tests/test_emu_collate.py ---------------------------
+import collate_cases as CC
+
+
+@pytest.mark.parametrize("B", CC.SLOT_COUNTS)
+def test_collate_at_slot_count_edges(B):
+    CC.check_slot_counts(B, None, "cuda")
+
+
+@pytest.mark.parametrize("n_feat", CC.ROW_FEATS)
+def test_collate_row_copy_paths(n_feat):
+    CC.check_row_copies(n_feat, None, "cuda")
+
+
+@pytest.mark.parametrize("field", ["edge_attr", "y", "cluster1", "cluster0"])
+def test_collate_without_one_field(field):
+    CC.check_without(field, None, "cuda")
+
+
+def test_collate_int64_targets_and_replaced_targets():
+    CC.check_int64_targets(None, "cuda")
+
+
+@pytest.mark.parametrize("batch_size", CC.OFFSET_BATCH_SIZES)
+def test_batch_offsets(batch_size):
+    CC.check_batch_offsets(batch_size, None, "cuda")
+
+
+def test_batch_offsets_without_ids():
+    CC.check_batch_offsets_no_ids(None, "cuda")
+
+
+def test_batch_offsets_capacity():
+    CC.check_batch_offsets_capacity(None, "cuda")
+
+
+@pytest.mark.parametrize("need_weights", [False, True])
+@pytest.mark.parametrize("which,batch_size", [("tiny", 65), ("tiny", 1025), ("mixed", 65)])
+def test_topology_from_the_resident_set_at_slot_count_edges(which, batch_size, need_weights):
+    CC.check_topology(which, batch_size, need_weights, None, "cuda")
+
+
+@pytest.mark.parametrize("which", range(CC.N_OUTSIDE_LISTS))
+def test_collate_ids_outside_the_set(which):
+    CC.check_collate_outside_ids(which, None, "cuda")
+
+
+def test_batch_offsets_ids_outside_the_set():
+    CC.check_offsets_outside_ids(None, "cuda")
+
+
+def test_batch_offsets_ids_outside_the_declared_set():
+    CC.check_offsets_outside_declared_set(None, "cuda")
+
+
+def test_collate_refusals():
+    CC.check_collate_refusals(None, "cuda")
+
+
+def test_batch_offsets_refusals():
+    CC.check_offsets_refusals(None, "cuda")
+
+
+def test_upload_ids_out_of_range():
+    CC.check_upload_ids_range(None, "cuda")
+
+
+def test_upload_ids_staging_ring():
+    CC.check_upload_ids_ring("cuda")
+
+
+def test_resident_set_image_round_trip(tmp_path):
+    CC.check_image_round_trip(str(tmp_path / "set.npz"), None, "cuda")
